@@ -205,8 +205,45 @@ static void element_matrix(int nloc, int d, const double* gc, double vc, const d
   }
 }
 
+// Cells in colour classes, no two cells of a class sharing a node (greedy, cells ascending): class k is
+// cells[cptr[k] .. cptr[k + 1]), ascending.  Assembling one class at a time, its cells in parallel, no two threads add into
+// the same block row and every operator entry is summed in the same order on every run, whatever the number of threads.
+static void colour_cells(int64_t ncell, int nloc, const int32_t* cell_nodes, std::vector<int64_t>& cptr,
+                         std::vector<int64_t>& cells) {
+  int64_t nnode = 0;
+  for (int64_t i = 0; i < ncell * nloc; ++i) nnode = std::max<int64_t>(nnode, (int64_t)cell_nodes[i] + 1);
+  std::vector<int64_t> nptr(nnode + 1, 0);                 // node -> cells (ascending)
+  for (int64_t i = 0; i < ncell * nloc; ++i) nptr[cell_nodes[i] + 1]++;
+  for (int64_t i = 0; i < nnode; ++i) nptr[i + 1] += nptr[i];
+  std::vector<int64_t> ncells(nptr[nnode]);
+  {
+    std::vector<int64_t> fill(nptr.begin(), nptr.end() - 1);
+    for (int64_t c = 0; c < ncell; ++c)
+      for (int a = 0; a < nloc; ++a) ncells[fill[cell_nodes[c * nloc + a]]++] = c;
+  }
+  std::vector<int32_t> colour(ncell);
+  std::vector<int64_t> taken;                              // taken[k] == c: a neighbour of cell c has colour k
+  for (int64_t c = 0; c < ncell; ++c) {
+    for (int a = 0; a < nloc; ++a) {
+      const int64_t n = cell_nodes[c * nloc + a];
+      for (int64_t p = nptr[n]; p < nptr[n + 1] && ncells[p] < c; ++p) taken[colour[ncells[p]]] = c;
+    }
+    size_t k = 0;
+    while (k < taken.size() && taken[k] == c) ++k;
+    if (k == taken.size()) taken.push_back(-1);
+    colour[c] = (int32_t)k;
+  }
+  cptr.assign(taken.size() + 1, 0);
+  for (int64_t c = 0; c < ncell; ++c) cptr[colour[c] + 1]++;
+  for (size_t k = 0; k < taken.size(); ++k) cptr[k + 1] += cptr[k];
+  cells.resize(ncell);
+  std::vector<int64_t> fill(cptr.begin(), cptr.end() - 1);
+  for (int64_t c = 0; c < ncell; ++c) cells[fill[colour[c]]++] = c;
+}
+
 // vals (nnzb, d, d) += nu*K + gamma*D + adv*N(w), scattered into a BSR matrix whose block rows are the nodes mapped
 // through row_map (nullptr: identity; row_map[node] < 0: row skipped) and whose block columns are all nodes.
+// Deterministic: the cells are assembled colour class by colour class (colour_cells), without atomics.
 int alfi_host_assemble_bsr(int64_t ncell, int nloc, int d, const int32_t* cell_nodes, const double* g,
                            const double* vol, const double* S, const double* bI, const double* T1, const double* w,
                            double nu, double gamma, double adv, const int32_t* row_map, const int32_t* rowptr,
@@ -215,12 +252,17 @@ int alfi_host_assemble_bsr(int64_t ncell, int nloc, int d, const int32_t* cell_n
   const int ndof = nloc * d;
   const bool do_adv = (adv != 0.0) && (w != nullptr);
   int err = 0;
+  std::vector<int64_t> cptr, cells;
+  colour_cells(ncell, nloc, cell_nodes, cptr, cells);
+  const int64_t ncolour = (int64_t)cptr.size() - 1;
 #pragma omp parallel
   {
     ElemWork W(nloc, d, S);
     std::vector<double> Ae((size_t)ndof * ndof), wk((size_t)nloc * d);
+    for (int64_t k = 0; k < ncolour; ++k)
 #pragma omp for schedule(dynamic, 256)
-    for (int64_t c = 0; c < ncell; ++c) {
+    for (int64_t i = cptr[k]; i < cptr[k + 1]; ++i) {
+      const int64_t c = cells[i];
       const int32_t* cn = cell_nodes + c * nloc;
       if (row_map) {
         bool any = false;
@@ -244,11 +286,7 @@ int alfi_host_assemble_bsr(int64_t ncell, int nloc, int d, const int32_t* cell_n
           }
           double* dst = vals + pos * d * d;
           for (int cc = 0; cc < d; ++cc)
-            for (int dd = 0; dd < d; ++dd) {
-              const double v = Ae[(size_t)(a * d + cc) * ndof + b * d + dd];
-#pragma omp atomic
-              dst[cc * d + dd] += v;
-            }
+            for (int dd = 0; dd < d; ++dd) dst[cc * d + dd] += Ae[(size_t)(a * d + cc) * ndof + b * d + dd];
         }
       }
     }

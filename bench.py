@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the multigrid hot path: V-cycles/s (and DoF*smooths/s) on the synthetic lid-driven cavity.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg4]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg4] [--dump-outputs DIR]
 
 A "step" is one multiplicative V-cycle (k pre- and post-smoothing FGMRES iterations with the additive vertex-star
 patch smoother on every level, Schoeberl prolongation, dense coarse solve) on the finest level, with all operators,
@@ -12,6 +12,12 @@ Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (patch_app
 inverse once per smoother iteration); its `achieved` is algorithmic bytes / device time measured live with HIP events on
 the library's stream during the timed region.  `cpu_baseline` times the C/OpenMP oracle port on the host cores on a
 bounded sample (the same hierarchy truncated by one level, scaled by the dof ratio).
+
+--dump-outputs DIR writes what the timed cycles hand their caller -- the finest-level iterate x after the last timed step
+(`warmup + steps` V-cycles from x = 0 on the seeded right-hand side) -- as DIR/x.npy, float64.  A vector larger than
+DUMP_BYTES_MAX is written as a fixed, seeded sample: DIR/x.npy holds the entries at the global dof numbers in
+DIR/x_index.npy.  The operators are assembled in a fixed order (alfi_host_assemble_bsr), so the same arguments give the
+same inputs on every run and two builds can be compared entry for entry.
 """
 import argparse
 import json
@@ -59,6 +65,27 @@ def config_mesh(cfg):
     return os.path.join(MESH_DIR, base) if isinstance(base, str) else None
 SETUP_KEYS = ("comm_init", "partition", "localize", "upload_factor")     # DistMultigrid.setup_s, reported per rank
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s spec, ~6.3 TB/s achievable)
+DUMP_BYTES_MAX = 64 * 10 ** 6     # --dump-outputs: all files together, .npy headers included
+
+
+def dump_indices(n):
+    """(global dof numbers, sampled) of the entries --dump-outputs writes of an n-vector: all of them when they fit in
+    DUMP_BYTES_MAX as float64, otherwise a fixed, seeded, ascending sample whose indices are written as well."""
+    if 8 * n + 128 <= DUMP_BYTES_MAX:
+        return np.arange(n), False
+    m = (DUMP_BYTES_MAX - 2 * 128) // 16
+    return np.sort(np.random.default_rng(0).choice(n, size=m, replace=False)), True
+
+
+def write_outputs(out_dir, x, idx, sampled):
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "x.npy"), np.ascontiguousarray(x, dtype=np.float64))
+    if sampled:
+        np.save(os.path.join(out_dir, "x_index.npy"), idx.astype(np.float64))
+    elif os.path.exists(os.path.join(out_dir, "x_index.npy")):       # left by an earlier, sampled dump
+        os.remove(os.path.join(out_dir, "x_index.npy"))
+    sys.stderr.write("[alfi bench] wrote x.npy (%d of the finest level's entries%s) to %s\n"
+                     % (len(idx), ", indices in x_index.npy" if sampled else "", out_dir))
 
 
 def describe(cfg):
@@ -273,6 +300,19 @@ def main_distributed(args, rank, world, local_rank):
     tmax = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
     dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
+    if args.dump_outputs:
+        # now: the untimed cycles below reuse dx.  Every global dof is owned by exactly one rank, so a sum over the ranks
+        # of their owned entries (zeros elsewhere) assembles the global vector at the sampled dofs
+        idx, sampled = dump_indices(L.n)
+        own, vals = dmg.fine.part.own_dofs(), dmg.owned(dx)
+        pos = np.minimum(np.searchsorted(idx, own), len(idx) - 1)
+        hit = idx[pos] == own
+        buf = np.zeros(len(idx))
+        buf[pos[hit]] = vals[hit]
+        xs = torch.tensor(buf, dtype=torch.float64, device="cuda")
+        dist.all_reduce(xs)
+        if rank == 0:
+            write_outputs(args.dump_outputs, xs.cpu().numpy(), idx, sampled)
 
     stage("post_measurements")
     # convergence sanity on the timed iterate: global residual norm
@@ -594,8 +634,13 @@ def main():
     ap.add_argument("--mesh", default=None,
                     help="config 5 only: gmsh 2.2 ASCII mesh of the channel (the reference's examples/bfs3d/coarse*.msh, "
                          "bfs3d.py:37-39) as the base mesh instead of the structured stand-in")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the iterate they computed (the finest level's x) to DIR/x.npy, "
+                         "float64; a seeded sample of at most 64 MB with its dof numbers in DIR/x_index.npy when larger")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     global BFS3D_MESH
     BFS3D_MESH = args.mesh
 
@@ -667,6 +712,9 @@ def main():
     ctx.prof_enable(False)
     timed_apply_all = ctx.prof_get()["PATCH_APPLY"]
     timed_apply = {dl.id: ctx.prof_get(dl.id)["PATCH_APPLY"] for dl in dmg.levels[1:]}
+    if args.dump_outputs:
+        idx, sampled = dump_indices(L.n)
+        write_outputs(args.dump_outputs, dx.get()[idx], idx, sampled)
     ctx.prof_enable(True)
     ctx.prof_reset()
     dxi = ctx.vec(L.n)

@@ -1,6 +1,7 @@
 """Pins against the reference's OWN native code: the five C kernels of alfi/bubble.py, compiled where they lie into
-oracle/_ref/libalfi_ref_bubble.so by oracle/build_ref.py (skipped when neither /root/reference nor the prebuilt library
-is there).
+oracle/_ref/libalfi_ref_bubble.so by oracle/build_ref.py.  What those kernels return on the seeded inputs below is also
+recorded in tests/golden/ref_bubble_kernels.npz (tests/golden/make_ref_kernels.py): where the kernels are built the live
+outputs are checked against that record, elsewhere the record stands in for them.
 
 1. the oracle's split / combine stencils (oracle.alfi_oracle.bubble_prolong_literal) are the reference kernels';
 2. BubbleTransfer.prolong (bubble.py:233-265) driven cell by cell through the REFERENCE kernels -- only the par_loop
@@ -18,15 +19,16 @@ import pytest
 from alfi_amd.problem import ThreeDimLidDrivenCavityProblem, build_hierarchy
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RECORDED = os.path.join(ROOT, "tests", "golden", "ref_bubble_kernels.npz")
 dp = ctypes.POINTER(ctypes.c_double)
 
 
-@pytest.fixture(scope="module")
-def ref():
+def load_reference_kernels():
+    """The reference kernels as a ctypes library, or None where oracle/build_ref.py can neither build nor find them."""
     from oracle import build_ref
     path = build_ref.build()
     if path is None or not os.path.exists(path):
-        pytest.skip("reference kernels not built (no /root/reference and no prebuilt oracle/_ref)")
+        return None
     lib = ctypes.CDLL(path)
     for name in ("split", "splitadj", "combine", "combineadj", "count"):
         getattr(lib, name).restype = None
@@ -34,40 +36,92 @@ def ref():
     return lib
 
 
+@pytest.fixture(scope="module")
+def ref():
+    """{output name: array} of the reference kernels on the seeded inputs (reference_kernel_outputs): live, and equal to the
+    record, where the kernels are built; the record otherwise."""
+    recorded = dict(np.load(RECORDED))
+    lib = load_reference_kernels()
+    if lib is None:
+        return recorded
+    live = reference_kernel_outputs(lib)
+    assert sorted(live) == sorted(recorded)
+    for key, v in live.items():
+        assert v.shape == recorded[key].shape, key
+        assert np.abs(v - recorded[key]).max() <= 1e-14 * max(np.abs(recorded[key]).max(), 1.0), key
+    return live
+
+
 def _p(a):
     return a.ctypes.data_as(dp)
 
 
-def test_split_combine_stencils_are_the_reference_kernels(ref):
+def stencil_inputs():
+    """Cell arrays of the stencil test, in the order they are drawn: both (8 x 3), p1 (4 x 3), fb (4 x 3)."""
     rng = np.random.default_rng(0)
+    both = rng.standard_normal((8, 3))
+    p1, fb = rng.standard_normal((4, 3)), rng.standard_normal((4, 3))
+    return both, p1, fb
+
+
+def transfer_case():
+    """ldc3d [P1+FB]^3, two levels: the hierarchy both transfer tests drive through the reference kernels."""
+    return build_hierarchy(ThreeDimLidDrivenCavityProblem(2), 1, 1, Re=10.0)
+
+
+def transfer_inputs(lv, seed):
+    """Coarse vector to prolong, then fine vector to restrict."""
+    rng = np.random.default_rng(seed)
+    uc = rng.standard_normal(lv[0].V.num_dofs)
+    rf = rng.standard_normal(lv[1].V.num_dofs)
+    return uc, rf
+
+
+def reference_kernel_outputs(ref):
+    """Everything the tests below take from the reference kernels, on their seeded inputs."""
+    out = {}
+    both, p1, fb = stencil_inputs()
+    a, b = np.zeros((4, 3)), np.zeros((4, 3))
+    ref.split(_p(a), _p(b), _p(both))
+    out["split_p1"], out["split_fb"] = a, b
+    c = np.zeros((8, 3))
+    ref.combine(_p(p1), _p(fb), _p(c))
+    out["combine"] = c
+    back = np.zeros((8, 3))                                                             # combine after split
+    ref.combine(_p(a.copy()), _p(b.copy()), _p(back))
+    out["combine_split"] = back
+    c = np.zeros((8, 3))
+    ref.splitadj(_p(p1), _p(fb), _p(c))
+    out["splitadj"] = c
+    a, b = np.zeros((4, 3)), np.zeros((4, 3))
+    ref.combineadj(_p(both), _p(a), _p(b))
+    out["combineadj_p1"], out["combineadj_fb"] = a, b
+    c1, c2, c3 = np.zeros((8, 3)), np.zeros((4, 3)), np.zeros((4, 3))
+    ref.count(_p(c1), _p(c2), _p(c3))
+    out["count_nodes"], out["count_faces"], out["count_vertices"] = c1, c2, c3
+    lv, _ = transfer_case()
+    Vc, Vf = lv[0].V, lv[1].V
+    for seed in (1, 2):
+        uc, rf = transfer_inputs(lv, seed)
+        out["prolong_%d" % seed] = prolong_with_reference_kernels(ref, Vc, Vf, uc)
+        out["restrict_%d" % seed] = restrict_with_reference_kernels(ref, Vc, Vf, rf)
+    return out
+
+
+def test_split_combine_stencils_are_the_reference_kernels(ref):
     a = np.vstack([np.eye(4), np.zeros((4, 4))])                                      # as restated in the oracle
     b = np.vstack([-(np.ones((4, 4)) - np.eye(4)) / 3.0, np.eye(4)])
     ac = np.hstack([np.eye(4), (np.ones((4, 4)) - np.eye(4)) / 3.0])
     bc = np.hstack([np.zeros((4, 4)), np.eye(4)])
-    both = rng.standard_normal((8, 3))
-    p1, fb = np.zeros((4, 3)), np.zeros((4, 3))
-    ref.split(_p(p1), _p(fb), _p(both))
-    assert np.allclose(p1, a.T @ both, atol=1e-15) and np.allclose(fb, b.T @ both, atol=1e-15)
-    p1, fb = rng.standard_normal((4, 3)), rng.standard_normal((4, 3))
-    out = np.zeros((8, 3))
-    ref.combine(_p(p1), _p(fb), _p(out))
-    assert np.allclose(out, ac.T @ p1 + bc.T @ fb, atol=1e-15)
+    both, p1, fb = stencil_inputs()
+    assert np.allclose(ref["split_p1"], a.T @ both, atol=1e-15) and np.allclose(ref["split_fb"], b.T @ both, atol=1e-15)
+    assert np.allclose(ref["combine"], ac.T @ p1 + bc.T @ fb, atol=1e-15)
     # combine after split is the identity on a cell (nodal -> hierarchical -> nodal)
-    q1, qb = np.zeros((4, 3)), np.zeros((4, 3))
-    ref.split(_p(q1), _p(qb), _p(both))
-    back = np.zeros((8, 3))
-    ref.combine(_p(q1), _p(qb), _p(back))
-    assert np.allclose(back, both, atol=1e-14)
+    assert np.allclose(ref["combine_split"], both, atol=1e-14)
     # the adjoint kernels are the transposes
-    out = np.zeros((8, 3))
-    ref.splitadj(_p(p1), _p(fb), _p(out))
-    assert np.allclose(out, a @ p1 + b @ fb, atol=1e-15)
-    q1, qb = np.zeros((4, 3)), np.zeros((4, 3))
-    ref.combineadj(_p(both), _p(q1), _p(qb))
-    assert np.allclose(q1, ac @ both, atol=1e-15) and np.allclose(qb, bc @ both, atol=1e-15)
-    c1, c2, c3 = np.zeros((8, 3)), np.zeros((4, 3)), np.zeros((4, 3))
-    ref.count(_p(c1), _p(c2), _p(c3))
-    assert (c1 == 1).all() and (c2 == 1).all() and (c3 == 1).all()
+    assert np.allclose(ref["splitadj"], a @ p1 + b @ fb, atol=1e-15)
+    assert np.allclose(ref["combineadj_p1"], ac @ both, atol=1e-15) and np.allclose(ref["combineadj_fb"], bc @ both, atol=1e-15)
+    assert (ref["count_nodes"] == 1).all() and (ref["count_faces"] == 1).all() and (ref["count_vertices"] == 1).all()
 
 
 def _subspace_prolongations(Vc, Vf):
@@ -156,17 +210,15 @@ def restrict_with_reference_kernels(ref, Vc, Vf, fine):
 
 def test_bubble_transfer_through_reference_kernels(ref):
     from oracle import alfi_oracle as O
-    lv, tr = build_hierarchy(ThreeDimLidDrivenCavityProblem(2), 1, 1, Re=10.0)
+    lv, tr = transfer_case()
     Vc, Vf, T = lv[0].V, lv[1].V, tr[0]
-    rng = np.random.default_rng(1)
-    uc = rng.standard_normal(Vc.num_dofs)
-    got = prolong_with_reference_kernels(ref, Vc, Vf, uc)
+    uc, rf = transfer_inputs(lv, 1)
+    got = ref["prolong_1"]
     lit = O.bubble_prolong_literal(Vc, Vf, uc)
     mat = T.P.to_scipy() @ uc
     assert np.abs(got - lit).max() < 1e-13 * np.abs(got).max()
     assert np.abs(got - mat).max() < 1e-13 * np.abs(got).max()
-    rf = rng.standard_normal(Vf.num_dofs)
-    gotr = restrict_with_reference_kernels(ref, Vc, Vf, rf)
+    gotr = ref["restrict_1"]
     matr = T.PT.to_scipy() @ rf
     assert np.abs(gotr - matr).max() < 1e-13 * np.abs(gotr).max()
 
@@ -177,22 +229,20 @@ def test_hip_prolong_and_restrict_against_reference_kernels(ref):
     the Schoeberl correction vanishes, transfer.py:259 / :274, and what is left is BubbleTransfer.prolong / .restrict,
     bubble.py:204-265) on ldc3d [P1+FB]^3, compared with the cell-by-cell evaluation through the reference kernels."""
     from alfi_amd import hip
-    lv, tr = build_hierarchy(ThreeDimLidDrivenCavityProblem(2), 1, 1, Re=10.0)
+    lv, tr = transfer_case()
     Vc, Vf, T = lv[0].V, lv[1].V, tr[0]
     ctx = hip.Context(0)
     dc, df = hip.Level(ctx, lv[0].A, lv[0].bc_dofs), hip.Level(ctx, lv[1].A, lv[1].bc_dofs)
     dt = hip.Transfer(ctx, dc, df, T)
     dt.update(T.nu, 0.0)
-    rng = np.random.default_rng(2)
-    uc = rng.standard_normal(Vc.num_dofs)
-    want = prolong_with_reference_kernels(ref, Vc, Vf, uc)
+    uc, rf = transfer_inputs(lv, 2)
+    want = ref["prolong_2"].copy()
     want[lv[1].bc_dofs] = 0.0                                  # alfi_prolong zeroes the fine Dirichlet dofs
     xc, xf = ctx.vec(uc), ctx.vec(Vf.num_dofs)
     dt.prolong(xc, xf)
     got = xf.get()
     assert np.abs(got - want).max() < 1e-13 * np.abs(want).max()
-    rf = rng.standard_normal(Vf.num_dofs)
-    wantr = restrict_with_reference_kernels(ref, Vc, Vf, rf.copy())
+    wantr = ref["restrict_2"].copy()
     wantr[lv[0].bc_dofs] = 0.0
     yf, yc = ctx.vec(rf), ctx.vec(Vc.num_dofs)
     dt.restrict(yf, yc, robust=True)
