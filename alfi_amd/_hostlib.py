@@ -42,6 +42,7 @@ def lib():
         _lib.alfi_host_interior_blocks.restype = ctypes.c_int
         _lib.alfi_host_bsr_transpose.restype = ctypes.c_int
         _lib.alfi_host_supg.restype = ctypes.c_int
+        _lib.alfi_host_burman.restype = ctypes.c_int
         # ALFI_HOST_THREADS overrides OMP_NUM_THREADS (torch.distributed.run exports OMP_NUM_THREADS=1 to every rank)
         nthr = int(os.environ.get("ALFI_HOST_THREADS", "0")) or cpu_share()
         _lib.alfi_host_set_num_threads(ctypes.c_int(nthr))
@@ -125,6 +126,31 @@ def supg(V, U, nu, weight, magic, rowptr=None, colidx=None, vals=None, F=None, n
                               _p(rowptr), _p(colidx), _p(vals), _p(F))
     if rc != 0:
         raise RuntimeError("supg failed (%d): sparsity pattern does not cover the mesh" % rc)
+
+
+def burman(table, U, weight, lists, vals=None, F=None, beta=None):
+    """Burman interior-penalty stabilisation (stabilisation.py:139-162, alfi_amd/burman.py) about the state U (num_nodes,
+    dim): adds the residual contribution to F (num_dofs) and / or the Newton linearisation to the BSR values ``vals``.
+    ``table``: burman.FacetTable of the level; ``lists``: its contributor lists for the level's sparsity
+    (FacetTable.contributors); ``beta`` (nfacet, may be None): receives beta_F of every facet."""
+    (bptr, bfac, bab), (nptr, nfac, na) = lists
+    t = table
+    U = np.ascontiguousarray(U, dtype=np.float64)
+    assert U.size == (len(nptr) - 1) * t.d
+    if vals is not None:
+        assert vals.shape == (len(bptr) - 1, t.d, t.d) and vals.flags.c_contiguous and vals.dtype == np.float64
+    if F is not None:
+        assert F.shape == (U.size,) and F.flags.c_contiguous and F.dtype == np.float64
+    if beta is not None:
+        assert beta.shape == (t.nf,) and beta.flags.c_contiguous and beta.dtype == np.float64
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (t.J, t.area, t.coef, t.ws, t.wn, t.phin)]
+    rc = lib().alfi_host_burman(ctypes.c_int64(t.nf), ctypes.c_int(t.nu), ctypes.c_int(t.nloc), ctypes.c_int(t.d),
+                                ctypes.c_int(len(t.ws)), ctypes.c_int(len(t.wn)), _p(t.union), _p(t.cfg), _p(arrs[0]),
+                                _p(arrs[1]), _p(arrs[2]), _p(arrs[3]), _p(arrs[4]), _p(arrs[5]), _p(U),
+                                ctypes.c_double(weight), ctypes.c_int64(len(bptr) - 1), _p(bptr), _p(bfac), _p(bab),
+                                _p(vals), ctypes.c_int64(len(nptr) - 1), _p(nptr), _p(nfac), _p(na), _p(F), _p(beta))
+    if rc != 0:
+        raise RuntimeError("burman failed (%d)" % rc)
 
 
 def contributors(cell_nodes, nnode, rowptr, colidx, nindex=None, partial=False):

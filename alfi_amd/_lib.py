@@ -73,6 +73,13 @@ SIGNATURES = {
     "alfi_level_set_supg": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, vp, vp, vp]),
     "alfi_level_supg": (ctypes.c_int, [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, ctypes.c_int, vp]),
     "alfi_level_apply_bc": (ctypes.c_int, [vp]),
+    "alfi_level_set_facet_blocks": (ctypes.c_int, [vp, ctypes.c_int]),
+    "alfi_level_set_burman": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [vp] * 14),
+    "alfi_level_burman": (ctypes.c_int, [vp, ctypes.c_double, vp, ctypes.c_int, vp]),
+    "alfi_patches_set_facet_correction": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int64, vp, vp, vp, vp]),
+    "alfi_level_set_facet_beta": (ctypes.c_int, [vp, vp, ctypes.c_double]),
+    "alfi_level_assemble_burman": (ctypes.c_int, [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, ctypes.c_double,
+                                                  ctypes.c_int]),
     "alfi_level_get_values": (ctypes.c_int, [vp, vp]),
     "alfi_level_size": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64)]),
     "alfi_spmv": (ctypes.c_int, [vp, vp, vp]),

@@ -198,6 +198,7 @@ int alfi_level_destroy(alfi_level* L) {
   dev_free(L->rev_nodes);
   dev_free(L->rev_ptr);
   dev_free(L->rev_pos);
+  dev_free(L->fc_ptr); dev_free(L->fc_col); dev_free(L->fc_fac); dev_free(L->fc_s); dev_free(L->fc_beta);
   dev_free(L->patch_ptr);
   dev_free(L->patch_dofs);
   dev_free(L->inv_ptr);
@@ -230,6 +231,7 @@ int alfi_level_update_values(alfi_level* L, const double* bvals) {
   alfi_ctx* ctx = L->ctx;
   ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   ALFI_CHECK(upload_bsr_values(ctx, &L->A, bvals));
+  L->fc_scale = 0.0;         // (host values: a Burman part is declared by alfi_level_set_facet_beta)
   L->A_own.vals = L->A.vals;
   L->A_int.vals = L->A_bnd.vals = L->A.vals;
   L->factored = false;
@@ -240,7 +242,10 @@ void free_assembly(AssemblyDev* S) {
   dev_free(S->cptr); dev_free(S->ccell); dev_free(S->cba); dev_free(S->cell_nodes); dev_free(S->grad); dev_free(S->vol);
   dev_free(S->etab); dev_free(S->bItab); dev_free(S->bc_code); dev_free(S->bc_all);
   dev_free(S->wq); dev_free(S->phi); dev_free(S->dphi); dev_free(S->d2phi); dev_free(S->hcell); dev_free(S->diag);
-  dev_free(S->wq8); dev_free(S->qtab);
+  dev_free(S->wq8); dev_free(S->qtab); dev_free(S->brc);
+  dev_free(S->funion); dev_free(S->fcfg); dev_free(S->fJ); dev_free(S->farea); dev_free(S->fcoef); dev_free(S->fws);
+  dev_free(S->fwn); dev_free(S->fphin); dev_free(S->fbptr); dev_free(S->fbfac); dev_free(S->fbab); dev_free(S->fnptr);
+  dev_free(S->fnfac); dev_free(S->fna);
   *S = AssemblyDev();
 }
 
@@ -270,7 +275,8 @@ int alfi_level_set_assembly(alfi_level* L, int64_t ncell, int nloc, const int32_
     for (int64_t k = k0; k < k1; ++k)
       if (cptr[k + 1] <= cptr[k]) { bad_block = k; return; }
   });
-  if (bad_block >= 0) return alfi_set_error(ctx, ALFI_E_ARG, "block %lld has no contributing cell", (long long)bad_block.load());
+  if (bad_block >= 0 && !(L->facet_blocks && !part))
+    return alfi_set_error(ctx, ALFI_E_ARG, "block %lld has no contributing cell", (long long)bad_block.load());
   host_parallel_ranges(npairs, [&](int64_t q0, int64_t q1) {
     for (int64_t q = q0; q < q1; ++q)
       if (ccell[q] < 0 || ccell[q] >= ncell || cba[q] >= nloc * nloc) { bad_pair = q; return; }
@@ -290,6 +296,8 @@ int alfi_level_set_assembly(alfi_level* L, int64_t ncell, int nloc, const int32_
   // the diagonal block of every block row (its contributor list = the cells around the node: the gather of element vectors);
   // the two nodes of a contributing pair are rows / columns of the local operator
   std::vector<int32_t> diag((size_t)nb, -1);
+  std::vector<int32_t> brc;            // facet-coupled level: (row, column) node of every block
+  if (L->facet_blocks) brc.resize((size_t)std::max<int64_t>(nnzb, 1) * 2, 0);
   {
     std::vector<int32_t> rowptr(nb + 1), colidx((size_t)std::max<int64_t>(nnzb, 1));
     ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -302,6 +310,7 @@ int alfi_level_set_assembly(alfi_level* L, int64_t ncell, int nloc, const int32_
         for (int64_t k = rowptr[r]; k < rowptr[r + 1]; ++k) {
           const int32_t c = colidx[k] & 0x7fffffff;       // (the sign bit marks the first block of a block row)
           if (c == r) diag[r] = (int32_t)k;
+          if (!brc.empty()) { brc[2 * k] = (int32_t)r; brc[2 * k + 1] = c; }
           for (int64_t q = cptr[k]; q < cptr[k + 1]; ++q) {
             const int32_t* cn = cell_nodes + (int64_t)ccell[q] * nloc;
             if (cn[cba[q] % nloc] != r || cn[cba[q] / nloc] != c) { stray = q; stray_block = k; return; }
@@ -346,6 +355,7 @@ int alfi_level_set_assembly(alfi_level* L, int64_t ncell, int nloc, const int32_
   if (rc == 0) rc = dev_upload(ctx, &S.etab, etab.data(), (int64_t)etab.size());
   if (rc == 0) rc = dev_upload(ctx, &S.bItab, bIref, (int64_t)nloc * nv);
   if (rc == 0) rc = dev_upload(ctx, &S.diag, diag.data(), nb);
+  if (rc == 0 && !brc.empty()) rc = dev_upload(ctx, &S.brc, brc.data(), nnzb * 2);
   if (rc != 0) {
     free_assembly(&S);
     return rc;
@@ -371,6 +381,7 @@ int alfi_level_assemble(alfi_level* L, double nu, double gamma, double adv, cons
   ALFI_CHECK(launch_operator_refresh(L, nu, gamma, adv, d_state, true, false, 0.0, 0.0, false, apply_bc != 0, L->A.vals));
   alfi_prof_end(ctx, t);
   L->factored = false;
+  L->fc_scale = 0.0;
   return 0;
 }
 
@@ -494,6 +505,168 @@ int alfi_level_supg(alfi_level* L, double nu, double weight, double magic, const
   if (d_F) ALFI_CHECK(launch_supg_residual(L, nu, weight, magic, d_state, d_F));
   alfi_prof_end(ctx, t);
   if (add_to_operator) L->factored = false;
+  return 0;
+}
+
+// Burman interior-penalty stabilisation (alfi/stabilisation.py:139-162; alfi_amd/burman.py): the facet tables and the facet
+// contributor lists of every block and every node, checked here once
+int alfi_level_set_facet_blocks(alfi_level* L, int on) {
+  if (L->asmb.ready) return alfi_set_error(L->ctx, ALFI_E_STATE, "alfi_level_set_facet_blocks after alfi_level_set_assembly");
+  L->facet_blocks = on != 0;
+  return 0;
+}
+
+int alfi_level_set_burman(alfi_level* L, int64_t nfacet, int nu, int nqs, int nqn, int ncfg, const int32_t* funion,
+                          const int32_t* cfg, const double* J, const double* area, const double* coef, const double* ws,
+                          const double* wn, const double* phin, const int64_t* bptr, const int32_t* bfac, const uint16_t* bab,
+                          const int64_t* nptr, const int32_t* nfac, const uint16_t* na) {
+  alfi_ctx* ctx = L->ctx;
+  AssemblyDev& S = L->asmb;
+  if (!S.ready) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_level_set_burman before alfi_level_set_assembly");
+  if (!L->facet_blocks) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_level_set_burman on a level without alfi_level_set_facet_blocks");
+  if (L->has_halo) return alfi_set_error(ctx, ALFI_E_STATE, "Burman terms on a partitioned level");
+  if (nfacet < 0 || nu < 1 || nu * nu > 65535 || nu < S.nloc || nqs < 1 || nqs > BURMAN_MAXQ || nqn < 1 || nqn > BURMAN_MAXQ ||
+      ncfg < 1 || S.nloc > BURMAN_MAXN)
+    return alfi_set_error(ctx, ALFI_E_ARG, "bad Burman table sizes (%d union nodes, %d / %d points)", nu, nqs, nqn);
+  if (!funion || !cfg || !J || !area || !coef || !ws || !wn || !phin || !bptr || !bfac || !bab || !nptr || !nfac || !na)
+    return alfi_set_error(ctx, ALFI_E_ARG, "NULL argument");
+  const int64_t nnzb = L->A.nnzb, nb = L->A.nbrows;
+  if (bptr[0] != 0 || nptr[0] != 0 || bptr[nnzb] != nfacet * nu * nu || nptr[nb] != nfacet * nu)
+    return alfi_set_error(ctx, ALFI_E_ARG, "facet contributor lists of the wrong length");
+  for (int64_t i = 0; i < nfacet * nu; ++i)
+    if (funion[i] < 0 || funion[i] >= nb) return alfi_set_error(ctx, ALFI_E_ARG, "facet node out of range");
+  for (int64_t f = 0; f < nfacet; ++f)
+    if (cfg[f] < 0 || cfg[f] >= ncfg) return alfi_set_error(ctx, ALFI_E_ARG, "facet configuration out of range");
+  for (int64_t k = 0; k < nnzb; ++k) {
+    if (bptr[k + 1] < bptr[k]) return alfi_set_error(ctx, ALFI_E_ARG, "facet contributor lists not ascending");
+    for (int64_t p = bptr[k]; p < bptr[k + 1]; ++p)
+      if (bfac[p] < 0 || bfac[p] >= nfacet || bab[p] >= nu * nu) return alfi_set_error(ctx, ALFI_E_ARG, "facet contributor out of range");
+  }
+  for (int64_t r = 0; r < nb; ++r) {
+    if (nptr[r + 1] < nptr[r]) return alfi_set_error(ctx, ALFI_E_ARG, "facet node lists not ascending");
+    for (int64_t p = nptr[r]; p < nptr[r + 1]; ++p)
+      if (nfac[p] < 0 || nfac[p] >= nfacet || na[p] >= nu || funion[(int64_t)nfac[p] * nu + na[p]] != r)
+        return alfi_set_error(ctx, ALFI_E_ARG, "facet node contributor %lld does not belong to node %lld", (long long)p, (long long)r);
+  }
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  dev_free(S.funion); dev_free(S.fcfg); dev_free(S.fJ); dev_free(S.farea); dev_free(S.fcoef); dev_free(S.fws); dev_free(S.fwn);
+  dev_free(S.fphin); dev_free(S.fbptr); dev_free(S.fbfac); dev_free(S.fbab); dev_free(S.fnptr); dev_free(S.fnfac); dev_free(S.fna);
+  S.funion = S.fcfg = S.fbfac = S.fnfac = nullptr;
+  S.fJ = S.farea = S.fcoef = S.fws = S.fwn = S.fphin = nullptr;
+  S.fbptr = S.fnptr = nullptr;
+  S.fbab = S.fna = nullptr;
+  S.burman_ready = false;
+  const int64_t nfe = std::max<int64_t>(nfacet, 1);
+  int rc = dev_upload(ctx, &S.funion, funion, nfe * nu);
+  if (rc == 0) rc = dev_upload(ctx, &S.fcfg, cfg, nfe);
+  if (rc == 0) rc = dev_upload(ctx, &S.fJ, J, nfe * nqs * nu);
+  if (rc == 0) rc = dev_upload(ctx, &S.farea, area, nfe);
+  if (rc == 0) rc = dev_upload(ctx, &S.fcoef, coef, nfe);
+  if (rc == 0) rc = dev_upload(ctx, &S.fws, ws, nqs);
+  if (rc == 0) rc = dev_upload(ctx, &S.fwn, wn, nqn);
+  if (rc == 0) rc = dev_upload(ctx, &S.fphin, phin, (int64_t)ncfg * nqn * S.nloc);
+  if (rc == 0) rc = dev_upload(ctx, &S.fbptr, bptr, nnzb + 1);
+  if (rc == 0) rc = dev_upload(ctx, &S.fbfac, bfac, std::max<int64_t>(bptr[nnzb], 1));
+  if (rc == 0) rc = dev_upload(ctx, &S.fbab, bab, std::max<int64_t>(bptr[nnzb], 1));
+  if (rc == 0) rc = dev_upload(ctx, &S.fnptr, nptr, nb + 1);
+  if (rc == 0) rc = dev_upload(ctx, &S.fnfac, nfac, std::max<int64_t>(nptr[nb], 1));
+  if (rc == 0) rc = dev_upload(ctx, &S.fna, na, std::max<int64_t>(nptr[nb], 1));
+  if (rc != 0) return rc;
+  S.nfacet = nfacet;
+  S.bnu = nu;
+  S.bnqs = nqs;
+  S.bnqn = nqn;
+  S.burman_ready = true;
+  return 0;
+}
+
+int alfi_level_burman(alfi_level* L, double weight, const double* d_state, int add_to_operator, double* d_F) {
+  alfi_ctx* ctx = L->ctx;
+  if (!L->asmb.burman_ready) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_level_burman before alfi_level_set_burman");
+  if (!d_state) return alfi_set_error(ctx, ALFI_E_ARG, "the Burman term needs the state");
+  if (!add_to_operator && !d_F) return 0;
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ctx->cur_tag = L->id;
+  int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);       // PCPatchComputeOp
+  ALFI_CHECK(launch_burman(L, weight, d_state, add_to_operator != 0, d_F));
+  alfi_prof_end(ctx, t);
+  if (add_to_operator) {
+    L->factored = false;
+    L->fc_scale += weight;
+  }
+  return 0;
+}
+
+// The refresh of a Burman-stabilised run: A = nu K + gamma D + adv N(state) + adv * the linearised Burman term, then the
+// boundary conditions (the cell pass writes the values, the facet pass adds to them, one Dirichlet pass)
+int alfi_level_assemble_burman(alfi_level* L, double nu, double gamma, double adv, const double* d_state, double weight,
+                               int apply_bc) {
+  alfi_ctx* ctx = L->ctx;
+  if (!L->asmb.burman_ready) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_level_assemble_burman before alfi_level_set_burman");
+  if (!d_state) return alfi_set_error(ctx, ALFI_E_ARG, "the Burman term needs the state");
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ctx->cur_tag = L->id;
+  int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);
+  ALFI_CHECK(launch_operator_refresh(L, nu, gamma, adv, d_state, true, false, 0.0, 0.0, false, false, L->A.vals));
+  if (adv != 0.0) ALFI_CHECK(launch_burman(L, adv * weight, d_state, true, nullptr));
+  if (apply_bc) ALFI_CHECK(launch_apply_bc(L));
+  alfi_prof_end(ctx, t);
+  L->factored = false;
+  L->fc_scale = adv * weight;
+  return 0;
+}
+
+// PCPATCH's interior-facet rule on a Burman level: Firedrake's PatchPC assembles into a patch's matrix the interior-facet
+// integrals of the facets whose two cells both belong to the patch only.  For a facet with one cell K in the patch, the K-side
+// term weight * adv * c_F beta_F S_F (its only part on patch dofs: the facet's own nodes are not patch dofs) is taken out of the
+// gathered A[P, P] before the inversion (small and big patch paths) and in the residual probe.
+int alfi_patches_set_facet_correction(alfi_level* L, int64_t nfacet, int64_t nrow, const int64_t* ptr, const int32_t* col,
+                                      const int32_t* fac, const double* s) {
+  alfi_ctx* ctx = L->ctx;
+  if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_set_facet_correction before alfi_patches_set");
+  if (!ptr || nfacet < 0 || nrow < 0) return alfi_set_error(ctx, ALFI_E_ARG, "NULL argument");
+  if (L->h_patch_ptr[L->npatch] != nrow * L->bs) return alfi_set_error(ctx, ALFI_E_ARG, "facet correction rows != patch nodes");
+  const int64_t ne = ptr[nrow];
+  if (ptr[0] != 0 || (ne > 0 && (!col || !fac || !s))) return alfi_set_error(ctx, ALFI_E_ARG, "bad facet correction lists");
+  for (int64_t p = 0; p < L->npatch; ++p) {
+    const int64_t r0 = L->h_patch_ptr[p], r1 = L->h_patch_ptr[p + 1];
+    if (r0 % L->bs || r1 % L->bs) return alfi_set_error(ctx, ALFI_E_ARG, "facet correction needs patches of whole nodes");
+    const int64_t nn = (r1 - r0) / L->bs;
+    for (int64_t r = r0 / L->bs; r < r1 / L->bs; ++r) {
+      if (ptr[r + 1] < ptr[r]) return alfi_set_error(ctx, ALFI_E_ARG, "facet correction lists not ascending");
+      for (int64_t q = ptr[r]; q < ptr[r + 1]; ++q)
+        if (col[q] < 0 || col[q] >= nn || fac[q] < 0 || fac[q] >= nfacet)
+          return alfi_set_error(ctx, ALFI_E_ARG, "facet correction entry %lld out of range", (long long)q);
+    }
+  }
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  dev_free(L->fc_ptr); dev_free(L->fc_col); dev_free(L->fc_fac); dev_free(L->fc_s); dev_free(L->fc_beta);
+  L->fc_ptr = nullptr; L->fc_col = nullptr; L->fc_fac = nullptr; L->fc_s = nullptr; L->fc_beta = nullptr;
+  int rc = dev_upload(ctx, &L->fc_ptr, ptr, nrow + 1);
+  if (rc == 0) rc = dev_upload(ctx, &L->fc_col, col, std::max<int64_t>(ne, 1));
+  if (rc == 0) rc = dev_upload(ctx, &L->fc_fac, fac, std::max<int64_t>(ne, 1));
+  if (rc == 0) rc = dev_upload(ctx, &L->fc_s, s, std::max<int64_t>(ne, 1));
+  if (rc == 0) rc = dev_alloc(ctx, &L->fc_beta, std::max<int64_t>(nfacet, 1));
+  if (rc != 0) return rc;
+  ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->fc_beta, 0, sizeof(double) * (size_t)std::max<int64_t>(nfacet, 1), ctx->stream));
+  L->fc_nfacet = nfacet;
+  L->fc_scale = 0.0;
+  return rc;
+}
+
+// beta_F of every facet and the weight of the Burman part of operator values assembled on the host (alfi_level_update_values)
+int alfi_level_set_facet_beta(alfi_level* L, const double* beta_host, double scale) {
+  alfi_ctx* ctx = L->ctx;
+  if (!L->fc_beta) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_level_set_facet_beta before alfi_patches_set_facet_correction");
+  if (!beta_host) return alfi_set_error(ctx, ALFI_E_ARG, "NULL argument");
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ALFI_HIP_CHECK(ctx, hipMemcpyAsync(L->fc_beta, beta_host, sizeof(double) * (size_t)std::max<int64_t>(L->fc_nfacet, 1),
+                                     hipMemcpyHostToDevice, ctx->stream));
+  ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  L->fc_scale = scale;
+  L->factored = false;
   return 0;
 }
 

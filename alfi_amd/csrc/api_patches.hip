@@ -9,6 +9,8 @@ int alfi_patches_set(alfi_level* L, int64_t npatch, const int64_t* pptr, const i
   if (npatch < 0 || (npatch > 0 && (!pptr || !pdofs))) return alfi_set_error(ctx, ALFI_E_ARG, "NULL patch arrays");
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  dev_free(L->fc_ptr); dev_free(L->fc_col); dev_free(L->fc_fac); dev_free(L->fc_s);
+  L->fc_ptr = nullptr; L->fc_col = nullptr; L->fc_fac = nullptr; L->fc_s = nullptr;
   dev_free(L->patch_ptr);
   dev_free(L->patch_dofs);
   dev_free(L->inv_ptr);
@@ -556,12 +558,15 @@ int alfi_patches_factor(alfi_level* L) {
     ALFI_CHECK(dev_alloc(ctx, &L->inv, L->inv_doubles));
     L->inv_shrunk = false;
   }
+  if (L->cond && L->fc_ptr && L->fc_scale != 0.0)
+    return alfi_set_error(ctx, ALFI_E_STATE, "condensed patch factors on a Burman level (the facet rule couples macro interiors)");
   if (L->cond) {
     ALFI_CHECK(launch_cond_factor(L));            // condensed factors: group inverses + Schur complements
   } else if (L->max_np > SMALL_PATCH_MAX) {
     ALFI_CHECK(launch_big_factor(L));             // macro-star sized patches: blocked Gauss-Jordan on the matrix cores
   } else {
     ALFI_CHECK(launch_patch_gather_dense(L));
+    if (L->fc_ptr && L->fc_scale != 0.0) ALFI_CHECK(launch_patch_facet_correct(L, 0, L->npatch, L->inv_ptr, L->inv, 0));
     ALFI_CHECK(launch_patch_invert(L));
   }
   ALFI_CHECK(build_patch_il(L));                  // small-patch levels: the wave-contiguous copy the apply streams

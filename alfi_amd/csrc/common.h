@@ -128,6 +128,8 @@ bool alfi_test_large_paths();
 int alfi_prof_begin(alfi_ctx* ctx, int kind);
 int alfi_prof_end(alfi_ctx* ctx, int token);
 
+constexpr int BURMAN_MAXQ = 32;        // points of a facet rule the Burman kernels take (3-D P3: 25 for the nonlinear rule)
+constexpr int BURMAN_MAXN = 20;        // nodes per cell the Burman kernels take ([P3]^3)
 constexpr int SMALL_PATCH_MAX = 160;   // register-resident inversion / one wave per patch up to here (kernels_patch.hip)
 constexpr int PATCH_MAX = 4096;        // blocked MFMA inversion / one workgroup per patch beyond (kernels_bigpatch.hip)
 
@@ -340,6 +342,27 @@ struct AssemblyDev {
   int nq8 = 0;                   // nq rounded up to a multiple of eight (zero-weight copies of point 0): two k-steps of the MFMA per chunk
   double* wq8 = nullptr;         // (nq8)
   double* qtab = nullptr;        // (nq8, nloc, 1 + (d+1) + (d+1)(d+2)/2): phi | dphi | upper triangle of d2phi per (point, node)
+  // facet-coupled levels (alfi_level_set_facet_blocks before alfi_level_set_assembly): blocks may have no contributing cell,
+  // so the Dirichlet kernels take every block's (row node, column node) from here instead of its first contributor
+  int32_t* brc = nullptr;        // (nnzb, 2) or NULL
+  // Burman interior-penalty term (alfi_level_set_burman; tables of alfi_amd/burman.py)
+  bool burman_ready = false;
+  int64_t nfacet = 0;
+  int bnu = 0, bnqs = 0, bnqn = 0;
+  int32_t* funion = nullptr;     // (nfacet, bnu) K+'s nodes, then K-'s nodes off the facet
+  int32_t* fcfg = nullptr;       // (nfacet) configuration of K+
+  double* fJ = nullptr;          // (nfacet, bnqs, bnu) jumps of the normal derivatives at the exact rule's points
+  double* farea = nullptr;       // (nfacet) |F|
+  double* fcoef = nullptr;       // (nfacet) 0.5 avg(h)^2
+  double* fws = nullptr;         // (bnqs) exact rule, weights summing to 1
+  double* fwn = nullptr;         // (bnqn) nonlinear rule
+  double* fphin = nullptr;       // (ncfg, bnqn, nloc) K+'s basis at the nonlinear rule's points, zero off the facet
+  int64_t* fbptr = nullptr;      // (nnzb + 1) facet contributors of every block
+  int32_t* fbfac = nullptr;      // facet
+  uint16_t* fbab = nullptr;      // a * bnu + b
+  int64_t* fnptr = nullptr;      // (nodes + 1) facet contributors of every node
+  int32_t* fnfac = nullptr;
+  uint16_t* fna = nullptr;
 };
 
 struct alfi_level {
@@ -359,6 +382,7 @@ struct alfi_level {
   int64_t npatch_int = 0;    // leading patches without ghost dofs
   bool distributed = false;  // smoother / SpMV exchange halos and all-reduce
   bool has_halo = false;
+  bool facet_blocks = false; // alfi_level_set_facet_blocks: blocks without a contributing cell are allowed (Burman levels)
   int64_t halo_nsend = 0, halo_nghost = 0;  // nodes
   int32_t* halo_send_nodes = nullptr;       // (nsend) owned nodes, grouped by destination
   double *halo_sendbuf = nullptr, *halo_recvbuf = nullptr;  // caller-owned unless own_halo_bufs
@@ -384,6 +408,17 @@ struct alfi_level {
   int64_t npatch = 0, sum_n = 0, sum_n2 = 0, inv_doubles = 0;
   int max_np = 0;
   int64_t* patch_ptr = nullptr;   // (npatch+1) offsets into patch_dofs / staging buffer
+  // PCPATCH's interior-facet rule on a Burman level (alfi_patches_set_facet_correction): per patch-local row node (patches of
+  // whole nodes, rows numbered patch_ptr[p] / bs + i), the entries (local column node, facet, s) of the K-side facet terms
+  // the patch matrix must NOT hold; the patch matrix is A[P, P] - fc_scale * beta_f * s * I_bs for every entry
+  int64_t* fc_ptr = nullptr;      // (total patch nodes + 1)
+  int32_t* fc_col = nullptr;
+  int32_t* fc_fac = nullptr;
+  double* fc_s = nullptr;
+  double* fc_beta = nullptr;      // (nfacet) beta_F of the state of the last refresh (alfi_level_assemble_burman / _burman, or
+                                  // alfi_level_set_facet_beta after host assembly)
+  int64_t fc_nfacet = 0;
+  double fc_scale = 0.0;          // adv * weight of the Burman part of the current operator values (0: none)
   int32_t* patch_dofs = nullptr;  // (sum_n)
   int64_t* inv_ptr = nullptr;     // (npatch+1) offsets (doubles) into inv
   int64_t* stage_ptr = nullptr;   // (npatch+1) offsets into stage (ld_p slots per patch, so 16-byte aligned)
@@ -627,6 +662,10 @@ int launch_operator_refresh(alfi_level* lvl, double nu, double gamma, double adv
                             bool with_supg, double weight, double magic, bool accumulate, bool apply_bc, double* out_vals);
 int launch_element_mult(alfi_level* lvl, double nu, double gamma, double adv, const double* d_state, const double* dx, double* dy);
 int launch_supg_residual(alfi_level* lvl, double nu, double weight, double magic, const double* d_state, double* d_F);
+int launch_burman(alfi_level* lvl, double weight, const double* d_state, bool add_to_operator, double* d_F);
+// subtract the facet terms PCPATCH leaves out from nb dense patch matrices (row-major, leading dimension: (n + 1) & ~1 when
+// big == 0, n rounded up to BIG_NB otherwise) of the patches p0 .. p0 + nb at dst + mat_ptr[i]
+int launch_patch_facet_correct(alfi_level* lvl, int64_t p0, int64_t nb, const int64_t* mat_ptr, double* dst, int big);
 bool element_kernel_exists(int d, int nloc);
 int launch_vals_from_lanes(alfi_ctx* ctx, const DevBSR& A, double* d_out);
 int launch_probe_fill(alfi_ctx* ctx, double* e, int64_t n);                                    // the +-1 probe vector of the coarse solvers

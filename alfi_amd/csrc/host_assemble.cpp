@@ -603,4 +603,100 @@ int alfi_host_supg(int64_t ncell, int nloc, int d, const int32_t* cell_nodes, co
   return err ? -2 : 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Burman interior-penalty stabilisation of the Scott-Vogelius pair (alfi/stabilisation.py:139-162, alfi/solver.py:226-234;
+// alfi_amd/burman.py states the form and its linearisation).  Per interior facet f (tables of burman.FacetTable):
+//   union (nf, nu): K+'s nodes, then K-'s nodes off F;  J (nf, nqs, nu): jumps of the normal derivatives at the points of the
+//   exact rule (weights ws, summing to 1);  area, coef (nf): |F| and 0.5 avg(h)^2;  cfg (nf): K+'s configuration, phin
+//   (ncfg, nqn, nloc): K+'s basis at the nonlinear rule's points (weights wn), zero off F.
+// Pass 1 (a facet each): beta = sum_q wn u.u-root, m[b][j] = sum_q wn phi_b u_j / root, jq[q][i] = jump of d_n u_i at point q.
+// Pass 2 (a BSR block each, vals may be NULL): the contributors (facet, a * nu + b) of the block in list order,
+//   block += weight coef (beta S_ab I + g_a (x) m_b),  S_ab = |F| sum_q ws J_qa J_qb,  g_a = |F| sum_q ws J_qa jq_q.
+// beta_out (nf, may be NULL): beta_F of every facet.
+// Pass 3 (a node each, F may be NULL): the contributors (facet, a) of the node, F[node] += weight coef beta g_a.
+// Every entry is summed by one thread in a fixed order: the result does not depend on the number of threads.
+// ---------------------------------------------------------------------------------------------------------------------
+int alfi_host_burman(int64_t nf, int nu, int nloc, int d, int nqs, int nqn, const int32_t* unodes, const int32_t* cfg,
+                     const double* J, const double* area, const double* coef, const double* ws, const double* wn,
+                     const double* phin, const double* U, double weight, int64_t nnzb, const int64_t* bptr,
+                     const int32_t* bfac, const uint16_t* bab, double* vals, int64_t nnode, const int64_t* nptr,
+                     const int32_t* nfac, const uint16_t* na, double* F, double* beta_out) {
+  if (d < 2 || d > 3 || nqs > 64 || nqn > 64 || nloc > 64) return -1;
+  const int rec = 1 + nqs * d + nloc * d;      // beta | jq (nqs, d) | m (nloc, d)
+  std::vector<double> R((size_t)std::max<int64_t>(nf, 1) * rec);
+#pragma omp parallel for schedule(static)
+  for (int64_t f = 0; f < nf; ++f) {
+    const int32_t* un = unodes + f * nu;
+    const double* ph = phin + (size_t)cfg[f] * nqn * nloc;
+    double* r = R.data() + (size_t)f * rec;
+    double beta = 0.0;
+    double* m = r + 1 + nqs * d;
+    for (int t = 0; t < nloc * d; ++t) m[t] = 0.0;
+    for (int q = 0; q < nqn; ++q) {
+      double u[3] = {0.0, 0.0, 0.0};
+      for (int a = 0; a < nloc; ++a)
+        for (int i = 0; i < d; ++i) u[i] += ph[q * nloc + a] * U[(int64_t)un[a] * d + i];
+      double uu = 1e-10;
+      for (int i = 0; i < d; ++i) uu += u[i] * u[i];
+      const double root = std::sqrt(uu);
+      beta += wn[q] * root;
+      for (int a = 0; a < nloc; ++a)
+        for (int i = 0; i < d; ++i) m[a * d + i] += wn[q] * ph[q * nloc + a] * u[i] / root;
+    }
+    r[0] = beta;
+    if (beta_out) beta_out[f] = beta;
+    const double* Jf = J + (size_t)f * nqs * nu;
+    for (int q = 0; q < nqs; ++q)
+      for (int i = 0; i < d; ++i) {
+        double t = 0.0;
+        for (int a = 0; a < nu; ++a) t += Jf[q * nu + a] * U[(int64_t)un[a] * d + i];
+        r[1 + q * d + i] = t;
+      }
+  }
+  if (vals) {
+#pragma omp parallel for schedule(dynamic, 1024)
+    for (int64_t k = 0; k < nnzb; ++k) {
+      double acc[9] = {0.0};
+      for (int64_t p = bptr[k]; p < bptr[k + 1]; ++p) {
+        const int64_t f = bfac[p];
+        const int a = bab[p] / nu, b = bab[p] % nu;
+        const double* Jf = J + (size_t)f * nqs * nu;
+        const double* r = R.data() + (size_t)f * rec;
+        double s = 0.0, g[3] = {0.0, 0.0, 0.0};
+        for (int q = 0; q < nqs; ++q) {
+          const double wa = ws[q] * Jf[q * nu + a];
+          s += wa * Jf[q * nu + b];
+          for (int i = 0; i < d; ++i) g[i] += wa * r[1 + q * d + i];
+        }
+        const double c = weight * coef[f], A = area[f];
+        for (int i = 0; i < d; ++i) {
+          acc[i * d + i] += c * r[0] * A * s;
+          if (b < nloc)
+            for (int j = 0; j < d; ++j) acc[i * d + j] += c * A * g[i] * r[1 + nqs * d + b * d + j];
+        }
+      }
+      for (int t = 0; t < d * d; ++t) vals[k * d * d + t] += acc[t];
+    }
+  }
+  if (F) {
+#pragma omp parallel for schedule(dynamic, 1024)
+    for (int64_t n = 0; n < nnode; ++n) {
+      double acc[3] = {0.0, 0.0, 0.0};
+      for (int64_t p = nptr[n]; p < nptr[n + 1]; ++p) {
+        const int64_t f = nfac[p];
+        const int a = na[p];
+        const double* Jf = J + (size_t)f * nqs * nu;
+        const double* r = R.data() + (size_t)f * rec;
+        const double c = weight * coef[f] * r[0] * area[f];
+        for (int q = 0; q < nqs; ++q) {
+          const double wa = ws[q] * Jf[q * nu + a];
+          for (int i = 0; i < d; ++i) acc[i] += c * wa * r[1 + q * d + i];
+        }
+      }
+      for (int i = 0; i < d; ++i) F[n * d + i] += acc[i];
+    }
+  }
+  return 0;
+}
+
 }  // extern "C"

@@ -206,13 +206,20 @@ template <int D>
 __global__ __launch_bounds__(256) void bc_code_kernel(int64_t nnzb, int nloc, const int64_t* __restrict__ cptr,
                                                        const int32_t* __restrict__ ccell, const uint16_t* __restrict__ cba,
                                                        const int32_t* __restrict__ cell_nodes, const uint8_t* __restrict__ bc_mask,
-                                                       uint8_t* __restrict__ code) {
+                                                       uint8_t* __restrict__ code, const int32_t* __restrict__ brc) {
   const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (k >= nnzb) return;
-  const int64_t q0 = cptr[k];
-  const int32_t cell = ccell[q0];
-  const int ba = cba[q0];
-  const int64_t rnode = cell_nodes[(int64_t)cell * nloc + ba % nloc], cnode = cell_nodes[(int64_t)cell * nloc + ba / nloc];
+  int64_t rnode, cnode;
+  if (brc) {                       // facet-coupled level: a block may have no contributing cell
+    rnode = brc[2 * k];
+    cnode = brc[2 * k + 1];
+  } else {
+    const int64_t q0 = cptr[k];
+    const int32_t cell = ccell[q0];
+    const int ba = cba[q0];
+    rnode = cell_nodes[(int64_t)cell * nloc + ba % nloc];
+    cnode = cell_nodes[(int64_t)cell * nloc + ba / nloc];
+  }
   unsigned c = rnode == cnode ? 64u : 0u;
 #pragma unroll
   for (int x = 0; x < D; ++x) {
@@ -684,14 +691,21 @@ template <int D>
 __global__ __launch_bounds__(256) void apply_bc_kernel(int64_t nnzb, int nloc, const int64_t* __restrict__ cptr,
                                                         const int32_t* __restrict__ ccell, const uint16_t* __restrict__ cba,
                                                         const int32_t* __restrict__ cell_nodes, const uint8_t* __restrict__ bc_mask,
-                                                        double* __restrict__ vals) {
+                                                        double* __restrict__ vals, const int32_t* __restrict__ brc) {
   constexpr int BB = D * D;
   const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (k >= nnzb) return;
-  const int64_t q0 = cptr[k];
-  const int32_t cell = ccell[q0];
-  const int ba = cba[q0];
-  const int64_t rnode = cell_nodes[(int64_t)cell * nloc + ba % nloc], cnode = cell_nodes[(int64_t)cell * nloc + ba / nloc];
+  int64_t rnode, cnode;
+  if (brc) {
+    rnode = brc[2 * k];
+    cnode = brc[2 * k + 1];
+  } else {
+    const int64_t q0 = cptr[k];
+    const int32_t cell = ccell[q0];
+    const int ba = cba[q0];
+    rnode = cell_nodes[(int64_t)cell * nloc + ba % nloc];
+    cnode = cell_nodes[(int64_t)cell * nloc + ba / nloc];
+  }
 #pragma unroll
   for (int cc = 0; cc < D; ++cc)
 #pragma unroll
@@ -707,6 +721,168 @@ __global__ void vals_from_lanes_kernel(const double* __restrict__ src, double* _
     dst[e] = src[bsr_val_index(1, e / bb, (int)(e % bb), bb)];
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Burman interior-penalty stabilisation (alfi/stabilisation.py:139-162, alfi/solver.py:226-234; the form, its Newton
+// linearisation and the tables: alfi_amd/burman.py; the host twin: csrc/host_assemble.cpp:alfi_host_burman, same arithmetic).
+//   burman_facet_kernel (a lane per facet): the compact record beta | jq (nqs, d) | m (nloc, d) -- O(nodes d) per facet --;
+//   burman_block_kernel (a lane per BSR block): block += sum over its facet contributors (f, a, b), in list order, of
+//     weight coef_f (beta S_ab I + g_a (x) m_b), S_ab and g_a formed from the jump table on the fly (no atomics);
+//   burman_node_kernel (a lane per node): F[node] += sum over (f, a) of weight coef_f beta g_a.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int D>
+__global__ __launch_bounds__(64) void burman_facet_kernel(int64_t nf, int nu, int nloc, int nqs, int nqn,
+                                                          const int32_t* __restrict__ un_all, const int32_t* __restrict__ cfg,
+                                                          const double* __restrict__ J, const double* __restrict__ wn,
+                                                          const double* __restrict__ phin, const double* __restrict__ U,
+                                                          double* __restrict__ R, double* __restrict__ beta_out) {
+  const int64_t f = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (f >= nf) return;
+  const int rec = 1 + nqs * D + nloc * D;
+  const int32_t* un = un_all + f * nu;
+  const double* ph = phin + (int64_t)cfg[f] * nqn * nloc;
+  double* r = R + f * rec;
+  double* m = r + 1 + nqs * D;
+  double uk[BURMAN_MAXN][D];
+  for (int a = 0; a < nloc; ++a)
+#pragma unroll
+    for (int i = 0; i < D; ++i) uk[a][i] = U[(int64_t)un[a] * D + i];
+  double mk[BURMAN_MAXN][D];
+  for (int a = 0; a < nloc; ++a)
+#pragma unroll
+    for (int i = 0; i < D; ++i) mk[a][i] = 0.0;
+  double beta = 0.0;
+  for (int q = 0; q < nqn; ++q) {
+    double u[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) u[i] = 0.0;
+    for (int a = 0; a < nloc; ++a)
+#pragma unroll
+      for (int i = 0; i < D; ++i) u[i] += ph[q * nloc + a] * uk[a][i];
+    double uu = 1e-10;
+#pragma unroll
+    for (int i = 0; i < D; ++i) uu += u[i] * u[i];
+    const double root = sqrt(uu);
+    beta += wn[q] * root;
+    for (int a = 0; a < nloc; ++a)
+#pragma unroll
+      for (int i = 0; i < D; ++i) mk[a][i] += wn[q] * ph[q * nloc + a] * u[i] / root;
+  }
+  r[0] = beta;
+  if (beta_out) beta_out[f] = beta;
+  for (int a = 0; a < nloc; ++a)
+#pragma unroll
+    for (int i = 0; i < D; ++i) m[a * D + i] = mk[a][i];
+  const double* Jf = J + f * nqs * nu;
+  for (int q = 0; q < nqs; ++q) {
+    double t[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) t[i] = 0.0;
+    for (int a = 0; a < nu; ++a) {
+      const double ja = Jf[q * nu + a];
+      const int64_t node = un[a];
+#pragma unroll
+      for (int i = 0; i < D; ++i) t[i] += ja * U[node * D + i];
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i) r[1 + q * D + i] = t[i];
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void burman_block_kernel(int64_t nnzb, int nu, int nloc, int nqs, const int64_t* __restrict__ bptr,
+                                                           const int32_t* __restrict__ bfac, const uint16_t* __restrict__ bab,
+                                                           const double* __restrict__ J, const double* __restrict__ ws,
+                                                           const double* __restrict__ area, const double* __restrict__ coef,
+                                                           const double* __restrict__ R, double weight, double* __restrict__ vals) {
+  constexpr int BB = D * D;
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= nnzb) return;
+  const int64_t p0 = bptr[k], p1 = bptr[k + 1];
+  if (p0 == p1) return;
+  const int rec = 1 + nqs * D + nloc * D;
+  double acc[BB];
+#pragma unroll
+  for (int t = 0; t < BB; ++t) acc[t] = 0.0;
+  for (int64_t p = p0; p < p1; ++p) {
+    const int64_t f = bfac[p];
+    const int a = bab[p] / nu, b = bab[p] % nu;
+    const double* Jf = J + f * nqs * nu;
+    const double* r = R + f * rec;
+    double s = 0.0, g[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) g[i] = 0.0;
+    for (int q = 0; q < nqs; ++q) {
+      const double wa = ws[q] * Jf[q * nu + a];
+      s += wa * Jf[q * nu + b];
+#pragma unroll
+      for (int i = 0; i < D; ++i) g[i] += wa * r[1 + q * D + i];
+    }
+    const double c = weight * coef[f], A = area[f];
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      acc[i * D + i] += c * r[0] * A * s;
+      if (b < nloc)
+#pragma unroll
+        for (int j = 0; j < D; ++j) acc[i * D + j] += c * A * g[i] * r[1 + nqs * D + b * D + j];
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < BB; ++t) vals[bsr_val_index(1, k, t, BB)] += acc[t];
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void burman_node_kernel(int64_t nnode, int nu, int nloc, int nqs, const int64_t* __restrict__ nptr,
+                                                          const int32_t* __restrict__ nfac, const uint16_t* __restrict__ na,
+                                                          const double* __restrict__ J, const double* __restrict__ ws,
+                                                          const double* __restrict__ area, const double* __restrict__ coef,
+                                                          const double* __restrict__ R, double weight, double* __restrict__ F) {
+  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (n >= nnode) return;
+  const int rec = 1 + nqs * D + nloc * D;
+  double acc[D];
+#pragma unroll
+  for (int i = 0; i < D; ++i) acc[i] = 0.0;
+  for (int64_t p = nptr[n]; p < nptr[n + 1]; ++p) {
+    const int64_t f = nfac[p];
+    const int a = na[p];
+    const double* Jf = J + f * nqs * nu;
+    const double* r = R + f * rec;
+    const double c = weight * coef[f] * r[0] * area[f];
+    for (int q = 0; q < nqs; ++q) {
+      const double wa = ws[q] * Jf[q * nu + a];
+#pragma unroll
+      for (int i = 0; i < D; ++i) acc[i] += c * wa * r[1 + q * D + i];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < D; ++i) F[n * D + i] += acc[i];
+}
+
+// PCPATCH's facet rule (alfi_patches_set_facet_correction): a thread per patch-local row node walks its entries in list order
+// and subtracts scale * beta_f * s from the d diagonal entries of the (row node, column node) block of the dense patch matrix
+template <int D>
+__global__ __launch_bounds__(64) void patch_facet_correct_kernel(int64_t p0, const int64_t* __restrict__ patch_ptr,
+                                                                 const int64_t* __restrict__ mat_ptr, double* __restrict__ dst,
+                                                                 int big, const int64_t* __restrict__ fc_ptr,
+                                                                 const int32_t* __restrict__ fc_col, const int32_t* __restrict__ fc_fac,
+                                                                 const double* __restrict__ fc_s, const double* __restrict__ beta,
+                                                                 double scale) {
+  const int64_t p = p0 + blockIdx.y;
+  const int64_t off = patch_ptr[p];
+  const int n = (int)(patch_ptr[p + 1] - off);
+  const int ld = big ? (n + big - 1) / big * big : ((n + 1) & ~1);
+  double* S = dst + mat_ptr[blockIdx.y];
+  for (int i = blockIdx.x * 64 + threadIdx.x; i < n / D; i += gridDim.x * 64) {
+    const int64_t rn = off / D + i;
+    for (int64_t q = fc_ptr[rn]; q < fc_ptr[rn + 1]; ++q) {
+      const double v = scale * beta[fc_fac[q]] * fc_s[q];
+      const int j = fc_col[q];
+#pragma unroll
+      for (int c = 0; c < D; ++c) S[(int64_t)(i * D + c) * ld + j * D + c] -= v;
+    }
+  }
+}
 
 }  // namespace
 
@@ -748,9 +924,9 @@ static int ensure_bc_code(alfi_level* L) {
   dim3 grid((unsigned)((nnzb + 255) / 256)), block(256);
   const uint8_t* mask = S.bc_all ? S.bc_all : L->bc_mask;
   if (L->bs == 2)
-    hipLaunchKernelGGL(bc_code_kernel<2>, grid, block, 0, ctx->stream, nnzb, S.nloc, S.cptr, S.ccell, S.cba, S.cell_nodes, mask, S.bc_code);
+    hipLaunchKernelGGL(bc_code_kernel<2>, grid, block, 0, ctx->stream, nnzb, S.nloc, S.cptr, S.ccell, S.cba, S.cell_nodes, mask, S.bc_code, S.brc);
   else
-    hipLaunchKernelGGL(bc_code_kernel<3>, grid, block, 0, ctx->stream, nnzb, S.nloc, S.cptr, S.ccell, S.cba, S.cell_nodes, mask, S.bc_code);
+    hipLaunchKernelGGL(bc_code_kernel<3>, grid, block, 0, ctx->stream, nnzb, S.nloc, S.cptr, S.ccell, S.cba, S.cell_nodes, mask, S.bc_code, S.brc);
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   return 0;
 }
@@ -871,15 +1047,78 @@ int launch_supg_residual(alfi_level* L, double nu, double weight, double magic, 
   return gather_cell_vectors(L, Fe, 1, d_F);
 }
 
+// vals += the linearised Burman term (add_to_operator) and / or d_F += its residual contribution, about d_state
+int launch_burman(alfi_level* L, double weight, const double* d_state, bool add_to_operator, double* d_F) {
+  alfi_ctx* ctx = L->ctx;
+  AssemblyDev& S = L->asmb;
+  const int d = L->bs;
+  const int64_t rec = 1 + (int64_t)S.bnqs * d + (int64_t)S.nloc * d;
+  ALFI_CHECK(ensure_scratch(ctx, sizeof(double) * (size_t)(std::max<int64_t>(S.nfacet, 1) * rec)));
+  double* R = (double*)ctx->asm_scratch;
+  // (the record buffer is nfacet * rec doubles in one piece, outside the set_assembly_scratch budget: 0.1-0.2 GB at config 5)
+  double* beta_out = (add_to_operator && L->fc_beta && L->fc_nfacet == S.nfacet) ? L->fc_beta : nullptr;
+  if (S.nfacet > 0) {
+    dim3 grid((unsigned)((S.nfacet + 63) / 64)), block(64);
+    if (d == 2)
+      hipLaunchKernelGGL(burman_facet_kernel<2>, grid, block, 0, ctx->stream, S.nfacet, S.bnu, S.nloc, S.bnqs, S.bnqn, S.funion, S.fcfg,
+                         S.fJ, S.fwn, S.fphin, d_state, R, beta_out);
+    else
+      hipLaunchKernelGGL(burman_facet_kernel<3>, grid, block, 0, ctx->stream, S.nfacet, S.bnu, S.nloc, S.bnqs, S.bnqn, S.funion, S.fcfg,
+                         S.fJ, S.fwn, S.fphin, d_state, R, beta_out);
+    ALFI_HIP_CHECK(ctx, hipGetLastError());
+  }
+  if (add_to_operator) {
+    const int64_t nnzb = L->A.nnzb;
+    dim3 grid((unsigned)((nnzb + 255) / 256)), block(256);
+    if (d == 2)
+      hipLaunchKernelGGL(burman_block_kernel<2>, grid, block, 0, ctx->stream, nnzb, S.bnu, S.nloc, S.bnqs, S.fbptr, S.fbfac, S.fbab, S.fJ,
+                         S.fws, S.farea, S.fcoef, (const double*)R, weight, L->A.vals);
+    else
+      hipLaunchKernelGGL(burman_block_kernel<3>, grid, block, 0, ctx->stream, nnzb, S.bnu, S.nloc, S.bnqs, S.fbptr, S.fbfac, S.fbab, S.fJ,
+                         S.fws, S.farea, S.fcoef, (const double*)R, weight, L->A.vals);
+    ALFI_HIP_CHECK(ctx, hipGetLastError());
+  }
+  if (d_F) {
+    const int64_t nnode = L->A.nbrows;
+    dim3 grid((unsigned)((nnode + 255) / 256)), block(256);
+    if (d == 2)
+      hipLaunchKernelGGL(burman_node_kernel<2>, grid, block, 0, ctx->stream, nnode, S.bnu, S.nloc, S.bnqs, S.fnptr, S.fnfac, S.fna, S.fJ,
+                         S.fws, S.farea, S.fcoef, (const double*)R, weight, d_F);
+    else
+      hipLaunchKernelGGL(burman_node_kernel<3>, grid, block, 0, ctx->stream, nnode, S.bnu, S.nloc, S.bnqs, S.fnptr, S.fnfac, S.fna, S.fJ,
+                         S.fws, S.farea, S.fcoef, (const double*)R, weight, d_F);
+    ALFI_HIP_CHECK(ctx, hipGetLastError());
+  }
+  return 0;
+}
+
+int launch_patch_facet_correct(alfi_level* L, int64_t p0, int64_t nb, const int64_t* mat_ptr, double* dst, int big) {
+  alfi_ctx* ctx = L->ctx;
+  if (nb <= 0) return 0;
+  const int64_t nn = (L->max_np / L->bs + 63) / 64;
+  for (int64_t b0 = 0; b0 < nb; b0 += 65535) {        // (grid y <= 65535)
+    const int64_t nbb = std::min<int64_t>(65535, nb - b0);
+    dim3 grid((unsigned)std::max<int64_t>(nn, 1), (unsigned)nbb), block(64);
+    if (L->bs == 2)
+      hipLaunchKernelGGL(patch_facet_correct_kernel<2>, grid, block, 0, ctx->stream, p0 + b0, L->patch_ptr, mat_ptr + b0, dst, big,
+                         L->fc_ptr, L->fc_col, L->fc_fac, L->fc_s, L->fc_beta, L->fc_scale);
+    else
+      hipLaunchKernelGGL(patch_facet_correct_kernel<3>, grid, block, 0, ctx->stream, p0 + b0, L->patch_ptr, mat_ptr + b0, dst, big,
+                         L->fc_ptr, L->fc_col, L->fc_fac, L->fc_s, L->fc_beta, L->fc_scale);
+    ALFI_HIP_CHECK(ctx, hipGetLastError());
+  }
+  return 0;
+}
+
 int launch_apply_bc(alfi_level* L) {
   alfi_ctx* ctx = L->ctx;
   const AssemblyDev& S = L->asmb;
   const int64_t nnzb = L->A.nnzb;
   dim3 grid((unsigned)((nnzb + 255) / 256)), block(256);
   if (L->bs == 2)
-    hipLaunchKernelGGL(apply_bc_kernel<2>, grid, block, 0, ctx->stream, nnzb, S.nloc, S.cptr, S.ccell, S.cba, S.cell_nodes, S.bc_all ? S.bc_all : L->bc_mask, L->A.vals);
+    hipLaunchKernelGGL(apply_bc_kernel<2>, grid, block, 0, ctx->stream, nnzb, S.nloc, S.cptr, S.ccell, S.cba, S.cell_nodes, S.bc_all ? S.bc_all : L->bc_mask, L->A.vals, S.brc);
   else
-    hipLaunchKernelGGL(apply_bc_kernel<3>, grid, block, 0, ctx->stream, nnzb, S.nloc, S.cptr, S.ccell, S.cba, S.cell_nodes, S.bc_all ? S.bc_all : L->bc_mask, L->A.vals);
+    hipLaunchKernelGGL(apply_bc_kernel<3>, grid, block, 0, ctx->stream, nnzb, S.nloc, S.cptr, S.ccell, S.cba, S.cell_nodes, S.bc_all ? S.bc_all : L->bc_mask, L->A.vals, S.brc);
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   return 0;
 }

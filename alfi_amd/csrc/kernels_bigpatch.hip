@@ -1541,12 +1541,15 @@ struct BigSource {
     } else if (T) {
       hipLaunchKernelGGL(big_dense_fill_kernel, dim3(64, (unsigned)nb), block, 0, ctx->stream, p0, T->m, T->KII, T->DII,
                          T->nu, T->gamma, d_scr_ptr, dst);
-    } else if (L->bs == 2) {
-      hipLaunchKernelGGL(big_gather_kernel<2>, dim3(16, (unsigned)nb), block, 0, ctx->stream, p0, L->A.rowptr, L->A.colidx,
-                         L->A.vals, L->A.flat, L->patch_ptr, L->patch_dofs, d_scr_ptr, dst);
     } else {
-      hipLaunchKernelGGL(big_gather_kernel<3>, dim3(16, (unsigned)nb), block, 0, ctx->stream, p0, L->A.rowptr, L->A.colidx,
-                         L->A.vals, L->A.flat, L->patch_ptr, L->patch_dofs, d_scr_ptr, dst);
+      if (L->bs == 2)
+        hipLaunchKernelGGL(big_gather_kernel<2>, dim3(16, (unsigned)nb), block, 0, ctx->stream, p0, L->A.rowptr, L->A.colidx,
+                           L->A.vals, L->A.flat, L->patch_ptr, L->patch_dofs, d_scr_ptr, dst);
+      else
+        hipLaunchKernelGGL(big_gather_kernel<3>, dim3(16, (unsigned)nb), block, 0, ctx->stream, p0, L->A.rowptr, L->A.colidx,
+                           L->A.vals, L->A.flat, L->patch_ptr, L->patch_dofs, d_scr_ptr, dst);
+      // a Burman level: PCPATCH's facet rule (the K-side terms of the facets with one cell in the patch come out)
+      if (L->fc_ptr && L->fc_scale != 0.0) (void)launch_patch_facet_correct(L, p0, nb, d_scr_ptr, dst, BIG_NB);
     }
   }
 };

@@ -61,7 +61,10 @@ __global__ __launch_bounds__(256) void patch_check_kernel(const int32_t* __restr
                                                            const int64_t* __restrict__ stage_ptr,
                                                            const double* __restrict__ stage, double tol,
                                                            unsigned long long* __restrict__ worst_bits,
-                                                           int32_t* __restrict__ flagged, int* __restrict__ nflag, int cap) {
+                                                           int32_t* __restrict__ flagged, int* __restrict__ nflag, int cap,
+                                                           const int64_t* __restrict__ fc_ptr, const int32_t* __restrict__ fc_col,
+                                                           const int32_t* __restrict__ fc_fac, const double* __restrict__ fc_s,
+                                                           const double* __restrict__ fc_beta, double fc_scale) {
   extern __shared__ unsigned char smem[];
   const int64_t p = blockIdx.x;
   const int64_t off = patch_ptr[p];
@@ -89,6 +92,11 @@ __global__ __launch_bounds__(256) void patch_check_kernel(const int32_t* __restr
       if (a >= 0) acc = __builtin_fma(vals[bsr_val_index(flat, lo + blk, rr * BS + cc, BS * BS)], y_s[a], acc);
     }
     acc = wave_sum_chk(acc);
+    if (fc_ptr) {              // a Burman level: the patch matrix is A[P, P] minus the facet terms PCPATCH leaves out
+      const int64_t rn = off / BS + r / BS;
+      for (int64_t q = fc_ptr[rn]; q < fc_ptr[rn + 1]; ++q)
+        acc -= fc_scale * fc_beta[fc_fac[q]] * fc_s[q] * y_s[fc_col[q] * BS + r % BS];
+    }
     const double res = fabs(acc - probe_entry(gr));
     if (!(res <= wmax)) wmax = (res == res) ? res : INFINITY;      // NaN -> +inf
   }
@@ -257,6 +265,7 @@ __global__ __launch_bounds__(256) void patch_repair_kernel(const int32_t* __rest
 static int launch_check(alfi_level* L, double tol) {
   alfi_ctx* ctx = L->ctx;
   if (L->npatch == 0) return 0;
+  const bool fc = L->fc_ptr && L->fc_scale != 0.0;
   double* e = nullptr;
   ALFI_HIP_CHECK(ctx, hipMalloc((void**)&e, sizeof(double) * (size_t)std::max<int64_t>(L->n, 1)));
   hipLaunchKernelGGL(probe_fill_kernel, dim3(1024), dim3(256), 0, ctx->stream, e, L->n);
@@ -268,10 +277,12 @@ static int launch_check(alfi_level* L, double tol) {
     dim3 grid((unsigned)L->npatch), block(256);
     if (L->bs == 2)
       hipLaunchKernelGGL(patch_check_kernel<2>, grid, block, lds, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals, L->A.flat,
-                         L->patch_ptr, L->patch_dofs, L->stage_ptr, L->stage, tol, worst, L->chk_list, nflag, L->chk_cap);
+                         L->patch_ptr, L->patch_dofs, L->stage_ptr, L->stage, tol, worst, L->chk_list, nflag, L->chk_cap,
+                         fc ? L->fc_ptr : nullptr, L->fc_col, L->fc_fac, L->fc_s, L->fc_beta, L->fc_scale);
     else
       hipLaunchKernelGGL(patch_check_kernel<3>, grid, block, lds, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals, L->A.flat,
-                         L->patch_ptr, L->patch_dofs, L->stage_ptr, L->stage, tol, worst, L->chk_list, nflag, L->chk_cap);
+                         L->patch_ptr, L->patch_dofs, L->stage_ptr, L->stage, tol, worst, L->chk_list, nflag, L->chk_cap,
+                         fc ? L->fc_ptr : nullptr, L->fc_col, L->fc_fac, L->fc_s, L->fc_beta, L->fc_scale);
     if (hipGetLastError() != hipSuccess) rc = alfi_set_error(ctx, ALFI_E_HIP, "patch_check_kernel launch failed");
   }
   (void)hipStreamSynchronize(ctx->stream);
@@ -384,6 +395,9 @@ int patch_verify_and_repair(alfi_level* L, int unpivoted_status) {
                           (long long)L->npatch, worst);
   constexpr int REPAIR_MAX_NP = PATCH_MAX;     // (a 2000-dof patch takes ~0.5 s of one workgroup: a rare-path safety net)
   if (L->cond) return cond_repair(L, tol, nflag, worst);
+  if (L->fc_ptr && L->fc_scale != 0.0)
+    return alfi_set_error(ctx, ALFI_E_SINGULAR, "%d patch inverses of a Burman level fail the residual probe (worst %.3e): the "
+                          "pivoted repair does not apply the PCPATCH facet rule", nflag, worst);
   if (L->max_np > REPAIR_MAX_NP)
     return alfi_set_error(ctx, ALFI_E_SINGULAR, "%d patch inverses fail the residual probe (worst %.3e) and the pivoted "
                           "repair handles patches of at most %d dofs", nflag, worst, (int)REPAIR_MAX_NP);

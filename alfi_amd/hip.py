@@ -318,6 +318,50 @@ class Level(object):
     def apply_bc(self):
         self.ctx.check(self.ctx.lib.alfi_level_apply_bc(self.h))
 
+    def set_facet_blocks(self, on=True):
+        """The level's sparsity couples the nodes of cells that share a facet (alfi_level_set_facet_blocks; before
+        ``set_assembly``): blocks without a contributing cell are accepted."""
+        self.ctx.check(self.ctx.lib.alfi_level_set_facet_blocks(self.h, 1 if on else 0))
+
+    def set_burman(self, table, rowptr, colidx):
+        """Interior-facet tables and contributor lists of the Burman term (alfi_level_set_burman); ``table``:
+        burman.FacetTable of the level, rowptr / colidx: the level's (facet-coupled) sparsity."""
+        t = table
+        (bptr, bfac, bab), (nptr, nfac, na) = t.contributors(rowptr, colidx, len(rowptr) - 1)
+        f64 = [np.ascontiguousarray(a, dtype=np.float64) for a in (t.J, t.area, t.coef, t.ws, t.wn, t.phin)]
+        i32 = [np.ascontiguousarray(a, dtype=np.int32) for a in (t.union, t.cfg, bfac, nfac)]
+        i64 = [np.ascontiguousarray(a, dtype=np.int64) for a in (bptr, nptr)]
+        u16 = [np.ascontiguousarray(a, dtype=np.uint16) for a in (bab, na)]
+        self.ctx.check(self.ctx.lib.alfi_level_set_burman(
+            self.h, int(t.nf), int(t.nu), len(t.ws), len(t.wn), int(t.phin.shape[0]), _ptr(i32[0]), _ptr(i32[1]), _ptr(f64[0]),
+            _ptr(f64[1]), _ptr(f64[2]), _ptr(f64[3]), _ptr(f64[4]), _ptr(f64[5]), _ptr(i64[0]), _ptr(i32[2]), _ptr(u16[0]),
+            _ptr(i64[1]), _ptr(i32[3]), _ptr(u16[1])))
+
+    def burman(self, weight, state, add_to_operator=True, F=None):
+        """Burman terms about ``state`` on the device (alfi_level_burman): ``weight`` times the linearisation into the
+        operator and / or the residual contribution added to the device vector ``F``."""
+        self.ctx.check(self.ctx.lib.alfi_level_burman(self.h, float(weight), state.ptr, 1 if add_to_operator else 0,
+                                                      F.ptr if F is not None else None))
+
+    def set_patch_facet_correction(self, nfacet, ptr, col, fac, s):
+        """PCPATCH's facet rule on a Burman level (alfi_patches_set_facet_correction): burman.patch_facet_corrections."""
+        ptr = np.ascontiguousarray(ptr, dtype=np.int64)
+        col, fac = (np.ascontiguousarray(a, dtype=np.int32) for a in (col, fac))
+        s = np.ascontiguousarray(s, dtype=np.float64)
+        self.ctx.check(self.ctx.lib.alfi_patches_set_facet_correction(self.h, int(nfacet), len(ptr) - 1, _ptr(ptr), _ptr(col),
+                                                                      _ptr(fac), _ptr(s)))
+
+    def set_facet_beta(self, beta, scale):
+        """beta_F of every facet and adv * weight of host-assembled operator values (alfi_level_set_facet_beta)."""
+        beta = np.ascontiguousarray(beta, dtype=np.float64)
+        self.ctx.check(self.ctx.lib.alfi_level_set_facet_beta(self.h, _ptr(beta), float(scale)))
+
+    def assemble_burman(self, nu, gamma, adv, state, weight, apply_bc=True):
+        """The refresh of a Burman-stabilised run (alfi_level_assemble_burman): A = nu K + gamma D + adv N(state) + adv *
+        weight * the linearised Burman term, then the boundary conditions."""
+        self.ctx.check(self.ctx.lib.alfi_level_assemble_burman(self.h, float(nu), float(gamma), float(adv), state.ptr,
+                                                               float(weight), 1 if apply_bc else 0))
+
     def assemble(self, nu, gamma, adv, state=None, apply_bc=True):
         """A = nu K + gamma D + adv N(state) written into the level's operator on the device (alfi_level_assemble);
         ``state``: DeviceVec / RawVec with the level's nodal field.  The patches must be factored again afterwards."""

@@ -44,6 +44,8 @@ class HipNavierStokesSolver(object):
                  stabilisation_weight=None, supg_magic=9.0, device_assembly=None):
         """discretisation: "pkp0" ([P_k(+FB)]^d - P0 on the uniform hierarchy, ConstantPressureSolver solver.py:561-602) or
         "sv" ([P_k]^d - P_{k-1}^dg on the barycentric hierarchy with macro-star patches, ScottVogeliusSolver :604-662).
+        stabilisation_type: None / "none", "supg" (P0-pressure pairs) or "burman" (the Scott-Vogelius pair: interior-penalty
+        term of stabilisation.py:139-162 on facet-coupled levels, alfi_amd.burman; not on partitioned levels).
         device_assembly: refresh the level operators of every Newton step ON THE DEVICE (alfi_level_assemble: what
         PatchPC.update does inside PCPATCH, solver.py:320, 325) instead of rediscretising on the host and re-uploading;
         default: on (viscous, grad-div, advection and SUPG terms), unless ALFI_DEVICE_ASSEMBLY=0."""
@@ -60,11 +62,22 @@ class HipNavierStokesSolver(object):
         # "shakib", the default), default weight 0.1 in 3-D and 1 in 2-D (stabilisation.py:52-54), supg_magic 9
         if stabilisation_type in ("none", None):
             stabilisation_type = None
-        if stabilisation_type not in (None, "supg"):
-            raise NotImplementedError("stabilisation type %r (built: supg for the P0-pressure pairs)" % stabilisation_type)
+        if stabilisation_type not in (None, "supg", "burman"):
+            raise NotImplementedError("stabilisation type %r (built: supg for the P0-pressure pairs, burman for the "
+                                      "Scott-Vogelius pair)" % stabilisation_type)
         if stabilisation_type == "supg" and self.sv:
             raise NotImplementedError("supg with a discontinuous P_k pressure couples grad p into the momentum block")
+        if stabilisation_type == "burman" and not self.sv:
+            raise NotImplementedError("burman is built for the Scott-Vogelius pair (discretisation='sv') only")
+        if stabilisation_type == "burman" and self._partitioned():
+            raise NotImplementedError("burman on partitioned levels: the ghost layer would need the facet neighbours")
         self.supg = stabilisation_type == "supg"
+        # Burman interior penalty (solver.py:226-228, stabilisation.py:139-162): weight 3e-3 unless given (the reference's
+        # SV run lines pass 5e-3)
+        self.burman = stabilisation_type == "burman"
+        if self.burman:
+            from .burman import DEFAULT_WEIGHT
+            self.burman_weight = float(stabilisation_weight) if stabilisation_weight is not None else DEFAULT_WEIGHT
         self.supg_weight = float(stabilisation_weight) if stabilisation_weight is not None else (0.1 if dim == 3 else 1.0)
         self.supg_magic = float(supg_magic)
         self.char_L, self.char_U = problem.char_length(), problem.char_velocity()
@@ -73,7 +86,7 @@ class HipNavierStokesSolver(object):
         self._values_on_device = False
         if self.sv:
             from .sv import build_sv_hierarchy, build_sv_pressure_coupling
-            self.levels, self.transfers = build_sv_hierarchy(problem, nref, k, Re=0.0, gamma=gamma)
+            self.levels, self.transfers = build_sv_hierarchy(problem, nref, k, Re=0.0, gamma=gamma, facet_coupling=self.burman)
         else:
             # with the device-side refresh nobody reads a host copy of the operators: the generator then delivers the sparsity
             # only and the first (Stokes) operator is formed on the device as well (no host assembly, no 8 GB upload at config 4)
@@ -176,6 +189,10 @@ class HipNavierStokesSolver(object):
         """True if ``flag`` holds on any rank (one rank here)."""
         return bool(flag)
 
+    def _partitioned(self):
+        """Whether the levels are partitioned over ranks (alfi_amd.dist.DistNavierStokesSolver)."""
+        return False
+
     def _lazy_generation(self):
         """Operators and transfers as recipes that assemble the rows somebody asks for (alfi_amd.lazy) instead of global
         values: for the partitioned solver, whose ranks only ever need their own rows."""
@@ -186,6 +203,12 @@ class HipNavierStokesSolver(object):
         self.hmg = HipMG(self.ctx, self.levels, self.transfers, self.params["fieldsplit_0"], restriction=restriction)
         self.saddle = hip.Saddle(self.hmg.mg, self.B, None if self.sv else self.vol, self.nu, self.gamma,
                                  remove_constant_nullspace=self.nullspace, mass_inv=self.Minv)
+        if getattr(self, "burman", False):   # PCPATCH's facet rule in the patch matrices of the Burman levels
+            from .burman import patch_facet_corrections
+            for L, obj in zip(self.levels, self.hmg.pc_objs):
+                if obj is not None:
+                    obj.level.set_patch_facet_correction(L.facets.nf, *patch_facet_corrections(L.V, L.facets, obj.patch_ptr,
+                                                                                               obj.patch_dofs))
 
     def _push_operators(self):
         """New operator values on every level: re-gather and re-invert the patches, new coarse inverse."""
@@ -203,9 +226,13 @@ class HipNavierStokesSolver(object):
         injected field."""
         self._dstate = []
         for L, dl in zip(self.levels, self.hmg.mg.levels):
+            if self.burman:
+                dl.set_facet_blocks(True)
             dl.set_assembly(L.V, L.A.rowptr, L.A.colidx, full_div=self.sv)
             if self.supg:
                 dl.set_supg(L.V)
+            if self.burman:
+                dl.set_burman(L.facets, L.A.rowptr, L.A.colidx)
             self._dstate.append(self.ctx.vec(L.n))
         # the Newton state z = (u | p), the residual F and the update live on the device; the finest level's state vector IS
         # the velocity part of z
@@ -251,6 +278,8 @@ class HipNavierStokesSolver(object):
         for dl, st in zip(mgl, self._dstate):
             if adv and self.supg:     # A = nu K + gamma D + N(w) + the linearised SUPG term, THEN the boundary conditions
                 dl.assemble_supg(self.nu, self.gamma, adv, st, self.supg_weight, self.supg_magic, True)
+            elif adv and self.burman:  # ... + adv * the linearised Burman term (a facet pass), then the boundary conditions
+                dl.assemble_burman(self.nu, self.gamma, adv, st, self.burman_weight, True)
             else:
                 dl.assemble(self.nu, self.gamma, adv, st if adv else None, True)
         self.ctx.sync()
@@ -283,6 +312,8 @@ class HipNavierStokesSolver(object):
         fin.assemble_mult(self.nu, self.gamma, 0.5 * adv, du if adv else None, du, Fu)
         if adv and self.supg:         # + the SUPG residual, gathered on the device into the same vector
             fin.supg(self.nu, self.supg_weight, self.supg_magic, du, False, Fu)
+        if adv and self.burman:       # + advect * the Burman residual (solver.py:233-234), facet pass + node gather
+            fin.burman(adv * self.burman_weight, du, False, Fu)
         self._dBT.mult(dp, Fu, mode=2)                                    # F_u += B^T p
         if self._load is not None:                                         # body force: F_u -= (f, v)
             self.ctx.axpy(Fu, self._dload, -1.0)
@@ -401,9 +432,22 @@ class HipNavierStokesSolver(object):
         A = _assemble(L, self.nu, self.gamma, adv, state, False, self.sv)
         if adv and self.supg:
             _hostlib.supg(L.V, state, self.nu, self.supg_weight, self.supg_magic, L.A.rowptr, L.A.colidx, A)
+        L.facet_beta = None
+        if adv and self.burman:
+            beta = np.empty(L.facets.nf)
+            self._host_burman(L)(state, adv * self.burman_weight, vals=A, beta=beta)
+            L.facet_beta = (beta, adv * self.burman_weight)      # for PCPATCH's facet rule in the patch factorisation
         if with_bc:
             _hostlib.apply_bc_bsr(L.V.num_nodes, L.V.dim, L.A.rowptr, L.A.colidx, A, np.repeat(L.V.bc_node_mask, L.V.dim))
         return A
+
+    def _host_burman(self, L):
+        """The host pass of the Burman term on level L (its contributor lists built once)."""
+        cache = self.__dict__.setdefault("_host_burman_cache", {})
+        if L.level not in cache:
+            from .burman import HostBurman
+            cache[L.level] = HostBurman(L)
+        return cache[L.level]
 
     def _rediscretise(self, u, adv):
         if self.device_assembly:
@@ -432,6 +476,10 @@ class HipNavierStokesSolver(object):
                 Fs = np.zeros_like(Fu)
                 _hostlib.supg(L.V, wind, self.nu, self.supg_weight, self.supg_magic, F=Fs)
                 Fu = Fu + Fs
+            if self.burman:
+                Fb = np.zeros_like(Fu)
+                self._host_burman(L)(wind, adv * self.burman_weight, F=Fb)
+                Fu = Fu + Fb
         Fu = Fu + self.B_raw.T @ p
         if self._load is not None:                   # body force (manufactured solutions, examples/mms.py): F_u -= (f, v)
             Fu = Fu - self._load

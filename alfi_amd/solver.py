@@ -180,6 +180,9 @@ class HipPatchPC(object):
         self.partition_of_unity = _truthy(opts.getString("patch_pc_patch_partition_of_unity", "false"))
         if self.partition_of_unity and self.multiplicative:
             raise NotImplementedError("partition_of_unity with multiplicative sweeps")
+        if self.multiplicative and getattr(L, "facet_coupling", False):
+            raise NotImplementedError("multiplicative patch sweeps on a facet-coupled (Burman) level: the sweep's dependency "
+                                      "waves assume cell coupling")
         sub_mat = opts.getString("patch_pc_patch_sub_mat_type", "seqdense")
         if sub_mat not in ("seqdense", "dense", "seqaij", "aij"):
             raise NotImplementedError("patch sub_mat_type %r" % sub_mat)
@@ -226,7 +229,8 @@ class HipPatchPC(object):
         import os
         if (ctype == "python" and getattr(L.V.mesh, "macro_mesh", None) is not None and not self.multiplicative
                 and os.environ.get("ALFI_CONDENSE", "1") != "0" and type(ctor).__name__ == "MacroStar"
-                and ctype == "python"):
+                and ctype == "python" and not getattr(L, "facet_coupling", False)):
+            # (not on facet-coupled levels: the Burman term couples the interiors of neighbouring macro cells)
             from .sv import macro_cell_groups
             self.level.set_patch_groups(macro_cell_groups(L.V, dofs))
             self.condensed = True
@@ -243,6 +247,9 @@ class HipPatchPC(object):
         """New operator values (Newton step / Reynolds continuation): re-gather and re-invert every patch, which is what
         PatchPC.update -> PCSetUp_PATCH does with save_operators (solver.py:320)."""
         self.level.update_values(pc.level_data.A.vals)
+        fb = getattr(pc.level_data, "facet_beta", None)     # host-assembled Burman values: beta_F and the term's weight
+        if fb is not None:
+            self.level.set_facet_beta(*fb)
         self.level.factor()
 
     def apply(self, pc, x, y):

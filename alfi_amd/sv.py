@@ -334,8 +334,13 @@ def build_sv_pressure_coupling(L, zero_bc_columns=True, both=False):
     return make(Bc * keep[cols][:, None, :] if zero_bc_columns else Bc), M, Minv
 
 
-def build_sv_hierarchy(problem, nref, k, Re, gamma=1e4, advect=True, patches=True):
-    """The Scott-Vogelius analogue of ``problem.build_hierarchy``: levels 0..nref on the bary hierarchy."""
+def build_sv_hierarchy(problem, nref, k, Re, gamma=1e4, advect=True, patches=True, facet_coupling=False):
+    """The Scott-Vogelius analogue of ``problem.build_hierarchy``: levels 0..nref on the bary hierarchy.
+
+    facet_coupling: the level graphs also couple the nodes of two cells that share a facet (the sparsity of the Burman
+    interior-penalty term, alfi_amd/burman.py), every level gets its interior-facet table ``L.facets`` and no condensation
+    groups (a facet of the macro skeleton couples the interiors of two macro cells).  The transfers keep the CELL graph:
+    SVSchoeberlTransfer.form has no stabilisation (transfer.py:295-299).  Off: bit for bit the hierarchy without it."""
     dim = problem.dim
     if k not in (2, 3) or (k == 3 and dim != 3):
         raise NotImplementedError("Scott-Vogelius velocities: [P2]^d, and [P3]^3 (the inf-sup stable 3-D pair of config 5)")
@@ -349,7 +354,12 @@ def build_sv_hierarchy(problem, nref, k, Re, gamma=1e4, advect=True, patches=Tru
         d = V.dim
         L = LevelData()
         L.V, L.level, L.n, L.bs = V, l, V.num_dofs, d
-        rowptr, colidx = _hostlib.node_graph(V.cell_nodes, V.num_nodes)
+        rowptr, colidx = cell_graph = _hostlib.node_graph(V.cell_nodes, V.num_nodes)
+        L.facet_coupling = bool(facet_coupling)
+        if facet_coupling:
+            from .burman import FacetTable, facet_coupled_graph
+            L.facets = FacetTable(V)
+            rowptr, colidx = facet_coupled_graph(V.cell_nodes, V.num_nodes, L.facets)
         g, vol = mesh.cell_geometry()
         tens = element.reference_tensors()
         wind = problem.driver(V.node_coords)
@@ -364,9 +374,10 @@ def build_sv_hierarchy(problem, nref, k, Re, gamma=1e4, advect=True, patches=Tru
             literal = os.environ.get("ALFI_MACROSTAR_LITERAL") == "1"
             L.patch_ptr, L.patch_dofs, L.patch_seeds = (macro_star_patches if literal else macro_star_patches_fast)(V)
             # the factors of these patches can be stored condensed: interiors of the macro cells + skeleton
-            L.patch_groups = macro_cell_groups(V, L.patch_dofs)
+            if not facet_coupling:
+                L.patch_groups = macro_cell_groups(V, L.patch_dofs)
         if l > 0:
-            transfers.append(build_sv_transfer_data(Vprev, V, nu, gamma, (rowptr, colidx)))
+            transfers.append(build_sv_transfer_data(Vprev, V, nu, gamma, cell_graph))
         levels.append(L)
         Vprev = V
     return levels, transfers

@@ -202,6 +202,39 @@ int alfi_level_assemble_supg(alfi_level* lvl, double nu, double gamma, double ad
 int alfi_level_supg(alfi_level* lvl, double nu, double weight, double magic, const double* d_state, int add_to_operator,
                     double* d_F);
 int alfi_level_apply_bc(alfi_level* lvl);
+/* Burman interior-penalty stabilisation of the Scott-Vogelius pair on the device (alfi/stabilisation.py:139-162,
+ * alfi/solver.py:226-234; the reference's `--stabilisation-type burman`): the project's first interior-facet term.
+ * alfi_level_set_facet_blocks(lvl, 1), BEFORE alfi_level_set_assembly, declares that the level's sparsity also couples the
+ * nodes of cells sharing a facet (blocks without a contributing cell are then accepted; unpartitioned levels only).
+ * alfi_level_set_burman (after alfi_level_set_assembly) hands over the interior-facet tables of alfi_amd/burman.py:
+ * funion (nfacet, nu) -- K+'s nodes, then K-'s nodes off the facet --, cfg (nfacet) configuration of K+, J (nfacet, nqs, nu)
+ * jumps of the normal derivatives at the points of the exact facet rule (weights ws, summing to 1), area / coef (nfacet)
+ * |F| and 0.5 avg(h)^2, wn (nqn) and phin (ncfg, nqn, nloc) the nonlinear rule and K+'s basis there (zero off the facet),
+ * and the contributor lists: per block (bptr (nnzb + 1), bfac, bab = a * nu + b) and per node (nptr (nodes + 1), nfac, na),
+ * each in a fixed order.  alfi_level_burman adds `weight` times the Newton linearisation of the term about d_state to the
+ * operator as it stands (add_to_operator != 0; between alfi_level_assemble(..., apply_bc = 0) and alfi_level_apply_bc) and /
+ * or its residual contribution to d_F (may be NULL).  alfi_level_assemble_burman is the refresh of a stabilised run:
+ * A = nu K + gamma D + adv N(state) + adv * weight * the linearised Burman term, then the boundary conditions.  One lane per
+ * facet forms a compact record (beta_F, the jumps of grad u, the derivative weights of beta_F), one lane per block / node
+ * sums its facet contributors in list order: no atomics, bitwise reproducible. */
+int alfi_level_set_facet_blocks(alfi_level* lvl, int on);
+int alfi_level_set_burman(alfi_level* lvl, int64_t nfacet, int nu, int nqs, int nqn, int ncfg, const int32_t* funion,
+                          const int32_t* cfg, const double* J, const double* area, const double* coef, const double* ws,
+                          const double* wn, const double* phin, const int64_t* bptr, const int32_t* bfac, const uint16_t* bab,
+                          const int64_t* nptr, const int32_t* nfac, const uint16_t* na);
+int alfi_level_burman(alfi_level* lvl, double weight, const double* d_state, int add_to_operator, double* d_F);
+int alfi_level_assemble_burman(alfi_level* lvl, double nu, double gamma, double adv, const double* d_state, double weight,
+                               int apply_bc);
+/* PCPATCH's interior-facet rule on a Burman level (Firedrake's PatchPC integrates into a patch's matrix only the facets whose
+ * two cells both belong to the patch).  After alfi_patches_set (patches of whole nodes): per patch-local row node -- rows
+ * numbered patch_ptr[p] / bs + i, nrow of them -- the entries (col: patch-local column node, fac: facet, s) with
+ * s = c_F |F| sum_q ws_q J_qa J_qb of the K-side terms of the facets with one cell K in the patch.  alfi_patches_factor then
+ * inverts A[P, P] - scale * beta_F * s * I_bs instead of A[P, P] (scale: adv * weight of the last Burman refresh, beta_F of its
+ * state; 0 after alfi_level_assemble / alfi_level_update_values), and probes against the same matrix.
+ * alfi_level_set_facet_beta: beta_F (nfacet) and the scale of operator values assembled on the host. */
+int alfi_patches_set_facet_correction(alfi_level* lvl, int64_t nfacet, int64_t nrow, const int64_t* ptr, const int32_t* col,
+                                      const int32_t* fac, const double* s);
+int alfi_level_set_facet_beta(alfi_level* lvl, const double* beta_host, double scale);
 /* the operator values in the host layout (nnzb, bs, bs) -- diagnostics / tests */
 int alfi_level_get_values(alfi_level* lvl, double* bvals_host);
 int alfi_level_size(alfi_level* lvl, int64_t* n);

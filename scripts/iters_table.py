@@ -24,8 +24,11 @@ def main():
     ap.add_argument("--nref-end", type=int, default=3)
     ap.add_argument("--re-max", type=int, default=1000)
     ap.add_argument("--gamma", type=float, default=1e4)
-    ap.add_argument("--stabilisation-type", default="none", choices=["none", "supg"])
+    ap.add_argument("--discretisation", default="pkp0", choices=["pkp0", "sv"])
+    ap.add_argument("--stabilisation-type", default="none", choices=["none", "supg", "burman"])
     ap.add_argument("--stabilisation-weight", type=float, default=None)
+    ap.add_argument("--smoothing", type=int, default=None)
+    ap.add_argument("--restriction", action="store_true")
     args = ap.parse_args()
     # continuation as in alfi.driver.get_default_parser / run_solver: 0 (Stokes), 1, 10, 100, then steps of 250
     res = [0, 1, 10, 100] + list(range(250, args.re_max + 1, 250))
@@ -35,7 +38,8 @@ def main():
     for nref in range(args.nref_start, args.nref_end + 1):
         prob = TwoDimLidDrivenCavityProblem(args.baseN) if args.dim == 2 else ThreeDimLidDrivenCavityProblem(args.baseN)
         s = HipNavierStokesSolver(prob, nref, args.k, gamma=args.gamma, stabilisation_type=args.stabilisation_type,
-                                  stabilisation_weight=args.stabilisation_weight)
+                                  stabilisation_weight=args.stabilisation_weight, discretisation=args.discretisation,
+                                  smoothing=args.smoothing, restriction=args.restriction)
         t0 = time.time()
         results = run_solver(s, res)
         rows.append((nref, s.n_u + s.n_p, results, time.time() - t0))
