@@ -129,18 +129,21 @@ def supg(V, U, nu, weight, magic, rowptr=None, colidx=None, vals=None, F=None, n
 
 
 def burman(table, U, weight, lists, vals=None, F=None, beta=None):
-    """Burman interior-penalty stabilisation (stabilisation.py:139-162, alfi_amd/burman.py) about the state U (num_nodes,
-    dim): adds the residual contribution to F (num_dofs) and / or the Newton linearisation to the BSR values ``vals``.
+    """Burman interior-penalty stabilisation (stabilisation.py:139-162, alfi_amd/burman.py) about the state U (nstate,
+    dim): adds the residual contribution to F (rows x dim) and / or the Newton linearisation to the BSR values ``vals``.
     ``table``: burman.FacetTable of the level; ``lists``: its contributor lists for the level's sparsity
-    (FacetTable.contributors); ``beta`` (nfacet, may be None): receives beta_F of every facet."""
+    (FacetTable.contributors); ``beta`` (nfacet, may be None): receives beta_F of every facet.  The state may be longer than
+    the rows (a rank-local table of a partitioned level: local nodes first, then the other nodes its facets reach)."""
     (bptr, bfac, bab), (nptr, nfac, na) = lists
     t = table
     U = np.ascontiguousarray(U, dtype=np.float64)
-    assert U.size == (len(nptr) - 1) * t.d
+    nrow = len(nptr) - 1
+    assert U.size % t.d == 0 and U.size >= nrow * t.d
+    assert t.nf == 0 or (int(t.union.min()) >= 0 and int(t.union.max()) < U.size // t.d), "facet node beyond the state"
     if vals is not None:
         assert vals.shape == (len(bptr) - 1, t.d, t.d) and vals.flags.c_contiguous and vals.dtype == np.float64
     if F is not None:
-        assert F.shape == (U.size,) and F.flags.c_contiguous and F.dtype == np.float64
+        assert F.shape == (nrow * t.d,) and F.flags.c_contiguous and F.dtype == np.float64
     if beta is not None:
         assert beta.shape == (t.nf,) and beta.flags.c_contiguous and beta.dtype == np.float64
     arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (t.J, t.area, t.coef, t.ws, t.wn, t.phin)]

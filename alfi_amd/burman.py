@@ -149,37 +149,70 @@ class FacetTable(object):
             self.onf[c] = on
             self.phin[c] = tab_n[key] * on[None, :]
 
+    def subset(self, facets, union):
+        """The table of the facets ``facets`` (indices into this table, ascending) with their union renumbered to ``union``
+        (len(facets), nu): the rank-local table of a partitioned level (alfi_amd.dist.FacetPart).  The per-configuration
+        tables are shared."""
+        t = object.__new__(FacetTable)
+        t.__dict__.update(self.__dict__)
+        facets = np.asarray(facets, dtype=np.int64)
+        for name in ("facet_ids", "cells", "normal", "area", "coef", "J", "cfg"):
+            setattr(t, name, getattr(self, name)[facets])
+        t.union = np.ascontiguousarray(union, dtype=np.int32)
+        assert t.union.shape == (facets.size, self.nu)
+        t.nf = int(facets.size)
+        return t
+
     def pairs(self):
         """(rows, cols) node pairs the facets couple: what the level graph gains with facet coupling."""
         u = self.union.astype(np.int64)
         return np.repeat(u, self.nu, axis=1).ravel(), np.tile(u, (1, self.nu)).ravel()
 
-    def contributors(self, rowptr, colidx, nnode):
+    def contributors(self, rowptr, colidx, nnode, partial=False):
         """Matrix lists: (bptr int64 (nnzb+1), bfac int32, bab uint16 = a * nu + b) for every BSR block, facets ascending;
-        residual lists: (nptr int64 (nnode+1), nfac int32, na uint16) for every node."""
+        residual lists: (nptr int64 (nnode+1), nfac int32, na uint16) for every node.  partial: the union may hold nodes
+        >= nnode (a rank-local table, its union in the numbering of the rank's state vector): only the pairs whose row and
+        column are below nnode -- rows and columns of the rank's localised sparsity -- and the nodes below nnode are listed."""
         nu, nf = self.nu, self.nf
         rowptr = np.asarray(rowptr, dtype=np.int64)
         colidx = np.asarray(colidx, dtype=np.int64)
         nnzb = colidx.shape[0]
         bkey = np.repeat(np.arange(nnode, dtype=np.int64), np.diff(rowptr)) * nnode + colidx
-        assert nnzb == 0 or (np.diff(bkey) > 0).all(), "unsorted block rows"
+        bord = None
+        if nnzb and not (np.diff(bkey) > 0).all():
+            # (a localised sparsity: columns in local numbering are not ascending inside a row)
+            assert partial, "unsorted block rows"
+            bord = np.argsort(bkey, kind="stable")
+            bkey = bkey[bord]
+            assert (np.diff(bkey) > 0).all(), "repeated blocks"
         r, c = self.pairs()
+        pair = np.arange(nf * nu * nu, dtype=np.int64)
+        if partial:
+            keep = (r < nnode) & (c < nnode)
+            r, c, pair = r[keep], c[keep], pair[keep]
+        else:
+            assert nf == 0 or int(self.union.max()) < nnode, "union node beyond the level's nodes"
         key = r * nnode + c
         blk = np.searchsorted(bkey, key)
         if key.size and (blk.max() >= nnzb or (bkey[np.minimum(blk, nnzb - 1)] != key).any()):
             raise ValueError("the level graph lacks facet-coupled blocks (build the hierarchy with facet_coupling=True)")
+        if bord is not None:
+            blk = bord[blk]
         o = np.argsort(blk, kind="stable")
         bptr = np.zeros(nnzb + 1, dtype=np.int64)
         np.cumsum(np.bincount(blk, minlength=nnzb), out=bptr[1:])
-        pair = np.arange(nf * nu * nu, dtype=np.int64)
         bfac = (pair[o] // (nu * nu)).astype(np.int32)
         bab = (pair[o] % (nu * nu)).astype(np.uint16)
         un = self.union.ravel().astype(np.int64)
+        slot = np.arange(un.size, dtype=np.int64)
+        if partial:
+            slot = slot[un < nnode]
+            un = un[slot]
         o2 = np.argsort(un, kind="stable")
         nptr = np.zeros(nnode + 1, dtype=np.int64)
         np.cumsum(np.bincount(un, minlength=nnode), out=nptr[1:])
-        nfac = (o2 // nu).astype(np.int32)
-        na = (o2 % nu).astype(np.uint16)
+        nfac = (slot[o2] // nu).astype(np.int32)
+        na = (slot[o2] % nu).astype(np.uint16)
         return (bptr, bfac, bab), (nptr, nfac, na)
 
 

@@ -275,7 +275,8 @@ int alfi_level_set_assembly(alfi_level* L, int64_t ncell, int nloc, const int32_
     for (int64_t k = k0; k < k1; ++k)
       if (cptr[k + 1] <= cptr[k]) { bad_block = k; return; }
   });
-  if (bad_block >= 0 && !(L->facet_blocks && !part))
+  // (a facet-coupled level: blocks that only facets couple -- on a partitioned one, the rank's blocks of those)
+  if (bad_block >= 0 && !L->facet_blocks)
     return alfi_set_error(ctx, ALFI_E_ARG, "block %lld has no contributing cell", (long long)bad_block.load());
   host_parallel_ranges(npairs, [&](int64_t q0, int64_t q1) {
     for (int64_t q = q0; q < q1; ++q)
@@ -524,17 +525,23 @@ int alfi_level_set_burman(alfi_level* L, int64_t nfacet, int nu, int nqs, int nq
   AssemblyDev& S = L->asmb;
   if (!S.ready) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_level_set_burman before alfi_level_set_assembly");
   if (!L->facet_blocks) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_level_set_burman on a level without alfi_level_set_facet_blocks");
-  if (L->has_halo) return alfi_set_error(ctx, ALFI_E_STATE, "Burman terms on a partitioned level");
+  // Partitioned: the rank's facets (those with a cell among its assembly cells) in the numbering of its state vector, whose
+  // union nodes may lie beyond the cells' nodes (the off-rank cell of a facet); only the pairs / nodes of local rows are listed
+  const bool part = L->has_halo;
   if (nfacet < 0 || nu < 1 || nu * nu > 65535 || nu < S.nloc || nqs < 1 || nqs > BURMAN_MAXQ || nqn < 1 || nqn > BURMAN_MAXQ ||
       ncfg < 1 || S.nloc > BURMAN_MAXN)
     return alfi_set_error(ctx, ALFI_E_ARG, "bad Burman table sizes (%d union nodes, %d / %d points)", nu, nqs, nqn);
   if (!funion || !cfg || !J || !area || !coef || !ws || !wn || !phin || !bptr || !bfac || !bab || !nptr || !nfac || !na)
     return alfi_set_error(ctx, ALFI_E_ARG, "NULL argument");
   const int64_t nnzb = L->A.nnzb, nb = L->A.nbrows;
-  if (bptr[0] != 0 || nptr[0] != 0 || bptr[nnzb] != nfacet * nu * nu || nptr[nb] != nfacet * nu)
+  if (bptr[0] != 0 || nptr[0] != 0 ||
+      (part ? (bptr[nnzb] > nfacet * nu * nu || nptr[nb] > nfacet * nu) : (bptr[nnzb] != nfacet * nu * nu || nptr[nb] != nfacet * nu)))
     return alfi_set_error(ctx, ALFI_E_ARG, "facet contributor lists of the wrong length");
-  for (int64_t i = 0; i < nfacet * nu; ++i)
-    if (funion[i] < 0 || funion[i] >= nb) return alfi_set_error(ctx, ALFI_E_ARG, "facet node out of range");
+  int64_t max_union = -1;
+  for (int64_t i = 0; i < nfacet * nu; ++i) {
+    if (funion[i] < 0 || (!part && funion[i] >= nb)) return alfi_set_error(ctx, ALFI_E_ARG, "facet node out of range");
+    max_union = std::max<int64_t>(max_union, funion[i]);
+  }
   for (int64_t f = 0; f < nfacet; ++f)
     if (cfg[f] < 0 || cfg[f] >= ncfg) return alfi_set_error(ctx, ALFI_E_ARG, "facet configuration out of range");
   for (int64_t k = 0; k < nnzb; ++k) {
@@ -574,6 +581,7 @@ int alfi_level_set_burman(alfi_level* L, int64_t nfacet, int nu, int nqs, int nq
   if (rc == 0) rc = dev_upload(ctx, &S.fna, na, std::max<int64_t>(nptr[nb], 1));
   if (rc != 0) return rc;
   S.nfacet = nfacet;
+  S.nstate = std::max<int64_t>(S.nstate, max_union + 1);      // (partitioned: the state vector covers the facets' nodes too)
   S.bnu = nu;
   S.bnqs = nqs;
   S.bnqn = nqn;

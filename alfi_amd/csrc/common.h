@@ -316,7 +316,8 @@ struct AssemblyDev {
   int nloc = 0;
   int64_t ncell = 0, npairs = 0;
   int64_t nstate = 0;            // nodes of the state vector the cells index (= the level's nodes; on a partitioned level the
-                                 // local nodes followed by the other nodes of the cells that touch them)
+                                 // local nodes followed by the other nodes of the cells that touch them, then -- Burman
+                                 // terms -- the other nodes of the rank's facets)
   bool full_div = false;         // grad-div term gamma (div u, div v) (Scott-Vogelius) instead of the cell-averaged one
   uint8_t* bc_code = nullptr;    // (nnzb) Dirichlet flags of every block's row / column dofs (built on first use)
   uint8_t* bc_all = nullptr;     // (n) partitioned levels: Dirichlet dofs among ALL local dofs, ghosts included

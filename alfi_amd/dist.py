@@ -441,6 +441,88 @@ def assembly_cells(V, part):
     return cells, cn.astype(np.int32), np.concatenate([part.nodes, extra])
 
 
+class FacetPart(object):
+    """What a rank needs for the Burman terms (alfi_amd.burman) of ITS operator rows and residual entries on a facet-coupled
+    level: every interior facet with a cell among the rank's assembly cells (the cells that touch a local node,
+    ``assembly_cells``).  That set is complete for every local row, owned or ghost: a facet's nodes lie in its two cells, so a
+    facet that contributes to row r has a cell touching r.
+
+    facets      indices into the level's FacetTable, ascending (= ascending global facet order)
+    table       the rank-local FacetTable of those facets, its union in the numbering of the state vector
+    state_nodes global node of every state entry: the local nodes (the level's local numbering), the other nodes of the
+                assembly cells, then the other nodes of the facets' off-rank cells -- each group ascending
+    cells, cell_nodes   assembly_cells' cells and their nodes in that numbering"""
+
+    def __init__(self, V, table, part):
+        self.part = part
+        self.cells, self.cell_nodes, nodes = assembly_cells(V, part)
+        inside = np.zeros(V.mesh.num_cells, dtype=bool)
+        inside[self.cells] = True
+        self.facets = np.flatnonzero(inside[table.cells].any(axis=1))
+        gun = table.union[self.facets].astype(np.int64)
+        pos = np.full(V.num_nodes, -1, dtype=np.int64)
+        pos[nodes] = np.arange(nodes.size)
+        extra = np.unique(gun[pos[gun] < 0])
+        pos[extra] = nodes.size + np.arange(extra.size)
+        self.state_nodes = np.concatenate([nodes, extra])
+        lun = pos[gun]
+        # the level graph holds the facet pairs, so the ghosts taken from the owned rows' columns cover every node of a facet
+        # that couples an owned node: such a facet reaches no node beyond the local ones
+        own = (lun < part.nb_own).any(axis=1)
+        assert (lun[own] < part.nb_loc).all(), "a facet of an owned node reaches a node outside the local node set"
+        self.table = table.subset(self.facets, lun)
+        self._lists = None
+
+    def lists(self, A):
+        """Contributor lists against the rank's localised sparsity ``A`` (localize_operator): the pairs of local rows and
+        local columns, the nodes of local rows."""
+        if self._lists is None:
+            self._lists = self.table.contributors(A.rowptr, A.colidx, self.part.nb_loc, partial=True)
+        return self._lists
+
+    def host(self, A, U, weight, vals=None, F=None, beta=None):
+        """The host pass (alfi_host_burman) on the rank's facets: U (len(state_nodes), d) the state in state numbering, vals
+        the rank's operator values (sparsity ``A``), F the rank's residual rows (nb_loc * d)."""
+        from . import _hostlib
+        _hostlib.burman(self.table, U, weight, self.lists(A), vals=vals, F=F, beta=beta)
+
+    def patch_facet_corrections(self, V, table, LL):
+        """PCPATCH's facet rule for the rank's owned patches (burman.patch_facet_corrections) in local numbering: rows and
+        columns patch-local in the order of LL.patch_dofs, facets numbered in the rank's table.  The facets with one cell in
+        an owned patch have that cell among the assembly cells, so all of them are the rank's."""
+        from .burman import patch_facet_corrections
+        bs = LL.bs
+        ld = np.asarray(LL.patch_dofs, dtype=np.int64)
+        gd = self.part.nodes[ld // bs] * bs + ld % bs
+        ptr, col, fac, sv = patch_facet_corrections(V, table, LL.patch_ptr, gd)
+        local = np.full(table.nf, -1, dtype=np.int64)
+        local[self.facets] = np.arange(self.facets.size)
+        lf = local[fac.astype(np.int64)]
+        assert (lf >= 0).all(), "a facet of an owned patch is not the rank's"
+        return ptr, col, lf.astype(np.int32), sv
+
+
+def local_host_operator(L, part, fpart, nu, gamma, adv, wind, weight):
+    """The rank's rows of a Burman level's operator assembled on the host, in local numbering (owned rows complete, ghost rows
+    restricted to local columns): nu K + gamma D (full) + adv N(wind) + adv * weight * the linearised Burman term of the rank's
+    facets, then the boundary conditions.  Returns (BSR, beta_F of the rank's facets or None)."""
+    from . import _hostlib
+    from .lazy import LazyOperator
+    V, d = L.V, L.bs
+    wind = np.ascontiguousarray(wind, dtype=np.float64).reshape(-1, d)
+    lazy = LazyOperator(V, L.A.rowptr, L.A.colidx, V.mesh.cell_geometry(), V.element.reference_tensors(), nu, gamma, adv,
+                        wind, full_div=True, with_bc=False)
+    A = localize_operator(lazy, part)
+    A = BSR(A.nbrows, A.nbcols, d, np.ascontiguousarray(A.rowptr, dtype=np.int32), np.ascontiguousarray(A.colidx, dtype=np.int32),
+            np.ascontiguousarray(A.vals))
+    beta = None
+    if adv:
+        beta = np.empty(fpart.table.nf)
+        fpart.host(A, wind[fpart.state_nodes], adv * weight, vals=A.vals, beta=beta)
+    _hostlib.apply_bc_bsr(part.nb_loc, d, A.rowptr, A.colidx, A.vals, np.repeat(V.bc_node_mask[part.nodes], d))
+    return A, beta
+
+
 def localize_level(L, part):
     """Operator rows of all local nodes (owned rows complete; ghost rows restricted to local columns -- they only feed the
     patch sub-matrix gather), owned Dirichlet dofs, owned patches; everything in local numbering."""
@@ -1107,7 +1189,8 @@ def _dist_ns_solver_class():
         (``_rediscretise_device``; on its host cores only with ALFI_DEVICE_ASSEMBLY=0).  The Newton state is DISTRIBUTED on the
         devices, every rank its owned velocity and pressure dofs (``StateExchange`` feeds the levels' refresh states from it;
         ``u`` / ``p`` gather it, collectively, when somebody asks); the barycentric hierarchy of the Scott-Vogelius pair and
-        the host-assembly path keep a replicated host state."""
+        the host-assembly path keep a replicated host state.  The Burman terms of the Scott-Vogelius pair are formed by every rank
+        over the facets of its cells (``FacetPart``), on the device or, with ALFI_DEVICE_ASSEMBLY=0, by the host pass."""
 
         def __init__(self, *args, min_dofs=400000, group=None, device_state=True, **kwargs):
             """device_state False: the Newton state replicated on the hosts and gathered after every linear solve (the loop of
@@ -1127,6 +1210,9 @@ def _dist_ns_solver_class():
         def _partitioned(self):
             return True
 
+        def _partitioned_burman(self):
+            return True
+
         def _lazy_generation(self):
             # rank-local generation: every rank assembles the operator / transfer rows of its partition only (config 4 on 8
             # ranks: 4.5 GB of host memory per rank instead of 25).  The HOST refresh of SUPG terms works on global values: with
@@ -1142,6 +1228,19 @@ def _dist_ns_solver_class():
             L = self.levels[-1]
             self.saddle = DistSaddle(self.dmg, self.B, self.vol, L.V.cell_nodes, self.nu, self.gamma,
                                      remove_constant_nullspace=self.nullspace, mass_inv=self.Minv if self.sv else None)
+            self._facet_parts = {}
+            if self.burman:
+                # every level with owned rows: the rank's facets; levels with owned patches: PCPATCH's facet rule for them
+                # (the patches were factored from the Stokes operators, which hold no Burman part: the rule applies from the
+                # first refresh with adv > 0 on)
+                with self._on_stream():
+                    for dl, LL in zip(self.dmg.levels, self.dmg.local_levels):
+                        if LL.part.nb_own == 0:
+                            continue
+                        Lg = self.levels[LL.level]
+                        fp = self._facet_parts[LL.level] = FacetPart(Lg.V, Lg.facets, LL.part)
+                        if LL.level > 0:
+                            dl.set_patch_facet_correction(fp.table.nf, *fp.patch_facet_corrections(Lg.V, Lg.facets, LL))
 
         def _push_operators(self):
             self.dmg.update(self.levels)
@@ -1179,12 +1278,20 @@ def _dist_ns_solver_class():
                         continue
                     L = self.levels[LL.level]
                     V = L.V
-                    cells, cn, nodes = assembly_cells(V, p)
+                    fp = self._facet_parts.get(LL.level)
+                    if fp is not None:               # the facet-coupled sparsity has blocks no cell contributes to
+                        dl.set_facet_blocks(True)
+                        cells, cn, nodes = fp.cells, fp.cell_nodes, fp.state_nodes
+                    else:
+                        cells, cn, nodes = assembly_cells(V, p)
                     dl.set_assembly(V, LL.A.rowptr, LL.A.colidx, full_div=self.sv, cells=cells, cell_nodes=cn)
                     bcn = np.flatnonzero(V.bc_node_mask[p.nodes])              # Dirichlet nodes among ALL local nodes
                     dl.set_assembly_bc((bcn[:, None] * L.bs + np.arange(L.bs)).ravel())
                     if self.supg:
                         dl.set_supg(V, cells=cells)
+                    if fp is not None:               # the rank's facets; the state grows by their off-rank cells' nodes
+                        dl.set_burman(fp.table, LL.A.rowptr, LL.A.colidx, lists=fp.lists(LL.A))
+                    assert dl.assembly_state_size() == nodes.size * L.bs
                     self._asm.append((nodes, self.ctx.vec(dl.assembly_state_size())))
                 L = self.levels[-1]
                 self._dres = self.ctx.vec(dmg.n_loc)
@@ -1314,6 +1421,8 @@ def _dist_ns_solver_class():
                         continue
                     if adv and self.supg:     # A = nu K + gamma D + N(w) + the linearised SUPG term, THEN the boundary conditions
                         dl.assemble_supg(self.nu, self.gamma, adv, asm[1], self.supg_weight, self.supg_magic, True)
+                    elif adv and self.burman:  # ... + adv * the linearised Burman term over the rank's facets, then the conditions
+                        dl.assemble_burman(self.nu, self.gamma, adv, asm[1], self.burman_weight, True)
                     else:
                         dl.assemble(self.nu, self.gamma, adv, asm[1] if adv else None, True)
                 self.dmg.sync()
@@ -1339,6 +1448,8 @@ def _dist_ns_solver_class():
                 fin.assemble_mult(self.nu, self.gamma, 0.5 * adv, st if adv else None, st, self._dres)
                 if adv and self.supg:         # + the SUPG residual of the rank's rows, gathered on the device into the same vector
                     fin.supg(self.nu, self.supg_weight, self.supg_magic, st, False, self._dres)
+                if adv and self.burman:       # + advect * the Burman residual of the rank's rows (its facets, node gather)
+                    fin.burman(adv * self.burman_weight, st, False, self._dres)
                 self._dp.set(np.ascontiguousarray(p[self._res_rows]) if len(self._res_rows) else np.zeros(1))
                 self._dBT.mult(self._dp, self._dwc)
                 fin.halo_reverse_add(self._dwc)
@@ -1364,6 +1475,8 @@ def _dist_ns_solver_class():
             if self.supg:
                 self._supg_host_needs_global_values()
                 return super()._rediscretise(u, adv)
+            if self.burman:
+                return self._rediscretise_burman_host(u, adv)
             from .lazy import LazyOperator
             for L, w in zip(self.levels, self._winds(u)):
                 V = L.V
@@ -1371,6 +1484,25 @@ def _dist_ns_solver_class():
                                    self.gamma, adv, np.ascontiguousarray(w), full_div=self.sv)
                 L.nu = self.nu
             self._push_operators()
+
+        def _rediscretise_burman_host(self, u, adv):
+            """ALFI_DEVICE_ASSEMBLY=0 with Burman terms: every rank assembles its rows on its host cores -- the cells' terms,
+            then the host pass over the rank's facets (local_host_operator) -- and hands them and beta_F of its facets (PCPATCH's
+            facet rule in the patch factorisation) to its levels."""
+            winds = self._winds(u)
+            with self._on_stream():
+                for dl, LL in zip(self.dmg.levels, self.dmg.local_levels):
+                    fp = self._facet_parts.get(LL.level)
+                    if fp is None:            # (ghost copies only: no patch and no product reads those rows)
+                        continue
+                    A, beta = local_host_operator(self.levels[LL.level], LL.part, fp, self.nu, self.gamma, adv, winds[LL.level],
+                                                  self.burman_weight)
+                    dl.update_values(A.vals)
+                    if beta is not None and LL.level > 0:
+                        dl.set_facet_beta(beta, adv * self.burman_weight)
+            for L in self.levels:
+                L.nu = self.nu
+            self.dmg.refactor(self.levels)
 
         def residual(self, u, p, adv):
             """F(u, p) with every rank assembling ITS rows of (nu K + gamma D + 1/2 N(u)) u only -- one pass over its own
@@ -1397,6 +1529,11 @@ def _dist_ns_solver_class():
                                          gamma=0.0 if self.sv else self.gamma, gamma_full=self.gamma if self.sv else 0.0,
                                          adv=0.5 * adv, wind=wind if adv else None, row_map=_row_map(V.num_nodes, rows))
             f_own = BSR(len(rows), V.num_nodes, d, ptr32, cols, vals).to_scipy() @ u
+            if adv and self.burman:           # + advect * the Burman residual of the rank's rows, over its facets
+                fp = self._facet_parts[L.level]
+                Fb = np.zeros(part.nb_loc * d)
+                fp.host(self.dmg.fine.A, wind[fp.state_nodes], adv * self.burman_weight, F=Fb)
+                f_own = f_own + Fb[:part.nb_own * d]
             Fu = np.zeros(self.n_u)
             for dofs, f in self.dmg.comm.all_gather_object((part.own_dofs(), f_own)):
                 Fu[dofs] = f

@@ -323,11 +323,12 @@ class Level(object):
         ``set_assembly``): blocks without a contributing cell are accepted."""
         self.ctx.check(self.ctx.lib.alfi_level_set_facet_blocks(self.h, 1 if on else 0))
 
-    def set_burman(self, table, rowptr, colidx):
+    def set_burman(self, table, rowptr, colidx, lists=None):
         """Interior-facet tables and contributor lists of the Burman term (alfi_level_set_burman); ``table``:
-        burman.FacetTable of the level, rowptr / colidx: the level's (facet-coupled) sparsity."""
+        burman.FacetTable of the level, rowptr / colidx: the level's (facet-coupled) sparsity.  lists: the contributor lists
+        if the caller has them (a partitioned level: alfi_amd.dist.FacetPart.lists)."""
         t = table
-        (bptr, bfac, bab), (nptr, nfac, na) = t.contributors(rowptr, colidx, len(rowptr) - 1)
+        (bptr, bfac, bab), (nptr, nfac, na) = lists if lists is not None else t.contributors(rowptr, colidx, len(rowptr) - 1)
         f64 = [np.ascontiguousarray(a, dtype=np.float64) for a in (t.J, t.area, t.coef, t.ws, t.wn, t.phin)]
         i32 = [np.ascontiguousarray(a, dtype=np.int32) for a in (t.union, t.cfg, bfac, nfac)]
         i64 = [np.ascontiguousarray(a, dtype=np.int64) for a in (bptr, nptr)]

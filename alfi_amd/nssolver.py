@@ -45,7 +45,8 @@ class HipNavierStokesSolver(object):
         """discretisation: "pkp0" ([P_k(+FB)]^d - P0 on the uniform hierarchy, ConstantPressureSolver solver.py:561-602) or
         "sv" ([P_k]^d - P_{k-1}^dg on the barycentric hierarchy with macro-star patches, ScottVogeliusSolver :604-662).
         stabilisation_type: None / "none", "supg" (P0-pressure pairs) or "burman" (the Scott-Vogelius pair: interior-penalty
-        term of stabilisation.py:139-162 on facet-coupled levels, alfi_amd.burman; not on partitioned levels).
+        term of stabilisation.py:139-162 on facet-coupled levels, alfi_amd.burman; on partitioned levels in
+        alfi_amd.dist.DistNavierStokesSolver, every rank the facets of its cells).
         device_assembly: refresh the level operators of every Newton step ON THE DEVICE (alfi_level_assemble: what
         PatchPC.update does inside PCPATCH, solver.py:320, 325) instead of rediscretising on the host and re-uploading;
         default: on (viscous, grad-div, advection and SUPG terms), unless ALFI_DEVICE_ASSEMBLY=0."""
@@ -69,7 +70,7 @@ class HipNavierStokesSolver(object):
             raise NotImplementedError("supg with a discontinuous P_k pressure couples grad p into the momentum block")
         if stabilisation_type == "burman" and not self.sv:
             raise NotImplementedError("burman is built for the Scott-Vogelius pair (discretisation='sv') only")
-        if stabilisation_type == "burman" and self._partitioned():
+        if stabilisation_type == "burman" and self._partitioned() and not self._partitioned_burman():
             raise NotImplementedError("burman on partitioned levels: the ghost layer would need the facet neighbours")
         self.supg = stabilisation_type == "supg"
         # Burman interior penalty (solver.py:226-228, stabilisation.py:139-162): weight 3e-3 unless given (the reference's
@@ -191,6 +192,10 @@ class HipNavierStokesSolver(object):
 
     def _partitioned(self):
         """Whether the levels are partitioned over ranks (alfi_amd.dist.DistNavierStokesSolver)."""
+        return False
+
+    def _partitioned_burman(self):
+        """Whether a partitioned solver forms the Burman terms of its ranks' rows (alfi_amd.dist.DistNavierStokesSolver)."""
         return False
 
     def _lazy_generation(self):

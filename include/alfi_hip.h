@@ -205,7 +205,7 @@ int alfi_level_apply_bc(alfi_level* lvl);
 /* Burman interior-penalty stabilisation of the Scott-Vogelius pair on the device (alfi/stabilisation.py:139-162,
  * alfi/solver.py:226-234; the reference's `--stabilisation-type burman`): the project's first interior-facet term.
  * alfi_level_set_facet_blocks(lvl, 1), BEFORE alfi_level_set_assembly, declares that the level's sparsity also couples the
- * nodes of cells sharing a facet (blocks without a contributing cell are then accepted; unpartitioned levels only).
+ * nodes of cells sharing a facet (blocks without a contributing cell are then accepted).
  * alfi_level_set_burman (after alfi_level_set_assembly) hands over the interior-facet tables of alfi_amd/burman.py:
  * funion (nfacet, nu) -- K+'s nodes, then K-'s nodes off the facet --, cfg (nfacet) configuration of K+, J (nfacet, nqs, nu)
  * jumps of the normal derivatives at the points of the exact facet rule (weights ws, summing to 1), area / coef (nfacet)
@@ -216,7 +216,11 @@ int alfi_level_apply_bc(alfi_level* lvl);
  * or its residual contribution to d_F (may be NULL).  alfi_level_assemble_burman is the refresh of a stabilised run:
  * A = nu K + gamma D + adv N(state) + adv * weight * the linearised Burman term, then the boundary conditions.  One lane per
  * facet forms a compact record (beta_F, the jumps of grad u, the derivative weights of beta_F), one lane per block / node
- * sums its facet contributors in list order: no atomics, bitwise reproducible. */
+ * sums its facet contributors in list order: no atomics, bitwise reproducible.
+ * On a partitioned level (as alfi_level_set_assembly there): the rank's facets -- those with a cell among its assembly cells --
+ * with funion in the numbering of its state vector, whose nodes may lie beyond the cells' nodes (a facet's off-rank cell: the
+ * state then grows to cover them, alfi_level_assembly_state_size); the lists hold the pairs of local rows and local columns
+ * (at most nfacet * nu^2) and the nodes of local rows (at most nfacet * nu). */
 int alfi_level_set_facet_blocks(alfi_level* lvl, int on);
 int alfi_level_set_burman(alfi_level* lvl, int64_t nfacet, int nu, int nqs, int nqn, int ncfg, const int32_t* funion,
                           const int32_t* cfg, const double* J, const double* area, const double* coef, const double* ws,

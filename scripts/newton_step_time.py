@@ -10,6 +10,7 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
 def main():
@@ -19,15 +20,14 @@ def main():
     ap.add_argument("--re", type=float, nargs="+", default=[10.0, 100.0])
     ap.add_argument("--supg", type=float, default=None, metavar="WEIGHT",
                     help="SUPG stabilisation with this weight (the reference's production runs: 0.05, generate_submission:18-20)")
+    ap.add_argument("--burman", type=float, default=None, metavar="WEIGHT",
+                    help="Burman stabilisation of the Scott-Vogelius configs (cfg5s, cfg5) with this weight")
     args = ap.parse_args()
-    import bench
     from alfi_amd.nssolver import HipNavierStokesSolver
-    from alfi_amd.problem import TwoDimLidDrivenCavityProblem, ThreeDimLidDrivenCavityProblem
-    dim, baseN, nref, ke, Re, k = bench.CONFIGS[args.config]
-    prob = TwoDimLidDrivenCavityProblem(baseN) if dim == 2 else ThreeDimLidDrivenCavityProblem(baseN)
+    from dist_newton_time import problem_and_options
+    prob, nref, ke, kw = problem_and_options(args)
     t0 = time.time()
-    s = HipNavierStokesSolver(prob, nref, ke, device_assembly=not args.host,
-                              stabilisation_type="supg" if args.supg is not None else None, stabilisation_weight=args.supg)
+    s = HipNavierStokesSolver(prob, nref, ke, device_assembly=not args.host, **kw)
     print("%s: %d velocity + %d pressure dofs, setup %.1f s, device assembly %s" % (args.config, s.n_u, s.n_p, time.time() - t0,
                                                                                   s.device_assembly), flush=True)
     for re in args.re:
