@@ -42,6 +42,7 @@ def lib():
         _lib.alfi_host_interior_blocks.restype = ctypes.c_int
         _lib.alfi_host_bsr_transpose.restype = ctypes.c_int
         _lib.alfi_host_supg.restype = ctypes.c_int
+        _lib.alfi_host_gls.restype = ctypes.c_int
         _lib.alfi_host_burman.restype = ctypes.c_int
         # ALFI_HOST_THREADS overrides OMP_NUM_THREADS (torch.distributed.run exports OMP_NUM_THREADS=1 to every rank)
         nthr = int(os.environ.get("ALFI_HOST_THREADS", "0")) or cpu_share()
@@ -106,26 +107,61 @@ def cell_size(mesh):
     return 2.0 * rad
 
 
-def supg(V, U, nu, weight, magic, rowptr=None, colidx=None, vals=None, F=None, nq=None):
-    """SUPG stabilisation (stabilisation.py:47-97, solver.py:204-234) about the state U (num_nodes, dim): adds the residual
-    contribution to F (num_dofs) and / or the Newton linearisation to the BSR values ``vals``.  Quadrature degree 2k."""
+def supg_rule(V, nq=None):
+    """(lam, wq): the quadrature rule of the SUPG / GLS terms on the space V -- degree 2k, n points per direction, exact to
+    2n - 1 >= 2k (the rule of ``supg``, ``gls`` and hip.DeviceLevel.set_supg)."""
     from .elements import simplex_quadrature
-    mesh, el, d = V.mesh, V.element, V.dim
+    el = V.element
     deg = 3 if (el.bubble or el.degree == 3) else el.degree                  # ufl degree of the (enriched) element
-    lam, wq = simplex_quadrature(d, nq or (deg + 1))                          # n points per direction: exact to 2n - 1 >= 2k
+    return simplex_quadrature(V.dim, nq or (deg + 1))
+
+
+def supg_points(V, nq=None):
+    """Physical coordinates (ncell, nq, dim) of the points of ``supg_rule`` in every cell of V's mesh, in rule order."""
+    lam, _ = supg_rule(V, nq)
+    m = V.mesh
+    return np.einsum("qv,cvx->cqx", lam, m.coords[m.cells])
+
+
+def _stabilisation(V, U, W, nu, weight, magic, rowptr, colidx, vals, F, nq, fq):
+    mesh, el, d = V.mesh, V.element, V.dim
+    lam, wq = supg_rule(V, nq)
     phi, dphi = el.tabulate(lam)
     d2phi = el.tabulate_hessian(lam)
     g, vol = mesh.cell_geometry()
     h = cell_size(mesh)
     cn = np.ascontiguousarray(V.cell_nodes, dtype=np.int32)
     U = np.ascontiguousarray(U, dtype=np.float64)
+    if fq is not None:
+        fq = np.ascontiguousarray(fq, dtype=np.float64)
+        assert fq.shape == (cn.shape[0], len(wq), d), "body force table must be (ncell, nq, dim) in supg_rule order"
     arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (g, vol, h, wq, phi, dphi, d2phi)]
-    rc = lib().alfi_host_supg(ctypes.c_int64(cn.shape[0]), ctypes.c_int(cn.shape[1]), ctypes.c_int(d), _p(cn), _p(arrs[0]),
-                              _p(arrs[1]), _p(arrs[2]), ctypes.c_int(len(wq)), _p(arrs[3]), _p(arrs[4]), _p(arrs[5]),
-                              _p(arrs[6]), _p(U), ctypes.c_double(nu), ctypes.c_double(weight), ctypes.c_double(magic),
-                              _p(rowptr), _p(colidx), _p(vals), _p(F))
+    head = (ctypes.c_int64(cn.shape[0]), ctypes.c_int(cn.shape[1]), ctypes.c_int(d), _p(cn), _p(arrs[0]), _p(arrs[1]),
+            _p(arrs[2]), ctypes.c_int(len(wq)), _p(arrs[3]), _p(arrs[4]), _p(arrs[5]), _p(arrs[6]), _p(U))
+    tail = (ctypes.c_double(nu), ctypes.c_double(weight), ctypes.c_double(magic), _p(rowptr), _p(colidx), _p(vals), _p(F),
+            _p(fq))
+    if W is None:
+        rc = lib().alfi_host_supg(*head, *tail)
+    else:
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        assert W.size == U.size, "the wind has the state's shape"
+        rc = lib().alfi_host_gls(*head, _p(W), *tail)
     if rc != 0:
-        raise RuntimeError("supg failed (%d): sparsity pattern does not cover the mesh" % rc)
+        raise RuntimeError("%s failed (%d): sparsity pattern does not cover the mesh" % ("supg" if W is None else "gls", rc))
+
+
+def supg(V, U, nu, weight, magic, rowptr=None, colidx=None, vals=None, F=None, nq=None, fq=None):
+    """SUPG stabilisation (stabilisation.py:47-97, solver.py:204-234) about the state U (num_nodes, dim): adds the residual
+    contribution to F (num_dofs) and / or the Newton linearisation to the BSR values ``vals``.  Quadrature degree 2k.
+    fq (ncell, nq, dim): the body force at the points of ``supg_rule`` (subtracted in the strong residual, solver.py:216-217)."""
+    _stabilisation(V, U, None, nu, weight, magic, rowptr, colidx, vals, F, nq, fq)
+
+
+def gls(V, U, W, nu, weight, magic, rowptr=None, colidx=None, vals=None, F=None, nq=None, fq=None):
+    """GLS stabilisation (stabilisation.py:47-97, solver.py:204-234): weight beta (Lu - f, L_W v) with the strong operator
+    applied to the test function about the wind W (num_nodes, dim; the state at the start of the solve, not differentiated).
+    Same contract as ``supg``."""
+    _stabilisation(V, U, W, nu, weight, magic, rowptr, colidx, vals, F, nq, fq)
 
 
 def burman(table, U, weight, lists, vals=None, F=None, beta=None):

@@ -72,6 +72,10 @@ SIGNATURES = {
     "alfi_level_assemble_mult": (ctypes.c_int, [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, vp, vp]),
     "alfi_level_set_supg": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, vp, vp, vp]),
     "alfi_level_supg": (ctypes.c_int, [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, ctypes.c_int, vp]),
+    "alfi_level_set_supg_load": (ctypes.c_int, [vp, vp]),
+    "alfi_level_assemble_gls": (ctypes.c_int, [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, vp, ctypes.c_double,
+                                               ctypes.c_double, ctypes.c_int]),
+    "alfi_level_gls": (ctypes.c_int, [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, vp, ctypes.c_int, vp]),
     "alfi_level_apply_bc": (ctypes.c_int, [vp]),
     "alfi_level_set_facet_blocks": (ctypes.c_int, [vp, ctypes.c_int]),
     "alfi_level_set_burman": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [vp] * 14),

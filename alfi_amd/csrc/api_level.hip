@@ -242,7 +242,7 @@ void free_assembly(AssemblyDev* S) {
   dev_free(S->cptr); dev_free(S->ccell); dev_free(S->cba); dev_free(S->cell_nodes); dev_free(S->grad); dev_free(S->vol);
   dev_free(S->etab); dev_free(S->bItab); dev_free(S->bc_code); dev_free(S->bc_all);
   dev_free(S->wq); dev_free(S->phi); dev_free(S->dphi); dev_free(S->d2phi); dev_free(S->hcell); dev_free(S->diag);
-  dev_free(S->wq8); dev_free(S->qtab); dev_free(S->brc);
+  dev_free(S->wq8); dev_free(S->qtab); dev_free(S->brc); dev_free(S->fq8);
   dev_free(S->funion); dev_free(S->fcfg); dev_free(S->fJ); dev_free(S->farea); dev_free(S->fcoef); dev_free(S->fws);
   dev_free(S->fwn); dev_free(S->fphin); dev_free(S->fbptr); dev_free(S->fbfac); dev_free(S->fbab); dev_free(S->fnptr);
   dev_free(S->fnfac); dev_free(S->fna);
@@ -379,7 +379,8 @@ int alfi_level_assemble(alfi_level* L, double nu, double gamma, double adv, cons
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->cur_tag = L->id;
   int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);       // PCPatchComputeOp
-  ALFI_CHECK(launch_operator_refresh(L, nu, gamma, adv, d_state, true, false, 0.0, 0.0, false, apply_bc != 0, L->A.vals));
+  ALFI_CHECK(launch_operator_refresh(L, nu, gamma, adv, d_state, true, ALFI_STAB_NONE, nullptr, 0.0, 0.0, false, apply_bc != 0,
+                                     L->A.vals));
   alfi_prof_end(ctx, t);
   L->factored = false;
   L->fc_scale = 0.0;
@@ -395,8 +396,26 @@ int alfi_level_assemble_supg(alfi_level* L, double nu, double gamma, double adv,
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->cur_tag = L->id;
   int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);
-  ALFI_CHECK(launch_operator_refresh(L, nu, gamma, adv, d_state, true, true, weight, magic, false, apply_bc != 0, L->A.vals));
+  ALFI_CHECK(launch_operator_refresh(L, nu, gamma, adv, d_state, true, ALFI_STAB_SUPG, nullptr, weight, magic, false, apply_bc != 0,
+                                     L->A.vals));
   alfi_prof_end(ctx, t);
+  L->factored = false;
+  return 0;
+}
+
+// The same for GLS: A = nu K + gamma D + adv N(state) + the linearised GLS term about the state with the wind d_wind
+int alfi_level_assemble_gls(alfi_level* L, double nu, double gamma, double adv, const double* d_state, const double* d_wind,
+                            double weight, double magic, int apply_bc) {
+  alfi_ctx* ctx = L->ctx;
+  if (!L->asmb.supg_ready) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_level_assemble_gls before alfi_level_set_supg");
+  if (!d_state || !d_wind) return alfi_set_error(ctx, ALFI_E_ARG, "GLS needs the state and the wind");
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ctx->cur_tag = L->id;
+  int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);
+  const int rc = launch_operator_refresh(L, nu, gamma, adv, d_state, true, ALFI_STAB_GLS, d_wind, weight, magic, false,
+                                         apply_bc != 0, L->A.vals);
+  alfi_prof_end(ctx, t);
+  if (rc != 0) return rc;
   L->factored = false;
   return 0;
 }
@@ -459,7 +478,8 @@ int alfi_level_set_supg(alfi_level* L, int nq, const double* wq, const double* p
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   dev_free(S.wq); dev_free(S.phi); dev_free(S.dphi); dev_free(S.d2phi); dev_free(S.hcell); dev_free(S.wq8); dev_free(S.qtab);
-  S.wq = S.phi = S.dphi = S.d2phi = S.hcell = S.wq8 = S.qtab = nullptr;
+  dev_free(S.fq8);
+  S.wq = S.phi = S.dphi = S.d2phi = S.hcell = S.wq8 = S.qtab = S.fq8 = nullptr;
   S.supg_ready = false;
   const int nv = L->bs + 1, nloc = S.nloc;
   ALFI_CHECK(dev_upload(ctx, &S.wq, wq, nq));
@@ -493,20 +513,56 @@ int alfi_level_set_supg(alfi_level* L, int nq, const double* wq, const double* p
   return 0;
 }
 
+// The body force at the points of alfi_level_set_supg's rule, (ncell, nq, d) in rule order (NULL: none), subtracted in the
+// strong residual of the SUPG and GLS terms; padded here to the linearisation kernel's eight-point chunks
+int alfi_level_set_supg_load(alfi_level* L, const double* fq) {
+  alfi_ctx* ctx = L->ctx;
+  AssemblyDev& S = L->asmb;
+  if (!S.supg_ready) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_level_set_supg_load before alfi_level_set_supg");
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  dev_free(S.fq8);
+  S.fq8 = nullptr;
+  if (!fq) return 0;
+  const int d = L->bs, nq = S.nq, nq8 = S.nq8;
+  std::vector<double> f8((size_t)S.ncell * nq8 * d, 0.0);
+  for (int64_t c = 0; c < S.ncell; ++c)
+    std::copy(fq + (size_t)c * nq * d, fq + (size_t)(c + 1) * nq * d, f8.begin() + (size_t)c * nq8 * d);
+  return dev_upload(ctx, &S.fq8, f8.data(), (int64_t)f8.size());
+}
+
+// SUPG (d_wind NULL) or GLS terms about d_state: the linearisation into the operator and / or the residual into d_F
+static int level_stabilisation(alfi_level* L, int stab, double nu, double weight, double magic, const double* d_state,
+                               const double* d_wind, int add_to_operator, double* d_F) {
+  alfi_ctx* ctx = L->ctx;
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ctx->cur_tag = L->id;
+  int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);       // PCPatchComputeOp
+  int rc = 0;
+  if (add_to_operator)
+    rc = launch_operator_refresh(L, nu, 0.0, 0.0, d_state, false, stab, d_wind, weight, magic, true, false, L->A.vals);
+  if (rc == 0 && d_F) rc = launch_supg_residual(L, nu, weight, magic, d_state, d_wind, d_F);
+  alfi_prof_end(ctx, t);
+  if (rc != 0) return rc;
+  if (add_to_operator) L->factored = false;
+  return 0;
+}
+
 int alfi_level_supg(alfi_level* L, double nu, double weight, double magic, const double* d_state, int add_to_operator, double* d_F) {
   alfi_ctx* ctx = L->ctx;
   if (!L->asmb.supg_ready) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_level_supg before alfi_level_set_supg");
   if (!d_state) return alfi_set_error(ctx, ALFI_E_ARG, "SUPG needs the state");
   if (!add_to_operator && !d_F) return 0;
-  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  ctx->cur_tag = L->id;
-  int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);       // PCPatchComputeOp
-  if (add_to_operator)
-    ALFI_CHECK(launch_operator_refresh(L, nu, 0.0, 0.0, d_state, false, true, weight, magic, true, false, L->A.vals));
-  if (d_F) ALFI_CHECK(launch_supg_residual(L, nu, weight, magic, d_state, d_F));
-  alfi_prof_end(ctx, t);
-  if (add_to_operator) L->factored = false;
-  return 0;
+  return level_stabilisation(L, ALFI_STAB_SUPG, nu, weight, magic, d_state, nullptr, add_to_operator, d_F);
+}
+
+int alfi_level_gls(alfi_level* L, double nu, double weight, double magic, const double* d_state, const double* d_wind,
+                   int add_to_operator, double* d_F) {
+  alfi_ctx* ctx = L->ctx;
+  if (!L->asmb.supg_ready) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_level_gls before alfi_level_set_supg");
+  if (!d_state || !d_wind) return alfi_set_error(ctx, ALFI_E_ARG, "GLS needs the state and the wind");
+  if (!add_to_operator && !d_F) return 0;
+  return level_stabilisation(L, ALFI_STAB_GLS, nu, weight, magic, d_state, d_wind, add_to_operator, d_F);
 }
 
 // Burman interior-penalty stabilisation (alfi/stabilisation.py:139-162; alfi_amd/burman.py): the facet tables and the facet
@@ -616,7 +672,7 @@ int alfi_level_assemble_burman(alfi_level* L, double nu, double gamma, double ad
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->cur_tag = L->id;
   int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);
-  ALFI_CHECK(launch_operator_refresh(L, nu, gamma, adv, d_state, true, false, 0.0, 0.0, false, false, L->A.vals));
+  ALFI_CHECK(launch_operator_refresh(L, nu, gamma, adv, d_state, true, ALFI_STAB_NONE, nullptr, 0.0, 0.0, false, false, L->A.vals));
   if (adv != 0.0) ALFI_CHECK(launch_burman(L, adv * weight, d_state, true, nullptr));
   if (apply_bc) ALFI_CHECK(launch_apply_bc(L));
   alfi_prof_end(ctx, t);

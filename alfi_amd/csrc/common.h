@@ -343,6 +343,7 @@ struct AssemblyDev {
   int nq8 = 0;                   // nq rounded up to a multiple of eight (zero-weight copies of point 0): two k-steps of the MFMA per chunk
   double* wq8 = nullptr;         // (nq8)
   double* qtab = nullptr;        // (nq8, nloc, 1 + (d+1) + (d+1)(d+2)/2): phi | dphi | upper triangle of d2phi per (point, node)
+  double* fq8 = nullptr;         // (ncell, nq8, d) or NULL: the body force at the points (alfi_level_set_supg_load), zero-padded
   // facet-coupled levels (alfi_level_set_facet_blocks before alfi_level_set_assembly): blocks may have no contributing cell,
   // so the Dirichlet kernels take every block's (row node, column node) from here instead of its first contributor
   int32_t* brc = nullptr;        // (nnzb, 2) or NULL
@@ -659,10 +660,14 @@ int launch_patch_sum_scale(alfi_level* lvl, const double* w, double* z, double* 
 int launch_bsr_spmv_dot(alfi_ctx* ctx, const DevBSR& A, const double* z, double* w, const double* V, int64_t stride, int nv,
                         double* partial, int* nblocks);
 // kernels_assemble.hip: the level operator from its cells (element blocks -> one fixed-order gather); out_vals: the operator's layout
+// stab: which residual-based stabilisation is linearised into the operator (d_wind: GLS's wind)
+enum { ALFI_STAB_NONE = 0, ALFI_STAB_SUPG = 1, ALFI_STAB_GLS = 2 };
 int launch_operator_refresh(alfi_level* lvl, double nu, double gamma, double adv, const double* d_state, bool with_elements,
-                            bool with_supg, double weight, double magic, bool accumulate, bool apply_bc, double* out_vals);
+                            int stab, const double* d_wind, double weight, double magic, bool accumulate, bool apply_bc,
+                            double* out_vals);
 int launch_element_mult(alfi_level* lvl, double nu, double gamma, double adv, const double* d_state, const double* dx, double* dy);
-int launch_supg_residual(alfi_level* lvl, double nu, double weight, double magic, const double* d_state, double* d_F);
+int launch_supg_residual(alfi_level* lvl, double nu, double weight, double magic, const double* d_state, const double* d_wind,
+                         double* d_F);
 int launch_burman(alfi_level* lvl, double weight, const double* d_state, bool add_to_operator, double* d_F);
 // subtract the facet terms PCPATCH leaves out from nb dense patch matrices (row-major, leading dimension: (n + 1) & ~1 when
 // big == 0, n rounded up to BIG_NB otherwise) of the patches p0 .. p0 + nb at dst + mat_ptr[i]

@@ -482,35 +482,46 @@ int alfi_host_set_num_threads(int n) {
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// SUPG stabilisation of the momentum equation (alfi/stabilisation.py:47-97 with the Shakib-Hughes-Johan coefficient,
-// alfi/solver.py:204-234: stabilisation_form = weight * beta * inner(Lu, dot(grad(v), u)) * dx(degree = 2k), state = u):
-//   Lu   = -nu div(2 sym grad u) + (grad u) u   (+ grad p, zero for the piecewise constant pressure)
+// SUPG and GLS stabilisation of the momentum equation (alfi/stabilisation.py:47-97 with the Shakib-Hughes-Johan coefficient,
+// alfi/solver.py:204-234, state = u, body force f):
+//   Lu   = -nu div(2 sym grad u) + (grad u) u - f   (+ grad p, zero for the piecewise constant pressure)
 //   beta = (4 u.u / h^2 + magic (4 nu / h^2)^2)^(-1/2)
+//   SUPG: weight * beta * inner(Lu, dot(grad(v), u)) * dx(degree = 2k)
+//   GLS:  weight * beta * inner(Lu, L_w v) * dx(degree = 2k),  L_w v = -nu div(2 sym grad v) + (grad v) w,
+//         w = the velocity at the start of the solve (z_last, solver.py:199, 205, 215), not differentiated
 // by quadrature (beta is not polynomial).  F (n dofs, may be NULL) += the residual contribution; vals (BSR, may be NULL)
-// += its Newton linearisation about u:
-//   dF[a,i; b,j] = int wgt [ dbeta_j (Lu)_i s_a + beta (dLu)_ij s_a + beta (Lu)_i phi_b d_j phi_a ],
-//   s_a = u.grad phi_a,  dbeta_j = -4 beta^3 u_j phi_b / h^2,
-//   (dLu)_ij = -nu (delta_ij Lap phi_b + d_i d_j phi_b) + delta_ij s_b + phi_b d_j u_i.
+// += its Newton linearisation about u.  The test side of basis pair (a, i) is the d-vector T_aik:
+//   SUPG: T_aik = delta_ik s_a,   GLS: T_aik = delta_ik (sw_a - nu Lap phi_a) - nu d_k d_i phi_a,
+//   s_a = u.grad phi_a,  sw_a = w.grad phi_a;
+//   F[a,i]        += wgt beta sum_k Lu_k T_aik,
+//   dF[a,i; b,j]  += wgt sum_k T_aik (dbeta_j Lu_k + beta (dLu)_kj)   (+ SUPG: wgt beta Lu_i phi_b d_j phi_a),
+//   dbeta_j = -4 beta^3 u_j phi_b / h^2,
+//   (dLu)_kj = -nu (delta_kj Lap phi_b + d_k d_j phi_b) + delta_kj s_b + phi_b d_j u_k.
 // phi (nq, nloc), dphi (nq, nloc, d+1), d2phi (nq, nloc, d+1, d+1): basis and its derivatives w.r.t. the barycentric
-// coordinates at the quadrature points; wq (nq) sums to 1; h (ncell): cell size; U (nnode, d): state.
+// coordinates at the quadrature points; wq (nq) sums to 1; h (ncell): cell size; U (nnode, d): state; W (nnode, d): the GLS
+// wind; fq (ncell, nq, d, may be NULL): the body force at the quadrature points.
 // ---------------------------------------------------------------------------------------------------------------------
-int alfi_host_supg(int64_t ncell, int nloc, int d, const int32_t* cell_nodes, const double* g, const double* vol,
-                   const double* h, int nq, const double* wq, const double* phi, const double* dphi, const double* d2phi,
-                   const double* U, double nu, double weight, double magic, const int32_t* rowptr, const int32_t* colidx,
-                   double* vals, double* F) {
+static int host_stabilisation(bool gls, int64_t ncell, int nloc, int d, const int32_t* cell_nodes, const double* g,
+                              const double* vol, const double* h, int nq, const double* wq, const double* phi,
+                              const double* dphi, const double* d2phi, const double* U, const double* W, const double* fq,
+                              double nu, double weight, double magic, const int32_t* rowptr, const int32_t* colidx,
+                              double* vals, double* F) {
   const int nv = d + 1;
   const int ndof = nloc * d;
   int err = 0;
 #pragma omp parallel
   {
-    std::vector<double> Ae((size_t)ndof * ndof), Fe(ndof), Uk((size_t)nloc * d), gp((size_t)nloc * d),
-        hs((size_t)nloc * d * d), lap(nloc), s(nloc);
+    std::vector<double> Ae((size_t)ndof * ndof), Fe(ndof), Uk((size_t)nloc * d), Wk((size_t)nloc * d), gp((size_t)nloc * d),
+        hs((size_t)nloc * d * d), lap(nloc), s(nloc), tq(nloc), C((size_t)d * ndof);
 #pragma omp for schedule(dynamic, 64)
     for (int64_t c = 0; c < ncell; ++c) {
       const int32_t* cn = cell_nodes + c * nloc;
       const double* gc = g + c * nv * d;
       for (int a = 0; a < nloc; ++a)
-        for (int x = 0; x < d; ++x) Uk[a * d + x] = U[(int64_t)cn[a] * d + x];
+        for (int x = 0; x < d; ++x) {
+          Uk[a * d + x] = U[(int64_t)cn[a] * d + x];
+          if (gls) Wk[a * d + x] = W[(int64_t)cn[a] * d + x];
+        }
       std::fill(Ae.begin(), Ae.end(), 0.0);
       std::fill(Fe.begin(), Fe.end(), 0.0);
       const double h2 = h[c] * h[c];
@@ -536,31 +547,49 @@ int alfi_host_supg(int64_t ncell, int nloc, int d, const int32_t* cell_nodes, co
             }
           lap[a] = l;
         }
-        // state at the point
-        double u[3] = {0, 0, 0}, Gu[3][3] = {{0}}, Lu[3] = {0, 0, 0};
+        // state (and wind) at the point
+        double u[3] = {0, 0, 0}, w[3] = {0, 0, 0}, Gu[3][3] = {{0}}, Lu[3] = {0, 0, 0};
         for (int a = 0; a < nloc; ++a)
           for (int i = 0; i < d; ++i) {
             const double ui = Uk[a * d + i];
             u[i] += ph[a] * ui;
+            if (gls) w[i] += ph[a] * Wk[a * d + i];
             for (int x = 0; x < d; ++x) Gu[i][x] += gp[a * d + x] * ui;
             Lu[i] -= nu * lap[a] * ui;                                             // -nu Lap u_i
             for (int j = 0; j < d; ++j) Lu[j] -= nu * hs[((size_t)a * d + j) * d + i] * ui;   // -nu d_j div u
           }
         for (int i = 0; i < d; ++i)
           for (int x = 0; x < d; ++x) Lu[i] += u[x] * Gu[i][x];
+        if (fq)
+          for (int i = 0; i < d; ++i) Lu[i] -= fq[((size_t)c * nq + q) * d + i];
         double uu = 0.0;
         for (int i = 0; i < d; ++i) uu += u[i] * u[i];
         const double vis = 4.0 * nu / h2;
         const double beta = 1.0 / std::sqrt(4.0 * uu / h2 + magic * vis * vis);
+        // s_a = u.grad phi_a; tq_a = the diagonal part of the test side (SUPG: s_a, GLS: w.grad phi_a - nu Lap phi_a)
         for (int a = 0; a < nloc; ++a) {
-          double t = 0.0;
-          for (int x = 0; x < d; ++x) t += u[x] * gp[a * d + x];
+          double t = 0.0, tw = 0.0;
+          for (int x = 0; x < d; ++x) {
+            t += u[x] * gp[a * d + x];
+            tw += w[x] * gp[a * d + x];
+          }
           s[a] = t;
+          tq[a] = gls ? tw - nu * lap[a] : t;
         }
         const double wt = wq[q] * vol[c] * weight;
-        for (int a = 0; a < nloc; ++a)
-          for (int i = 0; i < d; ++i) Fe[a * d + i] += wt * beta * Lu[i] * s[a];
-        if (vals) {
+        if (!gls) {
+          // (SUPG keeps the association of its first host pass: with fq = NULL the result is the same to the bit)
+          for (int a = 0; a < nloc; ++a)
+            for (int i = 0; i < d; ++i) Fe[a * d + i] += wt * beta * Lu[i] * s[a];
+        } else {
+          for (int a = 0; a < nloc; ++a)
+            for (int i = 0; i < d; ++i) {
+              double t = Lu[i] * tq[a];
+              for (int k = 0; k < d; ++k) t -= nu * Lu[k] * hs[((size_t)a * d + k) * d + i];
+              Fe[a * d + i] += wt * beta * t;
+            }
+        }
+        if (vals && !gls) {
           const double b3 = -4.0 * beta * beta * beta / h2;
           for (int a = 0; a < nloc; ++a)
             for (int i = 0; i < d; ++i) {
@@ -572,6 +601,27 @@ int alfi_host_supg(int64_t ncell, int nloc, int d, const int32_t* cell_nodes, co
                   row[b * d + j] += wt * (b3 * u[j] * ph[b] * Lu[i] * s[a] + beta * dL * s[a] +
                                           beta * Lu[i] * ph[b] * gp[a * d + j]);
                 }
+            }
+        } else if (vals) {
+          const double b3 = -4.0 * beta * beta * beta / h2;
+          // GLS: C[k][(b, j)] = wt (b3 u_j phi_b Lu_k + beta (dLu)_kj), row (a, i) = sum_k T_aik C[k]
+          for (int k = 0; k < d; ++k)
+            for (int b = 0; b < nloc; ++b)
+              for (int j = 0; j < d; ++j) {
+                double dL = -nu * hs[((size_t)b * d + k) * d + j] + ph[b] * Gu[k][j];
+                if (k == j) dL += -nu * lap[b] + s[b];
+                C[(size_t)k * ndof + b * d + j] = wt * (b3 * u[j] * ph[b] * Lu[k] + beta * dL);
+              }
+          for (int a = 0; a < nloc; ++a)
+            for (int i = 0; i < d; ++i) {
+              double* row = Ae.data() + (size_t)(a * d + i) * ndof;
+              const double* Ci = C.data() + (size_t)i * ndof;
+              for (int bj = 0; bj < ndof; ++bj) row[bj] += tq[a] * Ci[bj];
+              for (int k = 0; k < d; ++k) {
+                const double hk = -nu * hs[((size_t)a * d + k) * d + i];
+                const double* Ck = C.data() + (size_t)k * ndof;
+                for (int bj = 0; bj < ndof; ++bj) row[bj] += hk * Ck[bj];
+              }
             }
         }
       }
@@ -601,6 +651,23 @@ int alfi_host_supg(int64_t ncell, int nloc, int d, const int32_t* cell_nodes, co
     }
   }
   return err ? -2 : 0;
+}
+
+int alfi_host_supg(int64_t ncell, int nloc, int d, const int32_t* cell_nodes, const double* g, const double* vol,
+                   const double* h, int nq, const double* wq, const double* phi, const double* dphi, const double* d2phi,
+                   const double* U, double nu, double weight, double magic, const int32_t* rowptr, const int32_t* colidx,
+                   double* vals, double* F, const double* fq) {
+  return host_stabilisation(false, ncell, nloc, d, cell_nodes, g, vol, h, nq, wq, phi, dphi, d2phi, U, nullptr, fq, nu, weight,
+                            magic, rowptr, colidx, vals, F);
+}
+
+int alfi_host_gls(int64_t ncell, int nloc, int d, const int32_t* cell_nodes, const double* g, const double* vol,
+                  const double* h, int nq, const double* wq, const double* phi, const double* dphi, const double* d2phi,
+                  const double* U, const double* W, double nu, double weight, double magic, const int32_t* rowptr,
+                  const int32_t* colidx, double* vals, double* F, const double* fq) {
+  if (!W) return -1;
+  return host_stabilisation(true, ncell, nloc, d, cell_nodes, g, vol, h, nq, wq, phi, dphi, d2phi, U, W, fq, nu, weight, magic,
+                            rowptr, colidx, vals, F);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

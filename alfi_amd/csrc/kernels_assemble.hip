@@ -331,28 +331,40 @@ __device__ inline double supg_rsqrt(double x) {
   return y;
 }
 
+// GLS (GLS = true, alfi/solver.py:204-234 with the test side L_w v = -nu div(2 sym grad v) + (grad v) w, w = the wind W fixed
+// during the solve): entry ((a, i), (b, j)) = sum_q sum_k T_aik C1[q][(b, k, j)], T_aik = delta_ik wt (w . grad phi_a - nu lap_a)
+// - wt nu H_a[k][i]:
+//     = sum_q SAW[a][q] C1[q][(b,i,j)]  +  sum_(q,k) HW[(a,i)][(q,k)] C1[(q,k)][(b,j)]
+// GEMM 1 as for SUPG with the GLS diagonal part in the A operand; GEMM H (wave 1, instead of GEMM 2) runs over K = (point,
+// component), three times GEMM 2's depth in 3-D, its B operand C1 read in the (q, k) x (b, j) view (the column's (b, j) decoded
+// once per tile, outside the loop).  The wind adds D state quantities (18 in 3-D): the lanes r < NS - 16 reduce a second one.
+// fq8 (ncell, 8 nchunk, D; may be NULL): the body force at the points, subtracted in Lu (SUPG and GLS alike).
 // qtab: per point p (padded to a multiple of EIGHT with zero-weight copies of point 0) and local node a:
 //       [phi | dphi (d+1) | d2phi, upper triangle (d+1)(d+2)/2], derivatives w.r.t. the barycentric coordinates
-template <int D, int NLOC>
+template <int D, int NLOC, bool GLS>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void supg_matrix_kernel(int64_t c0, int64_t ncell, const int32_t* __restrict__ cell_nodes,
                                                            const double* __restrict__ grad, const double* __restrict__ vol,
                                                            const double* __restrict__ hcell, int nchunk,
                                                            const double* __restrict__ wq8, const double* __restrict__ qtab,
-                                                           const double* __restrict__ U, double nu, double weight, double magic,
+                                                           const double* __restrict__ U, const double* __restrict__ W,
+                                                           const double* __restrict__ fq8, double nu, double weight, double magic,
                                                            int add, double* __restrict__ E) {
   constexpr int NV = D + 1, DD = D * D, ND = NLOC * D, ND2 = NLOC * DD;
-  constexpr int NT1 = (ND2 + 15) / 16, NR2 = (ND + 15) / 16;       // column tiles of GEMM 1, row = column tiles of GEMM 2
+  constexpr int NT1 = (ND2 + 15) / 16, NR2 = (ND + 15) / 16;       // column tiles of GEMM 1, row = column tiles of GEMM 2 / H
   constexpr int NA = NT1 > NR2 * NR2 ? NT1 : NR2 * NR2;            // accumulator tiles of a wave
-  constexpr int NS = 2 * D + DD, NH2 = NV * (NV + 1) / 2, QT = 1 + NV + NH2;
-  static_assert(NLOC <= 16 && NS <= 16, "a lane per (point, local node)");
-  constexpr int LDS_CHUNK = 8 * NS * 16 + 2 * 128 * NR2 + 2 * 128 + 128 * NT1;
+  constexpr int NS0 = 2 * D + DD, NS = NS0 + (GLS ? D : 0), NH2 = NV * (NV + 1) / 2, QT = 1 + NV + NH2;
+  constexpr int STS = NS > 16 ? 32 : 16;                           // stride of a point's state quantities
+  static_assert(NLOC <= 16 && NS <= 32, "a lane per (point, local node), at most two state quantities per lane");
+  constexpr int N2 = GLS ? 8 * D * 16 * NR2 : 2 * 128 * NR2;      // operands of GEMM 2 (SUPG) / the A operand of GEMM H (GLS)
+  constexpr int LDS_CHUNK = 8 * NS * 16 + N2 + 8 * STS + 128 + 128 * NT1;
   constexpr int LDS_N = LDS_CHUNK > NLOC * ND2 ? LDS_CHUNK : NLOC * ND2;
   __shared__ double sm[LDS_N];
   double* CON = sm;                    // [8][NS][16]     contributions of basis function a to state quantity v at point p
-  double* GPs = CON + 8 * NS * 16;     // [8][16 NR2]     physical gradients, (a, x) -> a D + x: the A operand of GEMM 2
-  double* C2Ws = GPs + 128 * NR2;      // [8][16 NR2]     wt beta L_i phi_b at (b, i) -> b D + i: the B operand of GEMM 2
-  double* ST = C2Ws + 128 * NR2;       // [8][16]         u | grad u | second-order part of Lu
-  double* SAWT = ST + 128;             // [8][16]         wt s_a: the A operand of GEMM 1
+  double* GPs = CON + 8 * NS * 16;     // [8][16 NR2]     SUPG: physical gradients, (a, x) -> a D + x: the A operand of GEMM 2
+  double* C2Ws = GPs + 128 * NR2;      // [8][16 NR2]     SUPG: wt beta L_i phi_b at (b, i) -> b D + i: the B operand of GEMM 2
+  double* AH = GPs;                    // [8 D][16 NR2]   GLS: - wt nu H_a[k][i] at (q, k), (a, i) -> a D + i: the A operand of GEMM H
+  double* ST = GPs + N2;               // [8][STS]        u | grad u | second-order part of Lu (| w)
+  double* SAWT = ST + 8 * STS;         // [8][16]         wt s_a (GLS: wt (w . grad phi_a - nu lap_a)): the A operand of GEMM 1
   double* C1s = SAWT + 128;            // [8][16 NT1]     C1 at (b, i, j) -> (b D + i) D + j: the B operand of GEMM 1
                                        // (operand entries beyond the element's are zero: written once, before the loop)
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, q = lane >> 4, r = lane & 15, p = 4 * wv + q;
@@ -364,11 +376,23 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
   for (int i = 0; i < NV; ++i)
 #pragma unroll
     for (int x = 0; x < D; ++x) g[i][x] = grad[(cell * NV + i) * D + x];
-  double Ua[D];
+  double Ua[D], Wa[D];
   {
     const int64_t node = cell_nodes[cell * NLOC + aa];
 #pragma unroll
-    for (int x = 0; x < D; ++x) Ua[x] = r < NLOC ? U[node * D + x] : 0.0;
+    for (int x = 0; x < D; ++x) {
+      Ua[x] = r < NLOC ? U[node * D + x] : 0.0;
+      if constexpr (GLS) Wa[x] = r < NLOC ? W[node * D + x] : 0.0;
+    }
+  }
+  // GEMM H's B operand: this lane's column (b, j) of every column tile, as an offset into a point's C1 row
+  int hcol[NR2];
+  bool hval[NR2];
+#pragma unroll
+  for (int tc = 0; tc < NR2; ++tc) {
+    const int c = 16 * tc + r, b = c / D, j = c - b * D;
+    hval[tc] = c < ND;
+    hcol[tc] = c < ND ? b * DD + j : 0;
   }
   const double hc = hcell[cell], ih2 = 1.0 / (hc * hc), vw = vol[cell] * weight, vis = 4.0 * nu * ih2;
   for (int e = tid; e < LDS_CHUNK - 8 * NS * 16; e += 128) GPs[e] = 0.0;
@@ -429,8 +453,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
 #pragma unroll
         for (int x = 0; x < D; ++x) cl = __builtin_fma(hs[i][x], Ua[x], cl);
         con[(D + DD + i) * 16] = -nu * cl;
+        if constexpr (GLS) con[(NS0 + i) * 16] = ph * Wa[i];
       }
-      if (r < NLOC) {
+      if (!GLS && r < NLOC) {
 #pragma unroll
         for (int x = 0; x < D; ++x) GPs[p * 16 * NR2 + r * D + x] = gp[x];
       }
@@ -447,7 +472,14 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       double sv = 0.0;
 #pragma unroll
       for (int a = 0; a < 16; ++a) sv += con[a];
-      ST[p * 16 + r] = sv;
+      ST[p * STS + r] = sv;
+    }
+    if (NS > 16 && r + 16 < NS) {
+      const double* con = CON + (p * NS + r + 16) * 16;
+      double sv = 0.0;
+#pragma unroll
+      for (int a = 0; a < 16; ++a) sv += con[a];
+      ST[p * STS + r + 16] = sv;
     }
     __syncthreads();
     // ---- every lane: the state at ITS point
@@ -455,15 +487,16 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       double u[D], Gu[D][D], Lu[D], uu = 0.0;
 #pragma unroll
       for (int i = 0; i < D; ++i) {
-        u[i] = ST[p * 16 + i];
+        u[i] = ST[p * STS + i];
 #pragma unroll
-        for (int x = 0; x < D; ++x) Gu[i][x] = ST[p * 16 + D + i * D + x];
+        for (int x = 0; x < D; ++x) Gu[i][x] = ST[p * STS + D + i * D + x];
       }
 #pragma unroll
       for (int i = 0; i < D; ++i) {
-        double t = ST[p * 16 + D + DD + i];
+        double t = ST[p * STS + D + DD + i];
 #pragma unroll
         for (int x = 0; x < D; ++x) t = __builtin_fma(u[x], Gu[i][x], t);
+        if (fq8) t -= fq8[((int64_t)cell * 8 * nchunk + 8 * ch + p) * D + i];
         Lu[i] = t;
         uu = __builtin_fma(u[i], u[i], uu);
       }
@@ -477,7 +510,14 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
       // (- nu lap_b + s_b)),  C2W[(b, i)] = wt beta L_i phi_b;  as ROW node a = r: wt s_a
       if (r < NLOC) {
         const double dgb = __builtin_fma(-nu, la, saw), nb = -nu * beta, wb = wt * beta * ph;
-        SAWT[p * 16 + r] = wt * saw;
+        if constexpr (GLS) {
+          double sw = 0.0;
+#pragma unroll
+          for (int x = 0; x < D; ++x) sw = __builtin_fma(ST[p * STS + NS0 + x], gp[x], sw);
+          SAWT[p * 16 + r] = wt * __builtin_fma(-nu, la, sw);
+        } else {
+          SAWT[p * 16 + r] = wt * saw;
+        }
 #pragma unroll
         for (int i = 0; i < D; ++i) {
 #pragma unroll
@@ -487,7 +527,13 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
             if (i == j) t = __builtin_fma(beta, dgb, t);
             C1s[p * 16 * NT1 + (r * D + i) * D + j] = __builtin_fma(ph, wij, t);
           }
-          C2Ws[p * 16 * NR2 + r * D + i] = wb * Lu[i];
+          if constexpr (GLS) {
+            const double nw = -nu * wt;
+#pragma unroll
+            for (int k = 0; k < D; ++k) AH[(p * D + k) * 16 * NR2 + r * D + i] = nw * hs[k][i];
+          } else {
+            C2Ws[p * 16 * NR2 + r * D + i] = wb * Lu[i];
+          }
         }
       }
     }
@@ -501,6 +547,24 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
 #pragma unroll
         for (int t = 0; t < NT1; ++t)
           acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop1, C1s[pp * 16 * NT1 + 16 * t + r], acc[t], 0, 0, 0);
+      }
+    } else if constexpr (GLS) {
+      // ---- GEMM H: rows (a, i) of HW, K = (point, component k), columns (b, j) of C1 viewed as (q, k) x (b, j)
+#pragma unroll
+      for (int ks = 0; ks < 2 * D; ++ks) {
+        const int kk = 4 * ks + q, pp = kk / D, kq = kk - pp * D;
+        double aoph[NR2], boph[NR2];
+#pragma unroll
+        for (int tr = 0; tr < NR2; ++tr) {
+          aoph[tr] = AH[kk * 16 * NR2 + 16 * tr + r];
+          const double v = C1s[pp * 16 * NT1 + hcol[tr] + kq * D];
+          boph[tr] = hval[tr] ? v : 0.0;
+        }
+#pragma unroll
+        for (int tr = 0; tr < NR2; ++tr)
+#pragma unroll
+          for (int tc = 0; tc < NR2; ++tc)
+            acc[tr * NR2 + tc] = __builtin_amdgcn_mfma_f64_16x16x4f64(aoph[tr], boph[tc], acc[tr * NR2 + tc], 0, 0, 0);
       }
     } else {
       // ---- GEMM 2: rows (a, j) of GP, columns (b, i) of C2W
@@ -547,8 +611,13 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
         for (int reg = 0; reg < 4; ++reg) {
           const int r2 = 16 * tr + q + 4 * reg;
           if (r2 < ND && c2 < ND) {
-            const int a = r2 / D, j = r2 - a * D;
-            EB[a * ND2 + c2 * D + j] += acc[tr * NR2 + tc][reg];
+            if constexpr (GLS) {       // row (a, i), column (b, j)
+              const int a = r2 / D, i = r2 - a * D, b = c2 / D, j = c2 - b * D;
+              EB[a * ND2 + (b * D + i) * D + j] += acc[tr * NR2 + tc][reg];
+            } else {                   // row (a, j), column (b, i)
+              const int a = r2 / D, j = r2 - a * D;
+              EB[a * ND2 + c2 * D + j] += acc[tr * NR2 + tc][reg];
+            }
           }
         }
       }
@@ -563,14 +632,17 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void s
 // values are wave-uniform scalar operands), the state quantities accumulated on the way, then the element residual
 // F_(a,i) += wt beta Lu_i (u . grad phi_a).  (Round 4: the wave-per-cell kernel with the matrix part compiled out took 99.7 ms
 // for config 4's finest level -- five barriers per point with a handful of lanes busy between them.)
-template <int D, int NLOC>
+// GLS: F_(a,i) += wt beta [Lu_i (w . grad phi_a - nu lap_a) - nu sum_k Lu_k H_a[k][i]], the wind w interpolated with the state
+// and the basis Hessians formed again in the second pass.  fq8 (ncell, nq8, D; may be NULL): Lu -= f at the point.
+template <int D, int NLOC, bool GLS>
 __global__ __launch_bounds__(64) void supg_residual_cell_kernel(int64_t ncell, const int32_t* __restrict__ cell_nodes,
                                                                  const double* __restrict__ grad, const double* __restrict__ vol,
                                                                  const double* __restrict__ hcell, int nq,
                                                                  const double* __restrict__ wq, const double* __restrict__ phi,
                                                                  const double* __restrict__ dphi, const double* __restrict__ d2phi,
-                                                                 const double* __restrict__ U, double nu, double weight, double magic,
-                                                                 double* __restrict__ Fe) {
+                                                                 const double* __restrict__ U, const double* __restrict__ W,
+                                                                 const double* __restrict__ fq8, int nq8, double nu, double weight,
+                                                                 double magic, double* __restrict__ Fe) {
   constexpr int NV = D + 1;
   const int64_t slot = (int64_t)blockIdx.x * 64 + threadIdx.x;
   const bool valid = slot < ncell;
@@ -581,13 +653,14 @@ __global__ __launch_bounds__(64) void supg_residual_cell_kernel(int64_t ncell, c
 #pragma unroll
     for (int x = 0; x < D; ++x) g[i][x] = grad[(cell * NV + i) * D + x];
   const int32_t* cn = cell_nodes + cell * NLOC;
-  double Uk[NLOC][D], F[NLOC][D];
+  double Uk[NLOC][D], Wk[GLS ? NLOC : 1][D], F[NLOC][D];
 #pragma unroll
   for (int k = 0; k < NLOC; ++k) {
     const int64_t node = cn[k];
 #pragma unroll
     for (int x = 0; x < D; ++x) {
       Uk[k][x] = U[node * D + x];
+      if constexpr (GLS) Wk[k][x] = W[node * D + x];
       F[k][x] = 0.0;
     }
   }
@@ -599,10 +672,10 @@ __global__ __launch_bounds__(64) void supg_residual_cell_kernel(int64_t ncell, c
     const double* __restrict__ ph = phi + (size_t)q * NLOC;
     const double* __restrict__ dp = dphi + (size_t)q * NLOC * NV;
     const double* __restrict__ hp = d2phi + (size_t)q * NLOC * NV * NV;
-    double u[D], Gu[D][D], Ls[D];
+    double u[D], Gu[D][D], Ls[D], w[D];
 #pragma unroll
     for (int i = 0; i < D; ++i) {
-      u[i] = Ls[i] = 0.0;
+      u[i] = Ls[i] = w[i] = 0.0;
 #pragma unroll
       for (int x = 0; x < D; ++x) Gu[i][x] = 0.0;
     }
@@ -643,6 +716,7 @@ __global__ __launch_bounds__(64) void supg_residual_cell_kernel(int64_t ncell, c
       for (int i = 0; i < D; ++i) {
         const double ui = Uk[a][i];
         u[i] = __builtin_fma(pa, ui, u[i]);
+        if constexpr (GLS) w[i] = __builtin_fma(pa, Wk[a][i], w[i]);
 #pragma unroll
         for (int x = 0; x < D; ++x) Gu[i][x] = __builtin_fma(gp[x], ui, Gu[i][x]);
         Ls[i] = __builtin_fma(-nu * la, ui, Ls[i]);                                   // -nu Lap u_i
@@ -656,6 +730,7 @@ __global__ __launch_bounds__(64) void supg_residual_cell_kernel(int64_t ncell, c
       double t = Ls[i];
 #pragma unroll
       for (int x = 0; x < D; ++x) t = __builtin_fma(u[x], Gu[i][x], t);
+      if (fq8) t -= fq8[((int64_t)cell * nq8 + q) * D + i];
       c[i] = t;
       uu = __builtin_fma(u[i], u[i], uu);
     }
@@ -663,18 +738,61 @@ __global__ __launch_bounds__(64) void supg_residual_cell_kernel(int64_t ncell, c
     const double wb = wq[q] * vw * beta;
 #pragma unroll
     for (int i = 0; i < D; ++i) c[i] *= wb;
+    if constexpr (!GLS) {
 #pragma unroll
-    for (int a = 0; a < NLOC; ++a) {
-      double sa = 0.0;                   // u . grad phi_a (the gradient formed again: 12 FMAs against 3 registers kept per node)
+      for (int a = 0; a < NLOC; ++a) {
+        double sa = 0.0;                 // u . grad phi_a (the gradient formed again: 12 FMAs against 3 registers kept per node)
 #pragma unroll
-      for (int x = 0; x < D; ++x) {
-        double s = 0.0;
+        for (int x = 0; x < D; ++x) {
+          double s = 0.0;
 #pragma unroll
-        for (int i = 0; i < NV; ++i) s = __builtin_fma(dp[a * NV + i], g[i][x], s);
-        sa = __builtin_fma(u[x], s, sa);
+          for (int i = 0; i < NV; ++i) s = __builtin_fma(dp[a * NV + i], g[i][x], s);
+          sa = __builtin_fma(u[x], s, sa);
+        }
+#pragma unroll
+        for (int i = 0; i < D; ++i) F[a][i] = __builtin_fma(c[i], sa, F[a][i]);
       }
+    } else {
 #pragma unroll
-      for (int i = 0; i < D; ++i) F[a][i] = __builtin_fma(c[i], sa, F[a][i]);
+      for (int a = 0; a < NLOC; ++a) {
+        double ta = 0.0;                 // w . grad phi_a - nu lap_a, and - nu H_a: gradient and Hessian formed again
+#pragma unroll
+        for (int x = 0; x < D; ++x) {
+          double s = 0.0;
+#pragma unroll
+          for (int i = 0; i < NV; ++i) s = __builtin_fma(dp[a * NV + i], g[i][x], s);
+          ta = __builtin_fma(w[x], s, ta);
+        }
+        double M[NV][D];
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+#pragma unroll
+          for (int y = 0; y < D; ++y) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) s = __builtin_fma(hp[(a * NV + i) * NV + k], g[k][y], s);
+            M[i][y] = s;
+          }
+        double hs[D][D], la = 0.0;
+#pragma unroll
+        for (int x = 0; x < D; ++x)
+#pragma unroll
+          for (int y = x; y < D; ++y) {
+            double s = 0.0;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) s = __builtin_fma(g[i][x], M[i][y], s);
+            hs[x][y] = hs[y][x] = s;
+            if (x == y) la += s;
+          }
+        ta = __builtin_fma(-nu, la, ta);
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+          double t = c[i] * ta;
+#pragma unroll
+          for (int k = 0; k < D; ++k) t = __builtin_fma(-nu * c[k], hs[k][i], t);
+          F[a][i] += t;
+        }
+      }
     }
   }
   if (valid) {
@@ -932,11 +1050,13 @@ static int ensure_bc_code(alfi_level* L) {
 }
 
 // The level operator from its cells: vals = [vals +] sum over the contributing cells of
-//     (nu K_e + gamma D_e + adv N_e(state))   (with_elements)   +   the linearised SUPG term (with_supg),
+//     (nu K_e + gamma D_e + adv N_e(state))   (with_elements)   +   the linearised SUPG / GLS term (stab = ALFI_STAB_SUPG /
+//     ALFI_STAB_GLS; d_wind: the GLS wind; the level's load table, if any, in the strong residual),
 // Dirichlet rows / columns -> identity (apply_bc).  Cells in batches when the scratch of element blocks would exceed the ctx's
 // limit (alfi_ctx_set_assembly_scratch; config 4's finest level: 14.9 GB in one batch).
 int launch_operator_refresh(alfi_level* L, double nu, double gamma, double adv, const double* d_state, bool with_elements,
-                            bool with_supg, double weight, double magic, bool accumulate, bool apply_bc, double* out_vals) {
+                            int stab, const double* d_wind, double weight, double magic, bool accumulate, bool apply_bc,
+                            double* out_vals) {
   alfi_ctx* ctx = L->ctx;
   AssemblyDev& S = L->asmb;
   const int d = L->bs, nloc = S.nloc, ndof = nloc * d;
@@ -950,6 +1070,7 @@ int launch_operator_refresh(alfi_level* L, double nu, double gamma, double adv, 
 #ifndef ALFI_ELAY
 #define ALFI_ELAY 1
 #endif
+  const bool with_supg = stab != ALFI_STAB_NONE;
   const int elay = (ALFI_ELAY && !with_supg) ? 1 : 0;
   ALFI_CHECK(ensure_scratch(ctx, (size_t)(((batch + 63) / 64 * 64) * per_cell)));
   double* E = (double*)ctx->asm_scratch;
@@ -969,15 +1090,21 @@ int launch_operator_refresh(alfi_level* L, double nu, double gamma, double adv, 
       dim3 grid((unsigned)(c1 - c0)), block(128);
       const int add = with_elements ? 1 : 0;
 #define ALFI_SUPG_M(DV, NL)                                                                                                      \
-  hipLaunchKernelGGL((supg_matrix_kernel<DV, NL>), grid, block, 0, ctx->stream, c0, c1, S.cell_nodes, S.grad, S.vol, S.hcell,   \
-                     S.nq8 / 8, S.wq8, S.qtab, d_state, nu, weight, magic, add, E)
+  do {                                                                                                                           \
+    if (stab == ALFI_STAB_GLS)                                                                                                   \
+      hipLaunchKernelGGL((supg_matrix_kernel<DV, NL, true>), grid, block, 0, ctx->stream, c0, c1, S.cell_nodes, S.grad, S.vol,  \
+                         S.hcell, S.nq8 / 8, S.wq8, S.qtab, d_state, d_wind, S.fq8, nu, weight, magic, add, E);                 \
+    else                                                                                                                         \
+      hipLaunchKernelGGL((supg_matrix_kernel<DV, NL, false>), grid, block, 0, ctx->stream, c0, c1, S.cell_nodes, S.grad, S.vol, \
+                         S.hcell, S.nq8 / 8, S.wq8, S.qtab, d_state, (const double*)nullptr, S.fq8, nu, weight, magic, add, E); \
+  } while (0)
       if (d == 2 && nloc == 3) { ALFI_SUPG_M(2, 3); }
       else if (d == 2 && nloc == 6) { ALFI_SUPG_M(2, 6); }
       else if (d == 3 && nloc == 4) { ALFI_SUPG_M(3, 4); }
       else if (d == 3 && nloc == 8) { ALFI_SUPG_M(3, 8); }
       else if (d == 3 && nloc == 10) { ALFI_SUPG_M(3, 10); }
       else if (d == 3 && nloc == 14) { ALFI_SUPG_M(3, 14); }
-      else return alfi_set_error(ctx, ALFI_E_ARG, "no SUPG kernel for %d nodes per cell in %d-D", nloc, d);
+      else return alfi_set_error(ctx, ALFI_E_ARG, "no SUPG / GLS kernel for %d nodes per cell in %d-D", nloc, d);
 #undef ALFI_SUPG_M
       ALFI_HIP_CHECK(ctx, hipGetLastError());
     }
@@ -1024,8 +1151,9 @@ int launch_element_mult(alfi_level* L, double nu, double gamma, double adv, cons
   return gather_cell_vectors(L, Fe, 0, dy);
 }
 
-// d_F += the SUPG residual contribution about d_state
-int launch_supg_residual(alfi_level* L, double nu, double weight, double magic, const double* d_state, double* d_F) {
+// d_F += the SUPG (d_wind NULL) or GLS (wind d_wind) residual contribution about d_state, with the level's load table if any
+int launch_supg_residual(alfi_level* L, double nu, double weight, double magic, const double* d_state, const double* d_wind,
+                         double* d_F) {
   alfi_ctx* ctx = L->ctx;
   AssemblyDev& S = L->asmb;
   const int d = L->bs, nloc = S.nloc;
@@ -1033,8 +1161,16 @@ int launch_supg_residual(alfi_level* L, double nu, double weight, double magic, 
   double* Fe = (double*)ctx->asm_scratch;
   dim3 grid((unsigned)((S.ncell + 63) / 64)), block(64);
 #define ALFI_SR(DV, NL)                                                                                                          \
-  hipLaunchKernelGGL((supg_residual_cell_kernel<DV, NL>), grid, block, 0, ctx->stream, S.ncell, S.cell_nodes, S.grad, S.vol,    \
-                     S.hcell, S.nq, S.wq, S.phi, S.dphi, S.d2phi, d_state, nu, weight, magic, Fe)
+  do {                                                                                                                           \
+    if (d_wind)                                                                                                                  \
+      hipLaunchKernelGGL((supg_residual_cell_kernel<DV, NL, true>), grid, block, 0, ctx->stream, S.ncell, S.cell_nodes, S.grad, \
+                         S.vol, S.hcell, S.nq, S.wq, S.phi, S.dphi, S.d2phi, d_state, d_wind, S.fq8, S.nq8, nu, weight, magic,  \
+                         Fe);                                                                                                    \
+    else                                                                                                                         \
+      hipLaunchKernelGGL((supg_residual_cell_kernel<DV, NL, false>), grid, block, 0, ctx->stream, S.ncell, S.cell_nodes, S.grad,\
+                         S.vol, S.hcell, S.nq, S.wq, S.phi, S.dphi, S.d2phi, d_state, (const double*)nullptr, S.fq8, S.nq8, nu, \
+                         weight, magic, Fe);                                                                                     \
+  } while (0)
   if (d == 2 && nloc == 3) { ALFI_SR(2, 3); }
   else if (d == 2 && nloc == 6) { ALFI_SR(2, 6); }
   else if (d == 3 && nloc == 4) { ALFI_SR(3, 4); }

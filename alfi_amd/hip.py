@@ -290,10 +290,8 @@ class Level(object):
         ``_hostlib.supg`` (degree 2k) and the cell sizes.  ``cells`` (partitioned level): the cells given to
         ``set_assembly``."""
         from . import _hostlib
-        from .elements import simplex_quadrature
-        el, d = V.element, V.dim
-        deg = 3 if (el.bubble or el.degree == 3) else el.degree
-        lam, wq = simplex_quadrature(d, nq or (deg + 1))
+        el = V.element
+        lam, wq = _hostlib.supg_rule(V, nq)
         phi, dphi = el.tabulate(lam)
         d2phi = el.tabulate_hessian(lam)
         h = _hostlib.cell_size(V.mesh)
@@ -308,6 +306,27 @@ class Level(object):
         linearised SUPG term, then the boundary conditions."""
         self.ctx.check(self.ctx.lib.alfi_level_assemble_supg(self.h, float(nu), float(gamma), float(adv), state.ptr,
                                                              float(weight), float(magic), 1 if apply_bc else 0))
+
+    def set_supg_load(self, fq):
+        """The body force at the points of ``set_supg``'s rule, (ncell, nq, dim) -- see ``supg_load`` --, subtracted in the
+        strong residual of the SUPG and GLS terms (alfi_level_set_supg_load); None removes it."""
+        if fq is None:
+            self.ctx.check(self.ctx.lib.alfi_level_set_supg_load(self.h, None))
+            return
+        f = np.ascontiguousarray(fq, dtype=np.float64)
+        self.ctx.check(self.ctx.lib.alfi_level_set_supg_load(self.h, _ptr(f)))
+
+    def assemble_gls(self, nu, gamma, adv, state, wind, weight, magic, apply_bc=True):
+        """The refresh of a GLS-stabilised run in one pass (alfi_level_assemble_gls): A = nu K + gamma D + adv N(state) + the
+        linearised GLS term about ``state`` with the wind ``wind`` (device vectors), then the boundary conditions."""
+        self.ctx.check(self.ctx.lib.alfi_level_assemble_gls(self.h, float(nu), float(gamma), float(adv), state.ptr, wind.ptr,
+                                                            float(weight), float(magic), 1 if apply_bc else 0))
+
+    def gls(self, nu, weight, magic, state, wind, add_to_operator=True, F=None):
+        """GLS terms about ``state`` with the wind ``wind`` on the device (alfi_level_gls): the linearisation into the operator
+        and / or the residual contribution added to the device vector ``F``."""
+        self.ctx.check(self.ctx.lib.alfi_level_gls(self.h, float(nu), float(weight), float(magic), state.ptr, wind.ptr,
+                                                   1 if add_to_operator else 0, F.ptr if F is not None else None))
 
     def supg(self, nu, weight, magic, state, add_to_operator=True, F=None):
         """SUPG terms about ``state`` on the device (alfi_level_supg): the linearisation into the operator and / or the
@@ -816,3 +835,12 @@ class Saddle(object):
         if self.h:
             self.ctx.lib.alfi_saddle_destroy(self.h)
             self.h = None
+
+
+def supg_load(V, f, nq=None):
+    """The body force ``f(points (N, dim)) -> (N, dim)`` at the physical points of the SUPG / GLS rule on V's cells: the
+    (ncell, nq, dim) table of ``Level.set_supg_load`` and of ``_hostlib.supg(..., fq=)``."""
+    from . import _hostlib
+    x = _hostlib.supg_points(V, nq)
+    nc, nq_, d = x.shape
+    return np.ascontiguousarray(np.asarray(f(x.reshape(-1, d)), dtype=np.float64).reshape(nc, nq_, d))

@@ -44,7 +44,8 @@ class HipNavierStokesSolver(object):
                  stabilisation_weight=None, supg_magic=9.0, device_assembly=None):
         """discretisation: "pkp0" ([P_k(+FB)]^d - P0 on the uniform hierarchy, ConstantPressureSolver solver.py:561-602) or
         "sv" ([P_k]^d - P_{k-1}^dg on the barycentric hierarchy with macro-star patches, ScottVogeliusSolver :604-662).
-        stabilisation_type: None / "none", "supg" (P0-pressure pairs) or "burman" (the Scott-Vogelius pair: interior-penalty
+        stabilisation_type: None / "none", "supg" or "gls" (P0-pressure pairs; GLS's wind is the velocity at the start of each
+        ``solve``, solver.py:199, 205, 215) or "burman" (the Scott-Vogelius pair: interior-penalty
         term of stabilisation.py:139-162 on facet-coupled levels, alfi_amd.burman; on partitioned levels in
         alfi_amd.dist.DistNavierStokesSolver, every rank the facets of its cells).
         device_assembly: refresh the level operators of every Newton step ON THE DEVICE (alfi_level_assemble: what
@@ -63,16 +64,21 @@ class HipNavierStokesSolver(object):
         # "shakib", the default), default weight 0.1 in 3-D and 1 in 2-D (stabilisation.py:52-54), supg_magic 9
         if stabilisation_type in ("none", None):
             stabilisation_type = None
-        if stabilisation_type not in (None, "supg", "burman"):
-            raise NotImplementedError("stabilisation type %r (built: supg for the P0-pressure pairs, burman for the "
+        if stabilisation_type not in (None, "supg", "gls", "burman"):
+            raise NotImplementedError("stabilisation type %r (built: supg and gls for the P0-pressure pairs, burman for the "
                                       "Scott-Vogelius pair)" % stabilisation_type)
-        if stabilisation_type == "supg" and self.sv:
-            raise NotImplementedError("supg with a discontinuous P_k pressure couples grad p into the momentum block")
+        if stabilisation_type in ("supg", "gls") and self.sv:
+            raise NotImplementedError("%s with a discontinuous P_k pressure couples grad p into the momentum block"
+                                      % stabilisation_type)
+        if stabilisation_type == "gls" and self._partitioned():
+            raise NotImplementedError("gls on partitioned levels: the wind of every rank's cells would need its own exchange")
         if stabilisation_type == "burman" and not self.sv:
             raise NotImplementedError("burman is built for the Scott-Vogelius pair (discretisation='sv') only")
         if stabilisation_type == "burman" and self._partitioned() and not self._partitioned_burman():
             raise NotImplementedError("burman on partitioned levels: the ghost layer would need the facet neighbours")
         self.supg = stabilisation_type == "supg"
+        # GLS (solver.py:204-234): the SUPG coefficient, weights and quadrature, the test side L_w v about the wind w = z_last
+        self.gls = stabilisation_type == "gls"
         # Burman interior penalty (solver.py:226-228, stabilisation.py:139-162): weight 3e-3 unless given (the reference's
         # SV run lines pass 5e-3)
         self.burman = stabilisation_type == "burman"
@@ -154,6 +160,8 @@ class HipNavierStokesSolver(object):
         self._device_newer = False          # the device copy of the state is ahead of the host arrays
         self._device_current = False        # the device copy equals the host arrays
         self._load = None
+        self._fq = None                     # per level: the body force at the SUPG / GLS points (supg_load), or None
+        self._host_winds = None             # GLS on the host path: the wind on every level
         self.area = float(self.vol.sum())
 
     # -- the state: host arrays on request, resident on the device during the solves -------------------------------------
@@ -234,11 +242,13 @@ class HipNavierStokesSolver(object):
             if self.burman:
                 dl.set_facet_blocks(True)
             dl.set_assembly(L.V, L.A.rowptr, L.A.colidx, full_div=self.sv)
-            if self.supg:
+            if self.supg or self.gls:
                 dl.set_supg(L.V)
             if self.burman:
                 dl.set_burman(L.facets, L.A.rowptr, L.A.colidx)
             self._dstate.append(self.ctx.vec(L.n))
+        # GLS: the wind on every level, filled at the start of each solve (the finest from the resident state, then injected)
+        self._dwind = [self.ctx.vec(L.n) for L in self.levels] if self.gls else None
         # the Newton state z = (u | p), the residual F and the update live on the device; the finest level's state vector IS
         # the velocity part of z
         n = self.levels[-1].n + self.B_raw.shape[0]
@@ -280,9 +290,11 @@ class HipNavierStokesSolver(object):
         t0 = time.time()
         self._device_states(u)
         mgl = self.hmg.mg.levels
-        for dl, st in zip(mgl, self._dstate):
+        for l, (dl, st) in enumerate(zip(mgl, self._dstate)):
             if adv and self.supg:     # A = nu K + gamma D + N(w) + the linearised SUPG term, THEN the boundary conditions
                 dl.assemble_supg(self.nu, self.gamma, adv, st, self.supg_weight, self.supg_magic, True)
+            elif adv and self.gls:    # ... + the linearised GLS term with the solve's wind
+                dl.assemble_gls(self.nu, self.gamma, adv, st, self._dwind[l], self.supg_weight, self.supg_magic, True)
             elif adv and self.burman:  # ... + adv * the linearised Burman term (a facet pass), then the boundary conditions
                 dl.assemble_burman(self.nu, self.gamma, adv, st, self.burman_weight, True)
             else:
@@ -317,6 +329,8 @@ class HipNavierStokesSolver(object):
         fin.assemble_mult(self.nu, self.gamma, 0.5 * adv, du if adv else None, du, Fu)
         if adv and self.supg:         # + the SUPG residual, gathered on the device into the same vector
             fin.supg(self.nu, self.supg_weight, self.supg_magic, du, False, Fu)
+        if adv and self.gls:          # + the GLS residual with the solve's wind
+            fin.gls(self.nu, self.supg_weight, self.supg_magic, du, self._dwind[-1], False, Fu)
         if adv and self.burman:       # + advect * the Burman residual (solver.py:233-234), facet pass + node gather
             fin.burman(adv * self.burman_weight, du, False, Fu)
         self._dBT.mult(dp, Fu, mode=2)                                    # F_u += B^T p
@@ -341,6 +355,8 @@ class HipNavierStokesSolver(object):
             self._device_current = True
         if self._load is not None:
             self._push_load()
+        if self.gls:                  # the wind: z_last, the state at the start of this solve (solver.py:199, 205, 215)
+            self._device_winds()
         norm = lambda v: float(np.sqrt(self._zdot(v, v)))
         lin_its, newton_its = 0, 0
         t_r = time.time()
@@ -374,6 +390,12 @@ class HipNavierStokesSolver(object):
             self._shift_pressure()
             self._device_newer, self._device_current = True, False
         return lin_its, newton_its, hist, small_step, fnorm, f0
+
+    def _device_winds(self):
+        """GLS's wind on every level: the resident finest velocity copied, the coarser ones injected as the state is."""
+        self.ctx.copy(self._dwind[-1], self._dstate[-1], n=self.n_u)
+        for l in range(len(self.levels) - 1, 0, -1):
+            self.hmg.mg.transfers[l - 1].inject(self._dwind[l], self._dwind[l - 1])
 
     # -- the pieces of the device-resident loop a partitioned solver replaces (alfi_amd.dist.DistNavierStokesSolver) ------
     def _push_state(self):
@@ -435,8 +457,12 @@ class HipNavierStokesSolver(object):
         Newton-linearised advection (+ the linearised SUPG term, ``advect * stabilisation_form``, solver.py:233-234)."""
         state = np.ascontiguousarray(state)
         A = _assemble(L, self.nu, self.gamma, adv, state, False, self.sv)
+        fq = self._fq[L.level] if self._fq is not None else None
         if adv and self.supg:
-            _hostlib.supg(L.V, state, self.nu, self.supg_weight, self.supg_magic, L.A.rowptr, L.A.colidx, A)
+            _hostlib.supg(L.V, state, self.nu, self.supg_weight, self.supg_magic, L.A.rowptr, L.A.colidx, A, fq=fq)
+        if adv and self.gls:          # the wind of this solve (the state itself before any solve)
+            wind = self._host_winds[L.level] if self._host_winds is not None else state
+            _hostlib.gls(L.V, state, wind, self.nu, self.supg_weight, self.supg_magic, L.A.rowptr, L.A.colidx, A, fq=fq)
         L.facet_beta = None
         if adv and self.burman:
             beta = np.empty(L.facets.nf)
@@ -477,9 +503,15 @@ class HipNavierStokesSolver(object):
             J = BSR(L.A.nbrows, L.A.nbcols, L.bs, L.A.rowptr, L.A.colidx,
                     _assemble(L, self.nu, self.gamma, 1.0, wind, False, self.sv)).to_scipy()
             Fu = 0.5 * (Fu + J @ u)                  # A0 u + 1/2 N(u) u with N = J - A0
+            fq = self._fq[L.level] if self._fq is not None else None
             if self.supg:
                 Fs = np.zeros_like(Fu)
-                _hostlib.supg(L.V, wind, self.nu, self.supg_weight, self.supg_magic, F=Fs)
+                _hostlib.supg(L.V, wind, self.nu, self.supg_weight, self.supg_magic, F=Fs, fq=fq)
+                Fu = Fu + Fs
+            if self.gls:
+                Fs = np.zeros_like(Fu)
+                W = self._host_winds[-1] if self._host_winds is not None else wind
+                _hostlib.gls(L.V, wind, W, self.nu, self.supg_weight, self.supg_magic, F=Fs, fq=fq)
                 Fu = Fu + Fs
             if self.burman:
                 Fb = np.zeros_like(Fu)
@@ -492,6 +524,16 @@ class HipNavierStokesSolver(object):
         Fp = self.B_raw @ u
         return Fu, Fp
 
+    def _stabilisation_load(self, f):
+        """The body force at the SUPG / GLS points of every level (it depends on Re: once per solve), to the device levels when
+        they refresh their operators."""
+        if self._partitioned():
+            raise NotImplementedError("a body force with SUPG on partitioned levels: the rank-local load tables are not built")
+        self._fq = [hip.supg_load(L.V, f) for L in self.levels]
+        if self.device_assembly:
+            for fq, dl in zip(self._fq, self.hmg.mg.levels):
+                dl.set_supg_load(fq)
+
     # -- the solve loop ---------------------------------------------------------------------------------------------------
     def solve(self, re):
         t0 = time.time()
@@ -501,12 +543,15 @@ class HipNavierStokesSolver(object):
             adv, self.nu = 1.0, self.char_L * self.char_U / re
         self._set_parameters()
         self._load = None
+        self._fq = None
         if hasattr(self.problem, "rhs"):             # NavierStokesProblem.rhs (problem.py:46-47 of the reference): default none
-            if self.supg:
-                raise NotImplementedError("a body force with SUPG: the stabilisation's strong residual (stabilisation.py:"
-                                          "86-91) would have to carry it; built for rhs = 0 only")
             from .mms import load_vector
-            self._load = load_vector(self.levels[-1].V, lambda x: self.problem.rhs(x, re))
+            f = lambda x: self.problem.rhs(x, re)
+            self._load = load_vector(self.levels[-1].V, f)
+            if self.supg or self.gls:     # the strong residual carries the force too (solver.py:216-217): per level, per solve
+                self._stabilisation_load(f)
+        if self.gls and not self._device_state_resident():     # the wind z_last of this solve, on every level
+            self._host_winds = [np.ascontiguousarray(w) for w in self._winds(self.u.copy())]
         if self._device_state_resident():
             lin_its, newton_its, hist, small_step, fnorm, f0 = self._solve_on_device(re, adv)
             info = {"Re": re, "nu": self.nu, "linear_iter": lin_its, "nonlinear_iter": newton_its,

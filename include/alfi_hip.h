@@ -201,6 +201,17 @@ int alfi_level_assemble_supg(alfi_level* lvl, double nu, double gamma, double ad
                              double magic, int apply_bc);
 int alfi_level_supg(alfi_level* lvl, double nu, double weight, double magic, const double* d_state, int add_to_operator,
                     double* d_F);
+/* The body force in the strong residual (alfi/solver.py:216-217, `Lu -= rhs[0]`) of the SUPG and GLS terms:
+ * alfi_level_set_supg_load (after alfi_level_set_supg) hands over fq (ncell, nq, d), the force at the points of the rule given
+ * to alfi_level_set_supg in its order, or NULL to remove it.
+ * GLS (the reference's `--stabilisation-type gls`): `weight * beta * (Lu, L_w v)` with the strong operator applied to the test
+ * function about the wind d_wind (the velocity at the start of the solve: fixed during Newton, not differentiated; laid out
+ * like d_state).  alfi_level_assemble_gls and alfi_level_gls mirror alfi_level_assemble_supg and alfi_level_supg. */
+int alfi_level_set_supg_load(alfi_level* lvl, const double* fq);
+int alfi_level_assemble_gls(alfi_level* lvl, double nu, double gamma, double adv, const double* d_state, const double* d_wind,
+                            double weight, double magic, int apply_bc);
+int alfi_level_gls(alfi_level* lvl, double nu, double weight, double magic, const double* d_state, const double* d_wind,
+                   int add_to_operator, double* d_F);
 int alfi_level_apply_bc(alfi_level* lvl);
 /* Burman interior-penalty stabilisation of the Scott-Vogelius pair on the device (alfi/stabilisation.py:139-162,
  * alfi/solver.py:226-234; the reference's `--stabilisation-type burman`): the project's first interior-facet term.

@@ -25,7 +25,7 @@ def main():
     ap.add_argument("--re-max", type=int, default=1000)
     ap.add_argument("--gamma", type=float, default=1e4)
     ap.add_argument("--discretisation", default="pkp0", choices=["pkp0", "sv"])
-    ap.add_argument("--stabilisation-type", default="none", choices=["none", "supg", "burman"])
+    ap.add_argument("--stabilisation-type", default="none", choices=["none", "supg", "gls", "burman"])
     ap.add_argument("--stabilisation-weight", type=float, default=None)
     ap.add_argument("--smoothing", type=int, default=None)
     ap.add_argument("--restriction", action="store_true")

@@ -4,6 +4,7 @@ errors of velocity / velocity gradient / pressure and |div u_h| per refinement, 
 solve on the GPU.
 
   python scripts/mms.py --dim 2 --baseN 8 --nref 4 --k 2 --discretisation pkp0 --re 1 10 100
+  python scripts/mms.py --dim 3 --baseN 2 --nref 2 --k 1 --stabilisation-type supg --stabilisation-weight 0.05 --re 1
 """
 import argparse
 import os
@@ -28,12 +29,14 @@ def pressure_evaluator(s):
     return {"p_eval": lambda lam, cells: np.einsum("qj,cj->cq", pel.tabulate(lam)[0], pc[cells])}
 
 
-def study(dim, baseN, nrefs, k, disc, res, gamma=1e4, verbose=True):
+def study(dim, baseN, nrefs, k, disc, res, gamma=1e4, verbose=True, stabilisation_type=None, stabilisation_weight=None,
+          **solver_kw):
     out = {re: {n: [] for n in ("velocity", "velocitygrad", "pressure", "divergence")} for re in res}
     hs = []
     for nref in nrefs:
         prob = TwoDimLidDrivenCavityMMSProblem(baseN) if dim == 2 else ThreeDimLidDrivenCavityMMSProblem(baseN)
-        s = HipNavierStokesSolver(prob, nref, k, gamma=gamma, discretisation=disc)
+        s = HipNavierStokesSolver(prob, nref, k, gamma=gamma, discretisation=disc, stabilisation_type=stabilisation_type,
+                                  stabilisation_weight=stabilisation_weight, **solver_kw)
         hs.append(2.0 / (baseN * 2 ** nref))
         for re in res:
             z, info = s.solve(re)
@@ -57,8 +60,11 @@ def main():
     ap.add_argument("--discretisation", default="pkp0", choices=["pkp0", "sv"])
     ap.add_argument("--gamma", type=float, default=1e4)
     ap.add_argument("--re", type=float, nargs="+", default=[1, 10, 100])
+    ap.add_argument("--stabilisation-type", default="none", choices=["none", "supg", "gls"])
+    ap.add_argument("--stabilisation-weight", type=float, default=None)
     a = ap.parse_args()
-    hs, out = study(a.dim, a.baseN, range(1, a.nref + 1), a.k, a.discretisation, a.re, a.gamma)
+    hs, out = study(a.dim, a.baseN, range(1, a.nref + 1), a.k, a.discretisation, a.re, a.gamma,
+                    stabilisation_type=a.stabilisation_type, stabilisation_weight=a.stabilisation_weight)
     print("h =", hs)
     for re in a.re:
         print("Results for Re =", re)

@@ -22,10 +22,16 @@ def main():
                     help="SUPG stabilisation with this weight (the reference's production runs: 0.05, generate_submission:18-20)")
     ap.add_argument("--burman", type=float, default=None, metavar="WEIGHT",
                     help="Burman stabilisation of the Scott-Vogelius configs (cfg5s, cfg5) with this weight")
+    ap.add_argument("--gls", type=float, default=None, metavar="WEIGHT",
+                    help="GLS stabilisation of the P0-pressure configs with this weight")
     args = ap.parse_args()
     from alfi_amd.nssolver import HipNavierStokesSolver
     from dist_newton_time import problem_and_options
+    if args.gls is not None and (args.supg is not None or args.burman is not None):
+        raise SystemExit("--gls excludes --supg and --burman")
     prob, nref, ke, kw = problem_and_options(args)
+    if args.gls is not None:
+        kw.update(stabilisation_type="gls", stabilisation_weight=args.gls)
     t0 = time.time()
     s = HipNavierStokesSolver(prob, nref, ke, device_assembly=not args.host, **kw)
     print("%s: %d velocity + %d pressure dofs, setup %.1f s, device assembly %s" % (args.config, s.n_u, s.n_p, time.time() - t0,

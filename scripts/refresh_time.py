@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """The operator refresh and the residual evaluation of a Newton step in isolation, at a bench configuration's size (what
 PatchPC.update / the SNES residual cost in the reference, alfi/solver.py:320, 325, 204-234): every level's
-alfi_level_assemble(_supg) from a synthetic state, alfi_level_assemble_mult + alfi_level_supg on the finest level.
+alfi_level_assemble(_supg / _gls) from a synthetic state, alfi_level_assemble_mult + alfi_level_supg / _gls on the finest level.
 
-  python scripts/refresh_time.py cfg4 [--supg 0.05] [--reps 3]
+  python scripts/refresh_time.py cfg4 [--supg 0.05 | --gls 0.05] [--reps 3]
 
 Prints device time per call (HIP events of the library, class PATCH_FACTOR) and the algorithmic bytes of the finest level's
 three kernels; run under rocprofv3 --kernel-trace --stats / --pmc for the per-kernel numbers (scripts/gpu_r5f.sh)."""
@@ -21,15 +21,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("config")
     ap.add_argument("--supg", type=float, default=None)
+    ap.add_argument("--gls", type=float, default=None, metavar="WEIGHT")
     ap.add_argument("--reps", type=int, default=3)
     args = ap.parse_args()
+    if args.supg is not None and args.gls is not None:
+        raise SystemExit("--supg and --gls exclude each other")
+    stab = "supg" if args.supg is not None else ("gls" if args.gls is not None else None)
     import bench
     from alfi_amd.nssolver import HipNavierStokesSolver
     from alfi_amd.problem import TwoDimLidDrivenCavityProblem, ThreeDimLidDrivenCavityProblem
     dim, baseN, nref, ke, Re, k = bench.CONFIGS[args.config]
     prob = TwoDimLidDrivenCavityProblem(baseN) if dim == 2 else ThreeDimLidDrivenCavityProblem(baseN)
-    s = HipNavierStokesSolver(prob, nref, ke, stabilisation_type="supg" if args.supg is not None else None,
-                              stabilisation_weight=args.supg)
+    s = HipNavierStokesSolver(prob, nref, ke, stabilisation_type=stab,
+                              stabilisation_weight=args.supg if args.gls is None else args.gls)
     s.nu = s.char_L * s.char_U / Re
     ctx = s.ctx
     L = s.levels[-1]
@@ -62,22 +66,31 @@ def main():
         print("%-62s %8.2f ms device, %8.2f ms wall" % (what, dev, wall), flush=True)
 
     s._device_states(None)
+    if stab == "gls":                 # the wind: the synthetic state
+        s._device_winds()
 
     def refresh_all():
-        for dl, st in zip(mgl, s._dstate):
-            if args.supg is not None:
+        for l, (dl, st) in enumerate(zip(mgl, s._dstate)):
+            if stab == "supg":
                 dl.assemble_supg(s.nu, s.gamma, 1.0, st, s.supg_weight, s.supg_magic, True)
+            elif stab == "gls":
+                dl.assemble_gls(s.nu, s.gamma, 1.0, st, s._dwind[l], s.supg_weight, s.supg_magic, True)
             else:
                 dl.assemble(s.nu, s.gamma, 1.0, st, True)
-    timed("refresh of all %d levels%s" % (len(mgl), " with SUPG" if args.supg is not None else ""), refresh_all)
+    timed("refresh of all %d levels%s" % (len(mgl), " with %s" % stab.upper() if stab else ""), refresh_all)
     st = s._dstate[-1]
-    if args.supg is not None:
+    if stab == "supg":
         timed("finest level: assemble_supg", lambda: fin.assemble_supg(s.nu, s.gamma, 1.0, st, s.supg_weight, s.supg_magic, True))
+    if stab == "gls":
+        timed("finest level: assemble_gls", lambda: fin.assemble_gls(s.nu, s.gamma, 1.0, st, s._dwind[-1], s.supg_weight,
+                                                                     s.supg_magic, True))
     timed("finest level: assemble", lambda: fin.assemble(s.nu, s.gamma, 1.0, st, True))
     Fu = s._dres
     timed("finest level: matrix-free product (the residual's A(u) u)", lambda: fin.assemble_mult(s.nu, s.gamma, 0.5, st, st, Fu))
-    if args.supg is not None:
+    if stab == "supg":
         timed("finest level: SUPG residual", lambda: fin.supg(s.nu, s.supg_weight, s.supg_magic, st, False, Fu))
+    if stab == "gls":
+        timed("finest level: GLS residual", lambda: fin.gls(s.nu, s.supg_weight, s.supg_magic, st, s._dwind[-1], False, Fu))
     s.close()
 
 
