@@ -211,6 +211,7 @@ int alfi_level_destroy(alfi_level* L) {
   dev_free(L->mult_seq);
   free_mult_schedule(L);
   dev_free(L->status);
+  dev_free(L->tr_mirror);
   dev_free(L->chk);
   dev_free(L->chk_list);
   free_cond(L);
@@ -738,6 +739,41 @@ int alfi_level_apply_bc(alfi_level* L) {
   if (!L->asmb.ready) return alfi_set_error(L->ctx, ALFI_E_STATE, "alfi_level_apply_bc before alfi_level_set_assembly");
   L->factored = false;
   return launch_apply_bc(L);
+}
+
+int alfi_level_transpose(alfi_level* L) {
+  if (!L) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL level");
+  alfi_ctx* ctx = L->ctx;
+  if (L->distributed || L->n_own != L->n)
+    return alfi_set_error(ctx, ALFI_E_ARG, "alfi_level_transpose on a partitioned level: the mirror blocks of the ghost columns "
+                                           "belong to other ranks");
+  if (L->A.nbrows != L->A.nbcols) return alfi_set_error(ctx, ALFI_E_ARG, "alfi_level_transpose of a non-square operator");
+  if (L->tr_pattern < 0) return alfi_set_error(ctx, ALFI_E_ARG, "alfi_level_transpose: the sparsity is not structurally symmetric");
+  if (L->A.nnzb == 0) return 0;
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (L->tr_pattern == 0) {          // first use: the mirror map, checked on the host before any value is written
+    int* bad = nullptr;
+    int hbad = 0;
+    ALFI_CHECK(dev_alloc(ctx, &L->tr_mirror, L->A.nnzb));
+    ALFI_CHECK(dev_alloc(ctx, &bad, 1));
+    int rc = hipMemsetAsync(bad, 0, sizeof(int), ctx->stream) == hipSuccess ? 0 : ALFI_E_HIP;
+    if (rc == 0) rc = launch_transpose_mirror(ctx, L->A, L->tr_mirror, bad);
+    if (rc == 0 && hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = ALFI_E_HIP;
+    if (rc == 0 && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = ALFI_E_HIP;
+    dev_free(bad);
+    if (rc != 0 || hbad) {
+      dev_free(L->tr_mirror);
+      L->tr_mirror = nullptr;
+      if (rc != 0) return rc == ALFI_E_HIP ? alfi_set_error(ctx, ALFI_E_HIP, "alfi_level_transpose: mirror map failed") : rc;
+      L->tr_pattern = -1;
+      return alfi_set_error(ctx, ALFI_E_ARG, "alfi_level_transpose: %s", (hbad & 2) ? "block columns not ascending within a row"
+                                                                               : "the sparsity is not structurally symmetric");
+    }
+    L->tr_pattern = 1;
+  }
+  ALFI_CHECK(launch_transpose_swap(ctx, L->A, L->tr_mirror));
+  L->factored = false;         // patch and coarse factors belong to the other operator now (as after a refresh)
+  return 0;
 }
 
 int alfi_level_get_values(alfi_level* L, double* bvals) {

@@ -436,6 +436,9 @@ struct alfi_level {
   int32_t* dof_ptr = nullptr;     // (n+1) CSR dof -> positions in stage
   int32_t* dof_pos = nullptr;     // (sum_n)
   bool factored = false;
+  // alfi_level_transpose: mirror block of every block (cached at first use; 4 bytes per block), or the pattern's verdict
+  int32_t* tr_mirror = nullptr;
+  int tr_pattern = 0;             // 0: not checked yet, 1: structurally symmetric, -1: not (ALFI_E_ARG, values untouched)
   bool pou = false;               // patch_pc_patch_partition_of_unity: additive results weighted by 1 / multiplicity
   int* status = nullptr;          // device flag: nonzero if a zero pivot was met
   // residual probe of the stored inverses + pivoted repair (kernels_check.hip)
@@ -674,6 +677,10 @@ int launch_burman(alfi_level* lvl, double weight, const double* d_state, bool ad
 int launch_patch_facet_correct(alfi_level* lvl, int64_t p0, int64_t nb, const int64_t* mat_ptr, double* dst, int big);
 bool element_kernel_exists(int d, int nloc);
 int launch_vals_from_lanes(alfi_ctx* ctx, const DevBSR& A, double* d_out);
+// kernels_transpose.hip: mirror[k] = the block at (j, i) of block k at (i, j) (-1: none; *bad |= 1, unsorted row: |= 2), then
+// the in-place swap of every pair {k, mirror[k]} transposed
+int launch_transpose_mirror(alfi_ctx* ctx, const DevBSR& A, int32_t* mirror, int* bad);
+int launch_transpose_swap(alfi_ctx* ctx, const DevBSR& A, const int32_t* mirror);
 int launch_probe_fill(alfi_ctx* ctx, double* e, int64_t n);                                    // the +-1 probe vector of the coarse solvers
 int launch_probe_residual(alfi_ctx* ctx, const double* r, int64_t n, double* worst_host);   // max | r - e |, reduced on the device
 int launch_apply_bc(alfi_level* lvl);

@@ -1245,6 +1245,10 @@ def _dist_ns_solver_class():
         def _push_operators(self):
             self.dmg.update(self.levels)
 
+        def setup_adjoint(self, J):
+            raise NotImplementedError("adjoint solves on partitioned levels: J^T needs the mirror block of every ghost column, "
+                                      "and those belong to other ranks")
+
         def _supg_host_needs_global_values(self):
             from .lazy import LazyOperator
             if isinstance(self.levels[-1].A, LazyOperator):

@@ -388,6 +388,12 @@ class Level(object):
         self.ctx.check(self.ctx.lib.alfi_level_assemble(self.h, float(nu), float(gamma), float(adv),
                                                         state.ptr if state is not None else None, 1 if apply_bc else 0))
 
+    def transpose(self):
+        """The operator replaced by its block transpose on the device, in the same sparsity and bitwise (alfi_level_transpose:
+        the velocity block of the adjoint J^T).  Serial levels with a structurally symmetric pattern only; the patches and the
+        coarse grid must be factored again afterwards."""
+        self.ctx.check(self.ctx.lib.alfi_level_transpose(self.h))
+
     def get_values(self):
         """The operator values in the host layout (nnzb, bs, bs)."""
         out = np.empty((self.nnzb, self.bs, self.bs))

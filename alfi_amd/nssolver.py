@@ -162,6 +162,7 @@ class HipNavierStokesSolver(object):
         self._load = None
         self._fq = None                     # per level: the body force at the SUPG / GLS points (supg_load), or None
         self._host_winds = None             # GLS on the host path: the wind on every level
+        self._last_solve = None             # (re, adv) of the last solve: the adjoint's operators use the same parameters
         self.area = float(self.vol.sum())
 
     # -- the state: host arrays on request, resident on the device during the solves -------------------------------------
@@ -288,6 +289,14 @@ class HipNavierStokesSolver(object):
 
     def _rediscretise_device(self, u, adv):
         t0 = time.time()
+        self._refresh_device(u, adv)
+        t1 = time.time()
+        self._factor_levels()
+        self.timings["assemble_s"] += t1 - t0
+        self.timings["factor_s"] += time.time() - t1
+
+    def _refresh_device(self, u, adv):
+        """Every level's operator formed on the device about the current state (the first half of a Newton step's refresh)."""
         self._device_states(u)
         mgl = self.hmg.mg.levels
         for l, (dl, st) in enumerate(zip(mgl, self._dstate)):
@@ -300,15 +309,16 @@ class HipNavierStokesSolver(object):
             else:
                 dl.assemble(self.nu, self.gamma, adv, st if adv else None, True)
         self.ctx.sync()
-        t1 = time.time()
+
+    def _factor_levels(self):
+        """Patches of every level and the coarse grid factored from the operator values the device holds."""
+        mgl = self.hmg.mg.levels
         for L, dl in zip(self.levels, mgl):
             L.nu = self.nu
             if L.level > 0:
                 dl.factor_with_fallback()
         mgl[0].coarse_factor_auto()
         self.ctx.sync()
-        self.timings["assemble_s"] += t1 - t0
-        self.timings["factor_s"] += time.time() - t1
 
     def _residual_device(self, u, p, adv):
         """F_u = (nu K + gamma D) u + 1/2 N(u) u + B^T p - f: one matrix-free product, cell by cell, with HALF the advection
@@ -534,6 +544,19 @@ class HipNavierStokesSolver(object):
             for fq, dl in zip(self._fq, self.hmg.mg.levels):
                 dl.set_supg_load(fq)
 
+    # -- adjoint (alfi/solver.py:520-535; alfi_amd.adjoint) -----------------------------------------------------------------
+    def setup_adjoint(self, J):
+        """Keep the functional J (``value(solver, u, p)``, ``gradient(solver, u, p) -> (g_u, g_p or None)``) and create
+        ``self.solver_adjoint``, whose ``solve(rtol=None, atol=None)`` writes ``self.z_adj = (lam_u, lam_p)`` for the state of
+        the last ``solve(re)``: J_F(z)^T z_adj = -dJ/dz with homogeneous Dirichlet conditions."""
+        from .adjoint import setup_adjoint
+        return setup_adjoint(self, J)
+
+    def solve_adjoint(self, J, rtol=None, atol=None):
+        """``setup_adjoint(J)`` and one adjoint solve: returns (z_adj, info)."""
+        info = self.setup_adjoint(J).solve(rtol=rtol, atol=atol)
+        return self.z_adj, info
+
     # -- the solve loop ---------------------------------------------------------------------------------------------------
     def solve(self, re):
         t0 = time.time()
@@ -541,6 +564,7 @@ class HipNavierStokesSolver(object):
             adv, self.nu = 0.0, self.char_L * self.char_U                   # Stokes, solver.py:261-264
         else:
             adv, self.nu = 1.0, self.char_L * self.char_U / re
+        self._last_solve = (re, adv)
         self._set_parameters()
         self._load = None
         self._fq = None

@@ -250,6 +250,12 @@ int alfi_level_assemble_burman(alfi_level* lvl, double nu, double gamma, double 
 int alfi_patches_set_facet_correction(alfi_level* lvl, int64_t nfacet, int64_t nrow, const int64_t* ptr, const int32_t* col,
                                       const int32_t* fac, const double* s);
 int alfi_level_set_facet_beta(alfi_level* lvl, const double* beta_host, double scale);
+/* The operator replaced by its block transpose in the same sparsity (the velocity block of the adjoint J^T of a Newton step:
+ * block k at (i, j) receives A[j, i]^T), in place and bitwise.  The pattern must be structurally symmetric with ascending
+ * columns per row, checked once on the device (mirror map cached on the level: 4 bytes per block); otherwise ALFI_E_ARG and
+ * the values are untouched.  Partitioned / distributed levels: ALFI_E_ARG (the mirror blocks of ghost columns live on other
+ * ranks).  The patch and coarse factors are stale afterwards, as after a refresh. */
+int alfi_level_transpose(alfi_level* lvl);
 /* the operator values in the host layout (nnzb, bs, bs) -- diagnostics / tests */
 int alfi_level_get_values(alfi_level* lvl, double* bvals_host);
 int alfi_level_size(alfi_level* lvl, int64_t* n);

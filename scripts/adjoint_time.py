@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Cost of an adjoint solve (alfi_amd.adjoint, alfi_level_transpose) at a bench configuration's size, against the forward
+Newton step:  python scripts/adjoint_time.py cfg4 [--re 10 100 1000] [--stabilisation-type supg|gls] [--sv] [--host]
+
+After every forward ``solve(re)`` one adjoint solve with J = int w . u (LoadFunctional, w = e_x) about the converged state.
+Prints the refresh, transpose, factor and solve seconds of the adjoint, its Krylov iterations and those of the last Newton
+step of the forward solve (same operator state, same tolerances)."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def _ex(x):
+    w = np.zeros_like(x)
+    w[:, 0] = 1.0
+    return w
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("config")
+    ap.add_argument("--re", type=float, nargs="+", default=[10.0, 100.0, 1000.0])
+    ap.add_argument("--stabilisation-type", choices=["none", "supg", "gls"], default="none")
+    ap.add_argument("--stabilisation-weight", type=float, default=0.05)
+    ap.add_argument("--sv", action="store_true", help="cfg5s (Scott-Vogelius) with Burman stabilisation instead of CONFIG")
+    ap.add_argument("--burman-weight", type=float, default=5e-3)
+    ap.add_argument("--host", action="store_true", help="host assembly (the transpose still runs on the device values)")
+    args = ap.parse_args()
+    from alfi_amd.adjoint import LoadFunctional
+    from alfi_amd.nssolver import HipNavierStokesSolver
+    from dist_newton_time import problem_and_options
+    args.supg = args.stabilisation_weight if args.stabilisation_type == "supg" else None
+    args.burman = None
+    if args.sv:
+        args.config, args.supg, args.burman = "cfg5s", None, args.burman_weight
+    prob, nref, ke, kw = problem_and_options(args)
+    if args.stabilisation_type == "gls" and not args.sv:
+        kw.update(stabilisation_type="gls", stabilisation_weight=args.stabilisation_weight)
+    t0 = time.time()
+    s = HipNavierStokesSolver(prob, nref, ke, device_assembly=not args.host, **kw)
+    label = "%s%s" % (args.config, "" if args.sv or args.stabilisation_type == "none" else " " + args.stabilisation_type)
+    print("%s: %d velocity + %d pressure dofs, setup %.1f s, device assembly %s, levels nnzb %s"
+          % (label, s.n_u, s.n_p, time.time() - t0, s.device_assembly, [dl.nnzb for dl in s.hmg.mg.levels]), flush=True)
+    steps = []                                      # Krylov iterations of every forward Newton step
+    solve_name = "_zsolve" if s.device_assembly else "_linear_solve"
+    inner = getattr(s, solve_name)
+
+    def recording(*a):
+        r = inner(*a)
+        steps.append(r[-2])
+        return r
+    setattr(s, solve_name, recording)
+    s.setup_adjoint(LoadFunctional(_ex))
+    for re in args.re:
+        del steps[:]
+        t0 = time.time()
+        _, info = s.solve(re)
+        wall = time.time() - t0
+        n = max(info["nonlinear_iter"], 1)
+        a = s.solver_adjoint.solve()
+        print("Re %g: forward %d Newton steps, %d Krylov its (last step %s), converged %s, %.2f s per Newton step | "
+              "adjoint %d Krylov its, converged %s, |r| %.2e of |b| %.2e; refresh %.3f s, transpose %.4f s, factor %.3f s, "
+              "solve %.3f s, total %.3f s"
+              % (re, info["nonlinear_iter"], info["linear_iter"], steps[-1] if steps else "-", info["converged"], wall / n,
+                 a["linear_iter"], a["converged"], a["residual_norm"], a["rhs_norm"], a["refresh_s"], a["transpose_s"],
+                 a["factor_s"], a["solve_s"], 60.0 * a["time"]), flush=True)
+    # the transpose pass alone, every level, repeated (the operator returns to itself after an even number)
+    mgl = s.hmg.mg.levels
+    for dl in mgl:
+        dl.transpose()
+    s.ctx.sync()
+    reps = 10
+    t0 = time.time()
+    for _ in range(reps):
+        for dl in mgl:
+            dl.transpose()
+    s.ctx.sync()
+    dt = (time.time() - t0) / reps
+    bs = mgl[-1].bs
+    alg = sum(2 * 8 * bs * bs * dl.nnzb for dl in mgl)
+    print("transpose of all levels: %.3f ms, %.1f MB algorithmic (2 x 8 bs^2 nnzb), %.0f GB/s; finest level %d blocks"
+          % (1e3 * dt, alg / 1e6, alg / dt / 1e9, mgl[-1].nnzb), flush=True)
+    s.close()
+
+
+if __name__ == "__main__":
+    main()
