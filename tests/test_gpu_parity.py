@@ -500,35 +500,12 @@ def test_cycle_logic_with_the_device_inverses(ctx, setup):
     with independently inverted patches -- so a wrong Givens rotation, Hessenberg column, restriction or coarse correction
     cannot hide inside the inversion tolerance."""
     from oracle import alfi_oracle as O
+    from alfi_amd import hip
+    from tests.krylov_reference import oracle_mg_with_device_inverses
     lv, k = setup["lv"], setup["k"]
     dmg = setup["dmg"][True]
-    omg = O.build_oracle_mg(lv, setup["tr"], k, schoeberl_restriction=True)     # a private copy to modify
-    for L, dl, ol in list(zip(lv, dmg.levels, omg.levels))[1:]:
-        n = np.diff(L.patch_ptr)
-        ol["smoother"].inv = [dl.patch_inverse(p, int(n[p])) for p in range(len(n))]
-    for dt, ot in zip(dmg.transfers, omg.transfers):
-        m = ot.st.blk_dofs.shape[1]
-        binv = [dt.block_inverse(b, m) for b in range(ot.st.blk_dofs.shape[0])]
-        # the oracle solves with LU factors; feed it exact "LU factors" of the device inverse's action instead
-        ot.st.lu = None
-        ot.st._binv = binv
-
-        def patch_apply(x, st=ot.st):
-            y = np.zeros_like(x)
-            for d, X in zip(st.blk_dofs, st._binv):
-                y[d] = X @ x[d]
-            y[st.skel] = x[st.skel]
-            return y
-        ot.st._patch_apply = patch_apply
     # the coarse solve: the explicit inverse the device multiplies with (hip.coarse_inverse), not the oracle's sparse LU
-    from alfi_amd import hip
-    Cinv = hip.coarse_inverse(lv[0].A)
-
-    class _Coarse(object):
-        @staticmethod
-        def solve(v):
-            return Cinv @ v
-    omg.coarse_lu = _Coarse()
+    omg = oracle_mg_with_device_inverses(lv, setup["tr"], k, dmg, hip.coarse_inverse(lv[0].A), schoeberl_restriction=True)
     tol = 1e-10
     L, dl, ol = lv[-1], dmg.levels[-1], omg.levels[-1]
     b, x0 = rhs(L.n, L.bc_dofs, 21), rhs(L.n, L.bc_dofs, 22)
