@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the multigrid hot path: V-cycles/s (and DoF*smooths/s) on the synthetic lid-driven cavity.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg4] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg4] [--dump-outputs DIR] [--full]
 
 A "step" is one multiplicative V-cycle (k pre- and post-smoothing FGMRES iterations with the additive vertex-star
 patch smoother on every level, Schoeberl prolongation, dense coarse solve) on the finest level, with all operators,
@@ -10,8 +10,13 @@ ldc3d [P2+FB]^3-P0, N = 56 (10 707 315 velocity dofs, 185 193 star patches of up
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (patch_apply_kernel: streams every dense patch
 inverse once per smoother iteration); its `achieved` is algorithmic bytes / device time measured live with HIP events on
-the library's stream during the timed region.  `cpu_baseline` times the C/OpenMP oracle port on the host cores on a
-bounded sample (the same hierarchy truncated by one level, scaled by the dof ratio).
+the library's stream during the timed region.
+
+On one GPU a plain run does only what the headline figure needs: set-up, warm-up, the timed steps, --dump-outputs and the
+line; every figure in it comes from the set-up or the timed region.  --full adds what takes work of its own after the timed
+steps: one fully instrumented V-cycle (`events_ms`, `spmv_finest`), the residual of the timed iterate, F-cycles
+(`fcycle_ms`), the other restriction setting, the cycle without HIP events and `cpu_baseline`, which times the C/OpenMP
+oracle port on the host cores (see bench_cpu.py).  The multi-rank line (--gpus N > 1) always carries its per-rank figures.
 
 --dump-outputs DIR writes what the timed cycles hand their caller -- the finest-level iterate x after the last timed step
 (`warmup + steps` V-cycles from x = 0 on the seeded right-hand side) -- as DIR/x.npy, float64.  A vector larger than
@@ -607,114 +612,10 @@ def spawn_ranks(n):
     return 0
 
 
-def main():
-    # dmabuf IPC is the only mode the host driver of the GPU boxes supports (RCCL / tensor sharing across the rank processes);
-    # before anything initialises the GPU, also when the ranks come from torch.distributed.run with a bare environment
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--config", default=os.environ.get("ALFI_BENCH_CONFIG", "cfg4"), choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--patch-composition", default="additive", choices=["additive", "multiplicative"],
-                    help="multiplicative: symmetrised Gauss-Seidel patch sweeps ordered by the problem's "
-                         "relaxation_direction (alfi/solver.py:306-335); the headline metric is quoted on additive")
-    ap.add_argument("--restriction", action="store_true",
-                    help="Schoeberl's robust restriction (alfi/driver.py:41 `--restriction`, transfer.py:261-275): off by "
-                         "default as in the reference's CLI; its production lines switch it on (examples/Makefile:6-16). "
-                         "The single-GPU line always times the other setting as well and reports it as "
-                         "`other_restriction_setting`")
-    ap.add_argument("--outer", action="store_true",
-                    help="also time one outer linear solve (FGMRES + fieldsplit Schur, alfi/solver.py:386-422) and "
-                         "report it as `outer_solve`; not part of the headline metric")
-    ap.add_argument("--graph", action="store_true",
-                    help="after the timed (eager, event-instrumented) cycles also time the same cycles replayed as a "
-                         "hipGraph (alfi_ctx_set_graph) and report them as `graph_replay`; single GPU only")
-    ap.add_argument("--mesh", default=None,
-                    help="config 5 only: gmsh 2.2 ASCII mesh of the channel (the reference's examples/bfs3d/coarse*.msh, "
-                         "bfs3d.py:37-39) as the base mesh instead of the structured stand-in")
-    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
-                    help="after the timed steps write the iterate they computed (the finest level's x) to DIR/x.npy, "
-                         "float64; a seeded sample of at most 64 MB with its dof numbers in DIR/x_index.npy when larger")
-    ap.add_argument("--verbose", action="store_true")
-    args = ap.parse_args()
-    if args.steps < 1 or args.warmup < 0:
-        ap.error("--steps must be at least 1 and --warmup at least 0")
-    global BFS3D_MESH
-    BFS3D_MESH = args.mesh
-
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # plain `python bench.py --gpus N`: this process only starts the N rank processes (before anything here touches a
-        # GPU) and relays rank 0's JSON line; under torch.distributed.run the rank environment is already there
-        return spawn_ranks(args.gpus)
-    import torch
-    rank = int(os.environ.get("RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    force_dist = os.environ.get("ALFI_DIST_FORCE") == "1"       # 1-rank RCCL group: fixed cost of the exchange points
-    if force_dist and world == 1:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        os.environ.setdefault("MASTER_PORT", "29577")
-        os.environ.setdefault("RANK", "0")
-        os.environ.setdefault("WORLD_SIZE", "1")
-    if world > 1 or args.gpus > 1 or force_dist:
-        if world != args.gpus:
-            raise SystemExit("--gpus %d but the launcher started %d ranks (WORLD_SIZE)" % (args.gpus, world))
-        return main_distributed(args, rank, world, local_rank)
-
-    emit = claim_stdout()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs an MI355X: the HIP path has no CPU fallback")
-    torch.cuda.set_device(0)
-    from alfi_amd import hip
+def full_measurements(args, ctx, dmg, L, b, db, dx, elapsed):
+    """--full, single GPU: what the line reports beyond the headline, each from work of its own after the timed steps (new
+    vectors; the timed iterate dx is only read).  Returns the fields to add to the line."""
     from alfi_amd import _lib as _alfi_lib
-
-    t0 = time.time()
-    lv, tr, k = build_problem(args.config, args.verbose)
-    t_gen = time.time() - t0
-    ctx = hip.Context(0)
-    t0 = time.time()
-    dmg = hip.Multigrid(ctx, lv, tr, k, robust_restriction=args.restriction, verbose=args.verbose)
-    ctx.sync()
-    t_setup = time.time() - t0
-    L = lv[-1]
-    wavefronts = None
-    if args.patch_composition == "multiplicative":
-        from alfi_amd.relaxation import OrderedRelaxation, Options
-        wavefronts = []
-        for Lh, dl in zip(lv[1:], dmg.levels[1:]):
-            orl = OrderedRelaxation()
-            orl.name = "Star"
-            orl.opts = Options("", {"pc_patch_construction_Star_sort_order": "0+:1-"})   # ldc relaxation_direction
-            iterset = orl.iteration_order(Lh.V.mesh.coords[Lh.patch_seeds])
-            wavefronts.append(dl.set_multiplicative(iterset, True))
-    b = np.random.default_rng(0).standard_normal(L.n)
-    b[L.bc_dofs] = 0.0
-    db, dx = ctx.vec(b), ctx.vec(L.n)
-
-    for _ in range(args.warmup):
-        dmg.vcycle(db, dx)
-    ctx.sync()
-    # HIP events around the dominant kernel only in the timed cycles (the roofline block is computed from them); the table
-    # of all event classes and the SpMV figure come from one extra, untimed cycle.  ALFI_BENCH_PROF=0: no events at all
-    # (tuning runs), 1: every class in the timed cycles as well.
-    prof_mode = {"0": False, "1": True}.get(os.environ.get("ALFI_BENCH_PROF", "3"), 3)
-    ctx.prof_enable(prof_mode)
-    ctx.prof_reset()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        dmg.vcycle(db, dx)
-    ctx.sync()
-    torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
-    ctx.prof_enable(False)
-    timed_apply_all = ctx.prof_get()["PATCH_APPLY"]
-    timed_apply = {dl.id: ctx.prof_get(dl.id)["PATCH_APPLY"] for dl in dmg.levels[1:]}
-    if args.dump_outputs:
-        idx, sampled = dump_indices(L.n)
-        write_outputs(args.dump_outputs, dx.get()[idx], idx, sampled)
     ctx.prof_enable(True)
     ctx.prof_reset()
     dxi = ctx.vec(L.n)
@@ -722,7 +623,10 @@ def main():
     ctx.sync()
     ctx.prof_enable(False)
     prof_all = ctx.prof_get()
-    spmv_one_cycle = ctx.prof_get(dmg.levels[-1].id)["MATMULT"]
+    t_spmv_ms, n_spmv = ctx.prof_get(dmg.levels[-1].id)["MATMULT"]
+    bsz = L.bs
+    b_spmv = (8.0 * bsz * bsz + 4.0) * L.A.nnzb + 4.0 * (L.A.nbrows + 1) + 16.0 * L.n
+    spmv_gbs = b_spmv * n_spmv / (t_spmv_ms * 1e-3) / 1e9 if t_spmv_ms > 0 else 0.0
 
     # convergence sanity: the timed cycles must have reduced the residual (no skipped work)
     dr = ctx.vec(L.n)
@@ -768,6 +672,137 @@ def main():
         dmg.vcycle(db, dxn)
     ctx.sync()
     noevents_ms = 1e3 * (time.perf_counter() - t0) / max(args.steps, 2)
+    return {
+        "ms_per_step_without_events": noevents_ms,
+        "other_restriction_setting": {"robust_restriction": not args.restriction, "ms_per_step": other_ms,
+                                      "v_cycles_per_s": 1e3 / other_ms, "rel_residual_after_cycles": other_res,
+                                      "cycles": max(args.steps, 2) + n_warm,
+                                      "note": "same hierarchy, the reference's `--restriction` flag flipped "
+                                              "(examples/Makefile:6-16 passes it, driver.py:41 defaults it off); no events"},
+        "fcycle_ms": fcycle_ms,
+        "spmv_finest": {"achieved_GBps": spmv_gbs, "frac": spmv_gbs / HBM_PEAK_GBS,
+                        "avg_launch_us": 1e3 * t_spmv_ms / max(n_spmv, 1)},
+        "events_ms": {kname: round(v[0], 3) for kname, v in prof_all.items()},
+        "events_petsc_names": dict(_alfi_lib.PETSC_EVENT_NAMES),
+        "events_note": "device time per event class of ONE extra, fully instrumented V-cycle after the timed region; on "
+                       "launch-bound configurations (cfg2, cfg3) the event records lengthen the intervals they bracket and "
+                       "the classes sum to more than the cycle: use the kernel trace (profiles/r02_kernel_trace_*.txt) there",
+        "rel_residual_after_timed_cycles": res,
+    }
+
+
+def main():
+    # dmabuf IPC is the only mode the host driver of the GPU boxes supports (RCCL / tensor sharing across the rank processes);
+    # before anything initialises the GPU, also when the ranks come from torch.distributed.run with a bare environment
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--config", default=os.environ.get("ALFI_BENCH_CONFIG", "cfg4"), choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="single GPU: after the timed steps also measure and check what the headline figure does not need "
+                         "(instrumented cycle, residual, F-cycles, other restriction setting, cycle without events, "
+                         "cpu_baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--patch-composition", default="additive", choices=["additive", "multiplicative"],
+                    help="multiplicative: symmetrised Gauss-Seidel patch sweeps ordered by the problem's "
+                         "relaxation_direction (alfi/solver.py:306-335); the headline metric is quoted on additive")
+    ap.add_argument("--restriction", action="store_true",
+                    help="Schoeberl's robust restriction (alfi/driver.py:41 `--restriction`, transfer.py:261-275): off by "
+                         "default as in the reference's CLI; its production lines switch it on (examples/Makefile:6-16). "
+                         "With --full the single-GPU line times the other setting as well and reports it as "
+                         "`other_restriction_setting`")
+    ap.add_argument("--outer", action="store_true",
+                    help="also time one outer linear solve (FGMRES + fieldsplit Schur, alfi/solver.py:386-422) and "
+                         "report it as `outer_solve`; not part of the headline metric")
+    ap.add_argument("--graph", action="store_true",
+                    help="after the timed (eager, event-instrumented) cycles also time the same cycles replayed as a "
+                         "hipGraph (alfi_ctx_set_graph) and report them as `graph_replay`; single GPU only")
+    ap.add_argument("--mesh", default=None,
+                    help="config 5 only: gmsh 2.2 ASCII mesh of the channel (the reference's examples/bfs3d/coarse*.msh, "
+                         "bfs3d.py:37-39) as the base mesh instead of the structured stand-in")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the iterate they computed (the finest level's x) to DIR/x.npy, "
+                         "float64; a seeded sample of at most 64 MB with its dof numbers in DIR/x_index.npy when larger")
+    ap.add_argument("--verbose", action="store_true")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    global BFS3D_MESH
+    BFS3D_MESH = args.mesh
+
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # plain `python bench.py --gpus N`: this process only starts the N rank processes (before anything here touches a
+        # GPU) and relays rank 0's JSON line; under torch.distributed.run the rank environment is already there
+        return spawn_ranks(args.gpus)
+    import torch
+    rank = int(os.environ.get("RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    force_dist = os.environ.get("ALFI_DIST_FORCE") == "1"       # 1-rank RCCL group: fixed cost of the exchange points
+    if force_dist and world == 1:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", "29577")
+        os.environ.setdefault("RANK", "0")
+        os.environ.setdefault("WORLD_SIZE", "1")
+    if world > 1 or args.gpus > 1 or force_dist:
+        if world != args.gpus:
+            raise SystemExit("--gpus %d but the launcher started %d ranks (WORLD_SIZE)" % (args.gpus, world))
+        return main_distributed(args, rank, world, local_rank)
+
+    emit = claim_stdout()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs an MI355X: the HIP path has no CPU fallback")
+    torch.cuda.set_device(0)
+    from alfi_amd import hip
+
+    t0 = time.time()
+    lv, tr, k = build_problem(args.config, args.verbose)
+    t_gen = time.time() - t0
+    ctx = hip.Context(0)
+    t0 = time.time()
+    dmg = hip.Multigrid(ctx, lv, tr, k, robust_restriction=args.restriction, verbose=args.verbose)
+    ctx.sync()
+    t_setup = time.time() - t0
+    L = lv[-1]
+    wavefronts = None
+    if args.patch_composition == "multiplicative":
+        from alfi_amd.relaxation import OrderedRelaxation, Options
+        wavefronts = []
+        for Lh, dl in zip(lv[1:], dmg.levels[1:]):
+            orl = OrderedRelaxation()
+            orl.name = "Star"
+            orl.opts = Options("", {"pc_patch_construction_Star_sort_order": "0+:1-"})   # ldc relaxation_direction
+            iterset = orl.iteration_order(Lh.V.mesh.coords[Lh.patch_seeds])
+            wavefronts.append(dl.set_multiplicative(iterset, True))
+    b = np.random.default_rng(0).standard_normal(L.n)
+    b[L.bc_dofs] = 0.0
+    db, dx = ctx.vec(b), ctx.vec(L.n)
+
+    for _ in range(args.warmup):
+        dmg.vcycle(db, dx)
+    ctx.sync()
+    # HIP events around the dominant kernel only in the timed cycles (the roofline block is computed from them); with --full
+    # the table of all event classes and the SpMV figure come from one extra, untimed cycle.  ALFI_BENCH_PROF=0: no events
+    # at all (tuning runs), 1: every class in the timed cycles as well.
+    prof_mode = {"0": False, "1": True}.get(os.environ.get("ALFI_BENCH_PROF", "3"), 3)
+    ctx.prof_enable(prof_mode)
+    ctx.prof_reset()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        dmg.vcycle(db, dx)
+    ctx.sync()
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    ctx.prof_enable(False)
+    timed_apply_all = ctx.prof_get()["PATCH_APPLY"]
+    timed_apply = {dl.id: ctx.prof_get(dl.id)["PATCH_APPLY"] for dl in dmg.levels[1:]}
+    if args.dump_outputs:
+        idx, sampled = dump_indices(L.n)
+        write_outputs(args.dump_outputs, dx.get()[idx], idx, sampled)
+    full = full_measurements(args, ctx, dmg, L, b, db, dx, elapsed) if args.full else None
 
     graph_replay = None
     if args.graph:
@@ -810,10 +845,6 @@ def main():
     fin = dmg.levels[-1]
     ms_f, cnt_f = per_level[fin.id]
     finest_gbs = apply_bytes[fin.id] * cnt_f / (ms_f * 1e-3) / 1e9 if ms_f > 0 else 0.0
-    t_spmv_ms, n_spmv = spmv_one_cycle
-    bsz = L.bs
-    b_spmv = (8.0 * bsz * bsz + 4.0) * L.A.nnzb + 4.0 * (L.A.nbrows + 1) + 16.0 * L.n
-    spmv_gbs = b_spmv * n_spmv / (t_spmv_ms * 1e-3) / 1e9 if t_spmv_ms > 0 else 0.0
 
     # HBM traffic of the dominant kernel comes from rocprofv3 --pmc passes (FETCH_SIZE / WRITE_SIZE in separate runs,
     # scripts/gpu_check.sh + scripts/pmc_summary.py): hardware counters cannot be read from inside this process, so the
@@ -861,12 +892,6 @@ def main():
                    "cycle": "V(k,k), 1 cycle per step", "parallelism": "1 GPU",
                    "robust_restriction": bool(args.restriction),
                    "patch_composition": args.patch_composition, "wavefronts_per_sweep": wavefronts},
-        "ms_per_step_without_events": noevents_ms,
-        "other_restriction_setting": {"robust_restriction": not args.restriction, "ms_per_step": other_ms,
-                                      "v_cycles_per_s": 1e3 / other_ms, "rel_residual_after_cycles": other_res,
-                                      "cycles": max(args.steps, 2) + n_warm,
-                                      "note": "same hierarchy, the reference's `--restriction` flag flipped "
-                                              "(examples/Makefile:6-16 passes it, driver.py:41 defaults it off); no events"},
         "dof_smooths_per_s": L.n * smooths_per_cycle_finest * vps,
         "patch_factor_GB": [round(dl.factor_bytes() / 1e9, 3) for dl in dmg.levels[1:]],
         "coarse_solver": {"kind": "dense inverse" if dmg.levels[0].coarse_factor_bytes() == 8 * lv[0].n * lv[0].n
@@ -877,7 +902,6 @@ def main():
         # worst afterwards): a smoother degraded by ill-conditioned patch operators shows here
         "patch_probe": [dict(zip(("worst", "flagged", "repaired", "worst_after"), dl.patch_check())) for dl in dmg.levels[1:]],
         "patch_factor_bytes_per_dof_finest": dmg.levels[-1].factor_bytes() / float(L.n),
-        "fcycle_ms": fcycle_ms,
         "vcycle_algorithmic_GB": total_bytes / 1e9,
         "vcycle_hbm_frac_of_peak": total_bytes / 1e9 / (elapsed / args.steps) / HBM_PEAK_GBS,
         "roofline": {"kernel": apply_kernel_name(L), "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
@@ -885,17 +909,11 @@ def main():
                      "avg_launch_us": 1e3 * t_apply_ms / max(n_apply, 1), "launches": int(n_apply),
                      "bytes_per_launch_avg": bytes_apply_total / max(n_apply, 1),
                      "finest_level_GBps": finest_gbs, "finest_level_avg_launch_us": 1e3 * ms_f / max(cnt_f, 1)},
-        "spmv_finest": {"achieved_GBps": spmv_gbs, "frac": spmv_gbs / HBM_PEAK_GBS,
-                        "avg_launch_us": 1e3 * t_spmv_ms / max(n_spmv, 1)},
-        "events_ms": {kname: round(v[0], 3) for kname, v in prof_all.items()},
-        "events_petsc_names": dict(_alfi_lib.PETSC_EVENT_NAMES),
-        "events_note": "device time per event class of ONE extra, fully instrumented V-cycle after the timed region; on "
-                       "launch-bound configurations (cfg2, cfg3) the event records lengthen the intervals they bracket and "
-                       "the classes sum to more than the cycle: use the kernel trace (profiles/r02_kernel_trace_*.txt) there",
-        "rel_residual_after_timed_cycles": res,
         "setup_s": {"host_generation": round(t_gen, 1), "device_setup_incl_patch_inversion": round(t_setup, 1),
                     "host_peak_rss_GB": round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1e6, 1)},
     }
+    if full is not None:
+        out.update(full)
     if graph_replay is not None:
         out["graph_replay"] = graph_replay
     if args.outer:
@@ -923,7 +941,7 @@ def main():
                               "pressure_dofs": int(Bm.shape[0]), "divergence_setup_s": round(t_b, 1)}
         sad.close()
     baseline_failed = False
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             from bench_cpu import cpu_baseline
             out["cpu_baseline"] = cpu_baseline(args.config, lv, tr, k, vps, robust_restriction=args.restriction)
@@ -936,7 +954,8 @@ def main():
                                    "sample": "failed", "error": "%s: %s" % (type(e).__name__, e)}
             baseline_failed = True
     else:
-        out["cpu_baseline"] = {"value": None, "unit": "V-cycles/s", "cores": 0, "kind": "port", "sample": "skipped"}
+        out["cpu_baseline"] = {"value": None, "unit": "V-cycles/s", "cores": 0, "kind": "port",
+                               "sample": "skipped" if args.full else "skipped (bench.py --full times it)"}
     emit(json.dumps(out))
     dmg.close()
     ctx.close()

@@ -9,7 +9,8 @@ for C in cfg4 cfg3 cfg2; do
 for i in 1 2; do
   for T in new old; do
     D=$GRAFT_REPO_ROOT; [ $T = old ] && D=$GRAFT_REPO_ROOT/.r03tree
-    (cd $D && ALFI_BENCH_PROF=0 python bench.py --no-cpu-baseline --steps 20 --warmup 3 --config $C 2> /dev/null) | python -c "import sys, json; d = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('$C $T: %.3f ms per V-cycle, %.3f V-cycles/s, rel. residual %.6e' % (d['ms_per_step'], d['value'], d.get('rel_residual_after_timed_cycles', float('nan'))))"
+    F=$(grep -q -- '"--full"' $D/bench.py && echo --full)      # the residual needs --full where bench.py has it
+    (cd $D && ALFI_BENCH_PROF=0 python bench.py $F --no-cpu-baseline --steps 20 --warmup 3 --config $C 2> /dev/null) | python -c "import sys, json; d = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('$C $T: %.3f ms per V-cycle, %.3f V-cycles/s, rel. residual %.6e' % (d['ms_per_step'], d['value'], d.get('rel_residual_after_timed_cycles', float('nan'))))"
   done
 done
 done | tee $O/same_box.txt

@@ -10,7 +10,7 @@ usage: pmc_summary.py <fetch_dir> <write_dir> <kernel-name-prefix> <out.json> [t
 runs the level's apply kernel once (one launch per smoothed level before the first cycle).
 
 ``first``: only the first N launches of the kernel -- the V-cycle of ``bench.py --steps 1 --warmup 0`` (60 patch applies, 79
-SpMVs on config 4); the full cycles bench.py runs afterwards for ``fcycle_ms`` have a different mix of levels.
+SpMVs on config 4); the full cycles ``bench.py --full`` runs afterwards for ``fcycle_ms`` have a different mix of levels.
 ``grids``: ``max`` (only the launches on the kernel's largest grid: the finest level) or comma-separated Grid_Size values -- only launches of those sizes (config 5: the smoother's big_apply_kernel launches,
 903680 and 310272 threads; the transfers' interior solves use the same kernel on smaller grids).
 """
