@@ -140,6 +140,10 @@ SIGNATURES = {
     "alfi_csr_mult": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_double, ctypes.c_int]),
     "alfi_saddle_mult": (ctypes.c_int, [vp, vp, vp]),
     "alfi_saddle_precond": (ctypes.c_int, [vp, vp, vp]),
+    "alfi_saddle_set_velocity_solver": (ctypes.c_int, [vp, ctypes.c_int]),
+    "alfi_saddle_factor_velocity": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
+    "alfi_saddle_velocity_solve": (ctypes.c_int, [vp, vp, vp]),
+    "alfi_saddle_velocity_info": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]),
 }
 
 COMM_ID_BYTES = 128      # ALFI_COMM_ID_BYTES

@@ -98,7 +98,7 @@ class AdjointSolver(object):
             s._rediscretise(s.u.copy(), adv)
             s.ctx.sync()
         t1 = time.time()
-        for dl in mgl:
+        for dl in (mgl[-1:] if getattr(s, "allu", False) else mgl):     # allu factors the finest operator alone
             dl.transpose()
         s.ctx.sync()
         t2 = time.time()

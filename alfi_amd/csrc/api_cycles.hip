@@ -23,7 +23,7 @@ int alfi_coarse_set_inverse(alfi_level* L, const double* inv, int inv_is_device)
 
 // the coarse residual probe fails the setup beyond this (ALFI_COARSE_CHECK_FAIL; round 2 failed at 1e-5: ADVICE r2 -- at
 // Re 10 000 on fine coarse grids a merely ill-conditioned operator would have become a setup error)
-static double coarse_probe_fail() {
+double coarse_probe_fail() {
   static const double v = getenv("ALFI_COARSE_CHECK_FAIL") ? atof(getenv("ALFI_COARSE_CHECK_FAIL")) : 1e-2;
   return v;
 }

@@ -236,6 +236,7 @@ int alfi_level_update_values(alfi_level* L, const double* bvals) {
   L->A_own.vals = L->A.vals;
   L->A_int.vals = L->A_bnd.vals = L->A.vals;
   L->factored = false;
+  ++L->op_version;
   return 0;
 }
 
@@ -384,6 +385,7 @@ int alfi_level_assemble(alfi_level* L, double nu, double gamma, double adv, cons
                                      L->A.vals));
   alfi_prof_end(ctx, t);
   L->factored = false;
+  ++L->op_version;
   L->fc_scale = 0.0;
   return 0;
 }
@@ -401,6 +403,7 @@ int alfi_level_assemble_supg(alfi_level* L, double nu, double gamma, double adv,
                                      L->A.vals));
   alfi_prof_end(ctx, t);
   L->factored = false;
+  ++L->op_version;
   return 0;
 }
 
@@ -418,6 +421,7 @@ int alfi_level_assemble_gls(alfi_level* L, double nu, double gamma, double adv, 
   alfi_prof_end(ctx, t);
   if (rc != 0) return rc;
   L->factored = false;
+  ++L->op_version;
   return 0;
 }
 
@@ -545,7 +549,10 @@ static int level_stabilisation(alfi_level* L, int stab, double nu, double weight
   if (rc == 0 && d_F) rc = launch_supg_residual(L, nu, weight, magic, d_state, d_wind, d_F);
   alfi_prof_end(ctx, t);
   if (rc != 0) return rc;
-  if (add_to_operator) L->factored = false;
+  if (add_to_operator) {
+    L->factored = false;
+    ++L->op_version;
+  }
   return 0;
 }
 
@@ -658,6 +665,7 @@ int alfi_level_burman(alfi_level* L, double weight, const double* d_state, int a
   alfi_prof_end(ctx, t);
   if (add_to_operator) {
     L->factored = false;
+    ++L->op_version;
     L->fc_scale += weight;
   }
   return 0;
@@ -678,6 +686,7 @@ int alfi_level_assemble_burman(alfi_level* L, double nu, double gamma, double ad
   if (apply_bc) ALFI_CHECK(launch_apply_bc(L));
   alfi_prof_end(ctx, t);
   L->factored = false;
+  ++L->op_version;
   L->fc_scale = adv * weight;
   return 0;
 }
@@ -738,6 +747,7 @@ int alfi_level_set_facet_beta(alfi_level* L, const double* beta_host, double sca
 int alfi_level_apply_bc(alfi_level* L) {
   if (!L->asmb.ready) return alfi_set_error(L->ctx, ALFI_E_STATE, "alfi_level_apply_bc before alfi_level_set_assembly");
   L->factored = false;
+  ++L->op_version;
   return launch_apply_bc(L);
 }
 
@@ -773,6 +783,7 @@ int alfi_level_transpose(alfi_level* L) {
   }
   ALFI_CHECK(launch_transpose_swap(ctx, L->A, L->tr_mirror));
   L->factored = false;         // patch and coarse factors belong to the other operator now (as after a refresh)
+  ++L->op_version;
   return 0;
 }
 

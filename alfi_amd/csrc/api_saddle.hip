@@ -223,6 +223,7 @@ int alfi_saddle_destroy(alfi_saddle* S) {
   dev_free(S->wb);
   dev_free(S->wc);
   dev_free(S->dotbuf);
+  mf_free(S->vmf);
   delete S;
   return 0;
 }
@@ -272,9 +273,108 @@ static int saddle_schur(alfi_saddle* S, const double* q, double* yp) {
   return launch_scale_rows(S->ctx, yp, q, S->minv, -(S->nu + S->gamma), S->np_dofs);
 }
 
+// ---- fieldsplit_0 as an exact solve (solver_type allu, alfi/solver.py:346-352): multifrontal factors of the finest operator ----
+int alfi_saddle_set_velocity_solver(alfi_saddle* S, int kind) {
+  if (!S) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL saddle");
+  alfi_ctx* ctx = S->ctx;
+  if (kind != ALFI_VELOCITY_MG && kind != ALFI_VELOCITY_DIRECT)
+    return alfi_set_error(ctx, ALFI_E_ARG, "velocity solver kind %d (ALFI_VELOCITY_MG or ALFI_VELOCITY_DIRECT)", kind);
+  alfi_level* F = S->fine;
+  if (kind == ALFI_VELOCITY_DIRECT && (S->par || F->has_halo || F->n_own != F->n))
+    return alfi_set_error(ctx, ALFI_E_STATE, "the direct velocity solve needs a finest level owned by one rank");
+  if (kind == ALFI_VELOCITY_MG && S->vmf) {      // the factors are released with the mode
+    ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    mf_free(S->vmf);
+    S->vmf = nullptr;
+    S->vmf_residual = -1.0;
+  }
+  S->vkind = kind;
+  return 0;
+}
+
+// numeric factorisation of the finest operator's current values (the plan of the first call is kept while the sparsity and
+// the ordering request stay the same), then the residual probe || A x - e ||_inf, x = solve(e), of alfi_coarse_factor_sparse
+int alfi_saddle_factor_velocity(alfi_saddle* S, const double* node_coords, int dim, int leaf_nodes, int64_t max_bytes) {
+  if (!S) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL saddle");
+  alfi_ctx* ctx = S->ctx;
+  alfi_level* F = S->fine;
+  if (S->vkind != ALFI_VELOCITY_DIRECT)
+    return alfi_set_error(ctx, ALFI_E_STATE, "alfi_saddle_factor_velocity before alfi_saddle_set_velocity_solver(DIRECT)");
+  if (node_coords && (dim < 1 || dim > 3)) return alfi_set_error(ctx, ALFI_E_ARG, "node coordinates of dimension %d", dim);
+  if (max_bytes < 0) return alfi_set_error(ctx, ALFI_E_ARG, "negative memory cap");
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  S->vmf_residual = -1.0;
+  ALFI_HIP_CHECK(ctx, hipMemsetAsync(F->status, 0, sizeof(int), ctx->stream));
+  ALFI_CHECK(mf_factor_slot(F, &S->vmf, node_coords, dim, leaf_nodes, max_bytes));
+  int st = 0;
+  int rc = hipMemcpy(&st, F->status, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess ? 0 : ALFI_E_HIP;
+  if (rc == 0 && st != 0) rc = alfi_set_error(ctx, ALFI_E_SINGULAR, "zero pivot block in a front of the direct velocity factorisation");
+  double worst = 0.0;
+  if (rc == 0) {
+    double *de = nullptr, *dy = nullptr, *dr = nullptr;
+    rc = dev_alloc(ctx, &de, F->n);
+    if (rc == 0) rc = dev_alloc(ctx, &dy, F->n);
+    if (rc == 0) rc = dev_alloc(ctx, &dr, F->n);
+    if (rc == 0) rc = launch_probe_fill(ctx, de, F->n);
+    if (rc == 0) rc = mf_solve_slot(F, S->vmf, de, dy);
+    if (rc == 0) rc = launch_bsr_spmv(ctx, F->A, dy, dr, nullptr, 1.0, 0);
+    if (rc == 0) rc = launch_probe_residual(ctx, dr, F->n, &worst);
+    else (void)hipStreamSynchronize(ctx->stream);
+    dev_free(de);
+    dev_free(dy);
+    dev_free(dr);
+  }
+  if (rc == 0 && !(worst <= coarse_probe_fail()))
+    rc = alfi_set_error(ctx, ALFI_E_SINGULAR, "direct velocity factorisation fails the residual probe: || A x - e || = %.3e", worst);
+  if (rc != 0) {
+    mf_free(S->vmf);
+    S->vmf = nullptr;
+    return rc;
+  }
+  S->vmf_residual = worst;
+  S->vmf_version = F->op_version;
+  return 0;
+}
+
+// factors present and computed from the finest operator's current values
+static int velocity_ready(alfi_saddle* S) {
+  if (!S->vmf) return alfi_set_error(S->ctx, ALFI_E_STATE, "direct velocity solve before alfi_saddle_factor_velocity");
+  if (S->vmf_version != S->fine->op_version)
+    return alfi_set_error(S->ctx, ALFI_E_STATE, "direct velocity solve with factors of an earlier operator (the finest operator "
+                                                "changed since alfi_saddle_factor_velocity)");
+  return 0;
+}
+
+int alfi_saddle_velocity_solve(alfi_saddle* S, const double* db, double* dx) {
+  if (!S || !db || !dx || db == dx) return alfi_set_error(S ? S->ctx : nullptr, ALFI_E_ARG, "bad arguments");
+  if (S->vkind != ALFI_VELOCITY_DIRECT) return alfi_set_error(S->ctx, ALFI_E_STATE, "the velocity solver is not DIRECT");
+  ALFI_CHECK(velocity_ready(S));
+  return mf_solve_slot(S->fine, S->vmf, db, dx);
+}
+
+int alfi_saddle_velocity_info(alfi_saddle* S, int64_t* bytes, double* probe_residual) {
+  if (!S) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL saddle");
+  if (!S->vmf) return alfi_set_error(S->ctx, ALFI_E_STATE, "no direct velocity factorisation");
+  if (bytes) *bytes = mf_bytes(S->vmf);
+  if (probe_residual) *probe_residual = S->vmf_residual;
+  return 0;
+}
+
 int alfi_saddle_precond(alfi_saddle* S, const double* dx, double* dy) {
   alfi_ctx* ctx = S->ctx;
   const int64_t nu = S->nu_dofs, np = S->np_dofs;
+  if (S->vkind == ALFI_VELOCITY_DIRECT) {                                        // (never partitioned: refused when set)
+    alfi_level* F = S->fine;
+    ALFI_CHECK(velocity_ready(S));
+    ALFI_CHECK(mf_solve_slot(F, S->vmf, dx, dy));                               // y_u = A^-1 b_u
+    ALFI_CHECK(launch_csr_spmv(ctx, S->B, dy, S->tmp_p, dx + nu, 1.0, 1));      // q = b_p - B y_u
+    ALFI_CHECK(saddle_schur(S, S->tmp_p, dy + nu));                             // y_p = -(nu+gamma) M^-1 q
+    ALFI_CHECK(launch_csr_spmv(ctx, S->BT, dy + nu, S->tmp_u, dx, 1.0, 1));     // t = b_u - B^T y_p
+    ALFI_CHECK(mf_solve_slot(F, S->vmf, S->tmp_u, dy));                         // y_u = A^-1 t
+    if (S->remove_nullspace) ALFI_CHECK(launch_remove_mean(ctx, dy + nu, np));
+    return 0;
+  }
   if (S->par) {
     alfi_level* F = S->fine;
     ALFI_CHECK(launch_copy(ctx, S->wa, dx, nu));

@@ -436,6 +436,9 @@ struct alfi_level {
   int32_t* dof_ptr = nullptr;     // (n+1) CSR dof -> positions in stage
   int32_t* dof_pos = nullptr;     // (sum_n)
   bool factored = false;
+  // bumped by every change of the operator values (upload, device refresh, stabilisation added, boundary rows, transpose):
+  // factors of the whole operator record the version they were computed from (the direct velocity solve of alfi_saddle)
+  uint64_t op_version = 0;
   // alfi_level_transpose: mirror block of every block (cached at first use; 4 bytes per block), or the pattern's verdict
   int32_t* tr_mirror = nullptr;
   int tr_pattern = 0;             // 0: not checked yet, 1: structurally symmetric, -1: not (ALFI_E_ARG, values untouched)
@@ -567,6 +570,12 @@ struct alfi_saddle {
   int64_t ldv = 0;            // stride of V, Z: n rounded up to even
   double *V = nullptr, *Z = nullptr, *w = nullptr, *hs = nullptr, *tmp_u = nullptr, *tmp_p = nullptr;
   double* dotbuf = nullptr;   // result of alfi_saddle_dot (serial levels)
+  // fieldsplit_0 (alfi_saddle_set_velocity_solver): ALFI_VELOCITY_MG (the full cycle of mg) or ALFI_VELOCITY_DIRECT (multifrontal
+  // factors of the finest operator, held here -- not in fine->mf, which is the coarse slot when the finest level is level 0)
+  int vkind = 0;
+  struct MfDev* vmf = nullptr;
+  uint64_t vmf_version = 0;   // fine->op_version the factors were computed from
+  double vmf_residual = -1.0; // residual probe of the last factorisation
 };
 
 // ---- kernel launch wrappers (defined in the .hip files) --------------------------------------------------------------
@@ -593,6 +602,10 @@ int launch_big_apply_arrays(alfi_ctx* ctx, int64_t npatch, int max_np, const int
                             const double* x, double* stage);
 int mf_factor(alfi_level* lvl, const double* coords, int dim, int leaf_nodes);   // multifrontal L D U of the level operator
 int mf_solve(alfi_level* lvl, const double* b, double* x);
+// the same into / from a factor slot of the caller's (*slot: the plan of an earlier call, reused for the same ordering request).
+// max_bytes >= 0: the analysis refuses (ALFI_E_ARG) when factors + fronts exceed free device memory or max_bytes (> 0)
+int mf_factor_slot(alfi_level* lvl, struct MfDev** slot, const double* coords, int dim, int leaf_nodes, int64_t max_bytes);
+int mf_solve_slot(alfi_level* lvl, const struct MfDev* m, const double* b, double* x);
 void mf_free(struct MfDev* m);
 int64_t mf_bytes(const struct MfDev* m);
 int launch_coarse_factor(alfi_level* lvl, double* out);                                   // dense inverse of the whole level operator

@@ -461,9 +461,11 @@ static int mf_sweeps(alfi_ctx* ctx, const MfDev* m, const double* r, double* x) 
   return 0;
 }
 
-int mf_solve(alfi_level* L, const double* b, double* x) {
+int mf_solve(alfi_level* L, const double* b, double* x) { return mf_solve_slot(L, L->mf, b, x); }
+
+// x = A^-1 b with factors m of L's operator (the refinement step multiplies with L->A)
+int mf_solve_slot(alfi_level* L, const MfDev* m, const double* b, double* x) {
   alfi_ctx* ctx = L->ctx;
-  const MfDev* m = L->mf;
   ALFI_CHECK(mf_sweeps(ctx, m, b, x));
   for (int it = 0; it < m->refine; ++it) {
     ALFI_CHECK(launch_bsr_spmv(ctx, L->A, x, m->tmp_r, b, 1.0, 1));     // r = b - A x
@@ -487,8 +489,10 @@ static int mf_up(alfi_ctx* ctx, MfDev* m, T** dst, const std::vector<T>& src) {
 
 static int mf_numeric(alfi_level* L, MfDev* m);
 
-// ordering, symbolic factorisation and the device index arrays: *out owns everything (mf_free)
-static int mf_analyse(alfi_level* L, const double* coords, int dim, int leaf_nodes, MfDev** out) {
+// ordering, symbolic factorisation and the device index arrays: *out owns everything (mf_free).  max_bytes >= 0: the memory
+// guard -- refused before any device allocation when the factors plus the front storage of the numeric phase exceed the free
+// device memory, or max_bytes when that is positive
+static int mf_analyse(alfi_level* L, const double* coords, int dim, int leaf_nodes, int64_t max_bytes, MfDev** out) {
   alfi_ctx* ctx = L->ctx;
   const int bs = L->bs;
   const int64_t nbn = L->A.nbrows;
@@ -662,6 +666,21 @@ static int mf_analyse(alfi_level* L, const double* coords, int dim, int leaf_nod
   }
   m->h_sdof_ptr = sdp;
   m->fac_doubles = fac;
+  if (max_bytes >= 0) {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+      mf_free(m);
+      return alfi_set_error(ctx, ALFI_E_HIP, "hipMemGetInfo failed");
+    }
+    const double need = 8.0 * (double)(fac + tmp);
+    const double limit = max_bytes > 0 ? std::min((double)free_b, (double)max_bytes) : (double)free_b;
+    if (need > limit) {
+      mf_free(m);
+      return alfi_set_error(ctx, ALFI_E_ARG, "multifrontal factorisation needs %.0f bytes (factors %.0f + fronts %.0f) but the "
+                            "limit is %.0f bytes (free device memory %.0f, cap %lld)", need, 8.0 * (double)fac,
+                            8.0 * (double)tmp, limit, (double)free_b, (long long)max_bytes);
+    }
+  }
   int rc = 0;
 #define MF_TRY(call)            \
   do {                          \
@@ -826,21 +845,25 @@ static int mf_numeric(alfi_level* L, MfDev* m) {
 // (Re-)factorisation of the level operator.  The plan of an earlier call is reused when it was made for the same ordering
 // request (the sparsity of a level never changes; new values arrive through alfi_level_update_values).
 int mf_factor(alfi_level* L, const double* coords, int dim, int leaf_nodes) {
+  return mf_factor_slot(L, &L->mf, coords, dim, leaf_nodes, -1);
+}
+
+int mf_factor_slot(alfi_level* L, MfDev** slot, const double* coords, int dim, int leaf_nodes, int64_t max_bytes) {
   if (leaf_nodes <= 0) leaf_nodes = 64;
-  MfDev* m = L->mf;
+  MfDev* m = *slot;
   if (m && (m->leaf != leaf_nodes || m->with_coords != (coords != nullptr) || m->nnzb != L->A.nnzb || m->n != L->n)) {
     mf_free(m);
-    L->mf = m = nullptr;
+    *slot = m = nullptr;
   }
   if (!m) {
-    ALFI_CHECK(mf_analyse(L, coords, dim, leaf_nodes, &m));
+    ALFI_CHECK(mf_analyse(L, coords, dim, leaf_nodes, max_bytes, &m));
   }
   const int rc = mf_numeric(L, m);
   if (rc != 0) {
     mf_free(m);
-    L->mf = nullptr;
+    *slot = nullptr;
     return rc;
   }
-  L->mf = m;
+  *slot = m;
   return 0;
 }

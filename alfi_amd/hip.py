@@ -830,6 +830,39 @@ class Saddle(object):
     def precond(self, x, y):
         self.ctx.check(self.ctx.lib.alfi_saddle_precond(self.h, x.ptr, y.ptr))
 
+    VELOCITY_SOLVERS = {"mg": 0, "direct": 1}      # ALFI_VELOCITY_MG / ALFI_VELOCITY_DIRECT
+
+    def set_velocity_solver(self, kind):
+        """fieldsplit_0: "mg" (one full cycle of ``mg``, the default) or "direct" (exact solve with multifrontal factors of the
+        finest operator -- solver_type allu; ``factor_velocity`` after every change of that operator).  Switching back to "mg"
+        releases the factors.  A partitioned finest level refuses "direct" (AlfiHipError, ALFI_E_STATE)."""
+        if kind not in self.VELOCITY_SOLVERS:
+            raise ValueError("velocity solver %r (mg or direct)" % (kind,))
+        self.ctx.check(self.ctx.lib.alfi_saddle_set_velocity_solver(self.h, self.VELOCITY_SOLVERS[kind]))
+        self.velocity_solver = kind
+
+    def factor_velocity(self, node_coords=None, leaf_nodes=0, max_bytes=0):
+        """Factor the finest operator's current values for the direct fieldsplit_0 (symbolic plan kept from the first call);
+        ``max_bytes`` > 0 caps factors + front storage (the free device memory caps them always).  Returns the residual probe
+        || A x - e ||_inf of the new factors."""
+        if node_coords is None:
+            self.ctx.check(self.ctx.lib.alfi_saddle_factor_velocity(self.h, None, 0, int(leaf_nodes), int(max_bytes)))
+        else:
+            xy = np.ascontiguousarray(node_coords, dtype=np.float64)
+            self.ctx.check(self.ctx.lib.alfi_saddle_factor_velocity(self.h, _ptr(xy), int(xy.shape[1]), int(leaf_nodes),
+                                                                    int(max_bytes)))
+        return self.velocity_info()[1]
+
+    def velocity_info(self):
+        """(device bytes of the direct velocity factors, probe residual of the last factorisation)."""
+        b, r = ctypes.c_int64(), ctypes.c_double()
+        self.ctx.check(self.ctx.lib.alfi_saddle_velocity_info(self.h, ctypes.byref(b), ctypes.byref(r)))
+        return b.value, r.value
+
+    def velocity_solve(self, b, x):
+        """x = A^-1 b with the direct velocity factors (device vectors of the finest level's length)."""
+        self.ctx.check(self.ctx.lib.alfi_saddle_velocity_solve(self.h, b.ptr, x.ptr))
+
     def solve(self, b, x, rtol=1e-8, atol=1e-8, max_it=500, restart=30):
         """Returns (iterations, true residual norm)."""
         its, rn = ctypes.c_int(), ctypes.c_double()

@@ -11,6 +11,10 @@ Per Newton step (``snes_type newtonls``, basic line search, solver.py:463-472):
    F_u = A0 u + 1/2 N(u) u + B^T p,  F_p = B u   (N(u) v = (u.grad) v + (v.grad) u, so N(u) u = 2 (u.grad) u);
 3. device: J d = -F by ``alfi_saddle_solve`` (FGMRES + fieldsplit Schur full, PCMG full cycles, DGMassInv).
 
+``solver_type`` (alfi/solver.py:346-422): "almg" (the default, fieldsplit_0 = PCMG) or "allu" (fieldsplit_0 = an exact solve
+with the library's multifrontal factors of the finest operator: the ideal augmented-Lagrangian check, examples/Makefile
+``idealal``).  With allu a Newton step refreshes and factors the finest operator only -- no patches, no coarse grid.
+
 The generator plays Firedrake's role (assembly, setup time); the arithmetic of the solves is libalfi_hip.so's.
 """
 import time
@@ -19,7 +23,24 @@ import numpy as np
 
 from . import _hostlib, hip
 from .problem import BSR, build_hierarchy, build_pressure_coupling
-from .solver import HipMG, mg_levels_solver, fieldsplit_0_mg, outer_solver
+from .solver import HipMG, mg_levels_solver, fieldsplit_0_mg, fieldsplit_0_lu, outer_solver
+
+SOLVER_TYPES = ("almg", "allu", "alamg", "lu", "simple", "lsc")     # alfi/driver.py:18 (--solver-type)
+
+
+def check_solver_type(solver_type, partitioned=False):
+    """The reference's solver types: almg and allu are built; the others raise NotImplementedError with the reason, an unknown
+    name ValueError.  Host-only: runs before any device work."""
+    if solver_type not in SOLVER_TYPES:
+        raise ValueError("unknown solver_type %r (one of %s)" % (solver_type, ", ".join(SOLVER_TYPES)))
+    if solver_type == "lu":
+        raise NotImplementedError("solver_type 'lu' (a monolithic LU of the saddle-point Jacobian) needs pivoting on the zero "
+                                  "pressure block; the multifrontal fronts are factored without pivoting")
+    if solver_type in ("simple", "lsc", "alamg"):
+        raise NotImplementedError("solver_type %r needs an algebraic multigrid (hypre in the reference), which is not built"
+                                  % solver_type)
+    if solver_type == "allu" and partitioned:
+        raise NotImplementedError("solver_type 'allu' on partitioned levels: the multifrontal factorisation is single-rank")
 
 
 def _assemble(L, nu, gamma, adv, wind, with_bc, full_div=False):
@@ -41,7 +62,7 @@ class HipNavierStokesSolver(object):
 
     def __init__(self, problem, nref, k, gamma=1e4, smoothing=None, restriction=False, ctx=None, verbose=False,
                  snes_rtol=None, snes_atol=None, snes_stol=1e-6, snes_max_it=20, discretisation="pkp0", stabilisation_type=None,
-                 stabilisation_weight=None, supg_magic=9.0, device_assembly=None):
+                 stabilisation_weight=None, supg_magic=9.0, device_assembly=None, solver_type="almg", direct_max_bytes=0):
         """discretisation: "pkp0" ([P_k(+FB)]^d - P0 on the uniform hierarchy, ConstantPressureSolver solver.py:561-602) or
         "sv" ([P_k]^d - P_{k-1}^dg on the barycentric hierarchy with macro-star patches, ScottVogeliusSolver :604-662).
         stabilisation_type: None / "none", "supg" or "gls" (P0-pressure pairs; GLS's wind is the velocity at the start of each
@@ -50,8 +71,16 @@ class HipNavierStokesSolver(object):
         alfi_amd.dist.DistNavierStokesSolver, every rank the facets of its cells).
         device_assembly: refresh the level operators of every Newton step ON THE DEVICE (alfi_level_assemble: what
         PatchPC.update does inside PCPATCH, solver.py:320, 325) instead of rediscretising on the host and re-uploading;
-        default: on (viscous, grad-div, advection and SUPG terms), unless ALFI_DEVICE_ASSEMBLY=0."""
+        default: on (viscous, grad-div, advection and SUPG terms), unless ALFI_DEVICE_ASSEMBLY=0.
+        solver_type: "almg" (fieldsplit_0 = PCMG full cycle, the default) or "allu" (fieldsplit_0 = exact solve with multifrontal
+        factors of the finest operator, re-factored every Newton step; ``smoothing`` / ``restriction`` are then accepted and
+        ignored, as on the reference's idealal lines); "lu", "simple", "lsc", "alamg": NotImplementedError.
+        direct_max_bytes: allu only -- cap on the factors + front storage in bytes (0: the free device memory)."""
         import os
+        check_solver_type(solver_type, self._partitioned())
+        self.solver_type = solver_type
+        self.allu = solver_type == "allu"
+        self.direct_max_bytes = int(direct_max_bytes)
         self.problem, self.gamma, self.verbose = problem, float(gamma), verbose
         if device_assembly is None:
             device_assembly = os.environ.get("ALFI_DEVICE_ASSEMBLY", "1") != "0"
@@ -106,7 +135,9 @@ class HipNavierStokesSolver(object):
                                                              relaxation_direction=problem.relaxation_direction()), dim)
         else:
             mgl = mg_levels_solver(dim, smoothing=smoothing)
-        self.params = outer_solver(dim, fieldsplit_0_mg(mgl))
+        # (allu: the multigrid hierarchy is still built -- its levels and transfers carry the refresh and the state injection)
+        self._fieldsplit_0_mg = fieldsplit_0_mg(mgl)
+        self.params = outer_solver(dim, fieldsplit_0_lu() if self.allu else self._fieldsplit_0_mg)
         L = self.levels[-1]
         self.nu = self.char_L * self.char_U
         self.Minv = None
@@ -214,9 +245,11 @@ class HipNavierStokesSolver(object):
 
     def _create_device(self, restriction):
         self.ctx = self._ctx_arg or hip.Context(0)
-        self.hmg = HipMG(self.ctx, self.levels, self.transfers, self.params["fieldsplit_0"], restriction=restriction)
+        self.hmg = HipMG(self.ctx, self.levels, self.transfers, self._fieldsplit_0_mg, restriction=restriction)
         self.saddle = hip.Saddle(self.hmg.mg, self.B, None if self.sv else self.vol, self.nu, self.gamma,
                                  remove_constant_nullspace=self.nullspace, mass_inv=self.Minv)
+        if self.allu:
+            self.saddle.set_velocity_solver("direct")
         if getattr(self, "burman", False):   # PCPATCH's facet rule in the patch matrices of the Burman levels
             from .burman import patch_facet_corrections
             for L, obj in zip(self.levels, self.hmg.pc_objs):
@@ -225,7 +258,12 @@ class HipNavierStokesSolver(object):
                                                                                                obj.patch_dofs))
 
     def _push_operators(self):
-        """New operator values on every level: re-gather and re-invert the patches, new coarse inverse."""
+        """New operator values on every level: re-gather and re-invert the patches, new coarse inverse (allu: the finest
+        operator's values and its direct factorisation only)."""
+        if self.allu:
+            self.hmg.mg.levels[-1].update_values(self.levels[-1].A.vals)
+            self._factor_direct()
+            return
         self.hmg.update(self.levels)
         self.hmg.mg.levels[0].update_values(self.levels[0].A.vals)
         self.hmg.mg.levels[0].coarse_factor_auto()
@@ -269,6 +307,9 @@ class HipNavierStokesSolver(object):
         mgl = self.hmg.mg.levels
         for dl in mgl:
             dl.assemble(self.nu, self.gamma, 0.0, None, True)
+        if self.allu:                       # (the first Newton step factors the operator it solves with)
+            self.ctx.sync()
+            return
         for L, dl in zip(self.levels, mgl):
             if L.level > 0:
                 dl.factor_with_fallback()
@@ -300,6 +341,8 @@ class HipNavierStokesSolver(object):
         self._device_states(u)
         mgl = self.hmg.mg.levels
         for l, (dl, st) in enumerate(zip(mgl, self._dstate)):
+            if self.allu and l < len(mgl) - 1:      # allu solves with the finest operator alone
+                continue
             if adv and self.supg:     # A = nu K + gamma D + N(w) + the linearised SUPG term, THEN the boundary conditions
                 dl.assemble_supg(self.nu, self.gamma, adv, st, self.supg_weight, self.supg_magic, True)
             elif adv and self.gls:    # ... + the linearised GLS term with the solve's wind
@@ -311,13 +354,24 @@ class HipNavierStokesSolver(object):
         self.ctx.sync()
 
     def _factor_levels(self):
-        """Patches of every level and the coarse grid factored from the operator values the device holds."""
+        """Patches of every level and the coarse grid factored from the operator values the device holds (allu: the direct
+        factorisation of the finest operator instead)."""
+        if self.allu:
+            return self._factor_direct()
         mgl = self.hmg.mg.levels
         for L, dl in zip(self.levels, mgl):
             L.nu = self.nu
             if L.level > 0:
                 dl.factor_with_fallback()
         mgl[0].coarse_factor_auto()
+        self.ctx.sync()
+
+    def _factor_direct(self):
+        """allu: numeric factorisation of the finest operator the device holds (plan of the first call reused); the probe
+        residual of the new factors is kept in ``direct_residual``."""
+        for L in self.levels:
+            L.nu = self.nu
+        self.direct_residual = self.saddle.factor_velocity(max_bytes=self.direct_max_bytes)
         self.ctx.sync()
 
     def _residual_device(self, u, p, adv):
@@ -495,6 +549,8 @@ class HipNavierStokesSolver(object):
             return self._rediscretise_device(u, adv)
         winds = self._winds(u)
         for L, w in zip(self.levels, winds):
+            if self.allu and L is not self.levels[-1]:      # allu solves with the finest operator alone
+                continue
             L.A = BSR(L.A.nbrows, L.A.nbcols, L.bs, L.A.rowptr, L.A.colidx, self.level_values(L, w, adv, True))
             L.nu = self.nu
         self._push_operators()

@@ -6,7 +6,8 @@
   the ``patch_pc_patch_*`` / ``patch_sub_*`` keys the reference sets (solver.py:320-344, 599-602) and runs PCPATCH's
   setup and apply on the GPU.
 * ``mg_levels_solver`` / ``fieldsplit_0_mg``: the option dictionaries of ``get_parameters`` (solver.py:313-344, 359-379)
-  with the PatchPC swapped for ``HipPatchPC``.
+  with the PatchPC swapped for ``HipPatchPC``; ``fieldsplit_0_lu``: the exact velocity solve of solver_type allu
+  (solver.py:346-352), the library's multifrontal factorisation of the finest operator.
 * ``HipMG``: drives PCMG (full or multiplicative V) + FGMRES(k) from such a dictionary -- the stand-in for PETSc when
   petsc4py is not importable (it is not, in this image).  One ``apply`` = what ``fieldsplit_0``'s Richardson(1)/PCMG
   does to a right-hand side.
@@ -101,6 +102,24 @@ def fieldsplit_0_mg(mg_levels):
         "mg_coarse_pc_python_type": "firedrake.AssembledPC",
         "mg_coarse_assembled": {"mat_type": "aij", "pc_type": "lu"},
     }
+
+
+def fieldsplit_0_lu(use_mkl=False):
+    """alfi/solver.py:346-352, key for key: fieldsplit_0 of solver_type allu (the ideal augmented-Lagrangian check).  The LU
+    is the library's multifrontal factorisation of the finest operator (``hip.Saddle.factor_velocity``); the solver-package
+    keys are accepted and ignored."""
+    return {
+        "ksp_type": "preonly",
+        "ksp_max_it": 1,
+        "pc_type": "lu",
+        "pc_factor_mat_solver_type": "mkl_pardiso" if use_mkl else "mumps",
+        "mat_mumps_icntl_14": 150,
+    }
+
+
+def is_fieldsplit_0_lu(params):
+    """Whether a fieldsplit_0 dictionary asks for the exact velocity solve (preonly + pc_type lu)."""
+    return params.get("pc_type") == "lu" and params.get("ksp_type") == "preonly"
 
 
 def _resolve(dotted):
@@ -367,7 +386,9 @@ def outer_solver(tdim, fieldsplit_0, high_accuracy=False):
 class HipOuterSolver(object):
     """One linear solve of the reference's outer iteration (solver.py:386-422) on the GPU: KSPFGMRES (restart 30, the
     PETSc default the reference does not override) around PCFIELDSPLIT-Schur-full, fieldsplit_0 = the device PCMG
-    (``HipMG``), fieldsplit_1 = ``DGMassInv``.  ``solve(f, g)`` returns (u, p, iterations, true residual norm)."""
+    (``HipMG``, ``fieldsplit_0_mg``) or the exact solve of the finest operator (``fieldsplit_0_lu``: multifrontal factors,
+    only the finest level is uploaded), fieldsplit_1 = ``DGMassInv``.  ``solve(f, g)`` returns (u, p, iterations, true
+    residual norm)."""
 
     def __init__(self, ctx, levels, transfers, params, restriction=False, coarse_inv=None):
         from .problem import build_pressure_coupling
@@ -380,12 +401,26 @@ class HipOuterSolver(object):
         if fs1.get("ksp_type") != "preonly" or not str(fs1.get("pc_python_type", "")).endswith("DGMassInv"):
             raise NotImplementedError("fieldsplit_1 must be preonly + DGMassInv (solver.py:386-390)")
         self.ctx = ctx
-        self.hmg = HipMG(ctx, levels, transfers, params["fieldsplit_0"], restriction=restriction, coarse_inv=coarse_inv)
-        if not self.hmg.full:
-            raise NotImplementedError("fieldsplit_0 must use pc_mg_type full (solver.py:366)")
+        fs0 = params["fieldsplit_0"]
+        self.direct = is_fieldsplit_0_lu(fs0)
         L = levels[-1]
+        if self.direct:
+            # the saddle solve needs the finest level only: a one-level hierarchy around it (no patches, no coarse inverse)
+            self.hmg = None
+            dl = hip.Level(ctx, L.A, L.bc_dofs)
+            mg = hip.Multigrid.__new__(hip.Multigrid)
+            hip.Multigrid._from_device_levels(mg, ctx, [dl], [], 1, False)
+            self.mg = mg
+        else:
+            self.hmg = HipMG(ctx, levels, transfers, fs0, restriction=restriction, coarse_inv=coarse_inv)
+            if not self.hmg.full:
+                raise NotImplementedError("fieldsplit_0 must use pc_mg_type full (solver.py:366)")
+            self.mg = self.hmg.mg
         self.B, self.mass_diag = build_pressure_coupling(L)
-        self.saddle = hip.Saddle(self.hmg.mg, self.B, self.mass_diag, L.nu, L.gamma, remove_constant_nullspace=True)
+        self.saddle = hip.Saddle(self.mg, self.B, self.mass_diag, L.nu, L.gamma, remove_constant_nullspace=True)
+        if self.direct:
+            self.saddle.set_velocity_solver("direct")
+            self.saddle.factor_velocity()
         self.rtol, self.atol = float(params.get("ksp_rtol", 1e-5)), float(params.get("ksp_atol", 1e-50))
         self.max_it = int(params.get("ksp_max_it", 10000))
         self.restart = int(params.get("ksp_gmres_restart", 30))

@@ -456,6 +456,29 @@ int alfi_transfer_stats(int64_t* h2d_bytes, int64_t* d2h_bytes, int reset);
 /* y = [A B^T; B 0] x and y = P^-1 x on device vectors (tests, monitors) */
 int alfi_saddle_mult(alfi_saddle* s, const double* dx, double* dy);
 int alfi_saddle_precond(alfi_saddle* s, const double* dx, double* dy);
+/* fieldsplit_0 as an exact solve (solver_type allu: ``fieldsplit_0_lu``, preonly + LU, alfi/solver.py:346-352, 414) -- the
+ * ideal augmented-Lagrangian preconditioner, whose only approximation left is DGMassInv's Schur complement.
+ * alfi_saddle_set_velocity_solver: ALFI_VELOCITY_MG (default: one full cycle of the saddle's alfi_mg) or ALFI_VELOCITY_DIRECT:
+ * both fieldsplit_0 applications of alfi_saddle_precond / alfi_saddle_solve become y_u = A^-1 b_u with multifrontal factors of
+ * the FINEST level's operator (the solver of alfi_coarse_factor_sparse, stored with the saddle -- not in the level's coarse
+ * slot, so a finest level that is also level 0 keeps its coarse factors).  A partitioned finest level: ALFI_E_STATE.
+ * Switching back to MG releases the factors.
+ * alfi_saddle_factor_velocity: numeric factorisation of the finest operator's CURRENT values (symbolic plan and ordering made
+ * by the first call and kept while the sparsity and the ordering request are unchanged), then the residual probe
+ * || A x - e ||_inf (ALFI_E_SINGULAR beyond ALFI_COARSE_CHECK_FAIL, default 1e-2).  node_coords / dim / leaf_nodes as for
+ * alfi_coarse_factor_sparse.  Memory guard: before any device allocation of a new plan, ALFI_E_ARG when factors + front
+ * storage exceed the free device memory, or max_bytes when max_bytes > 0 (the message names both numbers).
+ * Readiness: every change of the finest operator (alfi_level_update_values, the device refreshes, a stabilisation term added
+ * to the operator, alfi_level_apply_bc, alfi_level_transpose) makes the factors stale; a solve with stale factors returns
+ * ALFI_E_STATE until alfi_saddle_factor_velocity runs again -- they are never used silently.
+ * alfi_saddle_velocity_solve: dx = A^-1 db alone (n_u doubles each, db != dx; tests).  alfi_saddle_velocity_info: device
+ * bytes of the stored factors and the probe residual of the last factorisation. */
+#define ALFI_VELOCITY_MG 0
+#define ALFI_VELOCITY_DIRECT 1
+int alfi_saddle_set_velocity_solver(alfi_saddle* s, int kind);
+int alfi_saddle_factor_velocity(alfi_saddle* s, const double* node_coords, int dim, int leaf_nodes, int64_t max_bytes);
+int alfi_saddle_velocity_solve(alfi_saddle* s, const double* db, double* dx);
+int alfi_saddle_velocity_info(alfi_saddle* s, int64_t* bytes, double* probe_residual);
 
 #ifdef __cplusplus
 }

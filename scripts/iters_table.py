@@ -4,6 +4,7 @@ outer Krylov iterations per Newton step for nref x Re with Reynolds continuation
 linear solve on the GPU (alfi_amd/nssolver.py).  Prints the nref / dofs / Re table of iters.py plus solve times.
 
   python scripts/iters_table.py --dim 2 --baseN 16 --nref-start 1 --nref-end 3 --re-max 1000
+  python scripts/iters_table.py ... --solver-type allu     (fieldsplit_0 = exact solve of the finest operator)
 """
 import argparse
 import os
@@ -29,6 +30,7 @@ def main():
     ap.add_argument("--stabilisation-weight", type=float, default=None)
     ap.add_argument("--smoothing", type=int, default=None)
     ap.add_argument("--restriction", action="store_true")
+    ap.add_argument("--solver-type", default="almg", choices=["almg", "allu"])
     args = ap.parse_args()
     # continuation as in alfi.driver.get_default_parser / run_solver: 0 (Stokes), 1, 10, 100, then steps of 250
     res = [0, 1, 10, 100] + list(range(250, args.re_max + 1, 250))
@@ -39,12 +41,13 @@ def main():
         prob = TwoDimLidDrivenCavityProblem(args.baseN) if args.dim == 2 else ThreeDimLidDrivenCavityProblem(args.baseN)
         s = HipNavierStokesSolver(prob, nref, args.k, gamma=args.gamma, stabilisation_type=args.stabilisation_type,
                                   stabilisation_weight=args.stabilisation_weight, discretisation=args.discretisation,
-                                  smoothing=args.smoothing, restriction=args.restriction)
+                                  smoothing=args.smoothing, restriction=args.restriction, solver_type=args.solver_type)
         t0 = time.time()
         results = run_solver(s, res)
         rows.append((nref, s.n_u + s.n_p, results, time.time() - t0))
         s.close()
-    print("nref\tdofs\t\t" + "\t".join("Re=%d" % r for r in tableres) + "\t(average Krylov iterations per Newton step)")
+    print("nref\tdofs\t\t" + "\t".join("Re=%d" % r for r in tableres) + "\t(average Krylov iterations per Newton step, %s)"
+          % args.solver_type)
     for nref, dofs, results, t in rows:
         print("%d\t%.2e\t" % (nref, dofs) + "\t".join(
             "%.2f" % (results[r]["linear_iter"] / max(1, results[r]["nonlinear_iter"])) for r in tableres))
