@@ -139,7 +139,7 @@ class AdjointSolver(object):
 
 def setup_adjoint(solver, J):
     """``solver.setup_adjoint(J)``: keep the functional and create ``solver.solver_adjoint``."""
-    if solver._partitioned():
+    if solver._partitioned:
         raise NotImplementedError("adjoint solves on partitioned levels: the mirror blocks of a rank's ghost columns belong to "
                                   "other ranks")
     solver.J_adj = J

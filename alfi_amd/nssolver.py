@@ -17,7 +17,10 @@ with the library's multifrontal factors of the finest operator: the ideal augmen
 
 The generator plays Firedrake's role (assembly, setup time); the arithmetic of the solves is libalfi_hip.so's.
 """
+import contextlib
+import os
 import time
+import warnings
 
 import numpy as np
 
@@ -68,7 +71,7 @@ class HipNavierStokesSolver(object):
         stabilisation_type: None / "none", "supg" or "gls" (P0-pressure pairs; GLS's wind is the velocity at the start of each
         ``solve``, solver.py:199, 205, 215) or "burman" (the Scott-Vogelius pair: interior-penalty
         term of stabilisation.py:139-162 on facet-coupled levels, alfi_amd.burman; on partitioned levels in
-        alfi_amd.dist.DistNavierStokesSolver, every rank the facets of its cells).
+        alfi_amd.dist_nssolver.DistNavierStokesSolver, every rank the facets of its cells).
         device_assembly: refresh the level operators of every Newton step ON THE DEVICE (alfi_level_assemble: what
         PatchPC.update does inside PCPATCH, solver.py:320, 325) instead of rediscretising on the host and re-uploading;
         default: on (viscous, grad-div, advection and SUPG terms), unless ALFI_DEVICE_ASSEMBLY=0.
@@ -76,8 +79,7 @@ class HipNavierStokesSolver(object):
         factors of the finest operator, re-factored every Newton step; ``smoothing`` / ``restriction`` are then accepted and
         ignored, as on the reference's idealal lines); "lu", "simple", "lsc", "alamg": NotImplementedError.
         direct_max_bytes: allu only -- cap on the factors + front storage in bytes (0: the free device memory)."""
-        import os
-        check_solver_type(solver_type, self._partitioned())
+        check_solver_type(solver_type, self._partitioned)
         self.solver_type = solver_type
         self.allu = solver_type == "allu"
         self.direct_max_bytes = int(direct_max_bytes)
@@ -99,12 +101,10 @@ class HipNavierStokesSolver(object):
         if stabilisation_type in ("supg", "gls") and self.sv:
             raise NotImplementedError("%s with a discontinuous P_k pressure couples grad p into the momentum block"
                                       % stabilisation_type)
-        if stabilisation_type == "gls" and self._partitioned():
+        if stabilisation_type == "gls" and self._partitioned:
             raise NotImplementedError("gls on partitioned levels: the wind of every rank's cells would need its own exchange")
         if stabilisation_type == "burman" and not self.sv:
             raise NotImplementedError("burman is built for the Scott-Vogelius pair (discretisation='sv') only")
-        if stabilisation_type == "burman" and self._partitioned() and not self._partitioned_burman():
-            raise NotImplementedError("burman on partitioned levels: the ghost layer would need the facet neighbours")
         self.supg = stabilisation_type == "supg"
         # GLS (solver.py:204-234): the SUPG coefficient, weights and quadrature, the test side L_w v about the wind w = z_last
         self.gls = stabilisation_type == "gls"
@@ -126,7 +126,7 @@ class HipNavierStokesSolver(object):
         else:
             # with the device-side refresh nobody reads a host copy of the operators: the generator then delivers the sparsity
             # only and the first (Stokes) operator is formed on the device as well (no host assembly, no 8 GB upload at config 4)
-            self._values_on_device = self.device_assembly and self._device_assembly_possible()
+            self._values_on_device = self.device_assembly
             self.levels, self.transfers = build_hierarchy(problem, nref, k, Re=0.0, gamma=gamma, lazy=self._lazy_generation(),
                                                           operator_values=not self._values_on_device)
         if self.sv:      # patch = macro with the problem's relaxation direction (solver.py:339-342), sparse-LU patch options
@@ -150,31 +150,7 @@ class HipNavierStokesSolver(object):
             self.B, self.B_raw, self.vol = build_pressure_coupling(L, both=True)
         self._create_device(restriction)
         self._asm_ready = False
-        if self.device_assembly and not self._device_assembly_possible():
-            self.device_assembly = False
-        if self.device_assembly:
-            failure = None
-            try:
-                self._setup_device_assembly()
-            except hip.AlfiHipError as e:
-                failure = e
-            # (partitioned: the outcome is agreed over the ranks -- one rank on the host path and the others on the device path
-            # would call different collectives)
-            if self._any_rank(failure is not None):
-                # (e.g. ALFI_SPMV=legacy: the refresh writes the lane-major operator layout) -- ADVICE r3: fall back, say so
-                import warnings
-                warnings.warn("device-side operator refresh not available (%s): the operators of every Newton step are "
-                              "assembled on the host" % (failure if failure is not None else "another rank failed to set it up",))
-                self.device_assembly = False
-        if self._values_on_device:
-            if self.device_assembly:
-                self._first_operators_on_device()
-            else:                           # the refresh could not be set up after all: the host assembler's Stokes operators
-                for Lv in self.levels:
-                    Lv.A = BSR(Lv.A.nbrows, Lv.A.nbcols, Lv.bs, Lv.A.rowptr, Lv.A.colidx,
-                               _assemble(Lv, self.nu, self.gamma, 0.0, None, True, full_div=self.sv))
-                self._values_on_device = False
-                self._push_operators()
+        self._start_device_assembly()
         self.rtol, self.atol = self.params["ksp_rtol"], self.params["ksp_atol"]
         tol2, tol3 = (1e-9, 1e-8), (1e-8, 1e-8)                            # snes_rtol / snes_atol, solver.py:484-499
         self.snes_rtol = snes_rtol if snes_rtol is not None else (tol2 if dim == 2 else tol3)[0]
@@ -225,18 +201,23 @@ class HipNavierStokesSolver(object):
         self._host_p = np.asarray(value, dtype=np.float64)
         self._device_current = False
 
-    # -- device side (overridden by alfi_amd.dist.DistNavierStokesSolver for partitioned levels) -------------------------
+    # -- device side (overridden by alfi_amd.dist_nssolver.DistNavierStokesSolver for partitioned levels) ----------------
+    _partitioned = False                    # whether the levels are partitioned over ranks
+
     def _any_rank(self, flag):
         """True if ``flag`` holds on any rank (one rank here)."""
         return bool(flag)
 
-    def _partitioned(self):
-        """Whether the levels are partitioned over ranks (alfi_amd.dist.DistNavierStokesSolver)."""
-        return False
+    def _on_stream(self):
+        """The context the device calls are made in (partitioned: the library's stream current for torch)."""
+        return contextlib.nullcontext()
 
-    def _partitioned_burman(self):
-        """Whether a partitioned solver forms the Burman terms of its ranks' rows (alfi_amd.dist.DistNavierStokesSolver)."""
-        return False
+    @contextlib.contextmanager
+    def _timed(self, key):
+        """The wall time of the block is added to ``timings[key]``."""
+        t = time.time()
+        yield
+        self.timings[key] += time.time() - t
 
     def _lazy_generation(self):
         """Operators and transfers as recipes that assemble the rows somebody asks for (alfi_amd.lazy) instead of global
@@ -248,6 +229,9 @@ class HipNavierStokesSolver(object):
         self.hmg = HipMG(self.ctx, self.levels, self.transfers, self._fieldsplit_0_mg, restriction=restriction)
         self.saddle = hip.Saddle(self.hmg.mg, self.B, None if self.sv else self.vol, self.nu, self.gamma,
                                  remove_constant_nullspace=self.nullspace, mass_inv=self.Minv)
+        self._ksp, self._device_transfers = self.saddle, list(zip(self.transfers, self.hmg.mg.transfers))
+        self._own_dofs = self._own_cells = slice(None)
+        self._n_own, self._np_own = self.levels[-1].n, self.B.shape[0]
         if self.allu:
             self.saddle.set_velocity_solver("direct")
         if getattr(self, "burman", False):   # PCPATCH's facet rule in the patch matrices of the Burman levels
@@ -269,8 +253,34 @@ class HipNavierStokesSolver(object):
         self.hmg.mg.levels[0].coarse_factor_auto()
 
     # -- operator refresh on the device ---------------------------------------------------------------------------------------
-    def _device_assembly_possible(self):
-        return True
+    def _start_device_assembly(self):
+        """The device-side refresh set up -- first the rank-local part, then the exchange of the distributed state -- or, if any
+        rank fails at either, host assembly on ALL ranks; then the first (Stokes) operators where the generator left them out.
+        Partitioned: every rank, failing or not, meets the others in ``_any_rank`` after each phase and nowhere else before it
+        (the phases' own collectives start only once all ranks have passed the agreement before them) -- one rank on the host
+        path and the others on the device path would call different collectives."""
+        phases = (self._setup_device_assembly, self._setup_state_exchange) if self.device_assembly else ()
+        for phase in phases:
+            failure = None
+            try:
+                phase()
+            except hip.AlfiHipError as e:
+                failure = e
+            if self._any_rank(failure is not None):
+                # (e.g. ALFI_SPMV=legacy: the refresh writes the lane-major operator layout): fall back, say so
+                warnings.warn("device-side operator refresh not available (%s): the operators of every Newton step are "
+                              "assembled on the host" % (failure if failure is not None else "another rank failed to set it up",))
+                self.device_assembly = False
+                break
+        if self._values_on_device:
+            if self.device_assembly:
+                self._first_operators_on_device()
+            else:                           # the refresh could not be set up after all: the host assembler's Stokes operators
+                for Lv in self.levels:
+                    Lv.A = BSR(Lv.A.nbrows, Lv.A.nbcols, Lv.bs, Lv.A.rowptr, Lv.A.colidx,
+                               _assemble(Lv, self.nu, self.gamma, 0.0, None, True, full_div=self.sv))
+                self._values_on_device = False
+                self._push_operators()
 
     def _setup_device_assembly(self):
         """Once: the cells, the reference tensors of the element and the contributor lists of every level go to the device
@@ -301,20 +311,33 @@ class HipNavierStokesSolver(object):
         self._dp, self._dFp = self.ctx.vec(self.B_raw.shape[0]), self.ctx.vec(self.B_raw.shape[0])
         self._asm_ready = True
 
+    def _setup_state_exchange(self):
+        """Second phase of the set-up: what needs the other ranks (nothing on one GPU)."""
+
+    def _device_levels(self):
+        """(device level, its state vector, its GLS wind or None) of every level this rank assembles, coarsest first."""
+        return list(zip(self.hmg.mg.levels, self._dstate, self._dwind or [None] * len(self.levels)))
+
+    def _assemble_level(self, dl, st, wind, adv):
+        """The operator of one device level formed about the state ``st`` (``wind``: GLS's)."""
+        if adv and self.supg:     # A = nu K + gamma D + N(w) + the linearised SUPG term, THEN the boundary conditions
+            dl.assemble_supg(self.nu, self.gamma, adv, st, self.supg_weight, self.supg_magic, True)
+        elif adv and self.gls:    # ... + the linearised GLS term with the solve's wind
+            dl.assemble_gls(self.nu, self.gamma, adv, st, wind, self.supg_weight, self.supg_magic, True)
+        elif adv and self.burman:  # ... + adv * the linearised Burman term (a facet pass), then the boundary conditions
+            dl.assemble_burman(self.nu, self.gamma, adv, st, self.burman_weight, True)
+        else:
+            dl.assemble(self.nu, self.gamma, adv, st if adv else None, True)
+
     def _first_operators_on_device(self):
         """The Stokes operators the hierarchy is created with (what build_hierarchy(Re=0) assembles on the host otherwise),
         formed on the device; patches and coarse grid factored."""
-        mgl = self.hmg.mg.levels
-        for dl in mgl:
-            dl.assemble(self.nu, self.gamma, 0.0, None, True)
-        if self.allu:                       # (the first Newton step factors the operator it solves with)
+        with self._on_stream():
+            for dl, _, _ in self._device_levels():
+                self._assemble_level(dl, None, None, 0.0)
             self.ctx.sync()
-            return
-        for L, dl in zip(self.levels, mgl):
-            if L.level > 0:
-                dl.factor_with_fallback()
-        mgl[0].coarse_factor_auto()
-        self.ctx.sync()
+        if not self.allu:                   # (allu: the first Newton step factors the operator it solves with)
+            self._factor_levels()
 
     def _device_states(self, u):
         """Current velocity on every level, on the device: the finest is the velocity part of the resident state (``u`` given:
@@ -329,29 +352,19 @@ class HipNavierStokesSolver(object):
             self.hmg.mg.transfers[l - 1].inject(self._dstate[l], self._dstate[l - 1])
 
     def _rediscretise_device(self, u, adv):
-        t0 = time.time()
-        self._refresh_device(u, adv)
-        t1 = time.time()
-        self._factor_levels()
-        self.timings["assemble_s"] += t1 - t0
-        self.timings["factor_s"] += time.time() - t1
+        with self._timed("assemble_s"):
+            self._refresh_device(u, adv)
+        with self._timed("factor_s"):
+            self._factor_levels()
 
     def _refresh_device(self, u, adv):
-        """Every level's operator formed on the device about the current state (the first half of a Newton step's refresh)."""
-        self._device_states(u)
-        mgl = self.hmg.mg.levels
-        for l, (dl, st) in enumerate(zip(mgl, self._dstate)):
-            if self.allu and l < len(mgl) - 1:      # allu solves with the finest operator alone
-                continue
-            if adv and self.supg:     # A = nu K + gamma D + N(w) + the linearised SUPG term, THEN the boundary conditions
-                dl.assemble_supg(self.nu, self.gamma, adv, st, self.supg_weight, self.supg_magic, True)
-            elif adv and self.gls:    # ... + the linearised GLS term with the solve's wind
-                dl.assemble_gls(self.nu, self.gamma, adv, st, self._dwind[l], self.supg_weight, self.supg_magic, True)
-            elif adv and self.burman:  # ... + adv * the linearised Burman term (a facet pass), then the boundary conditions
-                dl.assemble_burman(self.nu, self.gamma, adv, st, self.burman_weight, True)
-            else:
-                dl.assemble(self.nu, self.gamma, adv, st if adv else None, True)
-        self.ctx.sync()
+        """Every level's operator formed on the device about the current state (the first half of a Newton step's refresh);
+        allu solves with the finest operator alone."""
+        with self._on_stream():
+            self._device_states(u)
+            for dl, st, wind in self._device_levels()[-1 if self.allu else 0:]:
+                self._assemble_level(dl, st, wind, adv)
+            self.ctx.sync()
 
     def _factor_levels(self):
         """Patches of every level and the coarse grid factored from the operator values the device holds (allu: the direct
@@ -384,76 +397,41 @@ class HipNavierStokesSolver(object):
         F = self._dF.get()
         return F[:self.n_u], F[self.n_u:]
 
-    def _residual_on_device(self, adv):
-        """F(z) for the state resident in ``_dz`` into ``_dF`` = (F_u | F_p); nothing crosses to the host."""
-        fin = self.hmg.mg.levels[-1]
-        n_u, n_p = self.n_u, self.n_p
-        du, dp = self._dstate[-1], hip.view(self._dz, n_u, n_p)
-        Fu, Fp = hip.view(self._dF, 0, n_u), hip.view(self._dF, n_u, n_p)
-        fin.assemble_mult(self.nu, self.gamma, 0.5 * adv, du if adv else None, du, Fu)
+    def _velocity_residual(self, fin, st, wind, adv, out):
+        """out = (nu K + gamma D + 1/2 N(u)) u (+ the stabilisation's residual) for the finest level's state ``st``."""
+        fin.assemble_mult(self.nu, self.gamma, 0.5 * adv, st if adv else None, st, out)
         if adv and self.supg:         # + the SUPG residual, gathered on the device into the same vector
-            fin.supg(self.nu, self.supg_weight, self.supg_magic, du, False, Fu)
+            fin.supg(self.nu, self.supg_weight, self.supg_magic, st, False, out)
         if adv and self.gls:          # + the GLS residual with the solve's wind
-            fin.gls(self.nu, self.supg_weight, self.supg_magic, du, self._dwind[-1], False, Fu)
+            fin.gls(self.nu, self.supg_weight, self.supg_magic, st, wind, False, out)
         if adv and self.burman:       # + advect * the Burman residual (solver.py:233-234), facet pass + node gather
-            fin.burman(adv * self.burman_weight, du, False, Fu)
+            fin.burman(adv * self.burman_weight, st, False, out)
+
+    def _momentum_residual(self, fin, st, wind, dp, adv, Fu):
+        """Fu = the velocity terms + B^T p (partitioned: the rank's share of B^T p goes through the halo onto the owners)."""
+        self._velocity_residual(fin, st, wind, adv, Fu)
         self._dBT.mult(dp, Fu, mode=2)                                    # F_u += B^T p
-        if self._load is not None:                                         # body force: F_u -= (f, v)
-            self.ctx.axpy(Fu, self._dload, -1.0)
-        fin.zero_bc(Fu)                                                    # bc.zero(F), solver.py:282-286
-        self._dB.mult(du, Fp)                                              # F_p = B u
+
+    def _residual_on_device(self, adv):
+        """F(z) for the state resident in ``_dz`` into ``_dF`` = (F_u | F_p), every rank its owned entries; nothing crosses to
+        the host."""
+        fin, st, wind = self._device_levels()[-1]
+        n_u, n_p = self._n_own, max(self._np_own, 1)
+        Fu = hip.view(self._dF, 0, n_u)
+        with self._on_stream():
+            self._momentum_residual(fin, st, wind, hip.view(self._dz, n_u, n_p), adv, Fu)
+            if self._load is not None:                                         # body force: F_u -= (f, v)
+                self.ctx.axpy(Fu, self._dload, -1.0, n=n_u)
+            fin.zero_bc(Fu)                                                    # bc.zero(F), solver.py:282-286
+            self._dB.mult(st, hip.view(self._dF, n_u, n_p))                   # F_p = B u
 
     def _set_parameters(self):
-        for T, dt in zip(self.transfers, self.hmg.mg.transfers):            # AutoSchoeberlTransfer.rebuild, transfer.py:173-184
-            if T.nu != self.nu:
-                T.nu = self.nu
-                dt.update(self.nu, self.gamma)
+        with self._on_stream():
+            for T, dt in self._device_transfers:                            # AutoSchoeberlTransfer.rebuild, transfer.py:173-184
+                if T.nu != self.nu:
+                    T.nu = self.nu
+                    dt.update(self.nu, self.gamma)
         self.saddle.update(self.nu, self.gamma)
-
-    def _solve_on_device(self, re, adv):
-        """The Newton loop of ``solve`` with the state, the residual and the update resident in HBM: per step the operators
-        are refreshed from the state in place, J e = F is solved on the device (e = - update; the Krylov iterates of b and
-        - b mirror each other), z -= e, and only scalars -- norms, iteration counts -- reach the host."""
-        if not (self._device_newer or self._device_current):
-            self._push_state()
-            self._device_current = True
-        if self._load is not None:
-            self._push_load()
-        if self.gls:                  # the wind: z_last, the state at the start of this solve (solver.py:199, 205, 215)
-            self._device_winds()
-        norm = lambda v: float(np.sqrt(self._zdot(v, v)))
-        lin_its, newton_its = 0, 0
-        t_r = time.time()
-        self._residual_on_device(adv)
-        f0 = fnorm = norm(self._dF)
-        self.timings["residual_s"] += time.time() - t_r
-        hist = [fnorm]
-        small_step = False
-        while fnorm > max(self.snes_rtol * f0, self.snes_atol) and newton_its < self.snes_max_it and not small_step:
-            self._rediscretise_device(None, adv)
-            t_s = time.time()
-            its, rn = self._zsolve(self._dF, self._dd)
-            self._zaxpy(self._dz, self._dd, -1.0)
-            self._device_newer, self._device_current = True, False
-            self.timings["solve_s"] += time.time() - t_s
-            lin_its += its
-            newton_its += 1
-            self.timings["newton_steps"] += 1
-            t_r = time.time()
-            self._residual_on_device(adv)
-            fnorm = norm(self._dF)
-            self.timings["residual_s"] += time.time() - t_r
-            hist.append(fnorm)
-            # SNESConvergedDefault [3P] with snes_stol (solver.py:490, 498): the step is small relative to the iterate
-            if norm(self._dd) < self.snes_stol * norm(self._dz):
-                small_step = True
-            if self.verbose:
-                print("[alfi_amd] Re %g  Newton %d  |F| %.3e  (%d Krylov its, linear residual %.2e)"
-                      % (re, newton_its, fnorm, its, rn), flush=True)
-        if self.nullspace:                                                   # zero pressure integral, solver.py:273-277
-            self._shift_pressure()
-            self._device_newer, self._device_current = True, False
-        return lin_its, newton_its, hist, small_step, fnorm, f0
 
     def _device_winds(self):
         """GLS's wind on every level: the resident finest velocity copied, the coarser ones injected as the state is."""
@@ -461,31 +439,43 @@ class HipNavierStokesSolver(object):
         for l in range(len(self.levels) - 1, 0, -1):
             self.hmg.mg.transfers[l - 1].inject(self._dwind[l], self._dwind[l - 1])
 
-    # -- the pieces of the device-resident loop a partitioned solver replaces (alfi_amd.dist.DistNavierStokesSolver) ------
+    # -- the device-resident state: (u | p) on one GPU, (owned u | owned p) per rank on partitions -----------------------------
+    # (``_own_dofs`` / ``_own_cells`` index the rank's entries of a global velocity / pressure vector, ``_n_own`` / ``_np_own``
+    # count them, ``_ksp`` is the library's outer solver: set by ``_create_device``)
     def _push_state(self):
-        self._dz.set(np.concatenate([self._host_u, self._host_p]))
+        u, p = self._host_u[self._own_dofs], self._host_p[self._own_cells]
+        with self._on_stream():
+            self._dz.set(np.concatenate([u, p, np.zeros(self._dz.n - u.size - p.size)]))
 
     def _push_load(self):
         if getattr(self, "_dload", None) is None:
-            self._dload = self.ctx.vec(self.n_u)
-        self._dload.set(self._load)
+            self._dload = self.ctx.vec(max(self._n_own, 1))
+        with self._on_stream():
+            self._dload.set(np.ascontiguousarray(self._load[self._own_dofs]) if self._n_own else np.zeros(1))
 
     def _zdot(self, x, y):
-        return self.saddle.dot(x, y)
+        with self._on_stream():
+            return self._ksp.dot(x, y)
 
     def _zsolve(self, b, x):
-        return self.saddle.solve(b, x, self.rtol, self.atol, self.params["ksp_max_it"], 30)
+        with self._on_stream():
+            return self._ksp.solve(b, x, self.rtol, self.atol, self.params["ksp_max_it"], 30)
 
     def _zaxpy(self, y, x, a):
-        self.ctx.axpy(y, x, a)
+        with self._on_stream():
+            self.ctx.axpy(y, x, a, n=self._n_own + self._np_own)
 
     def _shift_pressure(self):
         """p -= (int p) / |domain| on the device."""
-        ctx = self.ctx
+        n_u, n_p = self._n_own, self._np_own
         if getattr(self, "_dvolz", None) is None:
-            self._dvolz = ctx.vec(np.concatenate([np.zeros(self.n_u), self.vol]))
-            self._dones = ctx.vec(np.ones(self.n_p))
-        ctx.axpy(self._dz, self._dones, -self._zdot(self._dvolz, self._dz) / self.area, n=self.n_p, y_off=self.n_u)
+            with self._on_stream():
+                self._dvolz = self.ctx.vec(np.concatenate([np.zeros(n_u), self.vol[self._own_cells],
+                                                           np.zeros(self._dz.n - n_u - n_p)]))
+                self._dones = self.ctx.vec(np.ones(max(n_p, 1)))
+        c = self._zdot(self._dvolz, self._dz) / self.area
+        with self._on_stream():
+            self.ctx.axpy(self._dz, self._dones, -c, n=n_p, y_off=n_u)
 
     def _device_state_resident(self):
         """Whether the Newton loop runs with the state on the device (the operators are refreshed there anyway)."""
@@ -593,7 +583,7 @@ class HipNavierStokesSolver(object):
     def _stabilisation_load(self, f):
         """The body force at the SUPG / GLS points of every level (it depends on Re: once per solve), to the device levels when
         they refresh their operators."""
-        if self._partitioned():
+        if self._partitioned:
             raise NotImplementedError("a body force with SUPG on partitioned levels: the rank-local load tables are not built")
         self._fq = [hip.supg_load(L.V, f) for L in self.levels]
         if self.device_assembly:
@@ -630,53 +620,108 @@ class HipNavierStokesSolver(object):
             self._load = load_vector(self.levels[-1].V, f)
             if self.supg or self.gls:     # the strong residual carries the force too (solver.py:216-217): per level, per solve
                 self._stabilisation_load(f)
-        if self.gls and not self._device_state_resident():     # the wind z_last of this solve, on every level
+        resident = self._device_state_resident()
+        if resident:
+            if not (self._device_newer or self._device_current):
+                self._push_state()
+                self._device_current = True
+            if self._load is not None:
+                self._push_load()
+            if self.gls:              # the wind: z_last, the state at the start of this solve (solver.py:199, 205, 215)
+                self._device_winds()
+        elif self.gls:                # ... on every level, on the host
             self._host_winds = [np.ascontiguousarray(w) for w in self._winds(self.u.copy())]
-        if self._device_state_resident():
-            lin_its, newton_its, hist, small_step, fnorm, f0 = self._solve_on_device(re, adv)
-            info = {"Re": re, "nu": self.nu, "linear_iter": lin_its, "nonlinear_iter": newton_its,
-                    "time": (time.time() - t0) / 60.0, "residual_history": hist,
-                    "converged": small_step or fnorm <= max(self.snes_rtol * f0, self.snes_atol),
-                    "converged_reason": "SNORM_RELATIVE" if small_step else "FNORM"}
-            return _StateHandle(self), info
-        u, p = self.u.copy(), self.p.copy()
-        lin_its, newton_its = 0, 0
-        t_r = time.time()
-        Fu, Fp = self.residual(u, p, adv)
-        self.timings["residual_s"] += time.time() - t_r
-        f0 = fnorm = float(np.sqrt(Fu @ Fu + Fp @ Fp))
+        return self._newton((_DeviceState if resident else _HostState)(self, adv), re, t0)
+
+    def _newton(self, state, re, t0):
+        """``snes_type newtonls`` with the basic line search around a state (``_HostState`` / ``_DeviceState``):
+        ``residual()`` evaluates F at the iterate and returns |F|, ``step()`` takes one Newton step and returns (Krylov
+        iterations, linear residual norm, |step|, |iterate|), ``finish()`` publishes the iterate and returns what ``solve``
+        returns as z."""
+        lin_its, newton_its, small_step = 0, 0, False
+        with self._timed("residual_s"):
+            f0 = fnorm = state.residual()
+        tol = max(self.snes_rtol * f0, self.snes_atol)
         hist = [fnorm]
-        small_step = False
-        while fnorm > max(self.snes_rtol * f0, self.snes_atol) and newton_its < self.snes_max_it and not small_step:
-            self._rediscretise(u, adv)
-            rhs = -np.concatenate([Fu, Fp])
-            t_s = time.time()
-            delta, its, rn = self._linear_solve(rhs)
-            self.timings["solve_s"] += time.time() - t_s
-            u += delta[:self.n_u]
-            p += delta[self.n_u:]
+        while fnorm > tol and newton_its < self.snes_max_it and not small_step:
+            its, rn, snorm, znorm = state.step()
             lin_its += its
             newton_its += 1
             self.timings["newton_steps"] += 1
-            t_r = time.time()
-            Fu, Fp = self.residual(u, p, adv)
-            self.timings["residual_s"] += time.time() - t_r
-            fnorm = float(np.sqrt(Fu @ Fu + Fp @ Fp))
+            with self._timed("residual_s"):
+                fnorm = state.residual()
             hist.append(fnorm)
             # SNESConvergedDefault [3P] with snes_stol (solver.py:490, 498): the step is small relative to the iterate
-            if np.linalg.norm(delta) < self.snes_stol * float(np.sqrt(u @ u + p @ p)):
-                small_step = True
+            small_step = snorm < self.snes_stol * znorm
             if self.verbose:
                 print("[alfi_amd] Re %g  Newton %d  |F| %.3e  (%d Krylov its, linear residual %.2e)"
                       % (re, newton_its, fnorm, its, rn), flush=True)
-        if self.nullspace:
-            p -= (self.vol @ p) / self.area                                  # zero pressure integral, solver.py:273-277
-        self.u, self.p = u, p
+        z = state.finish()
         info = {"Re": re, "nu": self.nu, "linear_iter": lin_its, "nonlinear_iter": newton_its,
-                "time": (time.time() - t0) / 60.0, "residual_history": hist,
-                "converged": small_step or fnorm <= max(self.snes_rtol * f0, self.snes_atol),
+                "time": (time.time() - t0) / 60.0, "residual_history": hist, "converged": small_step or fnorm <= tol,
                 "converged_reason": "SNORM_RELATIVE" if small_step else "FNORM"}
-        return (u, p), info
+        return z, info
+
+
+class _HostState(object):
+    """The Newton iterate as host arrays (``device_assembly=False``): J d = -F, z += d."""
+
+    def __init__(self, solver, adv):
+        self.s, self.adv = solver, adv
+        self.u, self.p = solver.u.copy(), solver.p.copy()
+
+    def residual(self):
+        self.Fu, self.Fp = self.s.residual(self.u, self.p, self.adv)
+        return float(np.sqrt(self.Fu @ self.Fu + self.Fp @ self.Fp))
+
+    def step(self):
+        s, u, p = self.s, self.u, self.p
+        s._rediscretise(u, self.adv)
+        rhs = -np.concatenate([self.Fu, self.Fp])
+        with s._timed("solve_s"):
+            delta, its, rn = s._linear_solve(rhs)
+        u += delta[:s.n_u]
+        p += delta[s.n_u:]
+        return its, rn, np.linalg.norm(delta), float(np.sqrt(u @ u + p @ p))
+
+    def finish(self):
+        s = self.s
+        if s.nullspace:
+            self.p -= (s.vol @ self.p) / s.area                              # zero pressure integral, solver.py:273-277
+        s.u, s.p = self.u, self.p
+        return self.u, self.p
+
+
+class _DeviceState(object):
+    """The Newton iterate, the residual and the update resident in HBM (``_dz``, ``_dF``, ``_dd``): per step the operators are
+    refreshed from the state in place, J e = F is solved on the device (e = - update; the Krylov iterates of b and - b mirror
+    each other), z -= e, and only scalars -- norms, iteration counts -- reach the host."""
+
+    def __init__(self, solver, adv):
+        self.s, self.adv = solver, adv
+
+    def _norm(self, v):
+        return float(np.sqrt(self.s._zdot(v, v)))
+
+    def residual(self):
+        self.s._residual_on_device(self.adv)
+        return self._norm(self.s._dF)
+
+    def step(self):
+        s = self.s
+        s._rediscretise_device(None, self.adv)
+        with s._timed("solve_s"):
+            its, rn = s._zsolve(s._dF, s._dd)
+            s._zaxpy(s._dz, s._dd, -1.0)
+            s._device_newer, s._device_current = True, False
+        return its, rn, self._norm(s._dd), self._norm(s._dz)
+
+    def finish(self):
+        s = self.s
+        if s.nullspace:                                                      # zero pressure integral, solver.py:273-277
+            s._shift_pressure()
+            s._device_newer, s._device_current = True, False
+        return _StateHandle(s)
 
 
 class _StateHandle(object):

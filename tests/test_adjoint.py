@@ -90,7 +90,6 @@ def test_load_functional_gradient(rs):
 
 def test_partitioned_solver_refuses_the_adjoint():
     """DistNavierStokesSolver.setup_adjoint: J^T needs the mirror blocks of the ghost columns, which other ranks hold."""
-    from alfi_amd.dist import _dist_ns_solver_class
-    cls = _dist_ns_solver_class()
+    from alfi_amd.dist import DistNavierStokesSolver as cls
     with pytest.raises(NotImplementedError, match="partitioned"):
         cls.setup_adjoint(object.__new__(cls), LoadFunctional(_wfield))

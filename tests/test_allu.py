@@ -67,8 +67,7 @@ def test_built_solver_types_pass_validation(no_device, solver_type):
 
 
 def test_partitioned_solver_refuses_allu_before_any_collective(no_device):
-    from alfi_amd.dist import _dist_ns_solver_class
-    cls = _dist_ns_solver_class()
+    from alfi_amd.dist import DistNavierStokesSolver as cls
     with pytest.raises(NotImplementedError, match="single-rank"):
         cls(TwoDimLidDrivenCavityProblem(4), 1, 2, solver_type="allu")
     with pytest.raises(NotImplementedError, match="algebraic multigrid"):
