@@ -3,6 +3,8 @@ import ctypes
 import os
 import numpy as np
 
+from . import env
+
 _lib = None
 
 
@@ -44,8 +46,7 @@ def lib():
         _lib.alfi_host_supg.restype = ctypes.c_int
         _lib.alfi_host_gls.restype = ctypes.c_int
         _lib.alfi_host_burman.restype = ctypes.c_int
-        # ALFI_HOST_THREADS overrides OMP_NUM_THREADS (torch.distributed.run exports OMP_NUM_THREADS=1 to every rank)
-        nthr = int(os.environ.get("ALFI_HOST_THREADS", "0")) or cpu_share()
+        nthr = env.host_threads() or cpu_share()
         _lib.alfi_host_set_num_threads(ctypes.c_int(nthr))
     return _lib
 

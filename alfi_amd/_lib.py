@@ -3,9 +3,10 @@ cannot be loaded; there is no CPU fallback (the oracle under oracle/ is test inf
 import ctypes
 import os
 
+from . import env
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# ALFI_HIP_LIB: an alternative build of the same library (kernel tuning experiments)
-LIB_PATH = os.environ.get("ALFI_HIP_LIB") or os.path.join(_HERE, "libalfi_hip.so")
+LIB_PATH = env.hip_lib() or os.path.join(_HERE, "libalfi_hip.so")
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_i64p = ctypes.POINTER(ctypes.c_int64)

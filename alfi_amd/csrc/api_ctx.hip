@@ -7,11 +7,6 @@
 
 static thread_local std::string g_create_error;
 
-bool alfi_test_large_paths() {
-  static const bool on = getenv("ALFI_TEST_LARGE_PATHS") && atoi(getenv("ALFI_TEST_LARGE_PATHS")) == 1;
-  return on;
-}
-
 int alfi_set_error(alfi_ctx* ctx, int code, const char* fmt, ...) {
   char buf[1024];
   va_list ap;
@@ -26,25 +21,24 @@ int alfi_set_error(alfi_ctx* ctx, int code, const char* fmt, ...) {
 }
 
 // ---- profiling ---------------------------------------------------------------------------------------------------------
-int alfi_prof_begin(alfi_ctx* ctx, int kind) {
-  if (!ctx->prof) return -1;
-  if (ctx->prof == 2 && kind != ALFI_EV_PATCH_APPLY && kind != ALFI_EV_COMM) return -1;
-  if (ctx->prof == 3 && kind != ALFI_EV_PATCH_APPLY) return -1;
+ProfScope::ProfScope(alfi_ctx* ctx, int kind) : ctx_(ctx) {
+  if (!ctx->prof) return;
+  if (ctx->prof == 2 && kind != ALFI_EV_PATCH_APPLY && kind != ALFI_EV_COMM) return;
+  if (ctx->prof == 3 && kind != ALFI_EV_PATCH_APPLY) return;
   if (ctx->ev_used == ctx->ev_pool.size()) {
     alfi_ctx::EvPair p;
-    if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return -1;
+    if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return;
     ctx->ev_pool.push_back(p);
   }
-  const int t = (int)ctx->ev_used++;
-  ctx->ev_pool[t].kind = kind;
-  ctx->ev_pool[t].tag = ctx->cur_tag;
-  (void)hipEventRecord(ctx->ev_pool[t].a, ctx->stream);
-  return t;
+  token_ = (int)ctx->ev_used++;
+  ctx->ev_pool[token_].kind = kind;
+  ctx->ev_pool[token_].tag = ctx->cur_tag;
+  (void)hipEventRecord(ctx->ev_pool[token_].a, ctx->stream);
 }
-int alfi_prof_end(alfi_ctx* ctx, int token) {
-  if (token < 0) return 0;
-  (void)hipEventRecord(ctx->ev_pool[token].b, ctx->stream);
-  return 0;
+void ProfScope::close() {
+  if (token_ < 0) return;
+  (void)hipEventRecord(ctx_->ev_pool[token_].b, ctx_->stream);
+  token_ = -1;
 }
 
 // the sticky device-side error word (bounded waits of persistent kernels), read after a synchronisation
@@ -58,8 +52,8 @@ int check_dev_err(alfi_ctx* ctx) {
 }
 
 // Chunk tables of the flat layout.  Large matrices: equal chunks of SPMV_CHUNK blocks (rows may continue into the next
-// chunk; the fix-up launch completes them).  Small ones (nnzb <= SPMV_ALIGNED_MAX, no row longer than a chunk, unless
-// ALFI_SPMV_ALIGNED=0): chunks of whole block rows, greedily packed, so the product is ONE launch.  break_row >= 0: a chunk
+// chunk; the fix-up launch completes them).  Small ones (nnzb <= SPMV_ALIGNED_MAX, no row longer than a chunk, not under
+// ALFI_TEST_LARGE_PATHS): chunks of whole block rows, greedily packed, so the product is ONE launch.  break_row >= 0: a chunk
 // boundary is forced in front of that block row (the owned prefix of a partitioned level); returns the number of chunks
 // before it in *nchunks_before.
 int build_chunk_tables(alfi_ctx* ctx, DevBSR* d, const int32_t* rowptr, int64_t nbrows, int64_t break_row,
@@ -193,9 +187,8 @@ static int comm_call(alfi_level* L, int op, int64_t offset, int64_t count) {
 // sum dred[offset .. offset+count) over the ranks
 int comm_allreduce(alfi_level* L, int64_t offset, int64_t count) {
   alfi_ctx* ctx = L->ctx;
-  int t = alfi_prof_begin(ctx, ALFI_EV_COMM);
+  ProfScope prof(ctx, ALFI_EV_COMM);   // to the end of the function
   ALFI_CHECK(comm_call(L, ALFI_COMM_ALLREDUCE, offset, count));
-  alfi_prof_end(ctx, t);
   return 0;
 }
 
@@ -203,31 +196,28 @@ int comm_allreduce(alfi_level* L, int64_t offset, int64_t count) {
 int halo_fwd(alfi_level* L, double* v) {
   alfi_ctx* ctx = L->ctx;
   if (!L->has_halo) return alfi_set_error(ctx, ALFI_E_STATE, "halo exchange on a level without alfi_level_set_partition");
-  int t = alfi_prof_begin(ctx, ALFI_EV_COMM);
+  ProfScope prof(ctx, ALFI_EV_COMM);   // to the end of the function
   ALFI_CHECK(launch_halo_pack(ctx, L->halo_sendbuf, v, L->halo_send_nodes, L->halo_nsend, L->bs));
   ALFI_CHECK(comm_call(L, ALFI_COMM_HALO_FWD, 0, 0));
   // (an own copy kernel: the runtime's device-to-device copy costs more per call than these surface-sized buffers take)
   ALFI_CHECK(launch_copy(ctx, v + L->n_own, L->halo_recvbuf, L->halo_nghost * L->bs));
-  alfi_prof_end(ctx, t);
   return 0;
 }
 
 // the same in two halves: pack + start the exchange | (caller launches work that needs no ghost value) | wait + unpack
 int halo_fwd_begin(alfi_level* L, const double* v) {
   alfi_ctx* ctx = L->ctx;
-  int t = alfi_prof_begin(ctx, ALFI_EV_COMM);
+  ProfScope prof(ctx, ALFI_EV_COMM);   // to the end of the function
   ALFI_CHECK(launch_halo_pack(ctx, L->halo_sendbuf, v, L->halo_send_nodes, L->halo_nsend, L->bs));
   ALFI_CHECK(comm_call(L, ALFI_COMM_HALO_FWD_BEGIN, 0, 0));
-  alfi_prof_end(ctx, t);
   return 0;
 }
 int halo_fwd_end(alfi_level* L, double* v) {
   alfi_ctx* ctx = L->ctx;
-  int t = alfi_prof_begin(ctx, ALFI_EV_COMM);
+  ProfScope prof(ctx, ALFI_EV_COMM);   // to the end of the function
   ALFI_CHECK(comm_call(L, ALFI_COMM_HALO_FWD_END, 0, 0));
   // (an own copy kernel: the runtime's device-to-device copy costs more per call than these surface-sized buffers take)
   ALFI_CHECK(launch_copy(ctx, v + L->n_own, L->halo_recvbuf, L->halo_nghost * L->bs));
-  alfi_prof_end(ctx, t);
   return 0;
 }
 
@@ -235,11 +225,10 @@ int halo_fwd_end(alfi_level* L, double* v) {
 int halo_rev(alfi_level* L, double* v) {
   alfi_ctx* ctx = L->ctx;
   if (!L->has_halo) return alfi_set_error(ctx, ALFI_E_STATE, "halo exchange on a level without alfi_level_set_partition");
-  int t = alfi_prof_begin(ctx, ALFI_EV_COMM);
+  ProfScope prof(ctx, ALFI_EV_COMM);   // to the end of the function
   ALFI_CHECK(launch_copy(ctx, L->halo_recvbuf, v + L->n_own, L->halo_nghost * L->bs));
   ALFI_CHECK(comm_call(L, ALFI_COMM_HALO_REV, 0, 0));
   ALFI_CHECK(launch_halo_add(ctx, v, L->halo_sendbuf, L->rev_nodes, L->rev_ptr, L->rev_pos, L->rev_nuniq, L->bs));
-  alfi_prof_end(ctx, t);
   return 0;
 }
 
@@ -247,29 +236,26 @@ int halo_rev(alfi_level* L, double* v) {
 // copies -- has the sum of all holders' values, added in one fixed order
 int halo_sum(alfi_level* L, double* v) {
   alfi_ctx* ctx = L->ctx;
-  int t = alfi_prof_begin(ctx, ALFI_EV_COMM);
+  ProfScope prof(ctx, ALFI_EV_COMM);   // to the end of the function
   ALFI_CHECK(launch_halo_pack(ctx, L->sum_sendbuf, v, L->sum_send_nodes, L->sum_nsend, L->bs));
   ALFI_CHECK(comm_call(L, ALFI_COMM_HALO_SUM, 0, 0));
   ALFI_CHECK(launch_halo_sum(ctx, v, L->sum_recvbuf, L->sum_nodes, L->sum_ptr, L->sum_src, L->sum_nshared, L->bs));
-  alfi_prof_end(ctx, t);
   return 0;
 }
 
 // reverse route in two halves (see halo_rev): ghost slots -> buffer, start | ... | wait, add onto the owners
 int halo_rev_begin(alfi_level* L, const double* v) {
   alfi_ctx* ctx = L->ctx;
-  int t = alfi_prof_begin(ctx, ALFI_EV_COMM);
+  ProfScope prof(ctx, ALFI_EV_COMM);   // to the end of the function
   ALFI_CHECK(launch_copy(ctx, L->halo_recvbuf, v + L->n_own, L->halo_nghost * L->bs));
   ALFI_CHECK(comm_call(L, ALFI_COMM_HALO_REV_BEGIN, 0, 0));
-  alfi_prof_end(ctx, t);
   return 0;
 }
 int halo_rev_end(alfi_level* L, double* v) {
   alfi_ctx* ctx = L->ctx;
-  int t = alfi_prof_begin(ctx, ALFI_EV_COMM);
+  ProfScope prof(ctx, ALFI_EV_COMM);   // to the end of the function
   ALFI_CHECK(comm_call(L, ALFI_COMM_HALO_REV_END, 0, 0));
   ALFI_CHECK(launch_halo_add(ctx, v, L->halo_sendbuf, L->rev_nodes, L->rev_ptr, L->rev_pos, L->rev_nuniq, L->bs));
-  alfi_prof_end(ctx, t);
   return 0;
 }
 
@@ -376,8 +362,7 @@ int alfi_ctx_set_comm(alfi_ctx* ctx, alfi_comm_fn fn, void* user, double* dred, 
   ctx->comm = fn;
   ctx->comm_user = user;
   ctx->dred = dred;
-  const char* e = getenv("ALFI_DIST_EXACT_NORM");   // default: |w - V h| by its own all-reduce, as PETSc's VecNorm; 0: see comm.hip
-  ctx->exact_norm = !(e && atoi(e) == 0);
+  ctx->exact_norm = alfi_env_dist_exact_norm();
   return 0;
 }
 

@@ -21,13 +21,6 @@ int alfi_coarse_set_inverse(alfi_level* L, const double* inv, int inv_is_device)
   return 0;
 }
 
-// the coarse residual probe fails the setup beyond this (ALFI_COARSE_CHECK_FAIL; round 2 failed at 1e-5: ADVICE r2 -- at
-// Re 10 000 on fine coarse grids a merely ill-conditioned operator would have become a setup error)
-double coarse_probe_fail() {
-  static const double v = getenv("ALFI_COARSE_CHECK_FAIL") ? atof(getenv("ALFI_COARSE_CHECK_FAIL")) : 1e-2;
-  return v;
-}
-
 // +-1 pattern for the residual probe of the coarse inverse
 int alfi_coarse_factor(alfi_level* L) {
   alfi_ctx* ctx = L->ctx;
@@ -68,8 +61,8 @@ int alfi_coarse_factor(alfi_level* L) {
       L->cinv_residual = worst;
       // (cond(A_0) ~ 1e8 at config 4: cond * eps * |X| |A| |e| leaves ~1e-7 even for a perfectly rounded inverse; the
       // residual of a backward-stable factorisation scales with the condition number, so a large one is REPORTED through
-      // alfi_coarse_residual and only one beyond coarse_probe_fail() -- default 1e-2, or a non-finite one -- fails the setup)
-      if (!(worst <= coarse_probe_fail()))
+      // alfi_coarse_residual and only one beyond alfi_env_coarse_check_fail() -- default 1e-2, or a non-finite one -- fails the setup)
+      if (!(worst <= alfi_env_coarse_check_fail()))
         rc = alfi_set_error(ctx, ALFI_E_SINGULAR, "coarse inverse fails the residual probe: || A X e - e || = %.3e", worst);
     }
   }
@@ -122,7 +115,7 @@ int alfi_coarse_factor_sparse(alfi_level* L, const double* coords, int dim, int 
   if (rc == 0) rc = coarse_probe(L, &worst);
   if (rc == 0) {
     L->cinv_residual = worst;
-    if (!(worst <= coarse_probe_fail()))
+    if (!(worst <= alfi_env_coarse_check_fail()))
       rc = alfi_set_error(ctx, ALFI_E_SINGULAR, "sparse coarse factorisation fails the residual probe: || A x - e || = %.3e", worst);
   }
   if (rc != 0) {
@@ -148,10 +141,9 @@ int alfi_coarse_residual(alfi_level* L, double* worst) {
 int alfi_coarse_solve(alfi_level* L, const double* db, double* dx) {
   if (!L->cinv && !L->mf) return alfi_set_error(L->ctx, ALFI_E_STATE, "alfi_coarse_solve before alfi_coarse_set_inverse");
   L->ctx->cur_tag = L->id;
-  int t = alfi_prof_begin(L->ctx, ALFI_EV_COARSE);
+  ProfScope prof(L->ctx, ALFI_EV_COARSE);   // to the end of the function
   if (L->mf) ALFI_CHECK(mf_solve(L, db, dx));
   else ALFI_CHECK(launch_dense_gemv(L->ctx, L->cinv, db, dx, L->n));
-  alfi_prof_end(L->ctx, t);
   return 0;
 }
 
@@ -359,16 +351,16 @@ int alfi_prolong(alfi_transfer* T, const double* dxc, double* dxf) {
   // coarse cell touching an owned node run locally (redundantly at partition boundaries), writes to ghost slots are scratch
   const bool par = T->fine->distributed;
   if (par) ALFI_CHECK(halo_fwd(T->coarse, const_cast<double*>(dxc)));
-  int t = alfi_prof_begin(ctx, ALFI_EV_PROLONG);
-  ALFI_CHECK(launch_bsr_spmv(ctx, T->P, dxc, dxf, nullptr, 0.0, 0));                 // rhs = P coarse        :247
-  alfi_prof_end(ctx, t);
+  {
+    ProfScope prof(ctx, ALFI_EV_PROLONG);
+    ALFI_CHECK(launch_bsr_spmv(ctx, T->P, dxc, dxf, nullptr, 0.0, 0));               // rhs = P coarse        :247
+  }
   if (par) ALFI_CHECK(halo_fwd(T->fine, dxf));
-  t = alfi_prof_begin(ctx, ALFI_EV_PROLONG);
+  ProfScope prof(ctx, ALFI_EV_PROLONG);   // to the end of the function
   ALFI_CHECK(launch_bsr_spmv(ctx, T->DI, dxf, T->bI, nullptr, 0.0, 0));              // b_I = (D rhs)_I       :249
   ALFI_CHECK(launch_block_gemv(T, T->bI, T->tI, false));                              // t = inv(A_II) b_I     :254-257
   ALFI_CHECK(launch_scatter_sub(ctx, dxf, T->blk_dofs, T->tI, T->gamma, T->nblk * T->m));  // fine = rhs - gamma t  :259
   ALFI_CHECK(launch_zero_dofs(ctx, dxf, T->fine->bc_dofs, T->fine->nbc));
-  alfi_prof_end(ctx, t);
   return 0;
 }
 
@@ -378,19 +370,18 @@ int alfi_restrict(alfi_transfer* T, const double* drf, double* drc, int robust) 
   ctx->cur_tag = T->fine->id;
   const bool par = T->fine->distributed;
   if (par && robust) ALFI_CHECK(halo_fwd(T->fine, const_cast<double*>(drf)));
-  int t = alfi_prof_begin(ctx, ALFI_EV_RESTRICT);
   if (robust) {
+    ProfScope prof(ctx, ALFI_EV_RESTRICT);
     ALFI_CHECK(launch_block_gemv(T, drf, T->tI, true));                               // t = inv(A_II) r_I     :265-270
     ALFI_CHECK(launch_bsr_spmv(ctx, T->DIT, T->tI, T->tmp_f, drf, T->gamma, 1));      // s = r - gamma D t     :272-274
     ALFI_CHECK(launch_bsr_spmv(ctx, T->PT, T->tmp_f, drc, nullptr, 0.0, 0));          // coarse = P^T s        :275
   } else {
+    ProfScope prof(ctx, ALFI_EV_RESTRICT);
     ALFI_CHECK(launch_bsr_spmv(ctx, T->PTp, drf, drc, nullptr, 0.0, 0));              // firedrake.restrict
   }
-  alfi_prof_end(ctx, t);
   if (par) ALFI_CHECK(halo_rev(T->coarse, drc));   // partial sums over the owned fine nodes -> the coarse owners
-  t = alfi_prof_begin(ctx, ALFI_EV_RESTRICT);
+  ProfScope prof(ctx, ALFI_EV_RESTRICT);   // to the end of the function
   ALFI_CHECK(launch_zero_dofs(ctx, drc, T->coarse->bc_dofs, T->coarse->nbc));
-  alfi_prof_end(ctx, t);
   return 0;
 }
 
@@ -454,9 +445,10 @@ static int vcycle(alfi_mg* mg, int l, const double* b, double* x, bool x_zero) {
   ALFI_CHECK(vcycle(mg, l - 1, C->mg_b, C->mg_x, true));
   ALFI_CHECK(alfi_prolong(T, C->mg_x, L->mg_r));                     // x += P x_{l-1}
   ctx->cur_tag = L->id;
-  int t = alfi_prof_begin(ctx, ALFI_EV_BLAS1);
-  ALFI_CHECK(launch_axpy(ctx, x, L->mg_r, 1.0, L->n_own));
-  alfi_prof_end(ctx, t);
+  {
+    ProfScope prof(ctx, ALFI_EV_BLAS1);
+    ALFI_CHECK(launch_axpy(ctx, x, L->mg_r, 1.0, L->n_own));
+  }
   ALFI_CHECK(alfi_smooth_fgmres(L, mg->k, b, x, 1));                 // post-smooth
   return 0;
 }

@@ -50,8 +50,6 @@ int halo_rev(alfi_level* L, double* v);
 int halo_sum(alfi_level* L, double* v);
 int halo_rev_begin(alfi_level* L, const double* v);
 int halo_rev_end(alfi_level* L, double* v);
-// api_cycles.hip
-double coarse_probe_fail();   // residual probe bound of the exact solves (ALFI_COARSE_CHECK_FAIL, default 1e-2)
 // api_level.hip
 void free_assembly(AssemblyDev* S);
 int level_spmv(alfi_level* L, const double* dx, double* dy, const double* db, int mode, bool ghosts_current = false);

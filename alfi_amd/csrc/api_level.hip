@@ -380,10 +380,11 @@ int alfi_level_assemble(alfi_level* L, double nu, double gamma, double adv, cons
   if (adv != 0.0 && !d_state) return alfi_set_error(ctx, ALFI_E_ARG, "advection needs the state");
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->cur_tag = L->id;
-  int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);       // PCPatchComputeOp
-  ALFI_CHECK(launch_operator_refresh(L, nu, gamma, adv, d_state, true, ALFI_STAB_NONE, nullptr, 0.0, 0.0, false, apply_bc != 0,
-                                     L->A.vals));
-  alfi_prof_end(ctx, t);
+  {
+    ProfScope prof(ctx, ALFI_EV_PATCH_FACTOR);       // PCPatchComputeOp
+    ALFI_CHECK(launch_operator_refresh(L, nu, gamma, adv, d_state, true, ALFI_STAB_NONE, nullptr, 0.0, 0.0, false, apply_bc != 0,
+                                       L->A.vals));
+  }
   L->factored = false;
   ++L->op_version;
   L->fc_scale = 0.0;
@@ -398,10 +399,11 @@ int alfi_level_assemble_supg(alfi_level* L, double nu, double gamma, double adv,
   if (!d_state) return alfi_set_error(ctx, ALFI_E_ARG, "SUPG needs the state");
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->cur_tag = L->id;
-  int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);
-  ALFI_CHECK(launch_operator_refresh(L, nu, gamma, adv, d_state, true, ALFI_STAB_SUPG, nullptr, weight, magic, false, apply_bc != 0,
-                                     L->A.vals));
-  alfi_prof_end(ctx, t);
+  {
+    ProfScope prof(ctx, ALFI_EV_PATCH_FACTOR);
+    ALFI_CHECK(launch_operator_refresh(L, nu, gamma, adv, d_state, true, ALFI_STAB_SUPG, nullptr, weight, magic, false,
+                                       apply_bc != 0, L->A.vals));
+  }
   L->factored = false;
   ++L->op_version;
   return 0;
@@ -415,11 +417,11 @@ int alfi_level_assemble_gls(alfi_level* L, double nu, double gamma, double adv, 
   if (!d_state || !d_wind) return alfi_set_error(ctx, ALFI_E_ARG, "GLS needs the state and the wind");
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->cur_tag = L->id;
-  int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);
-  const int rc = launch_operator_refresh(L, nu, gamma, adv, d_state, true, ALFI_STAB_GLS, d_wind, weight, magic, false,
-                                         apply_bc != 0, L->A.vals);
-  alfi_prof_end(ctx, t);
-  if (rc != 0) return rc;
+  {
+    ProfScope prof(ctx, ALFI_EV_PATCH_FACTOR);
+    ALFI_CHECK(launch_operator_refresh(L, nu, gamma, adv, d_state, true, ALFI_STAB_GLS, d_wind, weight, magic, false,
+                                       apply_bc != 0, L->A.vals));
+  }
   L->factored = false;
   ++L->op_version;
   return 0;
@@ -465,9 +467,8 @@ int alfi_level_assemble_mult(alfi_level* L, double nu, double gamma, double adv,
   if (!dx || !dy) return alfi_set_error(ctx, ALFI_E_ARG, "NULL argument");
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->cur_tag = L->id;
-  int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);
+  ProfScope prof(ctx, ALFI_EV_PATCH_FACTOR);   // to the end of the function
   ALFI_CHECK(launch_element_mult(L, nu, gamma, adv, d_state, dx, dy));
-  alfi_prof_end(ctx, t);
   return 0;
 }
 
@@ -542,13 +543,12 @@ static int level_stabilisation(alfi_level* L, int stab, double nu, double weight
   alfi_ctx* ctx = L->ctx;
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->cur_tag = L->id;
-  int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);       // PCPatchComputeOp
-  int rc = 0;
-  if (add_to_operator)
-    rc = launch_operator_refresh(L, nu, 0.0, 0.0, d_state, false, stab, d_wind, weight, magic, true, false, L->A.vals);
-  if (rc == 0 && d_F) rc = launch_supg_residual(L, nu, weight, magic, d_state, d_wind, d_F);
-  alfi_prof_end(ctx, t);
-  if (rc != 0) return rc;
+  {
+    ProfScope prof(ctx, ALFI_EV_PATCH_FACTOR);       // PCPatchComputeOp
+    if (add_to_operator)
+      ALFI_CHECK(launch_operator_refresh(L, nu, 0.0, 0.0, d_state, false, stab, d_wind, weight, magic, true, false, L->A.vals));
+    if (d_F) ALFI_CHECK(launch_supg_residual(L, nu, weight, magic, d_state, d_wind, d_F));
+  }
   if (add_to_operator) {
     L->factored = false;
     ++L->op_version;
@@ -660,9 +660,10 @@ int alfi_level_burman(alfi_level* L, double weight, const double* d_state, int a
   if (!add_to_operator && !d_F) return 0;
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->cur_tag = L->id;
-  int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);       // PCPatchComputeOp
-  ALFI_CHECK(launch_burman(L, weight, d_state, add_to_operator != 0, d_F));
-  alfi_prof_end(ctx, t);
+  {
+    ProfScope prof(ctx, ALFI_EV_PATCH_FACTOR);       // PCPatchComputeOp
+    ALFI_CHECK(launch_burman(L, weight, d_state, add_to_operator != 0, d_F));
+  }
   if (add_to_operator) {
     L->factored = false;
     ++L->op_version;
@@ -680,11 +681,12 @@ int alfi_level_assemble_burman(alfi_level* L, double nu, double gamma, double ad
   if (!d_state) return alfi_set_error(ctx, ALFI_E_ARG, "the Burman term needs the state");
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->cur_tag = L->id;
-  int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);
-  ALFI_CHECK(launch_operator_refresh(L, nu, gamma, adv, d_state, true, ALFI_STAB_NONE, nullptr, 0.0, 0.0, false, false, L->A.vals));
-  if (adv != 0.0) ALFI_CHECK(launch_burman(L, adv * weight, d_state, true, nullptr));
-  if (apply_bc) ALFI_CHECK(launch_apply_bc(L));
-  alfi_prof_end(ctx, t);
+  {
+    ProfScope prof(ctx, ALFI_EV_PATCH_FACTOR);
+    ALFI_CHECK(launch_operator_refresh(L, nu, gamma, adv, d_state, true, ALFI_STAB_NONE, nullptr, 0.0, 0.0, false, false, L->A.vals));
+    if (adv != 0.0) ALFI_CHECK(launch_burman(L, adv * weight, d_state, true, nullptr));
+    if (apply_bc) ALFI_CHECK(launch_apply_bc(L));
+  }
   L->factored = false;
   ++L->op_version;
   L->fc_scale = adv * weight;
@@ -822,22 +824,20 @@ int alfi_level_id(alfi_level* L, int* id) {
 int level_spmv(alfi_level* L, const double* dx, double* dy, const double* db, int mode, bool ghosts_current) {
   alfi_ctx* ctx = L->ctx;
   ctx->cur_tag = L->id;
-  int t;
   if (L->distributed && L->overlap && !ghosts_current) {
     ALFI_CHECK(halo_fwd_begin(L, dx));
-    t = alfi_prof_begin(ctx, ALFI_EV_MATMULT);
-    ALFI_CHECK(launch_bsr_spmv(ctx, L->A_int, dx, dy, db, 1.0, mode));
-    alfi_prof_end(ctx, t);
+    {
+      ProfScope prof(ctx, ALFI_EV_MATMULT);
+      ALFI_CHECK(launch_bsr_spmv(ctx, L->A_int, dx, dy, db, 1.0, mode));
+    }
     ALFI_CHECK(halo_fwd_end(L, const_cast<double*>(dx)));
-    t = alfi_prof_begin(ctx, ALFI_EV_MATMULT);
+    ProfScope prof(ctx, ALFI_EV_MATMULT);   // to the end of the function
     ALFI_CHECK(launch_bsr_spmv(ctx, L->A_bnd, dx, dy, db, 1.0, mode));
-    alfi_prof_end(ctx, t);
     return 0;
   }
   if (L->distributed && !ghosts_current) ALFI_CHECK(halo_fwd(L, const_cast<double*>(dx)));
-  t = alfi_prof_begin(ctx, ALFI_EV_MATMULT);
+  ProfScope prof(ctx, ALFI_EV_MATMULT);   // to the end of the function
   ALFI_CHECK(launch_bsr_spmv(ctx, L->A_own, dx, dy, db, 1.0, mode));
-  alfi_prof_end(ctx, t);
   return 0;
 }
 
@@ -857,36 +857,28 @@ int level_patch_apply(alfi_level* L, const double* dx, double* dy, bool* ghosts_
     // iteration order and, with symmetrise_sweep, back again in reverse order
     if (L->distributed) ALFI_CHECK(halo_fwd(L, const_cast<double*>(dx)));
     ALFI_HIP_CHECK(ctx, hipMemsetAsync(dy, 0, sizeof(double) * L->n, ctx->stream));
-    int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_APPLY);
-    const int64_t nw = (int64_t)L->mult_wave_ptr.size() - 1;
-    // ALFI_MULT_PERSISTENT=0: one launch per dependency wavefront (the schedule of rounds 1-3; kept for the bitwise comparison)
-    static const bool persistent = !(getenv("ALFI_MULT_PERSISTENT") && atoi(getenv("ALFI_MULT_PERSISTENT")) == 0);
-    if (persistent && L->mult_nitems > 0) {
-      // (a wait that runs into its bound sets the ctx's sticky error word, reported by the next synchronising call: no host
-      // synchronisation inside the smoother)
-      ALFI_CHECK(launch_patch_mult_persistent(L, dx, dy));
-      alfi_prof_end(ctx, t);
-      if (L->distributed) ALFI_CHECK(halo_rev(L, dy));
-      if (L->nbc > 0) {
-        t = alfi_prof_begin(ctx, ALFI_EV_PATCH_SCATTER);
-        ALFI_CHECK(launch_copy_dofs(ctx, dy, dx, L->bc_dofs, L->nbc));
-        alfi_prof_end(ctx, t);
+    const bool persistent = alfi_env_mult_persistent() && L->mult_nitems > 0;
+    {
+      ProfScope prof(ctx, ALFI_EV_PATCH_APPLY);
+      if (persistent) {
+        // (a wait that runs into its bound sets the ctx's sticky error word, reported by the next synchronising call: no host
+        // synchronisation inside the smoother)
+        ALFI_CHECK(launch_patch_mult_persistent(L, dx, dy));
+      } else {   // one launch per dependency wavefront
+        const int64_t nw = (int64_t)L->mult_wave_ptr.size() - 1;
+        for (int64_t w = 0; w < nw; ++w)
+          ALFI_CHECK(launch_patch_mult_wave(L, L->mult_seq + L->mult_wave_ptr[w], L->mult_wave_ptr[w + 1] - L->mult_wave_ptr[w],
+                                            dx, dy));
+        if (L->mult_symmetrise)
+          for (int64_t w = nw - 1; w >= 0; --w)
+            ALFI_CHECK(launch_patch_mult_wave(L, L->mult_seq + L->mult_wave_ptr[w],
+                                              L->mult_wave_ptr[w + 1] - L->mult_wave_ptr[w], dx, dy));
       }
-      return 0;
     }
-    for (int64_t w = 0; w < nw; ++w)
-      ALFI_CHECK(launch_patch_mult_wave(L, L->mult_seq + L->mult_wave_ptr[w], L->mult_wave_ptr[w + 1] - L->mult_wave_ptr[w],
-                                        dx, dy));
-    if (L->mult_symmetrise)
-      for (int64_t w = nw - 1; w >= 0; --w)
-        ALFI_CHECK(launch_patch_mult_wave(L, L->mult_seq + L->mult_wave_ptr[w],
-                                          L->mult_wave_ptr[w + 1] - L->mult_wave_ptr[w], dx, dy));
-    alfi_prof_end(ctx, t);
     if (L->distributed) ALFI_CHECK(halo_rev(L, dy));
     if (L->nbc > 0) {
-      t = alfi_prof_begin(ctx, ALFI_EV_PATCH_SCATTER);
+      ProfScope prof(ctx, ALFI_EV_PATCH_SCATTER);
       ALFI_CHECK(launch_copy_dofs(ctx, dy, dx, L->bc_dofs, L->nbc));
-      alfi_prof_end(ctx, t);
     }
     return 0;
   }

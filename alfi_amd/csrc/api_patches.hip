@@ -549,7 +549,7 @@ int alfi_patches_multiplicative_levels(alfi_level* L, int64_t* nwave) {
 int alfi_patches_factor(alfi_level* L) {
   alfi_ctx* ctx = L->ctx;
   if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_factor before alfi_patches_set");
-  int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_FACTOR);
+  ProfScope prof(ctx, ALFI_EV_PATCH_FACTOR);
   ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->status, 0, sizeof(int), ctx->stream));
   if (!L->cond && L->inv_shrunk) {                 // first dense factorisation of this patch set
     ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -570,7 +570,7 @@ int alfi_patches_factor(alfi_level* L) {
     ALFI_CHECK(launch_patch_invert(L));
   }
   ALFI_CHECK(build_patch_il(L));                  // small-patch levels: the wave-contiguous copy the apply streams
-  alfi_prof_end(ctx, t);
+  prof.close();
   int st = 0;
   ALFI_HIP_CHECK(ctx, hipMemcpyAsync(&st, L->status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));

@@ -325,7 +325,7 @@ int alfi_saddle_factor_velocity(alfi_saddle* S, const double* node_coords, int d
     dev_free(dy);
     dev_free(dr);
   }
-  if (rc == 0 && !(worst <= coarse_probe_fail()))
+  if (rc == 0 && !(worst <= alfi_env_coarse_check_fail()))
     rc = alfi_set_error(ctx, ALFI_E_SINGULAR, "direct velocity factorisation fails the residual probe: || A x - e || = %.3e", worst);
   if (rc != 0) {
     mf_free(S->vmf);

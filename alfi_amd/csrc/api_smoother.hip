@@ -38,52 +38,49 @@ static int smooth_fgmres_fused(alfi_level* L, int k, const double* db, double* d
   HsLayout hl(K);
   double *V = L->V, *Z = L->Z, *w = L->w, *hs = L->hs;
   double* hdots = hs + hl.hd;
-  int t;
   if (nonzero_guess) {
     ALFI_CHECK(alfi_residual(L, db, dx, w));
   } else {
     ALFI_HIP_CHECK(ctx, hipMemsetAsync(dx, 0, sizeof(double) * n, ctx->stream));
-    t = alfi_prof_begin(ctx, ALFI_EV_BLAS1);
+    ProfScope prof(ctx, ALFI_EV_BLAS1);
     ALFI_CHECK(launch_copy(ctx, w, db, n));
-    alfi_prof_end(ctx, t);
   }
-  t = alfi_prof_begin(ctx, ALFI_EV_BLAS1);
-  ALFI_CHECK(launch_norm_partials(ctx, w, n));
-  alfi_prof_end(ctx, t);
+  {
+    ProfScope prof(ctx, ALFI_EV_BLAS1);
+    ALFI_CHECK(launch_norm_partials(ctx, w, n));
+  }
   const int G = red_blocks_for(n);
   const double* normpart = ctx->red_partial;
   for (int j = 0; j < k; ++j) {
     double* zj = Z + (int64_t)j * ldv;
     ALFI_CHECK(launch_patch_apply_range(L, 0, L->npatch, w));                                   // stage <- patch solves of w
-    t = alfi_prof_begin(ctx, ALFI_EV_PATCH_SCATTER);
-    ALFI_CHECK(launch_patch_sum_scale(L, w, zj, V + (int64_t)j * ldv, normpart, G, hdots, hs, j, K));   // z_j, v_j, H column j-1
-    alfi_prof_end(ctx, t);
+    {
+      ProfScope prof(ctx, ALFI_EV_PATCH_SCATTER);
+      ALFI_CHECK(launch_patch_sum_scale(L, w, zj, V + (int64_t)j * ldv, normpart, G, hdots, hs, j, K));   // z_j, v_j, H column j-1
+    }
     int nb = 0;
     if (!flat_spmv) {
-      t = alfi_prof_begin(ctx, ALFI_EV_MATMULT);
+      ProfScope prof(ctx, ALFI_EV_MATMULT);
       ALFI_CHECK(launch_bsr_spmv_dot(ctx, L->A_own, zj, w, V, ldv, j + 1, ctx->red_partial, &nb));  // w = A z_j, V^T w partials
-      alfi_prof_end(ctx, t);
     } else {
       // long or very uneven block rows (the 3-D operators): the nnz-balanced product, then the dots as their own pass; up to
       // 256 partials per vector the projection kernel sums them itself, beyond a one-block reduction does
-      t = alfi_prof_begin(ctx, ALFI_EV_MATMULT);
-      ALFI_CHECK(launch_bsr_spmv(ctx, L->A_own, zj, w, nullptr, 1.0, 0));
-      alfi_prof_end(ctx, t);
-      t = alfi_prof_begin(ctx, ALFI_EV_BLAS1);
       const bool in_consumer = G <= 256;
+      {
+        ProfScope prof(ctx, ALFI_EV_MATMULT);
+        ALFI_CHECK(launch_bsr_spmv(ctx, L->A_own, zj, w, nullptr, 1.0, 0));
+      }
+      ProfScope prof(ctx, ALFI_EV_BLAS1);   // to the end of the branch
       ALFI_CHECK(launch_multi_dot(ctx, V, ldv, j + 1, w, in_consumer ? nullptr : hdots, n));
-      alfi_prof_end(ctx, t);
       nb = in_consumer ? G : 0;
     }
-    t = alfi_prof_begin(ctx, ALFI_EV_BLAS1);
+    ProfScope prof(ctx, ALFI_EV_BLAS1);   // to the end of the loop body
     ALFI_CHECK(launch_multi_axpy_norm(ctx, V, ldv, j + 1, hdots, w, n, ctx->red_partial2, nb));     // h, w -= V h, |w|^2 partials
-    alfi_prof_end(ctx, t);
     normpart = ctx->red_partial2;
   }
-  t = alfi_prof_begin(ctx, ALFI_EV_BLAS1);
+  ProfScope prof(ctx, ALFI_EV_BLAS1);   // to the end of the function
   ALFI_CHECK(launch_fgmres_finish_fused(ctx, normpart, G, hdots, hs, k, K));                       // H column k-1, y
   ALFI_CHECK(launch_update_solution(ctx, dx, Z, ldv, k, hs + hl.y, n));
-  alfi_prof_end(ctx, t);
   return 0;
 }
 
@@ -122,15 +119,13 @@ int alfi_smooth_fgmres(alfi_level* L, int k, const double* db, double* dx, int n
   // partitioned level: dots / norms are reduced into the caller's buffer and all-reduced there
   double* hdots = par ? ctx->dred : hs + hl.hd;
   double* nrm2 = par ? ctx->dred + RED_MAXV : nullptr;
-  int t;
   // r0 = b - A x (MatMult), beta = |r0|, v0 = r0 / beta
   if (nonzero_guess) {
     ALFI_CHECK(alfi_residual(L, db, dx, w));
   } else {
     ALFI_HIP_CHECK(ctx, hipMemsetAsync(dx, 0, sizeof(double) * L->n, ctx->stream));
-    t = alfi_prof_begin(ctx, ALFI_EV_BLAS1);
+    ProfScope prof(ctx, ALFI_EV_BLAS1);
     ALFI_CHECK(launch_copy(ctx, w, db, n));
-    alfi_prof_end(ctx, t);
   }
   // reductions: red_blocks_for(n) partials per vector.  Up to 256 of them (levels of <= 1 M dofs, where a smoother
   // iteration is a chain of launches of a few microseconds each) the kernel that needs a reduced value sums the partials
@@ -139,49 +134,51 @@ int alfi_smooth_fgmres(alfi_level* L, int k, const double* db, double* dx, int n
   // (G = n / 4096 partials per vector; a limit of 512 would include config 3's finest level, 319 partials: measured 18.31
   // against 18.13 ms per cycle, the re-summation in every consumer block costs more than the launch)
   const bool fused = !par && G <= 256 && k + 1 <= 16;
-  t = alfi_prof_begin(ctx, ALFI_EV_BLAS1);
-  ALFI_CHECK(launch_norm_partials(ctx, w, n));
-  if (par) ALFI_CHECK(launch_reduce_partials(ctx, ctx->red_partial, G, 1, nrm2));
-  alfi_prof_end(ctx, t);
+  {
+    ProfScope prof(ctx, ALFI_EV_BLAS1);
+    ALFI_CHECK(launch_norm_partials(ctx, w, n));
+    if (par) ALFI_CHECK(launch_reduce_partials(ctx, ctx->red_partial, G, 1, nrm2));
+  }
   if (par) ALFI_CHECK(comm_allreduce(L, RED_MAXV, 1));
-  t = alfi_prof_begin(ctx, ALFI_EV_BLAS1);
-  ALFI_CHECK(launch_norm_init_finish(ctx, par ? nrm2 : ctx->red_partial, par ? 1 : G, hs, K));
-  ALFI_CHECK(launch_scale_by_inv(ctx, V, w, hs + hl.beta, n));
-  alfi_prof_end(ctx, t);
+  {
+    ProfScope prof(ctx, ALFI_EV_BLAS1);
+    ALFI_CHECK(launch_norm_init_finish(ctx, par ? nrm2 : ctx->red_partial, par ? 1 : G, hs, K));
+    ALFI_CHECK(launch_scale_by_inv(ctx, V, w, hs + hl.beta, n));
+  }
   for (int j = 0; j < k; ++j) {
     bool zghosts = false;
     ALFI_CHECK(level_patch_apply(L, V + (int64_t)j * ldv, Z + (int64_t)j * ldv, &zghosts));   // z_j = M^-1 v_j
     ALFI_CHECK(level_spmv(L, Z + (int64_t)j * ldv, w, nullptr, 0, zghosts));                 // w = A z_j
-    t = alfi_prof_begin(ctx, ALFI_EV_BLAS1);
-    // h = V^T w (classical GS); fused: the partials stay in red_partial and the projection kernel sums them
-    ALFI_CHECK(launch_multi_dot(ctx, V, ldv, j + 1, w, fused ? nullptr : hdots, n));
     // partitioned: |w|^2 rides along in the same all-reduce; |w - V h|^2 = |w|^2 - |h|^2 then needs no second one
     const bool pyth = par && !ctx->exact_norm;
     const double* ww = pyth ? hdots + (j + 1) : nullptr;
-    if (pyth) {
-      ALFI_CHECK(launch_norm_partials(ctx, w, n));
-      ALFI_CHECK(launch_reduce_partials(ctx, ctx->red_partial, G, 1, hdots + (j + 1)));
+    {
+      ProfScope prof(ctx, ALFI_EV_BLAS1);
+      // h = V^T w (classical GS); fused: the partials stay in red_partial and the projection kernel sums them
+      ALFI_CHECK(launch_multi_dot(ctx, V, ldv, j + 1, w, fused ? nullptr : hdots, n));
+      if (pyth) {
+        ALFI_CHECK(launch_norm_partials(ctx, w, n));
+        ALFI_CHECK(launch_reduce_partials(ctx, ctx->red_partial, G, 1, hdots + (j + 1)));
+      }
     }
-    alfi_prof_end(ctx, t);
     if (par) ALFI_CHECK(comm_allreduce(L, 0, pyth ? j + 2 : j + 1));
-    t = alfi_prof_begin(ctx, ALFI_EV_BLAS1);
-    // w -= V h, |w|^2 partials (into the second partial buffer: the dot partials are still being read)
-    ALFI_CHECK(launch_multi_axpy_norm(ctx, V, ldv, j + 1, hdots, w, n, ctx->red_partial2, fused ? G : 0));
-    if (par && !pyth) ALFI_CHECK(launch_reduce_partials(ctx, ctx->red_partial2, G, 1, nrm2));
-    alfi_prof_end(ctx, t);
+    {
+      ProfScope prof(ctx, ALFI_EV_BLAS1);
+      // w -= V h, |w|^2 partials (into the second partial buffer: the dot partials are still being read)
+      ALFI_CHECK(launch_multi_axpy_norm(ctx, V, ldv, j + 1, hdots, w, n, ctx->red_partial2, fused ? G : 0));
+      if (par && !pyth) ALFI_CHECK(launch_reduce_partials(ctx, ctx->red_partial2, G, 1, nrm2));
+    }
     if (par && !pyth) ALFI_CHECK(comm_allreduce(L, RED_MAXV, 1));
-    t = alfi_prof_begin(ctx, ALFI_EV_BLAS1);
+    ProfScope prof(ctx, ALFI_EV_BLAS1);   // to the end of the loop body
     const double* part = par ? nrm2 : ctx->red_partial2;
     const int nblk = par ? 1 : G;
     if (j + 1 < k)   // Hessenberg column + v_{j+1} = w / |w| in one launch
       ALFI_CHECK(launch_hessenberg_scale(ctx, part, nblk, hdots, hs, j, K, V + (int64_t)(j + 1) * ldv, w, n, ww));
     else
       ALFI_CHECK(launch_hessenberg_update(ctx, part, nblk, hdots, hs, j, K, ww));
-    alfi_prof_end(ctx, t);
   }
-  t = alfi_prof_begin(ctx, ALFI_EV_BLAS1);
+  ProfScope prof(ctx, ALFI_EV_BLAS1);   // to the end of the function
   ALFI_CHECK(launch_fgmres_finish(ctx, hs, k, K));
   ALFI_CHECK(launch_update_solution(ctx, dx, Z, ldv, k, hs + hl.y, n));
-  alfi_prof_end(ctx, t);
   return 0;
 }

@@ -53,7 +53,7 @@ std::mutex g_api_mutex;     // ctxs of different threads may create their commun
 RcclApi* rccl() {
   std::lock_guard<std::mutex> lock(g_api_mutex);
   if (g_api.handle) return &g_api;
-  const char* names[] = {getenv("ALFI_RCCL_LIB"), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
+  const char* names[] = {alfi_env_rccl_lib(), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
   void* h = nullptr;
   for (const char* n : names) {
     if (!n || !*n) continue;
@@ -219,11 +219,7 @@ int alfi_ctx_comm_init(alfi_ctx* ctx, const void* id, int rank, int nranks) {
     native_destroy(ctx);
     return alfi_set_error(ctx, ALFI_E_HIP, "communicator resources: %s", hipGetErrorString(e));
   }
-  // |w - V h| of the partitioned FGMRES by its own all-reduce, as PETSc's VecNorm (the default).  ALFI_DIST_EXACT_NORM=0: from
-  // |w|^2 - |h|^2 with the dots' all-reduce (one reduction fewer per iteration; absolute error eps |w|^2, so a new direction
-  // that is small against w is mis-normalised -- measurements only)
-  const char* en = getenv("ALFI_DIST_EXACT_NORM");
-  ctx->exact_norm = !(en && atoi(en) == 0);
+  ctx->exact_norm = alfi_env_dist_exact_norm();
   return 0;
 }
 

@@ -8,6 +8,7 @@
 #include <thread>
 #include <vector>
 #include "alfi_hip.h"
+#include "env.h"   // every environment switch of the library
 
 // Every host <-> device copy the library makes is counted (alfi_transfer_stats): that a Newton step moves nothing but scalars
 // across PCIe is tested (tests/test_gpu_newton_state.py), not asserted.  Process-wide counters.
@@ -104,12 +105,6 @@ constexpr int RED_MAXV = 32;      // max simultaneous dot products
 
 int alfi_set_error(alfi_ctx* ctx, int code, const char* fmt, ...);
 
-// ALFI_TEST_LARGE_PATHS=1 -- a TEST HOOK, not a tuning switch: the size thresholds that select the kernels of the large levels
-// (nnz-balanced SpMV with the fix-up launch and the de-duplicated x gathers instead of whole-row chunks, the general smoother
-// chain instead of the fused iteration of small levels) are lowered to zero, so that the small hierarchies of the test suite
-// run the code the 10 M-dof levels run.  Read once per process.
-bool alfi_test_large_paths();
-
 #define ALFI_HIP_CHECK(ctx, call)                                                                      \
   do {                                                                                                 \
     hipError_t e_ = (call);                                                                            \
@@ -124,9 +119,22 @@ bool alfi_test_large_paths();
     if (rc_ != 0) return rc_; \
   } while (0)
 
-// RAII-less profiling scope: begin/end record events on the ctx stream when profiling is on.
-int alfi_prof_begin(alfi_ctx* ctx, int kind);
-int alfi_prof_end(alfi_ctx* ctx, int token);
+// Profiling scope: when profiling is on, the constructor records the start event of a (kind, ctx->cur_tag) pair on the ctx
+// stream, and close() -- or leaving the block, which an error return does too -- records its stop event.  A scope ends where
+// the timed launches end (an explicit block or close()), so that exchanges and other scopes stay outside; one that runs to the
+// end of its function, loop body or branch says so where it is declared: what is appended there is timed with it.  api_ctx.hip
+class ProfScope {
+ public:
+  ProfScope(alfi_ctx* ctx, int kind);
+  ~ProfScope() { close(); }
+  ProfScope(const ProfScope&) = delete;
+  ProfScope& operator=(const ProfScope&) = delete;
+  void close();
+
+ private:
+  alfi_ctx* ctx_;
+  int token_ = -1;   // index of the event pair, -1: nothing (left) to record
+};
 
 constexpr int BURMAN_MAXQ = 32;        // points of a facet rule the Burman kernels take (3-D P3: 25 for the nonlinear rule)
 constexpr int BURMAN_MAXN = 20;        // nodes per cell the Burman kernels take ([P3]^3)

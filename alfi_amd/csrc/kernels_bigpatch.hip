@@ -1560,9 +1560,7 @@ static int big_factor_core(alfi_ctx* ctx, const BigSource& src, int64_t npatch, 
                            const int64_t* d_patch_ptr, const int64_t* d_inv_ptr, double* inv, int* status,
                            double* dense_out = nullptr) {
   if (npatch == 0) return 0;
-  const int64_t budget = (int64_t)6 << 30;          // bytes of scratch (matrices + panels) per batch
-  const char* env = getenv("ALFI_BIG_SCRATCH_MB");
-  const int64_t limit = env ? (int64_t)atoll(env) << 20 : budget;
+  const int64_t limit = alfi_env_big_scratch_bytes();   // scratch (matrices + panels) per batch
   constexpr bool polish = true;   // one Newton-Schulz step after the blocked elimination (explicit pivot-block inverses lose
                                   // cond * eps: 2e-5 against LAPACK without it, 1e-8 with)
   const int64_t nscr = polish ? 3 : 1;            // X | a second copy of A_p | I - A X

@@ -357,8 +357,7 @@ static int cond_repair(alfi_level* L, double tol, int nflag, double worst) {
   if (rc != 0) return rc;
   L->chk_repaired = nflag - nflag2;
   L->chk_worst_after = worst2;
-  static const double fail = getenv("ALFI_PATCH_CHECK_FAIL") ? atof(getenv("ALFI_PATCH_CHECK_FAIL")) : 1e3 * tol;
-  if (nflag2 > 0 && !(worst2 <= fail))
+  if (nflag2 > 0 && !(worst2 <= alfi_env_patch_check_fail()))
     return alfi_set_error(ctx, ALFI_E_SINGULAR, "%d condensed patch factors still fail the residual probe after pivoted "
                           "re-inversion of their Schur complements (worst %.3e); use dense inverses "
                           "(alfi_patches_set_groups(NULL)) for this operator", nflag2, worst2);
@@ -369,8 +368,8 @@ static int cond_repair(alfi_level* L, double tol, int nflag, double worst) {
 // patch that met one holds non-finite entries and is caught by the probe).
 int patch_verify_and_repair(alfi_level* L, int unpivoted_status) {
   alfi_ctx* ctx = L->ctx;
-  static const bool enabled = !(getenv("ALFI_PATCH_CHECK") && atoi(getenv("ALFI_PATCH_CHECK")) == 0);
-  static const double tol = getenv("ALFI_PATCH_CHECK_TOL") ? atof(getenv("ALFI_PATCH_CHECK_TOL")) : 1e-6;
+  const bool enabled = alfi_env_patch_check();
+  const double tol = alfi_env_patch_check_tol();
   L->chk_worst = -1.0;
   L->chk_flagged = L->chk_repaired = 0;
   if (!enabled || L->npatch == 0) {
@@ -450,8 +449,7 @@ int patch_verify_and_repair(alfi_level* L, int unpivoted_status) {
   // meshes, more on finer levels at Re 10 000).  LAPACK -- the reference's patch solver -- would hand back the same
   // inverse without complaint, so this is reported (alfi_patches_check: worst residual afterwards, flagged != repaired), not
   // an error; only a residual beyond ALFI_PATCH_CHECK_FAIL (default 1000 x the tolerance) or a non-finite one fails the setup.
-  static const double fail = getenv("ALFI_PATCH_CHECK_FAIL") ? atof(getenv("ALFI_PATCH_CHECK_FAIL")) : 1e3 * tol;
-  if (nflag2 > 0 && !(worst2 <= fail))
+  if (nflag2 > 0 && !(worst2 <= alfi_env_patch_check_fail()))
     return alfi_set_error(ctx, ALFI_E_SINGULAR, "%d patch inverses still fail the residual probe after pivoted re-inversion "
                           "(worst %.3e): the patch operators are singular to working precision", nflag2, worst2);
   return 0;

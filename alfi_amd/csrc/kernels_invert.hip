@@ -367,11 +367,10 @@ extern "C" int64_t alfi_debug_invert_phases(int64_t* out) {     // out: 4096 x 8
 // returns 1 if the sizes are handled here, 0 if the caller should use the register kernel
 int launch_patch_invert_mfma(alfi_ctx* ctx, int64_t npatch, int max_np, const int64_t* patch_ptr, const int64_t* inv_ptr,
                              double* inv, int* status, int* handled) {
-  static const bool allow = !(getenv("ALFI_INVERT_MFMA") && atoi(getenv("ALFI_INVERT_MFMA")) == 0);
   *handled = 0;
   // up to 112 dofs the rank-1 register kernel (7 x 7 tiles, two workgroups per CU) is the faster one -- measured at
   // [P1+FB]^3's 111 dofs: 5.5 against 9.8 ms for 35 937 patches; ALFI_INVERT_MFMA=2 sends those sizes here too (tests)
-  static const bool all_sizes = getenv("ALFI_INVERT_MFMA") && atoi(getenv("ALFI_INVERT_MFMA")) == 2;
+  const bool allow = alfi_env_invert_mfma() != 0, all_sizes = alfi_env_invert_mfma() == 2;
   if (!allow || max_np <= 32 || max_np > 160 || (max_np <= 112 && !all_sizes)) return 0;
 #ifdef ALFI_INVERT_TIMING
   if (!g_invert_phases) {

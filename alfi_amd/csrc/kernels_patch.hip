@@ -1015,10 +1015,9 @@ int launch_patch_mult_persistent(alfi_level* L, const double* x, double* y) {
 int launch_patch_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double* x) {
   alfi_ctx* ctx = L->ctx;
   if (p1 <= p0) return 0;
-  int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_APPLY);
+  ProfScope prof(ctx, ALFI_EV_PATCH_APPLY);     // to the end of the function
   if (L->cond) {                                // condensed factors (kernels_bigpatch.hip)
     ALFI_CHECK(launch_cond_apply_range(L, p0, p1, x));
-    alfi_prof_end(ctx, t);
     return 0;
   }
   // levels with FEW star patches of 3-D size (the lower levels of a hierarchy: 125 and 729 patches under config 3's 35 937)
@@ -1030,7 +1029,6 @@ int launch_patch_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double
   const int64_t few = alfi_test_large_paths() ? 0 : 1000, fewer = alfi_test_large_paths() ? 0 : 256;
   if (L->max_np > SMALL_PATCH_MAX || (L->max_np > 64 && L->npatch <= fewer)) {     // kernels_bigpatch.hip
     ALFI_CHECK(launch_big_apply_range(L, p0, p1, x));
-    alfi_prof_end(ctx, t);
     return 0;
   }
   const int64_t cnt = p1 - p0;
@@ -1063,7 +1061,6 @@ int launch_patch_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double
                          L->patch_dofs, L->inv_ptr, L->stage_ptr, L->inv, x, L->stage);
   }
   ALFI_HIP_CHECK(ctx, hipGetLastError());
-  alfi_prof_end(ctx, t);
   return 0;
 }
 
@@ -1071,12 +1068,11 @@ int launch_patch_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double
 int launch_patch_sum_range(alfi_level* L, int64_t i0, int64_t i1, const double* x, double* y) {
   alfi_ctx* ctx = L->ctx;
   if (i1 <= i0) return 0;
-  int t = alfi_prof_begin(ctx, ALFI_EV_PATCH_SCATTER);
+  ProfScope prof(ctx, ALFI_EV_PATCH_SCATTER);   // to the end of the function
   dim3 grid((unsigned)((i1 - i0 + 255) / 256)), block(256);
   hipLaunchKernelGGL(patch_sum_kernel, grid, block, 0, ctx->stream, i0, i1, L->dof_ptr, L->dof_pos, L->stage, L->bc_mask,
                      x, y, L->pou ? 1 : 0);
   ALFI_HIP_CHECK(ctx, hipGetLastError());
-  alfi_prof_end(ctx, t);
   return 0;
 }
 

@@ -28,6 +28,7 @@ import ctypes
 
 import numpy as np
 
+from . import env
 from .problem import BSR
 
 COMM_ALLREDUCE, COMM_HALO_FWD, COMM_HALO_REV, COMM_HALO_FWD_BEGIN, COMM_HALO_FWD_END = 0, 1, 2, 3, 4
@@ -785,7 +786,6 @@ class DistMultigrid(object):
         calls back into this module, which exchanges through torch.distributed (the test transport: gloo, ranks sharing
         a GPU).  ALFI_DIST_TRANSPORT overrides.  on_stage(name): called at "partition", "localize", "comm_init",
         "upload_factor" (bench.py's per-rank stage markers); ``setup_s`` holds the seconds each took."""
-        import os
         import time
         import torch
         from . import hip
@@ -797,13 +797,12 @@ class DistMultigrid(object):
         if solo is not None:
             transport = "callback"
         if transport is None:
-            transport = os.environ.get("ALFI_DIST_TRANSPORT") or ("rccl" if self.comm.backend == "nccl" else "callback")
+            transport = env.dist_transport() or ("rccl" if self.comm.backend == "nccl" else "callback")
         if transport not in ("rccl", "callback"):
             raise ValueError("transport must be 'rccl' or 'callback'")
         self.transport = transport
         if overlap is None:
-            import os
-            overlap = os.environ.get("ALFI_DIST_OVERLAP", "1") != "0"
+            overlap = env.dist_overlap()
         self.overlap = overlap
         self._in_cycle = False
         self._red_views = {}
@@ -811,10 +810,8 @@ class DistMultigrid(object):
         # without it, the rule above from the halo sizes of the partition (use_overlap_rule=False: never)
         use_rule = False
         if overlap_min_dofs is None:
-            import os
-            if "ALFI_DIST_OVERLAP_MIN_DOFS" in os.environ:
-                overlap_min_dofs = int(os.environ["ALFI_DIST_OVERLAP_MIN_DOFS"])
-            else:
+            overlap_min_dofs = env.dist_overlap_min_dofs()
+            if overlap_min_dofs is None:
                 overlap_min_dofs = 1 << 62
                 use_rule = overlap and use_overlap_rule
         if device is None:

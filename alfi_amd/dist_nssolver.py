@@ -5,12 +5,11 @@ GPU): ``DistNavierStokesSolver`` puts ``HipNavierStokesSolver`` on ``DistMultigr
 A module of its own because it needs the single-GPU solver, the library wrappers and torch, which the partitioning of
 alfi_amd.dist alone does not; ``alfi_amd.dist.DistNavierStokesSolver`` / ``alfi_amd.dist.StateExchange`` import it on first
 use."""
-import os
 
 import numpy as np
 import torch
 
-from . import _hostlib, hip
+from . import _hostlib, env, hip
 from .dist import DistMultigrid, DistSaddle, FacetPart, HaloBuffers, assembly_cells, local_host_operator, localize_pressure
 from .lazy import LazyOperator, _row_map, _take_rows
 from .nssolver import HipNavierStokesSolver
@@ -124,7 +123,7 @@ class DistNavierStokesSolver(HipNavierStokesSolver):
         # rank-local generation: every rank assembles the operator / transfer rows of its partition only (config 4 on 8
         # ranks: 4.5 GB of host memory per rank instead of 25).  The HOST refresh of SUPG terms works on global values: with
         # SUPG the generation is rank-local only while the operators are refreshed on the device (the default).
-        return (not self.supg or self.device_assembly) and os.environ.get("ALFI_DIST_GLOBAL_GENERATION") != "1"
+        return (not self.supg or self.device_assembly) and not env.dist_global_generation()
 
     def _create_device(self, restriction):
         self.dmg = DistMultigrid(self.levels, self.transfers, self.params["fieldsplit_0"]["mg_levels"]["ksp_max_it"],

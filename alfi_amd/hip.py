@@ -6,7 +6,7 @@ Errors from the library become ``RuntimeError`` (the reference's plug-ins raise 
 import ctypes
 import numpy as np
 
-from . import _lib
+from . import _lib, env
 from ._lib import BsrHost, CsrHost, vp
 
 
@@ -535,13 +535,14 @@ class Level(object):
 
     def coarse_factor_auto(self, node_coords=None, mode=None, geometric=False):
         """The coarse factorisation the front ends use: ``mode`` "dense", "sparse" or "auto" (sparse from
-        ``coarse_sparse_min()`` dofs on).  The choice is remembered, so a later call without arguments (new operator values,
+        ``env.coarse_sparse_min()`` dofs on: dense inverse 8 n^2 bytes and one n x n GEMV per cycle, sparse O(n^{4/3}) bytes
+        and ~6 launches per tree height).  The choice is remembered, so a later call without arguments (new operator values,
         every Newton step) repeats it.  The sparse path bisects by graph level sets; ``geometric``: by ``node_coords`` instead
         (measured on ldc3d coarse grids: level sets give 13-15 % less fill, hence the default)."""
         if mode is not None or node_coords is not None or not hasattr(self, "_coarse_choice"):
             self._coarse_choice = (mode or "auto", node_coords if geometric else None)
         mode, node_coords = self._coarse_choice
-        if mode == "sparse" or (mode == "auto" and self.n >= coarse_sparse_min()):
+        if mode == "sparse" or (mode == "auto" and self.n >= env.coarse_sparse_min()):
             rc = self.coarse_factor_sparse(node_coords)
         else:
             rc = self.coarse_factor()
@@ -637,15 +638,7 @@ def coarse_inverse(A_bsr):
 def condense_patches(L):
     """Whether the level's patch factors are stored condensed: the generator supplied group labels (macro-star patches of
     the Scott-Vogelius hierarchy, sv.macro_cell_groups) and ALFI_CONDENSE is not 0."""
-    import os
-    return getattr(L, "patch_groups", None) is not None and os.environ.get("ALFI_CONDENSE", "1") != "0"
-
-
-def coarse_sparse_min():
-    """Coarse grids from this many dofs on get the sparse factorisation by default (dense inverse: 8 n^2 bytes and one n x n
-    GEMV per cycle; sparse: O(n^{4/3}) bytes and ~6 launches per tree height)."""
-    import os
-    return int(os.environ.get("ALFI_COARSE_SPARSE_MIN", 8192))
+    return getattr(L, "patch_groups", None) is not None and env.condense()
 
 
 class Multigrid(object):

@@ -18,13 +18,12 @@ with the library's multifrontal factors of the finest operator: the ideal augmen
 The generator plays Firedrake's role (assembly, setup time); the arithmetic of the solves is libalfi_hip.so's.
 """
 import contextlib
-import os
 import time
 import warnings
 
 import numpy as np
 
-from . import _hostlib, hip
+from . import _hostlib, env, hip
 from .problem import BSR, build_hierarchy, build_pressure_coupling
 from .solver import HipMG, mg_levels_solver, fieldsplit_0_mg, fieldsplit_0_lu, outer_solver
 
@@ -85,7 +84,7 @@ class HipNavierStokesSolver(object):
         self.direct_max_bytes = int(direct_max_bytes)
         self.problem, self.gamma, self.verbose = problem, float(gamma), verbose
         if device_assembly is None:
-            device_assembly = os.environ.get("ALFI_DEVICE_ASSEMBLY", "1") != "0"
+            device_assembly = env.device_assembly()
         self.device_assembly = bool(device_assembly)
         self.timings = {"assemble_s": 0.0, "factor_s": 0.0, "residual_s": 0.0, "solve_s": 0.0, "newton_steps": 0}
         self._ctx_arg = ctx

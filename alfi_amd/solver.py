@@ -16,7 +16,7 @@ import importlib
 
 import numpy as np
 
-from . import hip
+from . import env, hip
 from .relaxation import Options, PlexLike, patch_points_to_dofs
 
 SUPPORTED_PATCH_KEYS = {
@@ -245,9 +245,8 @@ class HipPatchPC(object):
         # solver.py:655-659): store the factors condensed -- interiors of the macro cells + skeleton -- unless the sweep is
         # multiplicative (that kernel multiplies with dense inverses)
         self.condensed = False
-        import os
         if (ctype == "python" and getattr(L.V.mesh, "macro_mesh", None) is not None and not self.multiplicative
-                and os.environ.get("ALFI_CONDENSE", "1") != "0" and type(ctor).__name__ == "MacroStar"
+                and env.condense() and type(ctor).__name__ == "MacroStar"
                 and ctype == "python" and not getattr(L, "facet_coupling", False)):
             # (not on facet-coupled levels: the Burman term couples the interiors of neighbouring macro cells)
             from .sv import macro_cell_groups

@@ -11,12 +11,11 @@ Everything here is host-side input generation (the role Firedrake plays for the 
 transfers and cycles is the same libalfi_hip.so entry points as for the PkP0 discretisation.  Implemented for k = 2 and,
 in 3-D, k = 3 (the inf-sup stable pair of config 5: macro stars of up to ~1600 dofs, macro-cell transfer blocks of 390).
 """
-import os
 
 import numpy as np
 import scipy.sparse as sp
 
-from . import _hostlib
+from . import _hostlib, env
 from .elements import NodalElement
 from .fespace import VectorFunctionSpace
 from .mesh import bary_refine, mesh_hierarchy
@@ -371,7 +370,7 @@ def build_sv_hierarchy(problem, nref, k, Re, gamma=1e4, advect=True, patches=Tru
         L.nu, L.gamma = nu, gamma
         if patches and l > 0:
             # (ALFI_MACROSTAR_LITERAL=1: the constructor's own point-by-point walk instead of the incidence products)
-            literal = os.environ.get("ALFI_MACROSTAR_LITERAL") == "1"
+            literal = env.macrostar_literal()
             L.patch_ptr, L.patch_dofs, L.patch_seeds = (macro_star_patches if literal else macro_star_patches_fast)(V)
             # the factors of these patches can be stored condensed: interiors of the macro cells + skeleton
             if not facet_coupling:
