@@ -64,6 +64,16 @@ int alfi_vec_gather(alfi_ctx* ctx, double* dst, const double* src, const int32_t
   return nidx == 0 ? 0 : launch_halo_pack(ctx, dst, src, d_idx, nidx, bs);
 }
 
+// dst[i*bs + c] = sum over k in [rowptr[i], rowptr[i+1]) of weights[k] * src[colidx[k]*bs + c]: a level's state on a non-nested
+// hierarchy, where a node of the level is a point evaluation of the finest field (bs 1, 2 or 3: the velocity blocks)
+int alfi_vec_gather_csr(alfi_ctx* ctx, double* dst, const double* src, const int32_t* d_rowptr, const int32_t* d_colidx,
+                        const double* d_weights, int64_t nrows, int bs) {
+  if (nrows < 0 || bs < 1 || bs > 3 || (nrows > 0 && (!dst || !src || !d_rowptr || !d_colidx || !d_weights)))
+    return alfi_set_error(ctx, ALFI_E_ARG, "bad weighted gather arguments");
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return nrows == 0 ? 0 : launch_gather_csr(ctx, dst, src, d_rowptr, d_colidx, d_weights, nrows, bs);
+}
+
 // dv[Dirichlet dofs of the level] = 0 (bc.zero(F), alfi/solver.py:282-286)
 int alfi_level_zero_bc(alfi_level* L, double* dv) {
   alfi_ctx* ctx = L->ctx;

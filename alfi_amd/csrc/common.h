@@ -659,6 +659,8 @@ int launch_csr_spmv(alfi_ctx* ctx, const DevCSR& A, const double* x, double* y, 
 int launch_scale_rows(alfi_ctx* ctx, double* y, const double* x, const double* d, double a, int64_t n);  // y = a d x
 int launch_remove_mean(alfi_ctx* ctx, double* x, int64_t n);
 int launch_inject_csr(alfi_ctx* ctx, const struct DevCSR& J, int bs, const double* xf, double* xc);
+int launch_gather_csr(alfi_ctx* ctx, double* dst, const double* src, const int32_t* rowptr, const int32_t* colidx,
+                      const double* w, int64_t nrows, int bs);   // bs 1, 2 or 3
 int launch_sum_to(alfi_ctx* ctx, const double* x, int64_t n, double* out);             // *out = sum(x), fixed order
 int launch_sub_scaled(alfi_ctx* ctx, double* x, int64_t n, const double* s, double f); // x -= f * *s
 int launch_add(alfi_ctx* ctx, double* y, const double* a, const double* b, int64_t n); // y = a + b

@@ -1554,6 +1554,38 @@ struct BigSource {
   }
 };
 
+// The offsets of a batch's matrices and panels in the scratch arena, made on the device from the patch sizes it already holds:
+// scr_ptr[i] = sum_{j<i} N_j^2, pan_ptr[i] = sum_{j<i} N_j BIG_NB (N_j = the size of patch p0 + j rounded up to BIG_NB) -- what
+// the host's batch loop computes.  One wave, an inclusive shuffle scan per 64 patches and a carry.  (Uploading the two tables
+// cost 16 bytes per patch and refactorisation: the only traffic of a Newton step that grew with the level.)
+__global__ __launch_bounds__(64) void big_offsets_kernel(int64_t p0, int64_t nb, const int64_t* __restrict__ patch_ptr,
+                                                         int64_t* __restrict__ scr_ptr, int64_t* __restrict__ pan_ptr) {
+  const int lane = threadIdx.x;
+  int64_t carry = 0, carry_n = 0;                      // sums of N_j^2 and of N_j over the patches before this chunk
+  for (int64_t base = 0; base < nb; base += 64) {
+    const int64_t i = base + lane;
+    int64_t N = 0;
+    if (i < nb) {
+      const int64_t n = patch_ptr[p0 + i + 1] - patch_ptr[p0 + i];
+      N = (n + BIG_NB - 1) / BIG_NB * BIG_NB;
+    }
+    int64_t sq = N * N, ln = N;                        // inclusive scans over the wave
+    for (int d = 1; d < 64; d <<= 1) {
+      const int64_t a = __shfl_up(sq, d, 64), b = __shfl_up(ln, d, 64);
+      if (lane >= d) {
+        sq += a;
+        ln += b;
+      }
+    }
+    if (i < nb) {
+      scr_ptr[i] = carry + sq - N * N;
+      pan_ptr[i] = (carry_n + ln - N) * BIG_NB;
+    }
+    carry += __shfl(sq, 63, 64);
+    carry_n += __shfl(ln, 63, 64);
+  }
+}
+
 // fill + blocked inversion of npatch matrices, in batches bounded by the scratch budget
 // dense_out != nullptr (one matrix): the inverse is delivered row-major n x n there instead of the row-piece layout
 static int big_factor_core(alfi_ctx* ctx, const BigSource& src, int64_t npatch, const int64_t* h_patch_ptr,
@@ -1568,7 +1600,6 @@ static int big_factor_core(alfi_ctx* ctx, const BigSource& src, int64_t npatch, 
   struct Batch {
     int64_t p0, p1, sdoubles, pdoubles;
     int Nmax;
-    std::vector<int64_t> scr_ptr, pan_ptr;
   };
   std::vector<Batch> batches;
   int64_t smax = 0, pmax = 0, nbmax = 0;
@@ -1583,8 +1614,6 @@ static int big_factor_core(alfi_ctx* ctx, const BigSource& src, int64_t npatch, 
       const int N = (n + BIG_NB - 1) / BIG_NB * BIG_NB;
       const int64_t need = ((int64_t)nscr * N * N + 2 * (int64_t)N * BIG_NB) * 8;
       if (p1 > p0 && (nscr * B.sdoubles + 2 * B.pdoubles) * 8 + need > limit) break;
-      B.scr_ptr.push_back(B.sdoubles);
-      B.pan_ptr.push_back(B.pdoubles);
       B.sdoubles += (int64_t)N * N;
       B.pdoubles += (int64_t)N * BIG_NB;
       if (N > B.Nmax) B.Nmax = N;
@@ -1625,10 +1654,9 @@ static int big_factor_core(alfi_ctx* ctx, const BigSource& src, int64_t npatch, 
   const dim3 block(256);
   for (const Batch& B : batches) {
     const int64_t p0 = B.p0, nb = B.p1 - B.p0;
-    // (pageable host source: the copy has left the host buffer when the call returns; the stream orders it after the
-    // previous batch's kernels)
-    e = hipMemcpyAsync(d_scr_ptr, B.scr_ptr.data(), (size_t)nb * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_pan_ptr, B.pan_ptr.data(), (size_t)nb * 8, hipMemcpyHostToDevice, ctx->stream);
+    // (the stream orders the new offsets after the previous batch's kernels)
+    hipLaunchKernelGGL(big_offsets_kernel, dim3(1), dim3(64), 0, ctx->stream, p0, nb, d_patch_ptr, d_scr_ptr, d_pan_ptr);
+    e = hipGetLastError();
     if (e != hipSuccess) break;
     src.fill(ctx, p0, nb, d_scr_ptr, scr);
     if (polish)   // the elimination overwrites its copy of A_p; the polish needs A_p again

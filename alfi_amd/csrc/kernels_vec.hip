@@ -1581,6 +1581,51 @@ int launch_inject_csr(alfi_ctx* ctx, const DevCSR& J, int bs, const double* xf, 
   return 0;
 }
 
+// weighted gather of block vectors (alfi_vec_gather_csr): dst node i = sum_k w_k src node c_k, a level's refresh state from the
+// exchanged finest velocity on a non-nested hierarchy (the injections composed down to the finest level).  One lane per
+// destination node: the row's indices and weights are read once, the BS components live in registers; FMA chain in CSR order,
+// so the result does not depend on the launch shape.  The chain of a non-empty row starts from -0.0, which adds nothing to any
+// value and keeps the sign of a zero: a one-entry row of weight 1.0 copies its source bit for bit.  An empty row gives +0.0.
+// V2 (BS == 2, src and dst 16-byte aligned): the two doubles of a node move as one 16-byte access.
+template <int BS, bool V2>
+__global__ __launch_bounds__(256) void gather_csr_kernel(int64_t nrows, const int32_t* __restrict__ rowptr,
+                                                         const int32_t* __restrict__ colidx, const double* __restrict__ w,
+                                                         const double* __restrict__ src, double* __restrict__ dst) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nrows; i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t k0 = rowptr[i], k1 = rowptr[i + 1];
+    double s[BS];
+#pragma unroll
+    for (int c = 0; c < BS; ++c) s[c] = k0 < k1 ? -0.0 : 0.0;
+    for (int32_t k = k0; k < k1; ++k) {
+      const double wk = w[k];
+      const double* x = src + (int64_t)colidx[k] * BS;
+      if (V2) {
+        const double2 x2 = *reinterpret_cast<const double2*>(x);
+        s[0] = __builtin_fma(wk, x2.x, s[0]);
+        s[BS - 1] = __builtin_fma(wk, x2.y, s[BS - 1]);
+      } else {
+#pragma unroll
+        for (int c = 0; c < BS; ++c) s[c] = __builtin_fma(wk, x[c], s[c]);
+      }
+    }
+    if (V2) {
+      *reinterpret_cast<double2*>(dst + i * BS) = make_double2(s[0], s[BS - 1]);
+    } else {
+#pragma unroll
+      for (int c = 0; c < BS; ++c) dst[i * BS + c] = s[c];
+    }
+  }
+}
+int launch_gather_csr(alfi_ctx* ctx, double* dst, const double* src, const int32_t* rowptr, const int32_t* colidx,
+                      const double* w, int64_t nrows, int bs) {
+  const bool v2 = bs == 2 && (((uintptr_t)dst | (uintptr_t)src) & 15) == 0;
+  if (bs == 1) ALFI_LAUNCH_EW((gather_csr_kernel<1, false>), nrows, nrows, rowptr, colidx, w, src, dst);
+  else if (v2) ALFI_LAUNCH_EW((gather_csr_kernel<2, true>), nrows, nrows, rowptr, colidx, w, src, dst);
+  else if (bs == 2) ALFI_LAUNCH_EW((gather_csr_kernel<2, false>), nrows, nrows, rowptr, colidx, w, src, dst);
+  else ALFI_LAUNCH_EW((gather_csr_kernel<3, false>), nrows, nrows, rowptr, colidx, w, src, dst);
+  return 0;
+}
+
 // ---- residual probe of the coarse solvers (alfi_coarse_factor / _sparse): e = a +-1 vector that is a function of the index, made
 // on the device, and || r - e ||_inf reduced there -- a refactorisation per Newton step moves 8 bytes, not two coarse vectors
 __device__ inline double probe_entry(int64_t i) {

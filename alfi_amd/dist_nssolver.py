@@ -23,11 +23,51 @@ class _StatePart(object):
         self.bs, self.send_counts, self.recv_counts = bs, send_counts, recv_counts
 
 
+def composed_injection(transfers, nlev, level, rows, n_fine=None):
+    """Rows ``rows`` of I_level . I_level+1 ... I_nlev-2 (scipy CSR, len(rows) x finest nodes): the nodal values of ``level`` as a
+    linear map of the finest field, the composition of the ``inject`` maps (alfi/solver.py:595).  I_l is ``inject_matrix`` of
+    transfers[l] -- the point evaluation of the barycentric hierarchy, sv.bary_injection -- or, where ``inject_map`` is set
+    (nested hierarchies: a coarse node IS a fine node), the 0/1 matrix of that map.  Formed from the top down through the rows
+    actually needed, C_l[rows] = I_l[rows] . C_l+1[columns of I_l[rows]]: no global product, the cost follows len(rows).  The
+    finest level gives identity rows.  Column indices sorted, duplicates summed, nothing eliminated afterwards (the sparse
+    product itself leaves out a sum that cancels to exactly 0.0).  Device-free.
+    n_fine: the finest level's node count; read off the last transfer when not given (a single level has none: give it)."""
+    import scipy.sparse as sp
+    rows = np.asarray(rows, dtype=np.int64)
+    if level == nlev - 1:
+        if n_fine is None:
+            T = transfers[nlev - 2]           # its fine space, or the block rows of its prolongation: the finest nodes
+            n_fine = T.Vf.num_nodes if hasattr(T, "Vf") else T.P.nbrows
+        return sp.csr_matrix((np.ones(rows.size), rows, np.arange(rows.size + 1)), shape=(rows.size, n_fine))
+    T = transfers[level]
+    imap = getattr(T, "inject_map", None)
+    if imap is not None:              # rows of a 0/1 matrix select rows of the next composition
+        return composed_injection(transfers, nlev, level + 1, np.asarray(imap, dtype=np.int64)[rows], n_fine)
+    I = sp.csr_matrix(T.inject_matrix)[rows]
+    cols = np.unique(I.indices)
+    C = composed_injection(transfers, nlev, level + 1, cols, n_fine)
+    I = sp.csr_matrix((I.data, np.searchsorted(cols, I.indices), I.indptr), shape=(rows.size, cols.size))
+    out = (I @ C).tocsr()
+    out.sum_duplicates()
+    out.sort_indices()
+    return out
+
+
+def _is_index_map(C):
+    """A composed injection whose rows all have one entry of weight exactly 1.0: an index gather."""
+    return C.nnz == C.shape[0] and np.array_equal(C.indptr, np.arange(C.shape[0] + 1)) and bool((C.data == 1.0).all())
+
+
 class StateExchange(object):
     """The distributed Newton state as input of the rank's operator refresh: every level's state vector (the level's local
-    nodes and the ring of nodes of the cells around them, alfi_level_set_assembly) filled ON THE DEVICE from the velocity the
-    ranks own on the finest level -- one halo exchange per refresh, then an index gather per level (on the nested hierarchies
-    a node of level l IS a node of the finest level: the composition of the ``inject`` maps, alfi/solver.py:595).
+    nodes and the ring of nodes of the cells around them, alfi_level_set_assembly; with Burman terms also the nodes of the
+    facets' off-rank cells) filled ON THE DEVICE from the velocity the ranks own on the finest level -- one halo exchange per
+    refresh, then one gather per level.  A level's state is the composition of the ``inject`` maps (alfi/solver.py:595) applied
+    to the finest velocity, ``composed_injection`` over the level's state nodes: on the nested hierarchies a node of level l IS a
+    node of the finest level and the gather is an index gather (alfi_vec_gather); on the barycentric hierarchy of the
+    Scott-Vogelius pair a node of level l is a point evaluation of the finest field, a few weights per row, and the gather is
+    the weighted one (alfi_vec_gather_csr).  Levels whose composed map is an index map -- the finest always -- take the index
+    gather on either hierarchy.
     The exchange runs through a level that exists only for its halo plan (identity operator): owned block = the rank's owned
     finest nodes in the finest level's local order, ghosts = every other finest node some level's refresh reads here; it
     therefore takes whichever transport the multigrid levels take (the library's RCCL communicator, or the callback)."""
@@ -37,15 +77,12 @@ class StateExchange(object):
         p = dmg.fine.part
         bs, rank, world = p.bs, dmg.comm.rank, dmg.comm.world
         nlev = len(levels)
-        to_fine = [None] * nlev                       # node of level l -> finest node at the same position
-        to_fine[-1] = np.arange(levels[-1].A.nbrows, dtype=np.int64)
-        for l in range(nlev - 2, -1, -1):
-            T = transfers[l]
-            if T.inject_map is None:
-                raise ValueError("non-nested hierarchy: no node-to-node inject")
-            to_fine[l] = to_fine[l + 1][np.asarray(T.inject_map, dtype=np.int64)]
-        need = [None if a is None else to_fine[dmg.lmin + i][np.asarray(a, dtype=np.int64)] for i, a in enumerate(asm_nodes)]
-        allneed = np.unique(np.concatenate([n for n in need if n is not None] + [np.zeros(0, dtype=np.int64)]))
+        n_fine = levels[-1].A.nbrows
+        # need[i]: local level i's state as rows over the finest nodes (rank-local: the rows this rank reads, nothing global)
+        need = [None if a is None else composed_injection(transfers, nlev, dmg.lmin + i, a, n_fine)
+                for i, a in enumerate(asm_nodes)]
+        allneed = np.unique(np.concatenate([C.indices for C in need if C is not None] + [np.zeros(0, dtype=np.int64)]))
+        allneed = allneed.astype(np.int64)
         ghosts = allneed[(allneed < p.lo) | (allneed >= p.hi)]               # ascending => grouped by owner
         owner = np.searchsorted(p.splits, ghosts, side="right") - 1
         recv_counts = np.bincount(owner, minlength=world).astype(np.int64)
@@ -70,21 +107,30 @@ class StateExchange(object):
         self.vec = ctx.vec(max(nb * bs, 1))
         # position of a finest node in that vector: owned -> its local index, ghost -> behind the owned block
         def pos(g):
+            g = np.asarray(g, dtype=np.int64)
             own = (g >= p.lo) & (g < p.hi)
             out = np.empty(g.shape[0], dtype=np.int64)
             out[own] = p.own_perm[g[own] - p.lo]
             out[~own] = p.nb_own + np.searchsorted(ghosts, g[~own])
             return out
-        self.idx = [None if n is None else ctx.ivec(pos(n)) for n in need]
+        # per level: an index list (alfi_vec_gather), or (rowptr, colidx, weights) in CSR order (alfi_vec_gather_csr)
+        self.idx, self.csr = [], []
+        for C in need:
+            index = C is not None and _is_index_map(C)
+            self.idx.append(ctx.ivec(pos(C.indices)) if index else None)
+            self.csr.append(None if C is None or index else
+                            (ctx.ivec(C.indptr), ctx.ivec(pos(C.indices)), ctx.vec(C.data if C.nnz else np.zeros(1))))
         self.bytes_received = int(len(ghosts)) * bs * 8
 
     def refresh(self, du_owned, states):
         """du_owned: device vector that starts with the rank's owned finest velocity; states[i]: device state of local level i."""
         self.ctx.copy(self.vec, du_owned, n=self.n_own)
         self.level.halo_forward(self.vec)
-        for ix, st in zip(self.idx, states):
+        for ix, csr, st in zip(self.idx, self.csr, states):
             if ix is not None:
                 self.ctx.gather(st, self.vec, ix, self.bs)
+            elif csr is not None:
+                self.ctx.gather_csr(st, self.vec, csr[0], csr[1], csr[2], self.bs)
 
     def close(self):
         self.level.close()
@@ -94,24 +140,24 @@ class DistNavierStokesSolver(HipNavierStokesSolver):
     """HipNavierStokesSolver with the device side on partitioned levels (one process per GPU): DistMultigrid + DistSaddle.
     Every rank rediscretises ITS OWN rows of the level operators -- on its device from the cells that touch its nodes
     (``_rediscretise_device``; on its host cores only with ALFI_DEVICE_ASSEMBLY=0).  The Newton state is DISTRIBUTED on the
-    devices, every rank its owned velocity and pressure dofs (``StateExchange`` feeds the levels' refresh states from it;
-    ``u`` / ``p`` gather it, collectively, when somebody asks); the barycentric hierarchy of the Scott-Vogelius pair and
-    the host-assembly path keep a replicated host state.  The Burman terms of the Scott-Vogelius pair are formed by every rank
+    devices for every discretisation, every rank its owned velocity and pressure dofs (``StateExchange`` feeds the levels'
+    refresh states from it -- index gathers on the nested hierarchies, weighted gathers of the composed point evaluations on the
+    barycentric hierarchy of the Scott-Vogelius pair; ``u`` / ``p`` gather it, collectively, when somebody asks); the
+    host-assembly path and ``device_state=False`` keep a replicated host state.  The Burman terms of the Scott-Vogelius pair are formed by every rank
     over the facets of its cells (``FacetPart``), on the device or, with ALFI_DEVICE_ASSEMBLY=0, by the host pass."""
 
     _partitioned = True
 
     def __init__(self, *args, min_dofs=400000, group=None, device_state=True, **kwargs):
-        """device_state False: the Newton state replicated on the hosts and gathered after every linear solve (the loop of
-        round 4; kept for comparisons)."""
+        """device_state False: the Newton state replicated on the hosts, every level's state formed there (``_winds``) and
+        uploaded, residual and update gathered after every step (the loop of round 4; kept for comparisons)."""
         self._min_dofs, self._group, self._want_device_state = min_dofs, group, bool(device_state)
         super().__init__(*args, **kwargs)
 
     def _device_state_resident(self):
-        # the state lives distributed on the devices -- every rank its owned velocity and pressure dofs -- whenever the
-        # operators are refreshed there and the hierarchy is nested (the barycentric one of the Scott-Vogelius pair injects
-        # by point evaluation: it keeps the replicated host state)
-        return self.device_assembly and not self.sv and getattr(self, "_exch", None) is not None
+        # the state lives distributed on the devices -- every rank its owned velocity and pressure dofs (P0: its cells', the
+        # Scott-Vogelius pair: the P_{k-1}^dg rows of its cells) -- whenever the operators are refreshed there
+        return self.device_assembly and getattr(self, "_exch", None) is not None
 
     def _any_rank(self, flag):
         return any(self.dmg.comm.all_gather_object(bool(flag)))
@@ -169,10 +215,10 @@ class DistNavierStokesSolver(HipNavierStokesSolver):
         """Once per solver, RANK-LOCAL (no collective: ``_start_device_assembly`` agrees on the outcome afterwards): every local
         level with owned rows gets the cells that touch its local nodes and the contributor lists of its local sparsity
         (alfi_level_set_assembly on a partitioned level: every term of the operator is formed on the device, cell by cell);
-        the state of a Newton step is then uploaded per level -- local nodes and the ring of nodes around them, a few
-        megabytes -- and the operators are rebuilt from it on the device.  Every discretisation the single-GPU solver
-        refreshes on the device: the P0-pressure pairs, the Scott-Vogelius pair (its per-level states come from the
-        replicated state by the sparse bary injection on the host, _winds) and the SUPG terms (element matrices of the rank's
+        the state of a Newton step then reaches every level's state vector -- local nodes and the ring of nodes around them, a
+        few megabytes -- through ``StateExchange`` (``device_state=False``: uploaded from the replicated host state) and the
+        operators are rebuilt from it on the device.  Every discretisation the single-GPU solver refreshes on the device: the
+        P0-pressure pairs, the Scott-Vogelius pair with or without Burman terms and the SUPG terms (element matrices of the rank's
         cells -- all cells that touch a local node -- gathered into the rank's rows).
         Ranks that hold only ghost copies of a level (the coarse side of the first distributed transfer) skip it: no patch
         and no product reads those rows."""
@@ -212,9 +258,10 @@ class DistNavierStokesSolver(HipNavierStokesSolver):
             self._dp, self._dFp = self.ctx.vec(max(len(rows), 1)), self.ctx.vec(max(len(rows), 1))
             self._dwc = self.ctx.vec(dmg.n_loc)
             self._exch = None
-            if not self.sv and self._want_device_state:
+            # the residual's pressure rows are the outer solve's (P0: the rank's cells; Scott-Vogelius: npc rows per cell)
+            assert np.array_equal(self._res_rows, self.saddle.cells)
+            if self._want_device_state:
                 # the distributed device-resident state: (owned velocity | owned pressure) per rank
-                assert np.array_equal(self._res_rows, self.saddle.cells)
                 n = self.saddle.n
                 self._dz, self._dF, self._dd = self.ctx.vec(n + 1), self.ctx.vec(n + 1), self.ctx.vec(n + 1)
         self._asm_ready = True
@@ -223,7 +270,7 @@ class DistNavierStokesSolver(HipNavierStokesSolver):
         """COLLECTIVE, and so a phase of its own, entered only once every rank has the rank-local part: the exchange that
         feeds every level's refresh from the distributed state (its gather of the ghost lists comes before any device call of
         its own)."""
-        if not self.sv and self._want_device_state:
+        if self._want_device_state:
             with self._on_stream():
                 self._exch = StateExchange(self.dmg, self.levels, self.transfers,
                                            [None if a is None else a[0] for a in self._asm], self.dmg.device)

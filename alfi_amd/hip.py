@@ -103,6 +103,13 @@ class Context(object):
         assert dst.n >= idx.n * bs
         self.check(self.lib.alfi_vec_gather(self.h, dst.ptr, src.ptr, idx.ptr, idx.n, int(bs)))
 
+    def gather_csr(self, dst, src, rowptr, colidx, weights, bs=1):
+        """dst[i*bs + c] = sum_k weights[k] * src[colidx[k]*bs + c] over CSR row i, on the device (alfi_vec_gather_csr; rowptr,
+        colidx: IntVecs, weights: a device vector; bs 1, 2 or 3)."""
+        nrows = rowptr.n - 1
+        assert nrows >= 0 and dst.n >= nrows * bs and colidx.n <= weights.n
+        self.check(self.lib.alfi_vec_gather_csr(self.h, dst.ptr, src.ptr, rowptr.ptr, colidx.ptr, weights.ptr, nrows, int(bs)))
+
     def comm_stats(self, reset=False):
         """(halo exchanges, all-reduces, doubles sent by this rank) since the last reset (alfi_ctx_comm_stats)."""
         a, b, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()

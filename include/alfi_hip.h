@@ -446,10 +446,14 @@ int alfi_csr_mult(alfi_csr* m, const double* dx, double* dy, const double* db, d
  * only scalars come back.  alfi_saddle_dot: x . y of two (velocity | pressure) vectors of the outer solve, summed over the
  * ranks on a partitioned finest level (every rank gets the same value), fixed summation order.  alfi_level_zero_bc: dv[Dirichlet
  * dofs of the level] = 0 (bc.zero(F), solver.py:282-286).  alfi_vec_gather: dst[i] = src[idx[i]], bs doubles per index (idx a
- * DEVICE array).  alfi_transfer_stats: bytes every host <-> device copy of the library has moved (process-wide). */
+ * DEVICE array).  alfi_vec_gather_csr: dst[i*bs + c] = sum_k weights[k] * src[colidx[k]*bs + c] over the CSR row i (DEVICE arrays;
+ * bs 1, 2 or 3), an FMA chain in CSR order that starts from -0.0 in a non-empty row (it adds nothing and keeps the sign of a
+ * zero): a one-entry row of weight 1.0 copies its source bit for bit; an empty row gives +0.0.  alfi_transfer_stats: bytes every host <-> device copy of the library has moved (process-wide). */
 int alfi_vec_axpy(alfi_ctx* ctx, double* dy, const double* dx, double a, int64_t n);   /* y += a x */
 int alfi_vec_copy(alfi_ctx* ctx, double* dy, const double* dx, int64_t n);
 int alfi_vec_gather(alfi_ctx* ctx, double* dst, const double* dsrc, const int32_t* d_idx, int64_t nidx, int bs);
+int alfi_vec_gather_csr(alfi_ctx* ctx, double* dst, const double* dsrc, const int32_t* d_rowptr, const int32_t* d_colidx,
+                        const double* d_weights, int64_t nrows, int bs);
 int alfi_level_zero_bc(alfi_level* lvl, double* dv);
 int alfi_saddle_dot(alfi_saddle* s, const double* dx, const double* dy, double* out_host);
 int alfi_transfer_stats(int64_t* h2d_bytes, int64_t* d2h_bytes, int reset);

@@ -6,10 +6,15 @@ stand-in for librccl (tests/mock_rccl), so the times are FUNCTIONAL (one GPU doe
 
     python scripts/dist_newton_time.py cfg4 --ranks 4 --re 10 100
     python scripts/dist_newton_time.py cfg5s --ranks 2 --burman 5e-3 --compare
+    python scripts/dist_newton_time.py cfg5s --ranks 2 --host-state
 
-The Scott-Vogelius configs (cfg5s, cfg5: the structured bfs3d stand-in) run with the replicated host state; --burman WEIGHT
-adds the interior-penalty term (every rank over the facets of its cells) and reports its per-rank cost: the refresh of all
-levels with and without the term and the term's residual pass on the finest level.
+Every config runs with the Newton state distributed on the devices -- the Scott-Vogelius ones (cfg5s, cfg5: the structured
+bfs3d stand-in) included, their coarse levels' states being weighted gathers of the exchanged finest velocity; --host-state
+selects the replicated host state instead (device_state=False: every level's state formed on the host and uploaded, residual
+and update gathered through the host), for comparisons.  Next to the times, every rank's bytes across PCIe per Newton step
+(alfi_transfer_stats: every copy the library makes, the larger direction).  --burman WEIGHT adds the interior-penalty term
+(every rank over the facets of its cells) and reports its per-rank cost: the refresh of all levels with and without the term
+and the term's residual pass on the finest level.
 
 The parent never touches the GPU: it starts the rank processes and relays rank 0's report; host assemblies during the Newton
 loops are counted (must be 0) and the Newton / Krylov counts printed next to the single-GPU solver's when --compare is given."""
@@ -37,11 +42,12 @@ def rank_main(args):
     from alfi_amd.problem import TwoDimLidDrivenCavityProblem, ThreeDimLidDrivenCavityProblem
     prob, nref, ke, kw = problem_and_options(args)
     t0 = time.time()
-    s = DistNavierStokesSolver(prob, nref, ke, min_dofs=args.min_dofs, **kw)
+    s = DistNavierStokesSolver(prob, nref, ke, min_dofs=args.min_dofs, device_state=not args.host_state, **kw)
     if rank == 0:
-        print("%s on %d ranks (transport %s): %d velocity + %d pressure dofs, setup %.1f s, device assembly %s, levels on "
-              "this rank %d.." % (args.config, world, s.dmg.transport, s.n_u, s.n_p, time.time() - t0, s.device_assembly,
-                                   s.dmg.lmin), flush=True)
+        print("%s on %d ranks (transport %s): %d velocity + %d pressure dofs, setup %.1f s, device assembly %s, state %s, "
+              "levels on this rank %d.." % (args.config, world, s.dmg.transport, s.n_u, s.n_p, time.time() - t0,
+                                            s.device_assembly, "distributed on the devices" if s._device_state_resident()
+                                            else "replicated on the hosts", s.dmg.lmin), flush=True)
     calls = []
     real, real_supg, real_burman = _hostlib.assemble_bsr, _hostlib.supg, _hostlib.burman
     _hostlib.assemble_bsr = lambda *a, **kw: (calls.append(1), real(*a, **kw))[1]
@@ -51,16 +57,20 @@ def rank_main(args):
         for kk in s.timings:
             s.timings[kk] = 0 if kk == "newton_steps" else 0.0
         dist.barrier()
+        s.ctx.transfer_stats(reset=True)
         t0 = time.time()
         _, info = s.solve(re)
         wall = time.time() - t0
         n = max(s.timings["newton_steps"], 1)
+        pcie = [None] * world
+        dist.all_gather_object(pcie, max(s.ctx.transfer_stats()) // n)
         if rank == 0:
             print("Re %g: %d Newton steps, %d Krylov its, converged %s, wall %.2f s = %.2f s per Newton step "
                   "(assemble %.3f, factor %.3f, residual %.3f, solve %.3f per step); host assemblies so far: %d"
                   % (re, info["nonlinear_iter"], info["linear_iter"], info["converged"], wall, wall / n,
                      s.timings["assemble_s"] / n, s.timings["factor_s"] / n, s.timings["residual_s"] / n,
                      s.timings["solve_s"] / n, len(calls)), flush=True)
+            print("Re %g: bytes across PCIe per Newton step, per rank: %s" % (re, pcie), flush=True)
     got = [None] * world
     dist.all_gather_object(got, len(calls))
     if rank == 0:
@@ -137,6 +147,8 @@ def main():
                     help="SUPG stabilisation with this weight (the reference's production runs: 0.05)")
     ap.add_argument("--burman", type=float, default=None, metavar="WEIGHT",
                     help="Burman stabilisation of the Scott-Vogelius configs with this weight (the reference's run lines: 5e-3)")
+    ap.add_argument("--host-state", action="store_true",
+                    help="the Newton state replicated on the hosts (device_state=False), for comparisons")
     ap.add_argument("--compare", action="store_true", help="also run the single-GPU solver (counts side by side)")
     ap.add_argument("--rank-process", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -162,7 +174,18 @@ def main():
                                        "--min-dofs", str(args.min_dofs), "--rank-process"] +
                                       (["--supg", str(args.supg)] if args.supg is not None else []) +
                                       (["--burman", str(args.burman)] if args.burman is not None else []) +
+                                      (["--host-state"] if args.host_state else []) +
                                       ["--re"] + [str(x) for x in args.re], env=env, cwd=ROOT))
+    done = False
+    try:
+        # a rank that fails leaves the others waiting in a collective: end them with it
+        while any(p.poll() is None for p in procs) and not any(p.poll() for p in procs):
+            time.sleep(0.2)
+        done = not any(p.poll() for p in procs)
+    finally:
+        for p in procs:
+            if not done and p.poll() is None:
+                p.kill()
     rc = [p.wait() for p in procs]
     if any(rc):
         raise SystemExit("rank exit codes %s" % rc)
