@@ -9,7 +9,7 @@ from .problem import (NavierStokesProblem, TwoDimLidDrivenCavityProblem,        
 def __getattr__(name):
     # the GPU-facing classes load libalfi_hip.so on first use (and fail loudly if it is missing)
     if name in ("HipPatchPC", "HipMG", "PC", "mg_levels_solver", "fieldsplit_0_mg", "fieldsplit_0_lu", "DGMassInv",
-                "outer_solver", "HipOuterSolver"):
+                "outer_solver", "HipOuterSolver", "graddiv_solver", "HipCG", "HipJacobiPC"):
         from . import solver
         return getattr(solver, name)
     if name in ("PkP0SchoeberlTransfer", "SVSchoeberlTransfer", "AutoSchoeberlTransfer", "CoarseCellPatches",

@@ -105,6 +105,9 @@ SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_int64)]),
     "alfi_patch_get_inverse": (ctypes.c_int, [vp, ctypes.c_int64, vp]),
     "alfi_smooth_fgmres": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_int]),
+    "alfi_level_set_jacobi": (ctypes.c_int, [vp, ctypes.c_int]),
+    "alfi_smooth_chebyshev": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, vp, vp, ctypes.c_int]),
+    "alfi_level_arnoldi": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.POINTER(ctypes.c_int)]),
     "alfi_coarse_factor": (ctypes.c_int, [vp]),
     "alfi_coarse_factor_sparse": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int]),
     "alfi_coarse_factor_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64)]),
@@ -127,6 +130,10 @@ SIGNATURES = {
     "alfi_mg_destroy": (ctypes.c_int, [vp]),
     "alfi_mg_vcycle": (ctypes.c_int, [vp, vp, vp]),
     "alfi_mg_fcycle": (ctypes.c_int, [vp, vp, vp]),
+    "alfi_mg_set_smoother": (ctypes.c_int, [vp, ctypes.c_int, vp, vp]),
+    "alfi_mg_set_cycles": (ctypes.c_int, [vp, ctypes.c_int]),
+    "alfi_mg_cg": (ctypes.c_int, [vp, vp, vp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                  ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
     "alfi_ctx_set_graph": (ctypes.c_int, [vp, ctypes.c_int]),
     "alfi_saddle_create": (ctypes.c_int, [vp, ctypes.POINTER(CsrHost), ctypes.POINTER(CsrHost), vp, ctypes.c_double,
                                           ctypes.c_double, ctypes.c_int, ctypes.POINTER(vp)]),

@@ -1,4 +1,5 @@
-// C ABI of libalfi_hip.so (include/alfi_hip.h), coarse solve, Schoeberl transfers, PCMG V / full cycles and their hipGraph replay.
+// C ABI of libalfi_hip.so (include/alfi_hip.h), coarse solve, Schoeberl transfers, PCMG V / W / full cycles, their hipGraph replay,
+// and CG preconditioned by one cycle.
 // (One file per concern since round 5: api_ctx / api_level / api_patches / api_smoother / api_cycles / api_saddle; the helpers they
 // share are declared in api_internal.h.)
 #include "api_internal.h"
@@ -423,11 +424,69 @@ int alfi_mg_destroy(alfi_mg* mg) {
   (void)hipStreamSynchronize(mg->ctx->stream);
   for (CycleGraph& g : mg->graphs)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
+  dev_free(mg->cg_r);
+  dev_free(mg->cg_z);
+  dev_free(mg->cg_p);
+  dev_free(mg->cg_w);
+  dev_free(mg->cg_s);
   delete mg;
   return 0;
 }
 
-// PCMGMCycle_Private [3P]: x_l <- V(b_l, x_l).  x_zero: the incoming x is known to be zero (every level below the one the
+// serial hierarchies only: what the Chebyshev smoother, the W-cycle and CG ask of every level
+static int mg_require_serial(alfi_mg* mg, const char* what) {
+  for (alfi_level* L : mg->levels)
+    if (level_is_partitioned(L)) return alfi_set_error(mg->ctx, ALFI_E_ARG, "%s on a partitioned hierarchy (serial levels only)", what);
+  return 0;
+}
+
+int alfi_mg_set_smoother(alfi_mg* mg, int type, const double* emin, const double* emax) {
+  if (!mg) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL multigrid");
+  alfi_ctx* ctx = mg->ctx;
+  if (type != ALFI_SMOOTHER_FGMRES && type != ALFI_SMOOTHER_CHEBYSHEV)
+    return alfi_set_error(ctx, ALFI_E_ARG, "smoother type %d (0 FGMRES, 1 Chebyshev)", type);
+  if (type == ALFI_SMOOTHER_FGMRES) {
+    mg->smoother = type;
+    return 0;
+  }
+  ALFI_CHECK(mg_require_serial(mg, "alfi_mg_set_smoother(Chebyshev)"));
+  const int nl = (int)mg->levels.size();
+  if (nl > 1 && (!emin || !emax)) return alfi_set_error(ctx, ALFI_E_ARG, "Chebyshev smoother without intervals");
+  for (int l = 1; l < nl; ++l)
+    if (!(emin[l - 1] > 0.0) || !(emax[l - 1] > emin[l - 1]) || !std::isfinite(emax[l - 1]))
+      return alfi_set_error(ctx, ALFI_E_ARG, "Chebyshev interval [%g, %g] of level %d: need 0 < emin < emax", emin[l - 1],
+                            emax[l - 1], l);
+  // the smoother's work vectors now, not in the first cycle: with graphs on that cycle may already be a capture
+  for (int l = 1; l < nl; ++l) ALFI_CHECK(ensure_cheb_workspace(mg->levels[l]));
+  mg->emin.assign((size_t)nl, 0.0);
+  mg->emax.assign((size_t)nl, 0.0);
+  for (int l = 1; l < nl; ++l) {
+    mg->emin[l] = emin[l - 1];
+    mg->emax[l] = emax[l - 1];
+  }
+  mg->smoother = type;
+  return 0;
+}
+
+int alfi_mg_set_cycles(alfi_mg* mg, int cycles) {
+  if (!mg) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL multigrid");
+  if (cycles != 1 && cycles != 2) return alfi_set_error(mg->ctx, ALFI_E_ARG, "cycles %d (1 V, 2 W)", cycles);
+  if (cycles > 1) ALFI_CHECK(mg_require_serial(mg, "alfi_mg_set_cycles(W)"));
+  mg->cycles = cycles;
+  return 0;
+}
+
+// the level smoother of the hierarchy (alfi_mg_set_smoother)
+static int mg_smooth(alfi_mg* mg, int l, const double* b, double* x, int nonzero_guess) {
+  alfi_level* L = mg->levels[l];
+  if (mg->smoother == ALFI_SMOOTHER_CHEBYSHEV)
+    return alfi_smooth_chebyshev(L, mg->k, mg->emin[l], mg->emax[l], b, x, nonzero_guess);
+  return alfi_smooth_fgmres(L, mg->k, b, x, nonzero_guess);
+}
+
+// PCMGMCycle_Private [3P]: x_l <- M(b_l, x_l), the V-cycle for cycles = 1 and the W-cycle for cycles = 2: level 1 visits the
+// coarse solve once, every level >= 2 recurses `cycles` times on the same restricted right-hand side, the later visits
+// continuing from the coarse iterate of the one before.  x_zero: the incoming x is known to be zero (every level below the one the
 // cycle starts on): the pre-smoother then runs with a zero initial guess -- r0 = b, no residual SpMV -- as PCMG does by
 // switching KSPSetInitialGuessNonzero off for the down-smoother of those levels; the result is the same bit for bit.
 static int vcycle(alfi_mg* mg, int l, const double* b, double* x, bool x_zero) {
@@ -438,18 +497,19 @@ static int vcycle(alfi_mg* mg, int l, const double* b, double* x, bool x_zero) {
   if (l == 0) return L->n_own > 0 ? alfi_coarse_solve(L, b, x) : 0;
   alfi_level* C = mg->levels[l - 1];
   alfi_transfer* T = mg->transfers[l - 1];
-  ALFI_CHECK(alfi_smooth_fgmres(L, mg->k, b, x, x_zero ? 0 : 1));    // pre-smooth
+  ALFI_CHECK(mg_smooth(mg, l, b, x, x_zero ? 0 : 1));                // pre-smooth
   ALFI_CHECK(alfi_residual(L, b, x, L->mg_r));                       // r = b - A x
   ALFI_CHECK(alfi_restrict(T, L->mg_r, C->mg_b, mg->robust));        // b_{l-1} = R r
   // x_{l-1} = 0: the coarse solve overwrites it, a smoother with a zero initial guess zeroes it itself
-  ALFI_CHECK(vcycle(mg, l - 1, C->mg_b, C->mg_x, true));
+  const int cycles = l == 1 ? 1 : mg->cycles;
+  for (int c = 0; c < cycles; ++c) ALFI_CHECK(vcycle(mg, l - 1, C->mg_b, C->mg_x, c == 0));
   ALFI_CHECK(alfi_prolong(T, C->mg_x, L->mg_r));                     // x += P x_{l-1}
   ctx->cur_tag = L->id;
   {
     ProfScope prof(ctx, ALFI_EV_BLAS1);
     ALFI_CHECK(launch_axpy(ctx, x, L->mg_r, 1.0, L->n_own));
   }
-  ALFI_CHECK(alfi_smooth_fgmres(L, mg->k, b, x, 1));                 // post-smooth
+  ALFI_CHECK(mg_smooth(mg, l, b, x, 1));                             // post-smooth
   return 0;
 }
 
@@ -493,7 +553,17 @@ static void cycle_signature(alfi_mg* mg, std::vector<uint64_t>* sig) {
   sig->clear();
   sig->push_back((uint64_t)mg->k);
   sig->push_back((uint64_t)mg->robust);
+  sig->push_back((uint64_t)mg->smoother);
+  sig->push_back((uint64_t)mg->cycles);
+  if (mg->smoother == ALFI_SMOOTHER_CHEBYSHEV)       // the interval becomes kernel arguments
+    for (size_t l = 1; l < mg->levels.size(); ++l) {
+      pushd(mg->emin[l]);
+      pushd(mg->emax[l]);
+    }
   for (alfi_level* L : mg->levels) {
+    sig->push_back((uint64_t)(L->jacobi ? 1 : 0));
+    push(L->jac_diag);
+    push(L->cheb_d);
     push(L->A.vals);
     push(L->inv);
     push(L->patch_ptr);
@@ -516,9 +586,18 @@ static void cycle_signature(alfi_mg* mg, std::vector<uint64_t>* sig) {
 // every level has what a cycle multiplies with: factored patches, a coarse inverse
 static int mg_ready(alfi_mg* mg) {
   alfi_ctx* ctx = mg->ctx;
-  for (size_t l = 1; l < mg->levels.size(); ++l)
-    if (mg->levels[l]->n_own > 0 && !mg->levels[l]->factored)
+  for (size_t l = 1; l < mg->levels.size(); ++l) {
+    alfi_level* L = mg->levels[l];
+    if (L->n_own > 0 && !level_pc_ready(L))
       return alfi_set_error(ctx, ALFI_E_STATE, "level %d: patches not factored", (int)l);
+    if (mg->smoother == ALFI_SMOOTHER_CHEBYSHEV) ALFI_CHECK(ensure_cheb_workspace(L));   // (a no-op after alfi_mg_set_smoother)
+    // a point-Jacobi level: the diagonal of the current operator values, extracted here and not inside the cycle, so that a
+    // captured cycle never holds the extraction and never multiplies with a stale diagonal
+    if (L->jacobi && L->jac_version != L->op_version) {
+      ALFI_CHECK(launch_jacobi_diag(ctx, L->A, L->jac_diag));
+      L->jac_version = L->op_version;
+    }
+  }
   // a rank that only holds ghost copies of its lowest level (the owner solves it) needs no coarse inverse
   alfi_level* C = mg->levels[0];
   if (C->n_own > 0 && !C->cinv && !C->mf) return alfi_set_error(ctx, ALFI_E_STATE, "coarse level has no inverse");
@@ -588,6 +667,76 @@ static int run_cycle(alfi_mg* mg, int kind, const double* db, double* dx) {
 int alfi_mg_vcycle(alfi_mg* mg, const double* db, double* dx) { return run_cycle(mg, 0, db, dx); }
 
 int alfi_mg_fcycle(alfi_mg* mg, const double* db, double* dx) { return run_cycle(mg, 1, db, dx); }
+
+// KSPCG [3P] with a zero initial guess and the unpreconditioned residual norm, preconditioned by one cycle of mg
+// (examples/graddiv/graddiv.py:85-95).  The step lengths are formed on the device from reduced scalars (kernels_cheb.hip);
+// the one read-back per iteration is |r|^2 for the convergence test, taken before the cycle so that no cycle is wasted.
+int alfi_mg_cg(alfi_mg* mg, const double* db, double* dx, double rtol, double atol, int max_it, int full, int* its,
+               double* rnorm) {
+  if (!mg) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL multigrid");
+  alfi_ctx* ctx = mg->ctx;
+  ALFI_CHECK(mg_require_serial(mg, "alfi_mg_cg"));
+  if (!db || !dx || db == dx || !its || !rnorm || max_it < 0 || !(rtol >= 0.0) || !(atol >= 0.0))
+    return alfi_set_error(ctx, ALFI_E_ARG, "alfi_mg_cg: bad arguments");
+  alfi_level* L = mg->levels.back();
+  const int64_t n = L->n;
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (!mg->cg_s) {
+    ALFI_CHECK(dev_alloc(ctx, &mg->cg_r, n));
+    ALFI_CHECK(dev_alloc(ctx, &mg->cg_z, n));
+    ALFI_CHECK(dev_alloc(ctx, &mg->cg_p, n));
+    ALFI_CHECK(dev_alloc(ctx, &mg->cg_w, n));
+    ALFI_CHECK(dev_alloc(ctx, &mg->cg_s, 4));
+  }
+  double *r = mg->cg_r, *z = mg->cg_z, *p = mg->cg_p, *w = mg->cg_w, *s = mg->cg_s;
+  auto precond = [&]() -> int {     // z = PCMG(r)
+    if (full) return run_cycle(mg, 1, r, z);
+    ALFI_HIP_CHECK(ctx, hipMemsetAsync(z, 0, sizeof(double) * n, ctx->stream));
+    return run_cycle(mg, 0, r, z);
+  };
+  auto dot = [&](const double* a, const double* b, double* out) -> int {
+    ProfScope prof(ctx, ALFI_EV_BLAS1);
+    return launch_multi_dot(ctx, a, 0, 1, b, out, n);
+  };
+  auto read_rr = [&](double* rr) -> int {
+    ALFI_HIP_CHECK(ctx, hipMemcpyAsync(rr, s + 3, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return check_dev_err(ctx);
+  };
+  ctx->cur_tag = L->id;
+  ALFI_HIP_CHECK(ctx, hipMemsetAsync(dx, 0, sizeof(double) * n, ctx->stream));
+  {
+    ProfScope prof(ctx, ALFI_EV_BLAS1);
+    ALFI_CHECK(launch_copy(ctx, r, db, n));                    // x = 0: r = b
+  }
+  ALFI_CHECK(dot(r, r, s + 3));
+  double rr = 0.0;
+  ALFI_CHECK(read_rr(&rr));
+  const double tol = std::max(rtol * std::sqrt(rr), atol);
+  int it = 0;
+  while (std::sqrt(rr) > tol && it < max_it && std::isfinite(rr)) {
+    const int cur = it & 1;
+    ALFI_CHECK(precond());
+    ctx->cur_tag = L->id;
+    ALFI_CHECK(dot(r, z, s + cur));                            // r . z of this iteration
+    {
+      ProfScope prof(ctx, ALFI_EV_BLAS1);
+      ALFI_CHECK(launch_cg_update_p(ctx, p, z, s, cur, it == 0 ? 1 : 0, n));   // p = z + (r.z / r.z of the last iteration) p
+    }
+    ALFI_CHECK(level_spmv(L, p, w, nullptr, 0));               // w = A p
+    ALFI_CHECK(dot(p, w, s + 2));
+    {
+      ProfScope prof(ctx, ALFI_EV_BLAS1);
+      ALFI_CHECK(launch_cg_update_xr(ctx, dx, r, p, w, s, cur, n));                // x += alpha p, r -= alpha w
+    }
+    ALFI_CHECK(dot(r, r, s + 3));
+    ++it;
+    ALFI_CHECK(read_rr(&rr));
+  }
+  *its = it;
+  *rnorm = std::sqrt(rr);
+  return 0;
+}
 
 int alfi_ctx_comm_stats(alfi_ctx* ctx, int64_t* halo_exchanges, int64_t* allreduces, int64_t* doubles_sent, int reset) {
   if (halo_exchanges) *halo_exchanges = ctx->comm_nhalo;

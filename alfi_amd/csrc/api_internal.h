@@ -54,10 +54,15 @@ int halo_rev_end(alfi_level* L, double* v);
 void free_assembly(AssemblyDev* S);
 int level_spmv(alfi_level* L, const double* dx, double* dy, const double* db, int mode, bool ghosts_current = false);
 int level_patch_apply(alfi_level* L, const double* dx, double* dy, bool* ghosts_current = nullptr);
+// the level has what its preconditioner application needs: factored patches, or the point-Jacobi switch
+inline bool level_pc_ready(const alfi_level* L) { return L->factored || L->jacobi; }
+// the entry points that exist on serial levels only (Chebyshev smoother, W-cycle, CG, Arnoldi, point Jacobi)
+inline bool level_is_partitioned(const alfi_level* L) { return L->distributed || L->has_halo || L->n_own != L->n; }
 // api_patches.hip
 void free_mult_schedule(alfi_level* L);
 // api_smoother.hip
 int ensure_fgmres_workspace(alfi_level* L, int k);
+int ensure_cheb_workspace(alfi_level* L);
 // api_saddle.hip
 int upload_csr(alfi_ctx* ctx, DevCSR* d, const alfi_csr_host* h);
 void free_csr(DevCSR* d);

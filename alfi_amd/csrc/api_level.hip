@@ -219,6 +219,10 @@ int alfi_level_destroy(alfi_level* L) {
   dev_free(L->Z);
   dev_free(L->w);
   dev_free(L->hs);
+  dev_free(L->jac_diag);
+  dev_free(L->cheb_r);
+  dev_free(L->cheb_z);
+  dev_free(L->cheb_d);
   if (L->cinv_owned) dev_free(L->cinv);
   mf_free(L->mf);
   dev_free(L->mg_b);
@@ -808,6 +812,20 @@ int alfi_level_get_values(alfi_level* L, double* bvals) {
   return rc;
 }
 
+int alfi_level_set_jacobi(alfi_level* L, int on) {
+  if (!L) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL level");
+  alfi_ctx* ctx = L->ctx;
+  if (level_is_partitioned(L))
+    return alfi_set_error(ctx, ALFI_E_ARG, "alfi_level_set_jacobi on a partitioned level (serial levels only)");
+  if (on && !L->jac_diag) {
+    ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    ALFI_CHECK(dev_alloc(ctx, &L->jac_diag, L->n));
+    L->jac_version = ~(uint64_t)0;
+  }
+  L->jacobi = on != 0;
+  return 0;
+}
+
 int alfi_level_size(alfi_level* L, int64_t* n) {
   *n = L->n;
   return 0;
@@ -852,6 +870,16 @@ int alfi_residual(alfi_level* L, const double* db, const double* dx, double* dr)
 int level_patch_apply(alfi_level* L, const double* dx, double* dy, bool* ghosts_current) {
   alfi_ctx* ctx = L->ctx;
   if (ghosts_current) *ghosts_current = false;
+  if (L->jacobi) {
+    // pc_type jacobi (alfi_level_set_jacobi; serial levels only): y = x / diag(A), the diagonal re-extracted when the operator
+    // values have changed since (stream-ordered, no synchronisation)
+    ProfScope prof(ctx, ALFI_EV_PATCH_APPLY);   // to the end of the branch
+    if (L->jac_version != L->op_version) {
+      ALFI_CHECK(launch_jacobi_diag(ctx, L->A, L->jac_diag));
+      L->jac_version = L->op_version;
+    }
+    return launch_jacobi_apply(ctx, dy, dx, L->jac_diag, L->bc_mask, L->n);
+  }
   if (L->mult) {
     // multiplicative sweep (PCApply_PATCH, local_type multiplicative [3P]): y = 0, then wavefront by wavefront in
     // iteration order and, with symmetrise_sweep, back again in reverse order

@@ -591,7 +591,7 @@ int alfi_patches_check(alfi_level* L, double* worst_residual, int64_t* flagged, 
 }
 
 int alfi_patch_apply(alfi_level* L, const double* dx, double* dy) {
-  if (!L->factored) return alfi_set_error(L->ctx, ALFI_E_STATE, "alfi_patch_apply before alfi_patches_factor");
+  if (!level_pc_ready(L)) return alfi_set_error(L->ctx, ALFI_E_STATE, "alfi_patch_apply before alfi_patches_factor");
   if (dx == dy) return alfi_set_error(L->ctx, ALFI_E_ARG, "alfi_patch_apply: x and y must not alias");
   L->ctx->cur_tag = L->id;
   return level_patch_apply(L, dx, dy);

@@ -1,4 +1,5 @@
-// C ABI of libalfi_hip.so (include/alfi_hip.h), the FGMRES(k) level smoother (KSPFGMRES + PCPATCH, alfi/solver.py:309-317).
+// C ABI of libalfi_hip.so (include/alfi_hip.h), the level smoothers: FGMRES(k) (KSPFGMRES + PCPATCH, alfi/solver.py:309-317) and
+// Chebyshev(k) (KSPCHEBYSHEV, examples/graddiv/graddiv.py:109-110), and the Arnoldi steps its interval is estimated from.
 // (One file per concern since round 5: api_ctx / api_level / api_patches / api_smoother / api_cycles / api_saddle; the helpers they
 // share are declared in api_internal.h.)
 #include "api_internal.h"
@@ -87,7 +88,7 @@ static int smooth_fgmres_fused(alfi_level* L, int k, const double* db, double* d
 int alfi_smooth_fgmres(alfi_level* L, int k, const double* db, double* dx, int nonzero_guess) {
   alfi_ctx* ctx = L->ctx;
   if (k < 1) return alfi_set_error(ctx, ALFI_E_ARG, "k must be >= 1");
-  if (!L->factored) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_smooth_fgmres before alfi_patches_factor");
+  if (!level_pc_ready(L)) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_smooth_fgmres before alfi_patches_factor");
   ALFI_CHECK(ensure_fgmres_workspace(L, k));
   ctx->cur_tag = L->id;
   {
@@ -103,7 +104,7 @@ int alfi_smooth_fgmres(alfi_level* L, int k, const double* db, double* dx, int n
     // 17.35 ms, config 4 163.1 / 163.3, config 5 27.24 / 27.10).
     constexpr int64_t small_n = 50000;
     const bool fusable = !alfi_test_large_paths() && !L->distributed && L->n_own == L->n && !L->mult && k + 1 <= 16 &&
-                         L->A_own.flat;
+                         L->A_own.flat && !L->jacobi;   // (the fused iteration launches the patch kernels itself)
     const bool short_rows = L->max_row_blocks <= 32 || L->n <= small_n;
     if (fusable && short_rows) return smooth_fgmres_fused(L, k, db, dx, nonzero_guess, !short_rows);
   }
@@ -180,5 +181,127 @@ int alfi_smooth_fgmres(alfi_level* L, int k, const double* db, double* dx, int n
   ProfScope prof(ctx, ALFI_EV_BLAS1);   // to the end of the function
   ALFI_CHECK(launch_fgmres_finish(ctx, hs, k, K));
   ALFI_CHECK(launch_update_solution(ctx, dx, Z, ldv, k, hs + hl.y, n));
+  return 0;
+}
+
+// ---- Chebyshev(k) smoother ---------------------------------------------------------------------------------------------------
+// (allocates: alfi_mg_set_smoother and the readiness check of a cycle call it, so that no cycle -- captured or not -- has to)
+int ensure_cheb_workspace(alfi_level* L) {
+  alfi_ctx* ctx = L->ctx;
+  if (L->cheb_d) return 0;
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ALFI_CHECK(dev_alloc(ctx, &L->cheb_r, L->n));
+  ALFI_CHECK(dev_alloc(ctx, &L->cheb_z, L->n));
+  ALFI_CHECK(dev_alloc(ctx, &L->cheb_d, L->n));
+  return 0;
+}
+
+// Saad, Iterative Methods for Sparse Linear Systems, Alg. 12.1 on the preconditioned operator M A with the spectrum assumed in
+// [emin, emax]: theta = (emax + emin) / 2, delta = (emax - emin) / 2, sigma_1 = theta / delta, rho_0 = 1 / sigma_1,
+//   d_0 = z_0 / theta,   d_i = rho_i rho_{i-1} d_{i-1} + (2 rho_i / delta) z_i,   rho_i = 1 / (2 sigma_1 - rho_{i-1}),
+// z_i = M (b - A x_i), x_{i+1} = x_i + d_i: the error after k steps is T_k((theta - M A) / delta) / T_k(theta / delta) e_0.
+// One residual, one preconditioner application and one fused update per step; the coefficients are host scalars passed as
+// kernel arguments, so there is no reduction and no read-back.
+int alfi_smooth_chebyshev(alfi_level* L, int k, double emin, double emax, const double* db, double* dx, int nonzero_guess) {
+  if (!L) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL level");
+  alfi_ctx* ctx = L->ctx;
+  if (level_is_partitioned(L))
+    return alfi_set_error(ctx, ALFI_E_ARG, "alfi_smooth_chebyshev on a partitioned level (serial levels only)");
+  if (k < 1) return alfi_set_error(ctx, ALFI_E_ARG, "k must be >= 1");
+  if (!(emin > 0.0) || !(emax > emin) || !std::isfinite(emax))
+    return alfi_set_error(ctx, ALFI_E_ARG, "Chebyshev interval [%g, %g]: need 0 < emin < emax", emin, emax);
+  if (!db || !dx || db == dx) return alfi_set_error(ctx, ALFI_E_ARG, "alfi_smooth_chebyshev: b and x must be distinct vectors");
+  if (!level_pc_ready(L)) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_smooth_chebyshev before alfi_patches_factor");
+  ALFI_CHECK(ensure_cheb_workspace(L));
+  ctx->cur_tag = L->id;
+  const int64_t n = L->n;
+  const double theta = 0.5 * (emax + emin), delta = 0.5 * (emax - emin), sigma1 = theta / delta;
+  double rho = 1.0 / sigma1;
+  for (int i = 0; i < k; ++i) {
+    const bool x_is_zero = i == 0 && !nonzero_guess;
+    const double* r = db;                                      // zero iterate: r = b, no product
+    if (!x_is_zero) {
+      ALFI_CHECK(alfi_residual(L, db, dx, L->cheb_r));         // r = b - A x
+      r = L->cheb_r;
+    }
+    ALFI_CHECK(level_patch_apply(L, r, L->cheb_z));            // z = M r
+    double a = 0.0, c = 1.0 / theta;
+    if (i > 0) {
+      const double rho_new = 1.0 / (2.0 * sigma1 - rho);
+      a = rho_new * rho;
+      c = 2.0 * rho_new / delta;
+      rho = rho_new;
+    }
+    ProfScope prof(ctx, ALFI_EV_BLAS1);   // to the end of the loop body
+    ALFI_CHECK(launch_cheb_update(ctx, L->cheb_d, dx, L->cheb_z, a, c, n, i > 0 ? 0 : (x_is_zero ? 2 : 1)));
+  }
+  return 0;
+}
+
+// m Arnoldi steps on M A from v0 (set-up of the Chebyshev interval, KSPChebyshevEstEigSet): classical Gram-Schmidt with the
+// smoother's multi-dot / multi-axpy kernels, the Hessenberg matrix assembled on the device, one synchronisation at the end.
+int alfi_level_arnoldi(alfi_level* L, int m, const double* dv0, double* H_host, int* m_done) {
+  if (!L) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL level");
+  alfi_ctx* ctx = L->ctx;
+  if (level_is_partitioned(L))
+    return alfi_set_error(ctx, ALFI_E_ARG, "alfi_level_arnoldi on a partitioned level (serial levels only)");
+  if (m < 1 || m > 30) return alfi_set_error(ctx, ALFI_E_ARG, "Arnoldi steps %d not in 1..30", m);
+  if (!dv0 || !H_host || !m_done) return alfi_set_error(ctx, ALFI_E_ARG, "NULL argument");
+  if (!level_pc_ready(L)) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_level_arnoldi before alfi_patches_factor");
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ctx->cur_tag = L->id;
+  const int64_t n = L->n, ld = (n + 1) & ~(int64_t)1;     // 16-byte aligned basis vectors
+  const int G = red_blocks_for(n);
+  const int ldh = m + 2;                                  // device Hessenberg: column j at Hd + j * ldh, slot m + 1 = |v0|
+  double *V = nullptr, *z = nullptr, *w = nullptr, *Hd = nullptr;
+  int rc = dev_alloc(ctx, &V, (int64_t)(m + 1) * ld);
+  if (rc == 0) rc = dev_alloc(ctx, &z, ld);
+  if (rc == 0) rc = dev_alloc(ctx, &w, ld);
+  if (rc == 0) rc = dev_alloc(ctx, &Hd, (int64_t)m * ldh);
+  if (rc == 0 && hipMemsetAsync(Hd, 0, sizeof(double) * m * ldh, ctx->stream) != hipSuccess) rc = ALFI_E_HIP;
+  auto run = [&]() -> int {
+    double* beta = Hd + (m + 1);
+    {
+      ProfScope prof(ctx, ALFI_EV_BLAS1);
+      ALFI_CHECK(launch_norm_partials(ctx, dv0, n));
+      ALFI_CHECK(launch_reduce_partials(ctx, ctx->red_partial, G, 1, beta));
+      ALFI_CHECK(launch_sqrt_inplace(ctx, beta));
+      ALFI_CHECK(launch_scale_by_inv(ctx, V, dv0, beta, n));                      // v_0 = v0 / |v0|
+    }
+    for (int j = 0; j < m; ++j) {
+      double* h = Hd + (int64_t)j * ldh;
+      ALFI_CHECK(level_spmv(L, V + (int64_t)j * ld, z, nullptr, 0));               // z = A v_j
+      ALFI_CHECK(level_patch_apply(L, z, w));                                     // w = M z
+      ProfScope prof(ctx, ALFI_EV_BLAS1);   // to the end of the loop body
+      ALFI_CHECK(launch_multi_dot(ctx, V, ld, j + 1, w, h, n));                   // h = V^T w
+      ALFI_CHECK(launch_multi_axpy_norm(ctx, V, ld, j + 1, h, w, n, ctx->red_partial2, 0));   // w -= V h, |w|^2 partials
+      ALFI_CHECK(launch_reduce_partials(ctx, ctx->red_partial2, G, 1, h + j + 1));
+      ALFI_CHECK(launch_sqrt_inplace(ctx, h + j + 1));                            // h_{j+1,j} = |w|
+      ALFI_CHECK(launch_scale_by_inv(ctx, V + (int64_t)(j + 1) * ld, w, h + j + 1, n));   // (a zero norm gives a zero vector)
+    }
+    return 0;
+  };
+  if (rc == 0) rc = run();
+  std::vector<double> Hh((size_t)m * ldh, 0.0);
+  if (rc == 0 && hipMemcpyAsync(Hh.data(), Hd, sizeof(double) * m * ldh, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+    rc = alfi_set_error(ctx, ALFI_E_HIP, "alfi_level_arnoldi: read-back failed");
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == 0) rc = alfi_set_error(ctx, ALFI_E_HIP, "alfi_level_arnoldi: sync failed");
+  dev_free(V);
+  dev_free(z);
+  dev_free(w);
+  dev_free(Hd);
+  if (rc != 0) return rc;
+  // breakdown: the first column whose subdiagonal entry is zero (to rounding, against the column) or not finite ends the basis
+  int done = m;
+  for (int j = 0; j < m && done == m; ++j) {
+    double cn = 0.0;
+    for (int i = 0; i <= j; ++i) cn = std::max(cn, std::fabs(Hh[(size_t)j * ldh + i]));
+    const double sub = Hh[(size_t)j * ldh + j + 1];
+    if (!std::isfinite(sub) || !std::isfinite(cn)) done = j;
+    else if (sub <= 1e-14 * cn) done = j + 1;
+  }
+  for (int i = 0; i <= m; ++i)
+    for (int j = 0; j < m; ++j) H_host[(size_t)i * m + j] = (j < done && i <= j + 1) ? Hh[(size_t)j * ldh + i] : 0.0;
+  *m_done = done;
   return 0;
 }

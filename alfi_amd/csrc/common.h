@@ -489,6 +489,12 @@ struct alfi_level {
   double* Z = nullptr;   // kmax x n
   double* w = nullptr;   // n
   double* hs = nullptr;  // small device arrays: Hessenberg etc.
+  // point-Jacobi level preconditioner (alfi_level_set_jacobi): replaces the patch solves in alfi_patch_apply and the smoothers
+  bool jacobi = false;
+  double* jac_diag = nullptr;        // (n) scalar diagonal of the operator, extracted from the diagonal blocks
+  uint64_t jac_version = ~(uint64_t)0;   // op_version jac_diag was extracted from
+  // Chebyshev smoother workspace (alfi_smooth_chebyshev): residual, preconditioned residual, direction (n each)
+  double *cheb_r = nullptr, *cheb_z = nullptr, *cheb_d = nullptr;
   // coarse dense inverse
   double* cinv = nullptr;
   bool cinv_owned = false;
@@ -546,6 +552,10 @@ struct alfi_mg {
   std::vector<alfi_transfer*> transfers;
   int k = 0;
   int robust = 0;
+  int smoother = 0;                 // alfi_mg_set_smoother: 0 FGMRES(k), 1 Chebyshev(k)
+  std::vector<double> emin, emax;   // Chebyshev interval of level l (index 0 unused)
+  int cycles = 1;                   // alfi_mg_set_cycles: recursions of every level >= 2 (1 V, 2 W)
+  double *cg_r = nullptr, *cg_z = nullptr, *cg_p = nullptr, *cg_w = nullptr, *cg_s = nullptr;   // alfi_mg_cg workspace
   std::vector<CycleGraph> graphs;
 };
 
@@ -711,3 +721,11 @@ int launch_patch_invert_mfma(alfi_ctx* ctx, int64_t npatch, int max_np, const in
                              double* inv, int* status, int* handled);   // kernels_invert.hip
 int launch_fgmres_finish_fused(alfi_ctx* ctx, const double* normpart, int nblocks, const double* h, double* hs, int k, int K);
 int launch_update_solution(alfi_ctx* ctx, double* x, const double* Z, int64_t stride, int k, const double* y, int64_t n);
+// kernels_cheb.hip: d = a d + c z, x += d (mode 0); mode 1: d = c z without reading d; mode 2: also x = d without reading x
+int launch_cheb_update(alfi_ctx* ctx, double* d, double* x, const double* z, double a, double c, int64_t n, int mode);
+int launch_jacobi_diag(alfi_ctx* ctx, const DevBSR& A, double* diag);              // scalar diagonal of the diagonal blocks
+int launch_jacobi_apply(alfi_ctx* ctx, double* y, const double* x, const double* diag, const uint8_t* bc, int64_t n);
+// CG steps with device-resident scalars s = [r.z (two slots, alternating), p.Ap, |r|^2]
+int launch_cg_update_xr(alfi_ctx* ctx, double* x, double* r, const double* p, const double* w, const double* s, int cur, int64_t n);
+int launch_cg_update_p(alfi_ctx* ctx, double* p, const double* z, const double* s, int cur, int first, int64_t n);
+int launch_sqrt_inplace(alfi_ctx* ctx, double* s);

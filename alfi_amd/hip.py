@@ -513,6 +513,24 @@ class Level(object):
     def smooth(self, k, b, x, nonzero_guess=True):
         self.ctx.check(self.ctx.lib.alfi_smooth_fgmres(self.h, int(k), b.ptr, x.ptr, 1 if nonzero_guess else 0))
 
+    def set_jacobi(self, on=True):
+        """pc_type jacobi (alfi_level_set_jacobi): the level's preconditioner application -- ``patch_apply`` and every smoother --
+        becomes y = x / diag(A) (y = x on Dirichlet dofs); such a level needs no patches.  Serial levels only."""
+        self.ctx.check(self.ctx.lib.alfi_level_set_jacobi(self.h, 1 if on else 0))
+
+    def smooth_chebyshev(self, k, emin, emax, b, x, nonzero_guess=True):
+        """k Chebyshev steps for the interval [emin, emax] on the preconditioned operator (alfi_smooth_chebyshev); x in place."""
+        self.ctx.check(self.ctx.lib.alfi_smooth_chebyshev(self.h, int(k), float(emin), float(emax), b.ptr, x.ptr,
+                                                          1 if nonzero_guess else 0))
+
+    def arnoldi(self, m, v0):
+        """m Arnoldi steps on (preconditioner x operator) from the device vector v0 (alfi_level_arnoldi).  Returns (H, m_done):
+        the (m + 1) x m Hessenberg matrix and the number of steps before a breakdown."""
+        H = np.zeros((int(m) + 1, int(m)))
+        done = ctypes.c_int()
+        self.ctx.check(self.ctx.lib.alfi_level_arnoldi(self.h, int(m), v0.ptr, _ptr(H), ctypes.byref(done)))
+        return H, done.value
+
     def set_coarse_inverse(self, inv):
         """inv: dense (n, n) numpy array (copied) or a device pointer (int) that stays owned by the caller."""
         if isinstance(inv, (int, np.integer)):
@@ -713,6 +731,57 @@ class Multigrid(object):
 
     def fcycle(self, b, x):
         self.ctx.check(self.ctx.lib.alfi_mg_fcycle(self.h, b.ptr, x.ptr))
+
+    SMOOTHERS = {"fgmres": 0, "chebyshev": 1}      # ALFI_SMOOTHER_FGMRES / ALFI_SMOOTHER_CHEBYSHEV
+    CYCLES = {"v": 1, "w": 2}
+
+    def set_smoother(self, kind, bounds=None):
+        """The level smoother of every cycle (alfi_mg_set_smoother): "fgmres" (default) or "chebyshev" with ``bounds`` = one
+        (emin, emax) pair per level 1 .. nlevels-1 (``chebyshev_bounds()``); the number of steps stays ``k``."""
+        if kind not in self.SMOOTHERS:
+            raise ValueError("smoother %r (fgmres or chebyshev)" % (kind,))
+        if kind == "fgmres":
+            self.ctx.check(self.ctx.lib.alfi_mg_set_smoother(self.h, 0, None, None))
+            return
+        b = np.ascontiguousarray(bounds, dtype=np.float64).reshape(-1, 2)
+        if b.shape[0] != len(self.levels) - 1:
+            raise ValueError("need one (emin, emax) pair per level above the coarsest: %d, got %d" % (len(self.levels) - 1, b.shape[0]))
+        emin, emax = np.ascontiguousarray(b[:, 0]), np.ascontiguousarray(b[:, 1])
+        self.ctx.check(self.ctx.lib.alfi_mg_set_smoother(self.h, 1, _ptr(emin), _ptr(emax)))
+
+    def set_cycle_type(self, kind):
+        """pc_mg_cycle_type (alfi_mg_set_cycles): "v" (default) or "w" -- every level >= 2 recurses twice."""
+        if kind not in self.CYCLES:
+            raise ValueError("cycle type %r (v or w)" % (kind,))
+        self.ctx.check(self.ctx.lib.alfi_mg_set_cycles(self.h, self.CYCLES[kind]))
+
+    def chebyshev_bounds(self, steps=10, esteig=(0.0, 0.1, 0.0, 1.1), seed=0):
+        """Chebyshev intervals of the levels 1 .. nlevels-1 the way KSPChebyshevEstEigSet sets them: ``steps`` Arnoldi steps on
+        (preconditioner x operator) from the vector ``numpy.random.default_rng(seed).standard_normal(n)`` with the Dirichlet
+        entries zeroed; lambda_max / lambda_min = the largest / smallest real part of the Ritz values; the interval is
+        (a lambda_min + b lambda_max, c lambda_min + d lambda_max) for esteig = (a, b, c, d).  Returns [(emin, emax), ...].
+        The intervals belong to the operators and patch factors of this moment: estimate again after either changes."""
+        a, b, c, d = (float(t) for t in esteig)
+        out = []
+        for L in self.levels[1:]:
+            v = np.random.default_rng(seed).standard_normal(L.n)
+            dv = self.ctx.vec(v)
+            L.zero_bc(dv)
+            H, m = L.arnoldi(steps, dv)
+            if m < 1:
+                raise AlfiHipError("chebyshev_bounds: the Arnoldi iteration broke down at once (zero operator?)")
+            ritz = np.linalg.eigvals(H[:m, :m]).real
+            lmin, lmax = float(ritz.min()), float(ritz.max())
+            out.append((a * lmin + b * lmax, c * lmin + d * lmax))
+        return out
+
+    def cg(self, b, x, rtol=1e-8, atol=0.0, max_it=200, full=False):
+        """CG with a zero initial guess and the unpreconditioned residual norm on the finest operator, preconditioned by one
+        cycle (``full``: the full cycle) per iteration (alfi_mg_cg).  Returns (iterations, recurrence residual norm)."""
+        its, rn = ctypes.c_int(), ctypes.c_double()
+        self.ctx.check(self.ctx.lib.alfi_mg_cg(self.h, b.ptr, x.ptr, float(rtol), float(atol), int(max_it), 1 if full else 0,
+                                               ctypes.byref(its), ctypes.byref(rn)))
+        return its.value, rn.value
 
     def close(self):
         if self.h:

@@ -8,7 +8,9 @@
 * ``mg_levels_solver`` / ``fieldsplit_0_mg``: the option dictionaries of ``get_parameters`` (solver.py:313-344, 359-379)
   with the PatchPC swapped for ``HipPatchPC``; ``fieldsplit_0_lu``: the exact velocity solve of solver_type allu
   (solver.py:346-352), the library's multifrontal factorisation of the finest operator.
-* ``HipMG``: drives PCMG (full or multiplicative V) + FGMRES(k) from such a dictionary -- the stand-in for PETSc when
+* ``graddiv_solver`` / ``HipCG``: the solver of the reference's grad-div experiment (examples/graddiv/graddiv.py:85-135): CG
+  preconditioned by one W-cycle with a Chebyshev(2) level smoother around the patch solves or point Jacobi.
+* ``HipMG``: drives PCMG (full or multiplicative V / W) + FGMRES(k) or Chebyshev(k) from such a dictionary -- the stand-in for PETSc when
   petsc4py is not importable (it is not, in this image).  One ``apply`` = what ``fieldsplit_0``'s Richardson(1)/PCMG
   does to a right-hand side.
 """
@@ -24,7 +26,7 @@ SUPPORTED_PATCH_KEYS = {
     "patch_pc_patch_statistics", "patch_pc_patch_symmetrise_sweep", "patch_pc_patch_precompute_element_tensors",
     "patch_pc_patch_construct_type", "patch_pc_patch_construct_dim", "patch_pc_patch_construct_python_type",
     "patch_pc_patch_sub_mat_type", "patch_pc_patch_dense_inverse", "patch_pc_patch_multiplicative",
-    "patch_sub_ksp_type", "patch_sub_pc_type", "patch_sub_pc_factor_mat_solver_type",
+    "patch_sub_ksp_type", "patch_sub_pc_type", "patch_sub_pc_factor_mat_solver_type", "patch_pc_patch_sub_pc_type",
 }
 
 
@@ -120,6 +122,108 @@ def fieldsplit_0_lu(use_mkl=False):
 def is_fieldsplit_0_lu(params):
     """Whether a fieldsplit_0 dictionary asks for the exact velocity solve (preonly + pc_type lu)."""
     return params.get("pc_type") == "lu" and params.get("ksp_type") == "preonly"
+
+
+def graddiv_solver(smoother="patch", patch="star"):
+    """The solver dictionary of the reference's grad-div experiment (examples/graddiv/graddiv.py:85-135), key for key, with
+    the ``mg_levels_`` keys nested under ``mg_levels`` and the PatchPC / MacroStar classes swapped for this package's: CG
+    (rtol 1e-8, at most 200 iterations, unpreconditioned norm) preconditioned by one PCMG W-cycle whose level smoother is
+    Chebyshev(2) around ``smoother`` = "patch" (additive ``patch`` = "star" or "macro" patches) or "jacobi"."""
+    sp = {
+        "mat_type": "aij",
+        "snes_type": "ksponly",
+        "ksp_type": "cg",
+        "ksp_rtol": 1e-8,
+        "ksp_atol": 0,
+        "ksp_max_it": 200,
+        "ksp_norm_type": "unpreconditioned",
+        "pc_type": "mg",
+        "pc_mg_cycle_type": "w",
+        "mg_coarse_ksp_type": "preonly",
+        "mg_coarse_pc_type": "python",
+        "mg_coarse_pc_python_type": "firedrake.AssembledPC",
+        "mg_coarse_assembled_pc_type": "lu",
+        "mg_coarse_assembled_pc_factor_mat_solver_type": "superlu_dist",
+    }
+    mgl = {"ksp_type": "chebyshev", "ksp_max_it": 2}
+    if smoother == "patch":
+        mgl.update({
+            "pc_type": "python",
+            "pc_python_type": "alfi_amd.HipPatchPC",
+            "patch_pc_patch_save_operators": True,
+            "patch_pc_patch_partition_of_unity": False,
+            "patch_pc_patch_multiplicative": False,
+            "patch_pc_patch_symmetrise_sweep": False,
+            "patch_sub_ksp_type": "preonly",
+            "patch_sub_pc_type": "lu",
+        })
+        if patch == "macro":
+            mgl.update({
+                "patch_pc_patch_construct_type": "python",
+                "patch_pc_patch_construct_python_type": "alfi_amd.MacroStar",
+                "patch_pc_patch_sub_mat_type": "aij",
+                "patch_pc_patch_sub_pc_type": "lu",
+                "patch_sub_pc_factor_mat_solver_type": "umfpack",
+            })
+        elif patch == "star":
+            mgl.update({
+                "patch_pc_patch_construct_type": "star",
+                "patch_pc_patch_construct_dim": 0,
+                "patch_pc_patch_sub_mat_type": "dense",
+            })
+        else:
+            raise NotImplementedError("Unknown patch type %s" % patch)
+    elif smoother == "jacobi":
+        mgl["pc_type"] = "jacobi"
+    else:
+        raise NotImplementedError("smoother %r (patch or jacobi; the reference's amg column is hypre)" % (smoother,))
+    sp["mg_levels"] = mgl
+    return sp
+
+
+BUILT_SMOOTHERS = ("fgmres", "chebyshev")
+
+
+def parse_mg_options(params):
+    """What ``HipMG`` reads from a ``pc_type mg`` dictionary, checked without touching a device: dict(smoother, k, pc, full,
+    cycle, esteig, esteig_steps, eigenvalues)."""
+    if params.get("pc_type") != "mg":
+        raise ValueError("expected the fieldsplit_0_mg dictionary (pc_type mg)")
+    mgl = params["mg_levels"]
+    ksp = mgl.get("ksp_type")
+    if ksp not in BUILT_SMOOTHERS:
+        raise NotImplementedError("level smoother ksp_type %r: built are %s" % (ksp, ", ".join(BUILT_SMOOTHERS)))
+    if ksp == "fgmres" and mgl.get("ksp_convergence_test") != "skip":
+        raise NotImplementedError("level smoother must be fgmres with convergence_test skip (solver.py:314-317)")
+    pc = mgl.get("pc_type")
+    if pc not in ("python", "jacobi"):
+        raise NotImplementedError("level pc_type must be python or jacobi")
+    cycle = str(params.get("pc_mg_cycle_type", "v")).lower()
+    if cycle not in ("v", "w"):
+        raise NotImplementedError("pc_mg_cycle_type %r (v or w)" % (cycle,))
+    out = {"smoother": ksp, "k": int(mgl["ksp_max_it"]), "pc": pc, "cycle": cycle,
+           "full": params.get("pc_mg_type", "multiplicative") == "full",
+           "esteig": None, "esteig_steps": None, "eigenvalues": None}
+    if ksp == "chebyshev":
+        def numbers(key, default, count):
+            text = str(mgl.get(key, default))
+            try:
+                vals = tuple(float(t) for t in text.split(","))
+            except ValueError:
+                raise ValueError("%s: %r is not a comma-separated list of numbers" % (key, text))
+            if len(vals) != count:
+                raise ValueError("%s: %r must hold %d numbers" % (key, text, count))
+            return vals
+        out["esteig"] = numbers("ksp_chebyshev_esteig", "0,0.1,0,1.1", 4)
+        out["esteig_steps"] = int(mgl.get("ksp_chebyshev_esteig_steps", 10))
+        if not 1 <= out["esteig_steps"] <= 30:
+            raise ValueError("ksp_chebyshev_esteig_steps %d not in 1..30" % out["esteig_steps"])
+        if mgl.get("ksp_chebyshev_eigenvalues") is not None:
+            emin, emax = numbers("ksp_chebyshev_eigenvalues", None, 2)
+            if not 0.0 < emin < emax:
+                raise ValueError("ksp_chebyshev_eigenvalues: need 0 < emin < emax, got %r" % (mgl["ksp_chebyshev_eigenvalues"],))
+            out["eigenvalues"] = (emin, emax)
+    return out
 
 
 def _resolve(dotted):
@@ -282,19 +386,19 @@ class HipPatchPC(object):
 
 
 class HipMG(object):
-    """PCMG + KSPFGMRES(k) driven by the reference's option dictionary (solver.py:359-379), device resident."""
+    """PCMG + KSPFGMRES(k) or KSPCHEBYSHEV(k) driven by the reference's option dictionary (solver.py:359-379,
+    examples/graddiv/graddiv.py:99-139), device resident.  ``mg_levels``: ``ksp_type`` fgmres | chebyshev with ``ksp_max_it``;
+    for chebyshev ``ksp_chebyshev_esteig`` ("a,b,c,d", default "0,0.1,0,1.1"), ``ksp_chebyshev_esteig_steps`` (default 10) or
+    ``ksp_chebyshev_eigenvalues`` ("emin,emax": no estimate is run); ``pc_type`` python (``pc_python_type``) | jacobi.
+    ``pc_mg_cycle_type`` v | w.  The Chebyshev intervals are estimated at construction and again by ``update``."""
 
     def __init__(self, ctx, levels, transfers, params, restriction=False, coarse_inv=None):
-        if params.get("pc_type") != "mg":
-            raise ValueError("expected the fieldsplit_0_mg dictionary (pc_type mg)")
+        self.opts = o = parse_mg_options(params)
         mgl = params["mg_levels"]
-        if mgl.get("ksp_type") != "fgmres" or mgl.get("ksp_convergence_test") != "skip":
-            raise NotImplementedError("level smoother must be fgmres with convergence_test skip (solver.py:314-317)")
-        if mgl.get("pc_type") != "python":
-            raise NotImplementedError("level pc_type must be python")
-        self.k = int(mgl["ksp_max_it"])
-        self.full = params.get("pc_mg_type", "multiplicative") == "full"
-        pc_cls = _resolve(mgl["pc_python_type"])
+        self.k = o["k"]
+        self.full = o["full"]
+        jacobi = o["pc"] == "jacobi"
+        pc_cls = None if jacobi else _resolve(mgl["pc_python_type"])
         self.ctx = ctx
         self.pcs, self.pc_objs = [], []
         dlevels = []
@@ -312,7 +416,7 @@ class HipMG(object):
                 self.pc_objs.append(None)
                 continue
             pc = PC(ctx, L, options=mgl)
-            obj = pc_cls()
+            obj = HipJacobiPC() if jacobi else pc_cls()
             obj.initialize(pc)
             self.pcs.append(pc)
             self.pc_objs.append(obj)
@@ -320,12 +424,27 @@ class HipMG(object):
         self.mg = hip.Multigrid.__new__(hip.Multigrid)
         hip.Multigrid._from_device_levels(self.mg, ctx, dlevels, transfers, self.k, restriction)
         self.n = levels[-1].n
+        if o["cycle"] != "v":
+            self.mg.set_cycle_type(o["cycle"])
+        self.bounds = None
+        if o["smoother"] == "chebyshev":
+            self._set_chebyshev()
+
+    def _set_chebyshev(self):
+        o = self.opts
+        if o["eigenvalues"] is not None:
+            self.bounds = [o["eigenvalues"]] * (len(self.mg.levels) - 1)
+        else:
+            self.bounds = self.mg.chebyshev_bounds(o["esteig_steps"], o["esteig"])
+        self.mg.set_smoother("chebyshev", self.bounds)
 
     def update(self, levels):
         for pc, obj, L in zip(self.pcs, self.pc_objs, levels):
             if obj is not None:
                 pc.level_data = L
                 obj.update(pc)
+        if self.opts["smoother"] == "chebyshev":       # the intervals belong to the old operators and patch factors
+            self._set_chebyshev()
 
     def apply(self, b, x):
         """x <- PCMG(b): one full cycle (pc_mg_type full) or one V-cycle from a zero initial guess."""
@@ -338,6 +457,84 @@ class HipMG(object):
             self.mg.vcycle(db, dx)
         if xwb is not None:
             xwb[:] = dx.get()
+
+
+class HipJacobiPC(object):
+    """``pc_type jacobi`` on a level (examples/graddiv/graddiv.py:137-139) behind the same protocol: y = x / diag(A), y = x on
+    Dirichlet dofs.  No patches, no factorisation."""
+
+    def initialize(self, pc):
+        L = pc.level_data
+        self.level = hip.Level(pc.ctx, L.A, L.bc_dofs)
+        self.level.set_jacobi(True)
+        self.n = L.n
+
+    def update(self, pc):
+        self.level.update_values(pc.level_data.A.vals)
+
+    def apply(self, pc, x, y):
+        dx, _ = _as_device(pc.ctx, x, self.n)
+        dy, ywb = _as_device(pc.ctx, y, self.n)
+        self.level.patch_apply(dx, dy)
+        if ywb is not None:
+            ywb[:] = dy.get()
+
+    def applyTranspose(self, pc, x, y):
+        self.apply(pc, x, y)
+
+
+class HipCG(object):
+    """The reference's grad-div solve on the GPU (examples/graddiv/graddiv.py:85-135, 155-172): KSPCG with a zero initial
+    guess and the unpreconditioned norm around one PCMG cycle (``HipMG``), driven by the ``graddiv_solver`` dictionary.
+    ``transfer``: the Schoeberl prolongation and restriction (the reference's ``--transfer``); False: the plain nodal
+    (bubble-corrected in 3-D) prolongation P and its transpose -- the same device transfer with gamma = 0 in its interior
+    solves, which makes both directions exactly P and P^T (the non-robust restriction would be the transpose of the PLAIN
+    nodal interpolation, which differs from P^T for the bubble-corrected 3-D pair and would leave CG an unsymmetric
+    preconditioner).  ``solve(b) -> (x, iterations, residual norm)``; iterations =
+    ``ksp_max_it`` means the solve did not converge."""
+
+    def __init__(self, ctx, levels, transfers, params, transfer=True):
+        if params.get("ksp_type") != "cg" or params.get("ksp_norm_type", "unpreconditioned") != "unpreconditioned":
+            raise NotImplementedError("outer solver must be cg with the unpreconditioned norm (graddiv.py:88, 94)")
+        self.ctx, self.transfer = ctx, bool(transfer)
+        self.rtol, self.atol = float(params.get("ksp_rtol", 1e-5)), float(params.get("ksp_atol", 1e-50))
+        self.max_it = int(params.get("ksp_max_it", 10000))
+        self.hmg = HipMG(ctx, levels, transfers, params, restriction=True)
+        self.mg = self.hmg.mg
+        self._transfers = list(transfers)
+        self._plain_transfers()
+        self.n = levels[-1].n
+        self._b, self._x = ctx.vec(self.n), ctx.vec(self.n)
+
+    def _plain_transfers(self):
+        # prolong (I - gamma E inv(A_II) E^T D) P and restrict P^T (I - gamma D E inv(A_II) E^T) at gamma = 0: P and P^T
+        if not self.transfer:
+            for dt, T in zip(self.mg.transfers, self._transfers):
+                dt.update(T.nu, 0.0)
+
+    def update(self, levels, transfers=None):
+        """New operator values on every level (a new gamma): patch factors, Chebyshev intervals and -- with ``transfers``, the
+        new TransferData -- the interior solves of the Schoeberl transfer."""
+        if transfers is not None:
+            self._transfers = list(transfers)
+            for dt, T in zip(self.mg.transfers, self._transfers):
+                dt.update(T.nu, T.gamma if self.transfer else 0.0)
+        L0 = self.mg.levels[0]
+        L0.update_values(levels[0].A.vals)
+        L0.coarse_factor_auto()
+        self.hmg.update(levels)
+
+    def solve(self, b, x=None):
+        self._b.set(np.asarray(b, dtype=np.float64))
+        its, rn = self.mg.cg(self._b, self._x, self.rtol, self.atol, self.max_it, full=self.hmg.full)
+        out = self._x.get()
+        if x is not None:
+            x[:] = out
+            out = x
+        return out, its, rn
+
+    def close(self):
+        self.mg.close()
 
 
 class DGMassInv(object):

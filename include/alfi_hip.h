@@ -322,6 +322,24 @@ int alfi_patch_get_inverse(alfi_level* lvl, int64_t p, double* out_host);
  * place; nonzero_guess = 0 treats the incoming x as zero.  Entirely device-resident (no host synchronisation). */
 int alfi_smooth_fgmres(alfi_level* lvl, int k, const double* db, double* dx, int nonzero_guess);
 
+/* ---- level smoother: PETSc KSPCHEBYSHEV + point Jacobi, examples/graddiv/graddiv.py:109-110, 137-139 ------------------ */
+/* pc_type jacobi: on != 0 makes the level's preconditioner application y_i = x_i / A_ii (y = x on Dirichlet dofs; a zero
+ * diagonal entry counts as 1, as in PCJacobi) instead of the patch solves -- for alfi_patch_apply and every smoother of the
+ * level.  The scalar diagonal is taken from the diagonal blocks of the operator and taken again whenever the operator values
+ * have changed.  Such a level needs no patches and no factorisation to be cycle-ready.  Serial levels only (ALFI_E_ARG). */
+int alfi_level_set_jacobi(alfi_level* lvl, int on);
+/* k steps of the Chebyshev iteration for the interval [emin, emax] on the preconditioned operator M A (M = alfi_patch_apply):
+ * the error is multiplied by T_k((theta - M A) / delta) / T_k(theta / delta), theta = (emax + emin) / 2, delta = (emax -
+ * emin) / 2 (Saad, Alg. 12.1).  Per step one residual, one preconditioner application and one fused update
+ * d <- a d + c z, x <- x + d; no inner product, no norm, no host synchronisation.  x is updated in place; nonzero_guess = 0
+ * treats the incoming x as zero.  ALFI_E_ARG for k < 1, emin <= 0, emax <= emin or a partitioned level (x untouched). */
+int alfi_smooth_chebyshev(alfi_level* lvl, int k, double emin, double emax, const double* db, double* dx, int nonzero_guess);
+/* m <= 30 Arnoldi steps (classical Gram-Schmidt) on M A from the device vector dv0: the (m + 1) x m Hessenberg matrix, row-major,
+ * in host memory; *m_done < m on breakdown (the columns from m_done on are zero).  The eigenvalues of its leading m_done x m_done
+ * block estimate the spectrum the Chebyshev interval is set from (KSPChebyshevEstEigSet).  Set-up code: it allocates, and
+ * synchronises once at the end.  Serial levels only (ALFI_E_ARG). */
+int alfi_level_arnoldi(alfi_level* lvl, int m, const double* dv0, double* H_host, int* m_done);
+
 /* ---- coarse solve: firedrake.AssembledPC + LU [3P], alfi/solver.py:369-378 ---------------------------------------- */
 /* alfi_coarse_factor: the level operator's dense inverse (n x n doubles on the device, n <= 131072) by the library's own
  * blocked Gauss-Jordan on the FP64 matrix cores (64-wide pivot blocks, rank-64 trailing updates as v_mfma_f64_16x16x4,
@@ -389,9 +407,28 @@ int alfi_mg_destroy(alfi_mg* mg);
 int alfi_mg_vcycle(alfi_mg* mg, const double* db, double* dx);
 /* pc_mg_type full (solver.py:366): x <- F(b), x need not be initialised (PCMGFCycle_Private) */
 int alfi_mg_fcycle(alfi_mg* mg, const double* db, double* dx);
+/* The level smoother of every cycle of mg: ALFI_SMOOTHER_FGMRES (default, alfi_smooth_fgmres) or ALFI_SMOOTHER_CHEBYSHEV
+ * (alfi_smooth_chebyshev) with the interval [emin_host[l-1], emax_host[l-1]] on level l = 1 .. nlevels-1; the number of steps
+ * stays the k of alfi_mg_create.  The intervals belong to the operators and patch factors they were estimated from.
+ * Chebyshev: serial levels only (ALFI_E_ARG). */
+#define ALFI_SMOOTHER_FGMRES 0
+#define ALFI_SMOOTHER_CHEBYSHEV 1
+int alfi_mg_set_smoother(alfi_mg* mg, int type, const double* emin_host, const double* emax_host);
+/* PCMGSetCycleType: cycles = 1 V-cycle (default), 2 W-cycle.  In PCMGMCycle_Private level 1 visits the coarse solve once and
+ * every level >= 2 recurses `cycles` times on the same restricted right-hand side, continuing from the previous coarse
+ * iterate.  alfi_mg_vcycle and the V-cycles inside alfi_mg_fcycle become that cycle.  W: serial levels only (ALFI_E_ARG). */
+int alfi_mg_set_cycles(alfi_mg* mg, int cycles);
+/* KSPCG with a zero initial guess and ksp_norm_type unpreconditioned (examples/graddiv/graddiv.py:85-95), preconditioned by one
+ * cycle of mg per iteration (full != 0: alfi_mg_fcycle, else alfi_mg_vcycle from a zero iterate) on the finest level's
+ * operator: stops when ||r|| <= max(rtol ||b||, atol) or after max_it iterations; *iterations and the recurrence residual norm
+ * come back.  The step lengths are formed on the device; one scalar (|r|^2) is read back per iteration.  db, dx: distinct
+ * device vectors of the finest level's length.  Serial levels only (ALFI_E_ARG). */
+int alfi_mg_cg(alfi_mg* mg, const double* db, double* dx, double rtol, double atol, int max_it, int full, int* iterations,
+               double* residual_norm);
 /* on != 0: alfi_mg_vcycle / alfi_mg_fcycle replay their launch sequence as a hipGraph from the second call with the same
  * (db, dx) pair on (the small levels of a hierarchy are launch-bound).  New operator values in place need no new capture;
- * new (nu, gamma), patches, coarse inverse or smoother length re-capture.  Runs with profiling on or on partitioned
+ * new (nu, gamma), patches, coarse inverse, smoother length, smoother type, Chebyshev interval, Jacobi switch or cycle count
+ * re-capture (W-cycles are captured like V-cycles).  Runs with profiling on or on partitioned
  * levels stay eager. */
 int alfi_ctx_set_graph(alfi_ctx* ctx, int on);
 
