@@ -9,7 +9,7 @@ The wind is the state itself, so the Newton linearisation (UFL differentiates th
 
     DR_B[du](v) = c_F beta_F int_F J(du).J(v)  +  c_F (|F|^-1 int_F u.du / sqrt(u.u + 1e-10)) int_F J(u).J(v).
 
-Per facet the union of the two cells' nodes (9 for [P2]^2, 30 for [P3]^3; K+'s nodes first) carries the jumps of the
+Per facet the union of the two cells' nodes (9 for [P2]^2, 16 for [P3]^2, 30 for [P3]^3; K+'s nodes first) carries the jumps of the
 normal derivatives at the points of an EXACT facet rule (S_F = int_F [d_n phi_a][d_n phi_b] is a polynomial of degree
 2(k-1) on F: n = k points per direction); beta_F and the derivative weights m_(b,j) = |F|^-1 int_F phi_b u_j / sqrt(u.u +
 1e-10) are not polynomial and use the rule NONLINEAR_RULE below (degree 2k + 2, UFL's estimate for sqrt of a degree-2k

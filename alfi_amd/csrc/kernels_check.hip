@@ -121,6 +121,17 @@ __global__ __launch_bounds__(256) void patch_check_kernel(const int32_t* __restr
 // A x_j = e_j column by column through the LU factors is backward stable per column: cond(A) eps.)
 // DENSE: the matrix is not gathered from the level operator but copied from ``dense`` (row-major, leading dimension
 // ``dense_ld``) -- the Schur complement of a condensed patch (patch_ptr = CondDev::sptr, inv = CondDev::sinv).
+// fc (a Burman level, fc.ptr != NULL): the patch matrix is A[P, P] minus the facet terms PCPATCH leaves out, as in
+// patch_facet_correct_kernel and patch_check_kernel -- a thread per patch row subtracts its entries after the gather.
+struct RepairFacetRule {
+  const int64_t* ptr = nullptr;
+  const int32_t* col = nullptr;
+  const int32_t* fac = nullptr;
+  const double* s = nullptr;
+  const double* beta = nullptr;
+  double scale = 0.0;
+};
+
 template <int BS, bool DENSE>
 __global__ __launch_bounds__(256) void patch_repair_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
                                                             const double* __restrict__ vals, int flat,
@@ -129,7 +140,8 @@ __global__ __launch_bounds__(256) void patch_repair_kernel(const int32_t* __rest
                                                             const int64_t* __restrict__ inv_ptr, double* __restrict__ inv,
                                                             const int32_t* __restrict__ list, double* __restrict__ scratch,
                                                             int64_t scratch_stride, int* __restrict__ status,
-                                                            const double* __restrict__ dense, int dense_ld) {
+                                                            const double* __restrict__ dense, int dense_ld,
+                                                            RepairFacetRule fc) {
   extern __shared__ unsigned char smem[];
   const int64_t p = list[blockIdx.x];
   const int64_t off = patch_ptr[p];
@@ -166,6 +178,16 @@ __global__ __launch_bounds__(256) void patch_repair_kernel(const int32_t* __rest
     }
   }
   __syncthreads();
+  if (!DENSE && fc.ptr) {
+    for (int r = tid; r < n; r += 256) {
+      const int64_t rn = off / BS + r / BS;
+      for (int64_t q = fc.ptr[rn]; q < fc.ptr[rn + 1]; ++q) {
+        const int c = fc.col[q] * BS + r % BS;
+        if (c < n) W[(int64_t)r * n + c] -= fc.scale * fc.beta[fc.fac[q]] * fc.s[q];
+      }
+    }
+    __syncthreads();
+  }
   // ---- P A = L U
   for (int k = 0; k < n; ++k) {
     // pivot search: largest |W[i][k]|, i >= k (ties: smallest i)
@@ -338,7 +360,7 @@ static int cond_repair(alfi_level* L, double tol, int nflag, double worst) {
     const int Np = (sp + 63) / 64 * 64;              // the padded leading dimension of the setup's Schur scratch (BIG_NB)
     hipLaunchKernelGGL((patch_repair_kernel<3, true>), dim3(1), dim3(256), lds, ctx->stream, (const int32_t*)nullptr,
                        (const int32_t*)nullptr, (const double*)nullptr, 0, L->cd.sptr, (const int32_t*)nullptr, L->cd.sinv_ptr,
-                       L->cd.sinv, L->chk_list + i, scratch, (int64_t)0, L->status, (const double*)sig, Np);
+                       L->cd.sinv, L->chk_list + i, scratch, (int64_t)0, L->status, (const double*)sig, Np, RepairFacetRule{});
     if (hipGetLastError() != hipSuccess) rc = alfi_set_error(ctx, ALFI_E_HIP, "patch_repair_kernel launch failed");
   }
   int st = 0;
@@ -394,9 +416,9 @@ int patch_verify_and_repair(alfi_level* L, int unpivoted_status) {
                           (long long)L->npatch, worst);
   constexpr int REPAIR_MAX_NP = PATCH_MAX;     // (a 2000-dof patch takes ~0.5 s of one workgroup: a rare-path safety net)
   if (L->cond) return cond_repair(L, tol, nflag, worst);
-  if (L->fc_ptr && L->fc_scale != 0.0)
-    return alfi_set_error(ctx, ALFI_E_SINGULAR, "%d patch inverses of a Burman level fail the residual probe (worst %.3e): the "
-                          "pivoted repair does not apply the PCPATCH facet rule", nflag, worst);
+  // a Burman level: the repair subtracts the facet terms PCPATCH leaves out from the gathered matrix (RepairFacetRule)
+  RepairFacetRule fc;
+  if (L->fc_ptr && L->fc_scale != 0.0) fc = RepairFacetRule{L->fc_ptr, L->fc_col, L->fc_fac, L->fc_s, L->fc_beta, L->fc_scale};
   if (L->max_np > REPAIR_MAX_NP)
     return alfi_set_error(ctx, ALFI_E_SINGULAR, "%d patch inverses fail the residual probe (worst %.3e) and the pivoted "
                           "repair handles patches of at most %d dofs", nflag, worst, (int)REPAIR_MAX_NP);
@@ -421,11 +443,11 @@ int patch_verify_and_repair(alfi_level* L, int unpivoted_status) {
     if (L->bs == 2)
       hipLaunchKernelGGL((patch_repair_kernel<2, false>), grid, block, lds, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals,
                          L->A.flat, L->patch_ptr, L->patch_dofs, L->inv_ptr, L->inv, L->chk_list + b0, scratch, stride,
-                         L->status, (const double*)nullptr, 0);
+                         L->status, (const double*)nullptr, 0, fc);
     else
       hipLaunchKernelGGL((patch_repair_kernel<3, false>), grid, block, lds, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals,
                          L->A.flat, L->patch_ptr, L->patch_dofs, L->inv_ptr, L->inv, L->chk_list + b0, scratch, stride,
-                         L->status, (const double*)nullptr, 0);
+                         L->status, (const double*)nullptr, 0, fc);
     if (hipGetLastError() != hipSuccess) rc = alfi_set_error(ctx, ALFI_E_HIP, "patch_repair_kernel launch failed");
   }
   int st = 0;

@@ -55,8 +55,9 @@ class NodalElement(object):
             assert dim == 3, "FacetBubble enrichment is only needed for k < tdim in 3-D here"
         if degree == 3:
             # the velocity element of the reference's 3-D Scott-Vogelius pair (solver.py:625-630, config 5): 4 vertex,
-            # 12 edge (two per edge, at 1/3 and 2/3) and 4 face nodes; no cell-interior node in 3-D
-            assert dim == 3 and not bubble, "P3 is provided for tetrahedra (the 2-D pairs of the reference use k = 2)"
+            # 12 edge (two per edge, at 1/3 and 2/3) and 4 face nodes; no cell-interior node in 3-D.  On triangles (the k = 3
+            # lines of the reference's iters2dsv target): 3 vertex, 6 edge nodes and ONE node at the cell's barycentre
+            assert not bubble, "P3 is a plain Lagrange element here (no FacetBubble enrichment)"
         self.dim, self.degree, self.bubble = dim, degree, bubble
         self.name = "P%d%s" % (degree, "+FB" if bubble else "")
         nv = dim + 1
@@ -71,17 +72,21 @@ class NodalElement(object):
                 t = (sub + 1.0) / (self.nodes_per_edge + 1.0)
                 p[a], p[b] = 1.0 - t, t
                 bary.append(p)
-        if bubble or degree == 3:
+        if dim == 3 and (bubble or degree == 3):
             for i in range(4):
                 ent.append((2, i, 0))
                 p = np.full(4, 1.0 / 3.0)
                 p[i] = 0.0
                 bary.append(p)
+        if dim == 2 and degree == 3:
+            ent.append((2, 0, 0))                   # entity dimension 2 = the cell itself in 2-D
+            bary.append(np.full(3, 1.0 / 3.0))
         self.entity_nodes = ent                     # (entity dim, local entity number, sub-index on the entity) per node
         self.node_bary = np.array(bary)             # (nloc, dim+1)
         self.nloc = len(ent)
         self.has_edge_nodes = degree >= 2
-        self.has_face_nodes = bubble or degree == 3
+        self.has_face_nodes = dim == 3 and (bubble or degree == 3)
+        self.has_cell_nodes = dim == 2 and degree == 3      # nodes in the cell interior (faces stay "faces" of tetrahedra)
         if bubble:
             fb = self.node_bary[-4:]
             phi, _ = self._primal(fb)               # (4 faces, nprimal)
@@ -110,10 +115,11 @@ class NodalElement(object):
 
     def _p3(self, lam):
         """Cubic Lagrange basis on equispaced nodes: vertices 1/2 l (3l - 1)(3l - 2); edge (a, b) node nearer a:
-        9/2 la lb (3 la - 1), nearer b: 9/2 la lb (3 lb - 1); face (i, j, k): 27 li lj lk."""
+        9/2 la lb (3 la - 1), nearer b: 9/2 la lb (3 lb - 1); face (i, j, k): 27 li lj lk -- four of them on a
+        tetrahedron, the one cell bubble 27 l0 l1 l2 on a triangle."""
         npts, nv = lam.shape
         ne = self.local_edges.shape[0]
-        n = nv + 2 * ne + 4
+        n = nv + 2 * ne + (4 if nv == 4 else 1)
         phi = np.empty((npts, n))
         dphi = np.zeros((npts, n, nv))
         for i in range(nv):
@@ -129,6 +135,11 @@ class NodalElement(object):
             phi[:, k1] = 4.5 * la * lb * (3 * lb - 1)
             dphi[:, k1, a] = 4.5 * lb * (3 * lb - 1)
             dphi[:, k1, b] = 4.5 * la * (6 * lb - 1)
+        if nv == 3:
+            l0, l1, l2 = lam[:, 0], lam[:, 1], lam[:, 2]
+            phi[:, -1] = 27 * l0 * l1 * l2
+            dphi[:, -1, 0], dphi[:, -1, 1], dphi[:, -1, 2] = 27 * l1 * l2, 27 * l0 * l2, 27 * l0 * l1
+            return phi, dphi
         beta, dbeta = self._bubbles(lam)
         phi[:, nv + 2 * ne:] = beta
         dphi[:, nv + 2 * ne:, :] = dbeta

@@ -60,7 +60,8 @@ class VectorFunctionSpace(object):
         nv, ne, nf = mesh.num_vertices, mesh.num_edges, mesh.num_faces
         npe = getattr(element, "nodes_per_edge", 1 if element.has_edge_nodes else 0)
         self.nodes_per_edge = npe
-        sizes = [nv, ne * npe, nf if element.has_face_nodes else 0]
+        cell_nodes_ = getattr(element, "has_cell_nodes", False)      # a fourth group: one node per cell, at its barycentre
+        sizes = [nv, ne * npe, nf if element.has_face_nodes else 0, mesh.num_cells if cell_nodes_ else 0]
         self.raw_offsets = np.concatenate([[0], np.cumsum(sizes)])
         self.num_nodes = int(self.raw_offsets[-1])
         pos = [mesh.coords]
@@ -71,6 +72,8 @@ class VectorFunctionSpace(object):
             pos.append((x0[:, None, :] + t[None, :, None] * (x1 - x0)[:, None, :]).reshape(-1, mesh.dim))
         if element.has_face_nodes:
             pos.append(mesh.coords[mesh.faces].mean(axis=1))
+        if cell_nodes_:
+            pos.append(mesh.coords[mesh.cells].mean(axis=1))
         pos = np.concatenate(pos)
         if reorder:
             order = morton_order(pos)                      # new -> raw
@@ -91,6 +94,8 @@ class VectorFunctionSpace(object):
                 same = mesh.cells[:, a] < mesh.cells[:, b]
                 s_glob = np.where(same, sub, npe - 1 - sub)
                 cols.append(self.raw_offsets[1] + mesh.cell_edges[:, loc].astype(np.int64) * npe + s_glob)
+            elif edim == self.dim:
+                cols.append(self.raw_offsets[3] + np.arange(mesh.num_cells, dtype=np.int64))
             else:
                 cols.append(self.raw_offsets[2] + mesh.cell_faces[:, loc])
         self.cell_nodes = np.ascontiguousarray(self.raw2new[np.stack(cols, axis=1)], dtype=np.int32)
@@ -101,6 +106,8 @@ class VectorFunctionSpace(object):
             en = self.raw2new[self.raw_offsets[1]:self.raw_offsets[2]]
             self.edge_nodes = en if npe == 1 else en.reshape(ne, npe)
         self.face_nodes = self.raw2new[self.raw_offsets[2]:self.raw_offsets[3]] if element.has_face_nodes else None
+        # cell_interior_nodes[c]: the node at the barycentre of cell c (never on the boundary, hence never Dirichlet)
+        self.cell_interior_nodes = self.raw2new[self.raw_offsets[3]:self.raw_offsets[4]] if cell_nodes_ else None
         # Dirichlet nodes: the whole boundary (ldc2d.py:22-25, ldc3d.py:17-20) unless ``dirichlet`` (a callable on the
         # boundary facet centroids) selects a part of it (bfs3d.py:23-26: inflow and walls, the outflow stays natural)
         vm, em, fm = mesh.boundary_entities(dirichlet)
@@ -146,6 +153,11 @@ class VectorFunctionSpace(object):
             for j in range(3):
                 seed.append(m.faces[:, j].astype(np.int64))
                 node.append(self.face_nodes.astype(np.int64))
+        if self.cell_interior_nodes is not None:
+            # the star of a vertex holds its cells: PCPATCH keeps the dofs in their interiors
+            for j in range(self.dim + 1):
+                seed.append(m.cells[:, j].astype(np.int64))
+                node.append(self.cell_interior_nodes.astype(np.int64))
         seed, node = np.concatenate(seed), np.concatenate(node)
         keep = ~self.bc_node_mask[node]
         if seeds is not None:
@@ -301,6 +313,8 @@ def skeleton_node_mask(Vf):
         mask[Vf.edge_nodes] = coarse_support_size(m, m.edges) <= m.dim
     if Vf.element.has_face_nodes:
         mask[Vf.face_nodes] = coarse_support_size(m, m.faces) <= m.dim
+    if getattr(Vf, "cell_interior_nodes", None) is not None:
+        mask[Vf.cell_interior_nodes] = False        # inside a fine cell, hence inside one coarse cell
     return mask
 
 

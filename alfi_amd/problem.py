@@ -305,6 +305,11 @@ def build_hierarchy(problem, nref, k, Re, gamma=1e4, advect=True, patches=True, 
     device (alfi_level_assemble; HipNavierStokesSolver does, every Newton step) and has no use for a host copy."""
     t0 = time.time()
     dim = problem.dim
+    if dim == 2 and k == 3:
+        # (before this the element constructor refused P3 on triangles with an AssertionError)
+        raise NotImplementedError("[P3]^2-P0 on the uniform hierarchy: the cubic triangle is built for the Scott-Vogelius pair "
+                                  "(discretisation='sv') only -- no SUPG kernels for it, and its thirds are not nodes of the "
+                                  "refined space, so inject is not a nodal map")
     element = velocity_element(dim, k)
     mh = problem.mesh_hierarchy("uniform", nref)
     nu = problem.char_length() * problem.char_velocity() / Re if Re > 0 else problem.char_length() * problem.char_velocity()

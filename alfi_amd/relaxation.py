@@ -293,7 +293,10 @@ def patch_points_to_dofs(V, dm, patches):
         nodes = []
         for p in np.unique(pts):
             p = int(p)
-            if dm.vStart <= p < dm.eStart:
+            if p < dm.vStart:
+                if V.cell_interior_nodes is not None:
+                    nodes.append(int(V.cell_interior_nodes[p]))
+            elif dm.vStart <= p < dm.eStart:
                 nodes.append(int(V.vertex_nodes[p - dm.vStart]))
             elif dm.eStart <= p < dm.fStart and V.element.has_edge_nodes:
                 nodes.extend(int(q) for q in np.atleast_1d(V.edge_nodes[p - dm.eStart]))

@@ -8,8 +8,9 @@ the levels are not nested, only their macro meshes are), ``SVSchoeberlTransfer``
 ``prolong`` as the standard transfer (transfer.py:284-290).
 
 Everything here is host-side input generation (the role Firedrake plays for the reference); the arithmetic of smoother,
-transfers and cycles is the same libalfi_hip.so entry points as for the PkP0 discretisation.  Implemented for k = 2 and,
-in 3-D, k = 3 (the inf-sup stable pair of config 5: macro stars of up to ~1600 dofs, macro-cell transfer blocks of 390).
+transfers and cycles is the same libalfi_hip.so entry points as for the PkP0 discretisation.  Implemented for k = 2 and
+k = 3 (3-D: the inf-sup stable pair of config 5, macro stars of up to ~1600 dofs, macro-cell transfer blocks of 390; 2-D:
+cubic triangles with one node in every cell, macro stars of 146 dofs at a 6-valent vertex, transfer blocks of 92).
 """
 
 import numpy as np
@@ -56,7 +57,8 @@ def macro_star_patches_fast(V):
     points of C(v) that are not macro vertices, i.e. in terms of the entities that carry nodes
       vertices:  v and the non-macro vertices (macro-cell barycentres) of C(v);
       edges:     the edges of C(v) and the edges holding one of those barycentres;
-      faces:     the faces of C(v), the faces holding an edge of C(v), the faces holding one of those barycentres.
+      faces:     the faces of C(v), the faces holding an edge of C(v), the faces holding one of those barycentres;
+      cells:     the cells holding v or one of those barycentres, i.e. the children of the macro cells holding v.
     tests/test_sv.py checks equality with the literal constructor patch by patch (2-D and 3-D)."""
     import scipy.sparse as sp
     mesh, d = V.mesh, V.dim
@@ -90,6 +92,9 @@ def macro_star_patches_fast(V):
             fe.append(order[np.searchsorted(ekey[order], lo * nv + hi)])
         Mfe = inc(np.repeat(np.arange(nf), 3), np.stack(fe, axis=1).ravel(), (nf, ne))
         F = (Mfc @ Cv + Mfe @ Ec + Mfv @ Bv).tocsc()
+    Cc = None
+    if V.cell_interior_nodes is not None:
+        Cc = (Cv + Mvc.T.tocsr() @ Bv).tocsc()
     en = None if V.edge_nodes is None else np.asarray(V.edge_nodes, dtype=np.int64).reshape(ne, -1)
     ptr, dofs, seeds = [0], [], []
     comp = np.arange(d, dtype=np.int64)
@@ -100,6 +105,8 @@ def macro_star_patches_fast(V):
             nodes.append(en[E.indices[E.indptr[j]:E.indptr[j + 1]]].ravel())
         if F is not None:
             nodes.append(V.face_nodes[F.indices[F.indptr[j]:F.indptr[j + 1]]].astype(np.int64))
+        if Cc is not None:
+            nodes.append(V.cell_interior_nodes[Cc.indices[Cc.indptr[j]:Cc.indptr[j + 1]]].astype(np.int64))
         nodes = np.unique(np.concatenate(nodes))
         nodes = nodes[~V.bc_node_mask[nodes]]
         if nodes.size == 0:
@@ -341,8 +348,9 @@ def build_sv_hierarchy(problem, nref, k, Re, gamma=1e4, advect=True, patches=Tru
     groups (a facet of the macro skeleton couples the interiors of two macro cells).  The transfers keep the CELL graph:
     SVSchoeberlTransfer.form has no stabilisation (transfer.py:295-299).  Off: bit for bit the hierarchy without it."""
     dim = problem.dim
-    if k not in (2, 3) or (k == 3 and dim != 3):
-        raise NotImplementedError("Scott-Vogelius velocities: [P2]^d, and [P3]^3 (the inf-sup stable 3-D pair of config 5)")
+    if k not in (2, 3):
+        raise NotImplementedError("Scott-Vogelius velocities: [P2]^d and [P3]^d (k = 3: the cubic lines of the reference's "
+                                  "iters2dsv target and the inf-sup stable 3-D pair of config 5)")
     element = NodalElement(dim, k, False)
     mh = [bary_refine(m) for m in mesh_hierarchy(problem.mesh(), nref)]
     nu = problem.char_length() * problem.char_velocity() / Re if Re > 0 else problem.char_length() * problem.char_velocity()
