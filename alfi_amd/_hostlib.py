@@ -46,6 +46,7 @@ def lib():
         _lib.alfi_host_supg.restype = ctypes.c_int
         _lib.alfi_host_gls.restype = ctypes.c_int
         _lib.alfi_host_burman.restype = ctypes.c_int
+        _lib.alfi_host_find_groups.restype = ctypes.c_int64
         nthr = env.host_threads() or cpu_share()
         _lib.alfi_host_set_num_threads(ctypes.c_int(nthr))
     return _lib
@@ -53,6 +54,19 @@ def lib():
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def find_groups(bs, rowptr, colidx, patch_ptr, patch_dofs):
+    """Group labels for condensed patch factors from the block sparsity alone (csrc/find_groups.h, the rule of
+    alfi_patches_find_groups): one label per entry of ``patch_dofs``, -1 = skeleton."""
+    rp = np.ascontiguousarray(rowptr, dtype=np.int32)
+    ci = np.ascontiguousarray(colidx, dtype=np.int32)
+    pp = np.ascontiguousarray(patch_ptr, dtype=np.int64)
+    pd = np.ascontiguousarray(patch_dofs, dtype=np.int32)
+    out = np.empty(len(pd), dtype=np.int32)
+    lib().alfi_host_find_groups(ctypes.c_int(bs), ctypes.c_int64(len(rp) - 1), ctypes.c_int64(len(pp) - 1), _p(pp), _p(pd),
+                                _p(rp), _p(ci), _p(out))
+    return out
 
 
 def node_graph(cell_nodes, nnode):

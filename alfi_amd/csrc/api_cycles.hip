@@ -566,6 +566,8 @@ static void cycle_signature(alfi_mg* mg, std::vector<uint64_t>* sig) {
     push(L->cheb_d);
     push(L->A.vals);
     push(L->inv);
+    push(L->cd.mat);
+    push(L->cd.sinv);
     push(L->patch_ptr);
     push(L->patch_dofs);
     push(L->cinv);

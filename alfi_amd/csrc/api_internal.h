@@ -60,6 +60,8 @@ inline bool level_pc_ready(const alfi_level* L) { return L->factored || L->jacob
 inline bool level_is_partitioned(const alfi_level* L) { return L->distributed || L->has_halo || L->n_own != L->n; }
 // api_patches.hip
 void free_mult_schedule(alfi_level* L);
+// a level that condensed itself goes back to dense inverses for good (api_patches.hip); true: it was factored, factor it again
+bool auto_cond_to_dense(alfi_level* L);
 // api_smoother.hip
 int ensure_fgmres_workspace(alfi_level* L, int k);
 int ensure_cheb_workspace(alfi_level* L);

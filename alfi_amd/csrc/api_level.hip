@@ -722,6 +722,9 @@ int alfi_patches_set_facet_correction(alfi_level* L, int64_t nfacet, int64_t nro
   }
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  // the facet rule changes the patch matrices and belongs to levels whose sparsity couples macro interiors: a level that
+  // condensed itself at an earlier factorisation goes back to dense inverses (and is factored again below)
+  const bool refactor = auto_cond_to_dense(L);
   dev_free(L->fc_ptr); dev_free(L->fc_col); dev_free(L->fc_fac); dev_free(L->fc_s); dev_free(L->fc_beta);
   L->fc_ptr = nullptr; L->fc_col = nullptr; L->fc_fac = nullptr; L->fc_s = nullptr; L->fc_beta = nullptr;
   int rc = dev_upload(ctx, &L->fc_ptr, ptr, nrow + 1);
@@ -733,6 +736,7 @@ int alfi_patches_set_facet_correction(alfi_level* L, int64_t nfacet, int64_t nro
   ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->fc_beta, 0, sizeof(double) * (size_t)std::max<int64_t>(nfacet, 1), ctx->stream));
   L->fc_nfacet = nfacet;
   L->fc_scale = 0.0;
+  if (refactor) ALFI_CHECK(alfi_patches_factor(L));
   return rc;
 }
 

@@ -2,6 +2,7 @@
 // (One file per concern since round 5: api_ctx / api_level / api_patches / api_smoother / api_cycles / api_saddle; the helpers they
 // share are declared in api_internal.h.)
 #include "api_internal.h"
+#include "find_groups.h"
 
 // ---- patches -------------------------------------------------------------------------------------------------------------
 int alfi_patches_set(alfi_level* L, int64_t npatch, const int64_t* pptr, const int32_t* pdofs) {
@@ -27,6 +28,8 @@ int alfi_patches_set(alfi_level* L, int64_t npatch, const int64_t* pptr, const i
   L->inv = nullptr; L->stage = nullptr; L->dof_ptr = nullptr; L->dof_pos = nullptr;
   L->factored = false;
   free_cond(L);
+  L->cond_auto = false;
+  L->cond_decided = false;
   L->inv_shrunk = false;
   L->npatch = npatch;
   const int64_t sum_n = npatch > 0 ? pptr[npatch] : 0;
@@ -98,7 +101,20 @@ int alfi_patches_set(alfi_level* L, int64_t npatch, const int64_t* pptr, const i
   return 0;
 }
 
-int alfi_patches_set_groups(alfi_level* L, const int32_t* group) {
+// the block sparsity of the level on the host (row starts are marked in the sign bit of the flat layout: masked by the readers)
+static int download_sparsity(alfi_level* L, std::vector<int32_t>* rowptr, std::vector<int32_t>* colidx) {
+  alfi_ctx* ctx = L->ctx;
+  const int64_t nb = L->A.nbrows, nnzb = L->A.nnzb;
+  rowptr->resize(nb + 1);
+  colidx->resize(nnzb > 0 ? nnzb : 1);
+  ALFI_HIP_CHECK(ctx, hipMemcpy(rowptr->data(), L->A.rowptr, sizeof(int32_t) * (nb + 1), hipMemcpyDeviceToHost));
+  if (nnzb > 0) ALFI_HIP_CHECK(ctx, hipMemcpy(colidx->data(), L->A.colidx, sizeof(int32_t) * nnzb, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// alfi_patches_set_groups for the caller's labels and for the library's own (alfi_patches_factor, which has the sparsity on
+// the host already: sparsity = {rowptr, colidx}, else NULL)
+static int set_groups_impl(alfi_level* L, const int32_t* group, const std::vector<int32_t>* const* sparsity = nullptr) {
   alfi_ctx* ctx = L->ctx;
   if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_set_groups before alfi_patches_set");
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -108,10 +124,11 @@ int alfi_patches_set_groups(alfi_level* L, const int32_t* group) {
   if (!group) return 0;                                  // back to dense inverses (allocated by alfi_patches_factor)
   if (L->mult) return alfi_set_error(ctx, ALFI_E_STATE, "condensed patch factors do not support multiplicative sweeps");
   const int bs = L->bs;
-  const int64_t npatch = L->npatch, nb = L->A.nbrows, nnzb = L->A.nnzb;
-  std::vector<int32_t> rowptr(nb + 1), colidx(nnzb > 0 ? nnzb : 1);
-  ALFI_HIP_CHECK(ctx, hipMemcpy(rowptr.data(), L->A.rowptr, sizeof(int32_t) * (nb + 1), hipMemcpyDeviceToHost));
-  if (nnzb > 0) ALFI_HIP_CHECK(ctx, hipMemcpy(colidx.data(), L->A.colidx, sizeof(int32_t) * nnzb, hipMemcpyDeviceToHost));
+  const int64_t npatch = L->npatch, nb = L->A.nbrows;
+  std::vector<int32_t> own_rowptr, own_colidx;
+  if (!sparsity) ALFI_CHECK(download_sparsity(L, &own_rowptr, &own_colidx));
+  const std::vector<int32_t>& rowptr = sparsity ? *sparsity[0] : own_rowptr;
+  const std::vector<int32_t>& colidx = sparsity ? *sparsity[1] : own_colidx;
   const std::vector<int64_t>& pp = L->h_patch_ptr;
   const std::vector<int32_t>& pd = L->h_patch_dofs;
   const int64_t sum_n = pp[npatch];
@@ -258,7 +275,7 @@ int alfi_patches_set_groups(alfi_level* L, const int32_t* group) {
     std::vector<int32_t> ch_patch, ch_row, xp_grp, bp_grp, g_xp(g_m.size()), g_bp(g_m.size()), u_dst;
     std::vector<int64_t> chptr((size_t)npatch + 1, 0), uptr((size_t)npatch + 1, 0), xp_ptr((size_t)npatch + 1, 0),
         bp_ptr((size_t)npatch + 1, 0);
-    int lds_front = 0, lds_back = 0;
+    int lds_front = 0, lds_back = 0, max_pairs = 0;
     for (int64_t p = 0; p < npatch; ++p) {
       const int s = (int)(sptr[p + 1] - sptr[p]), ld = (s + 1) & ~1;
       for (int r = 0; r < ld; r += COND_SIGMA_ROWS) {
@@ -284,6 +301,7 @@ int alfi_patches_set_groups(alfi_level* L, const int32_t* group) {
       if (qe - qb != uo) return alfi_set_error(ctx, ALFI_E_ARG, "patch %lld: inconsistent skeleton contributions", (long long)p);
       u_dst.resize((size_t)uptr[p + 1]);
       for (int32_t q = qb; q < qe; ++q) u_dst[uptr[p] + s_uidx[q]] = q - qb;
+      max_pairs = std::max(max_pairs, std::max(xp, bp));
       lds_front = std::max(lds_front, (int)((pp[p + 1] - pp[p] + p_nI[p] + uo + 2) * (int64_t)sizeof(double)));
       lds_back = std::max(lds_back, (int)((s + uo + 2) * (int64_t)sizeof(double)));
     }
@@ -348,6 +366,7 @@ int alfi_patches_set_groups(alfi_level* L, const int32_t* group) {
     L->h_cond_chptr = chptr;
     L->cond_lds_front = lds_front;
     L->cond_lds_back = lds_back;
+    L->cond_max_pairs = max_pairs;
     ALFI_CHECK(dev_alloc(ctx, &cd.tmp, sum_n > 0 ? sum_n : 1));
     L->cond_allocs.push_back(cd.tmp);
   }
@@ -373,12 +392,68 @@ int alfi_patches_set_groups(alfi_level* L, const int32_t* group) {
   L->cond_lds_bytes = lds_max;
   L->cond_umax = umax;
   L->cond_max_s = smax;
+  L->cond_max_m = g_m.empty() ? 0 : *std::max_element(g_m.begin(), g_m.end());
+  return 0;
+}
+
+int alfi_patches_set_groups(alfi_level* L, const int32_t* group) {
+  const int rc = set_groups_impl(L, group);
+  // the caller has decided for this patch set, NULL (dense inverses) included: no search for groups at the factorisation
+  L->cond_auto = false;
+  L->cond_decided = rc == 0;
+  return rc;
+}
+
+static int find_groups(alfi_level* L, int32_t* group_out, int64_t* npatch_grouped, std::vector<int32_t>* rowptr_out = nullptr,
+                       std::vector<int32_t>* colidx_out = nullptr) {
+  alfi_ctx* ctx = L->ctx;
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<int32_t> own_rowptr, own_colidx;
+  std::vector<int32_t>& rowptr = rowptr_out ? *rowptr_out : own_rowptr;
+  std::vector<int32_t>& colidx = colidx_out ? *colidx_out : own_colidx;
+  ALFI_CHECK(download_sparsity(L, &rowptr, &colidx));
+  const int64_t ng = alfi_find_groups_host(L->bs, L->A.nbrows, L->npatch, L->h_patch_ptr.data(), L->h_patch_dofs.data(),
+                                           rowptr.data(), colidx.data(), group_out);
+  if (npatch_grouped) *npatch_grouped = ng;
+  return 0;
+}
+
+int alfi_patches_find_groups(alfi_level* L, int32_t* group_out) {
+  alfi_ctx* ctx = L->ctx;
+  if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_find_groups before alfi_patches_set");
+  if (!group_out) return alfi_set_error(ctx, ALFI_E_ARG, "group_out is NULL");
+  return find_groups(L, group_out, nullptr);
+}
+
+int alfi_ctx_set_condense_min_bytes(alfi_ctx* ctx, int64_t min_bytes) {
+  ctx->condense_min_bytes = min_bytes;
+  return 0;
+}
+
+int alfi_patches_condensed(alfi_level* L, int* mode) {
+  if (mode) *mode = !L->cond ? 0 : (L->cond_auto ? 2 : 1);
   return 0;
 }
 
 int alfi_patches_factor_bytes(alfi_level* L, int64_t* bytes) {
   *bytes = L->cond ? 8 * (L->cond_mat_doubles + L->cond_sinv_doubles) : 8 * L->inv_doubles;
   return 0;
+}
+
+// A level that condensed itself (or has not decided yet) and now gets something the condensed factors do not support --
+// multiplicative sweeps, PCPATCH's facet rule -- goes back to dense inverses for good.  The condensed storage is released here
+// (the two are never held together); returns whether the level was factored: the caller factors it again.
+bool auto_cond_to_dense(alfi_level* L) {
+  bool refactor = false;
+  if (L->cond && L->cond_auto) {
+    refactor = L->factored;
+    free_cond(L);
+    L->cond_auto = false;
+    L->factored = false;
+  }
+  L->cond_decided = true;
+  return refactor;
 }
 
 void free_mult_schedule(alfi_level* L) {
@@ -404,7 +479,10 @@ int alfi_patches_set_multiplicative(alfi_level* L, int64_t nit, const int64_t* i
   if (ctx->dev_err) ALFI_HIP_CHECK(ctx, hipMemset(ctx->dev_err, 0, 16));
   if (nit == 0) return 0;
   if (nit < 0 || !iterset) return alfi_set_error(ctx, ALFI_E_ARG, "bad iteration set");
-  if (L->cond) return alfi_set_error(ctx, ALFI_E_STATE, "multiplicative sweeps need dense patch inverses (alfi_patches_set_groups(NULL))");
+  if (L->cond && !L->cond_auto)
+    return alfi_set_error(ctx, ALFI_E_STATE, "multiplicative sweeps need dense patch inverses (alfi_patches_set_groups(NULL))");
+  // (groups the library found itself are its own business: the sweeps read dense inverses, so such a level goes back to them
+  // below, once the arguments have been checked, and is factored again at the end)
   if (L->pou) return alfi_set_error(ctx, ALFI_E_STATE, "partition of unity applies to the additive smoother");
   // partitioned levels: every rank sweeps over its own patches with the residual of its local vector (ghost slots hold
   // the rank's own contributions only) and the ghost contributions are added onto their owners at the end -- what
@@ -425,11 +503,12 @@ int alfi_patches_set_multiplicative(alfi_level* L, int64_t nit, const int64_t* i
   }
   for (int64_t t = 0; t < nit; ++t)
     if (iterset[t] < 0 || iterset[t] >= L->npatch) return alfi_set_error(ctx, ALFI_E_ARG, "iteration set entry out of range");
+  // every argument is checked: now a level that condensed itself goes back to dense inverses (auto_cond_to_dense)
+  const bool refactor = auto_cond_to_dense(L);
   // sparsity of the operator on the host (row starts are marked in the sign bit of the flat layout)
-  const int64_t nb = L->A.nbrows, nnzb = L->A.nnzb;
-  std::vector<int32_t> rowptr(nb + 1), colidx(nnzb > 0 ? nnzb : 1);
-  ALFI_HIP_CHECK(ctx, hipMemcpy(rowptr.data(), L->A.rowptr, sizeof(int32_t) * (nb + 1), hipMemcpyDeviceToHost));
-  if (nnzb > 0) ALFI_HIP_CHECK(ctx, hipMemcpy(colidx.data(), L->A.colidx, sizeof(int32_t) * nnzb, hipMemcpyDeviceToHost));
+  const int64_t nb = L->A.nbrows;
+  std::vector<int32_t> rowptr, colidx;
+  ALFI_CHECK(download_sparsity(L, &rowptr, &colidx));
   // wavefront of position t = 1 + max wavefront of earlier positions whose patch holds a node in the closure of patch t
   // (closure = columns of the patch's block rows).  node_wave[c] = last wavefront that wrote node c.
   std::vector<int32_t> node_wave(nb, -1), wave_of(nit);
@@ -532,6 +611,7 @@ int alfi_patches_set_multiplicative(alfi_level* L, int64_t nit, const int64_t* i
     ALFI_CHECK(dev_alloc(ctx, &L->mult_ctl, 4));
     L->mult_nitems = (int32_t)N;
   }
+  if (refactor) ALFI_CHECK(alfi_patches_factor(L));
   return 0;
 }
 
@@ -549,6 +629,32 @@ int alfi_patches_multiplicative_levels(alfi_level* L, int64_t* nwave) {
 int alfi_patches_factor(alfi_level* L) {
   alfi_ctx* ctx = L->ctx;
   if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_factor before alfi_patches_set");
+  if (!L->cond_decided) {
+    // first factorisation of a patch set the caller gave no groups for: a serial, additive level whose dense inverses would take
+    // condense_min_bytes or more looks for groups in its own sparsity (find_groups.h) and stores condensed factors if it finds
+    // any.
+    L->cond_decided = true;
+    const int64_t thr = ctx->condense_min_bytes;
+    const bool serial = L->n_own == L->n && !L->distributed && !L->has_halo;
+    // (never a Burman level: its sparsity couples cells across facets, alfi_level_set_facet_blocks, and PCPATCH's facet rule,
+    // alfi_patches_set_facet_correction, changes the patch matrices)
+    const bool facets = L->facet_blocks || L->fc_ptr;
+    if (thr >= 0 && !L->cond && !L->mult && serial && !facets && L->npatch > 0 && 8 * L->inv_doubles >= thr) {
+      std::vector<int32_t> group((size_t)L->sum_n), rowptr, colidx;
+      int64_t grouped = 0;
+      ALFI_CHECK(find_groups(L, group.data(), &grouped, &rowptr, &colidx));
+      if (grouped > 0) {
+        // (the finder keeps to the limits of the format; a failure here is an error like any other)
+        const std::vector<int32_t>* sparsity[2] = {&rowptr, &colidx};
+        const int rc = set_groups_impl(L, group.data(), sparsity);
+        if (rc != 0) {
+          free_cond(L);
+          return rc;
+        }
+        L->cond_auto = true;
+      }
+    }
+  }
   ProfScope prof(ctx, ALFI_EV_PATCH_FACTOR);
   ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->status, 0, sizeof(int), ctx->stream));
   if (!L->cond && L->inv_shrunk) {                 // first dense factorisation of this patch set
@@ -604,11 +710,85 @@ int alfi_patches_stats(alfi_level* L, int64_t* npatch, int64_t* sum_n, int64_t* 
   return 0;
 }
 
+// The dense inverse of a condensed patch, assembled on the host from its factors (a diagnostic: FP64 on the host, no kernel):
+// column j is the block factorisation applied to e_j in the operation order of the apply,
+//     t_g = X_g x_g,  rhs = x_S - sum_g B_g t_g,  y_S = inv(Sigma) rhs,  y_g = t_g - W_g y_S[S_g].
+static int cond_get_inverse(alfi_level* L, int64_t p, double* out) {
+  alfi_ctx* ctx = L->ctx;
+  const CondDev& cd = L->cd;
+  const int64_t off = L->h_patch_ptr[p];
+  const int n = (int)(L->h_patch_ptr[p + 1] - off);
+  const int64_t g0 = L->h_cond_gptr[p], g1 = L->h_cond_gptr[p + 1];
+  const int ng = (int)(g1 - g0);
+  const int s = (int)(L->h_sptr[p + 1] - L->h_sptr[p]), nI = n - s, ld = (s + 1) & ~1;
+  ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  auto down = [&](void* dst, const void* src, size_t bytes) {
+    return bytes == 0 ? hipSuccess : hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+  };
+  std::vector<int32_t> slot(n), g_off(ng), g_m(ng), g_sc(ng);
+  std::vector<int64_t> g_mat(ng), g_sidx(ng);
+  std::vector<double> sinv((size_t)s * ld);
+  int64_t sinv_off = 0;
+  ALFI_HIP_CHECK(ctx, down(slot.data(), cd.slot + off, sizeof(int32_t) * n));
+  ALFI_HIP_CHECK(ctx, down(g_off.data(), cd.g_off + g0, sizeof(int32_t) * ng));
+  ALFI_HIP_CHECK(ctx, down(g_m.data(), cd.g_m + g0, sizeof(int32_t) * ng));
+  ALFI_HIP_CHECK(ctx, down(g_sc.data(), cd.g_sc + g0, sizeof(int32_t) * ng));
+  ALFI_HIP_CHECK(ctx, down(g_mat.data(), cd.g_mat + g0, sizeof(int64_t) * ng));
+  ALFI_HIP_CHECK(ctx, down(g_sidx.data(), cd.g_sidx + g0, sizeof(int64_t) * ng));
+  ALFI_HIP_CHECK(ctx, down(&sinv_off, cd.sinv_ptr + p, sizeof(int64_t)));
+  ALFI_HIP_CHECK(ctx, down(sinv.data(), cd.sinv + sinv_off, sizeof(double) * sinv.size()));
+  std::vector<std::vector<double>> mat(ng);
+  std::vector<std::vector<int32_t>> si(ng);
+  for (int g = 0; g < ng; ++g) {
+    mat[g].resize((size_t)cond_group_doubles(g_m[g], g_sc[g]));
+    si[g].resize(g_sc[g]);
+    ALFI_HIP_CHECK(ctx, down(mat[g].data(), cd.mat + g_mat[g], sizeof(double) * mat[g].size()));
+    ALFI_HIP_CHECK(ctx, down(si[g].data(), cd.sidx + g_sidx[g], sizeof(int32_t) * g_sc[g]));
+  }
+  std::vector<double> x(n), y(n), rhs(s);
+  for (int j = 0; j < n; ++j) {                    // column j of the inverse in the condensed order
+    std::fill(x.begin(), x.end(), 0.0);
+    x[j] = 1.0;
+    for (int i = 0; i < s; ++i) rhs[i] = x[nI + i];
+    for (int g = 0; g < ng; ++g) {
+      const int m = g_m[g], sc = g_sc[g], o = g_off[g], ldm = cond_ldim(m), ldsc = cond_ldim(sc);
+      const double* X = mat[g].data();
+      const double* B = X + (size_t)ldm * m;
+      for (int i = 0; i < m; ++i) {
+        double acc = 0.0;
+        for (int k = 0; k < m; ++k) acc += X[(size_t)k * ldm + i] * x[o + k];
+        y[o + i] = acc;                            // t_g
+      }
+      for (int i = 0; i < sc; ++i) {
+        double acc = 0.0;
+        for (int k = 0; k < m; ++k) acc += B[(size_t)k * ldsc + i] * y[o + k];
+        rhs[si[g][i]] -= acc;
+      }
+    }
+    for (int i = 0; i < s; ++i) {
+      double acc = 0.0;
+      for (int k = 0; k < s; ++k) acc += sinv[patch_inv_index(i, k, s, ld)] * rhs[k];
+      y[nI + i] = acc;
+    }
+    for (int g = 0; g < ng; ++g) {
+      const int m = g_m[g], sc = g_sc[g], o = g_off[g], ldm = cond_ldim(m);
+      const double* W = mat[g].data() + (size_t)ldm * m + (size_t)cond_ldim(sc) * m;
+      for (int i = 0; i < m; ++i) {
+        double acc = 0.0;
+        for (int k = 0; k < sc; ++k) acc += W[(size_t)k * ldm + i] * y[nI + si[g][k]];
+        y[o + i] -= acc;
+      }
+    }
+    for (int i = 0; i < n; ++i) out[(int64_t)slot[i] * n + slot[j]] = y[i];
+  }
+  return 0;
+}
+
 int alfi_patch_get_inverse(alfi_level* L, int64_t p, double* out) {
   alfi_ctx* ctx = L->ctx;
   if (!L->factored) return alfi_set_error(ctx, ALFI_E_STATE, "patches not factored");
   if (p < 0 || p >= L->npatch) return alfi_set_error(ctx, ALFI_E_ARG, "patch index out of range");
-  if (L->cond) return alfi_set_error(ctx, ALFI_E_STATE, "condensed patch factors hold no dense inverse");
+  if (L->cond) return cond_get_inverse(L, p, out);
   const int64_t n = L->h_patch_ptr[p + 1] - L->h_patch_ptr[p];
   const int64_t ld = (n + 1) & ~(int64_t)1;
   std::vector<double> tmp(n * ld);

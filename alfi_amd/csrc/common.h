@@ -62,6 +62,9 @@ struct alfi_ctx {
   void* asm_scratch = nullptr;      // element blocks / element vectors of the operator refresh (kernels_assemble.hip), grow-only
   size_t asm_scratch_bytes = 0;
   int64_t asm_scratch_limit = (int64_t)24 << 30;   // bytes of element blocks per batch of cells (alfi_ctx_set_assembly_scratch)
+  // a level without caller-supplied groups whose dense inverses would take at least this many bytes looks for groups itself when
+  // it factors (alfi_ctx_set_condense_min_bytes; negative: never)
+  int64_t condense_min_bytes = alfi_default_condense_min_bytes();
   bool own_stream = false;
   std::string err;
   // profiling
@@ -461,6 +464,8 @@ struct alfi_level {
   // condensed patch factors (alfi_patches_set_groups)
   bool cond = false;
   bool inv_shrunk = false;               // the dense inverse storage was released in favour of the condensed factors
+  bool cond_auto = false;                // the groups are the library's own (alfi_patches_find_groups at the first factorisation)
+  bool cond_decided = false;             // this patch set has had its decision: groups of the caller, found ones, or dense
   CondDev cd;
   std::vector<void*> cond_allocs;        // every device array cd points to
   std::vector<int64_t> h_sptr;           // host copy of cd.sptr (sizes of the Schur complements)
@@ -469,6 +474,8 @@ struct alfi_level {
   std::vector<int64_t> h_cond_chptr;      // (npatch+1) chunks of the three-launch condensed apply
   std::vector<int64_t> h_cond_gcptr;      // (npatch+1) group chunks of the patches
   int cond_lds_gfront = 0, cond_lds_gback = 0;
+  int cond_max_m = 0;                     // largest group: <= 16 -> four groups per wave in the factorisation (cond_group16_kernel)
+  int cond_max_pairs = 0;                 // most row pairs of X / W or of B in one patch: waves per patch of cond_front / cond_back
   std::vector<int64_t> h_cond_gptr;      // host copy of cd.gptr
   // multiplicative sweeps: positions of the iteration sequence grouped into dependency wavefronts
   bool mult = false, mult_symmetrise = false;

@@ -74,3 +74,10 @@ inline bool alfi_env_dist_exact_norm() {
 // ALFI_RCCL_LIB (default unset; when librccl is loaded, at the first alfi_ctx_comm_init) -- a library tried before librccl.so.1,
 // librccl.so and the ROCm install's copy (the test suite's shared-memory stand-in); NULL when unset.
 inline const char* alfi_env_rccl_lib() { return getenv("ALFI_RCCL_LIB"); }
+
+// NOT an environment switch (and on purpose not tied to the test hook at the top of this file: the small hierarchies of the
+// test suite keep their dense inverses) -- the default of alfi_ctx_set_condense_min_bytes, kept with the other defaults: a level
+// without caller-supplied groups whose dense patch inverses would take at least this many bytes looks for condensable groups
+// when it factors.  1 GiB: config 4's two large levels (3.8 and 31.9 GB) condense; its 0.44 GB level, 729-patch launches that
+// are launch-bound either way, keeps the one-launch dense apply (three launches per apply would cost it 2 x 20 launches a cycle).
+inline int64_t alfi_default_condense_min_bytes() { return (int64_t)1 << 30; }

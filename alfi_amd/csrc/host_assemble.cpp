@@ -18,6 +18,8 @@
 #include <vector>
 #include <omp.h>
 
+#include "find_groups.h"
+
 extern "C" {
 
 // Node-to-node adjacency (two nodes are coupled iff they share a cell), sorted columns.
@@ -764,6 +766,13 @@ int alfi_host_burman(int64_t nf, int nu, int nloc, int d, int nqs, int nqn, cons
     }
   }
   return 0;
+}
+
+// The group finder of libalfi_hip.so's alfi_patches_find_groups (find_groups.h) on host arrays: the CPU leg of its tests.
+// Returns the number of patches that got groups.
+int64_t alfi_host_find_groups(int bs, int64_t nbrows, int64_t npatch, const int64_t* patch_ptr, const int32_t* patch_dofs,
+                              const int32_t* rowptr, const int32_t* colidx, int32_t* group_out) {
+  return alfi_find_groups_host(bs, nbrows, npatch, patch_ptr, patch_dofs, rowptr, colidx, group_out);
 }
 
 }  // extern "C"

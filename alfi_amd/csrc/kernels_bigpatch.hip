@@ -366,8 +366,8 @@ __global__ __launch_bounds__(256) void big_store_kernel(int64_t p0, const int64_
   const int ld = (n + 1) & ~1;
   const double* S = scr + scr_ptr[blockIdx.y];
   double* T = inv + inv_ptr[p];
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < (int64_t)ld * n; e += (int64_t)gridDim.x * 256) {
-    const int r = (int)(e / n), c = (int)(e % n);
+  for (int e = (int)blockIdx.x * 256 + threadIdx.x; e < ld * n; e += (int)gridDim.x * 256) {   // (ld n <= 4096^2: int)
+    const int r = e / n, c = e % n;
     T[patch_inv_index(r, c, n, ld)] = r < n ? S[(int64_t)r * N + c] : 0.0;
   }
 }
@@ -832,8 +832,8 @@ __global__ __launch_bounds__(256) void cond_fill_kernel(int64_t p0, CondDev cd, 
   }
   for (int64_t e = m0 + threadIdx.x; e < m1; e += 256) cd.mat[e] = 0.0;
   double* S = scr + scr_ptr[blockIdx.x];
-  for (int64_t e = threadIdx.x; e < (int64_t)N * N; e += 256) {
-    const int r = (int)(e / N), c = (int)(e % N);
+  for (int e = threadIdx.x; e < N * N; e += 256) {        // (N <= 4096: int arithmetic, no 64-bit division)
+    const int r = e / N, c = e % N;
     S[e] = (r == c && r >= s) ? 1.0 : 0.0;
   }
   __syncthreads();
@@ -880,9 +880,13 @@ __global__ __launch_bounds__(256) void cond_fill_kernel(int64_t p0, CondDev cd, 
 // 3, 9 or 45 entries; with the full 64 x 64 elimination for every group this kernel was the largest of config 5's
 // re-factorisation, 84 of 173 ms).  The padding rows are identity rows: their pivots are 1 and their multipliers 0, so the
 // entries of the group come out the same for every GM.
-template <int GM>
+// SW: the shuffle width -- 64: a wave per group; 16: FOUR groups per wave, one per 16 lanes (cond_group16_kernel; lane = the
+// lane inside its segment, scmax = the largest sc of the wave: the column loop is uniform, loads and stores predicated).  The
+// operations of a row and their order do not depend on SW: the same bits.
+template <int GM, int SW = 64>
 __device__ __noinline__ void cond_group_body(int m, int sc, int ldm, double* __restrict__ X, double* __restrict__ W, int lane,
-                                                int* __restrict__ status) {
+                                                int* __restrict__ status, int scmax = -1) {
+  if (scmax < 0) scmax = sc;
   double a[GM], a0[GM];                      // row `lane` of the matrix being inverted / of A_gg itself
 #pragma unroll
   for (int j = 0; j < GM; ++j) {
@@ -892,13 +896,13 @@ __device__ __noinline__ void cond_group_body(int m, int sc, int ldm, double* __r
   bool bad = false;
 #pragma unroll
   for (int k = 0; k < GM; ++k) {
-    const double piv = __shfl(a[k], k, 64);
+    const double piv = __shfl(a[k], k, SW);
     if (piv == 0.0) bad = true;
     const double ip = 1.0 / piv;
     const double mk = (lane == k) ? 0.0 : a[k] * ip;
 #pragma unroll
     for (int j = 0; j < GM; ++j) {
-      const double rk = __shfl(a[j], k, 64);
+      const double rk = __shfl(a[j], k, SW);
       if (j == k)
         a[j] = (lane == k) ? ip : -mk;
       else
@@ -914,22 +918,22 @@ __device__ __noinline__ void cond_group_body(int m, int sc, int ldm, double* __r
   // W[:, c] solves A_gg w = A[g, S_g][:, c]: w = X b, then two steps of iterative refinement w += X (b - A_gg w).  The
   // explicit inverse alone leaves a residual of cond(A_gg) * eps * |b|, and |b| ~ gamma here (the grad-div coupling to
   // the skeleton): measured 2.6e-5 in the patch probe for [P3]^3 against 1e-9 with the refinement.
-  for (int c = 0; c < sc; ++c) {
-    const double b = lane < m ? W[(int64_t)c * ldm + lane] : 0.0;
+  for (int c = 0; c < scmax; ++c) {
+    const double b = (lane < m && c < sc) ? W[(int64_t)c * ldm + lane] : 0.0;
     double w = 0.0;
 #pragma unroll
-    for (int k = 0; k < GM; ++k) w = __builtin_fma(a[k], __shfl(b, k, 64), w);
+    for (int k = 0; k < GM; ++k) w = __builtin_fma(a[k], __shfl(b, k, SW), w);
     for (int it = 0; it < 2; ++it) {
       double r = b;
 #pragma unroll
-      for (int k = 0; k < GM; ++k) r = __builtin_fma(-a0[k], __shfl(w, k, 64), r);
+      for (int k = 0; k < GM; ++k) r = __builtin_fma(-a0[k], __shfl(w, k, SW), r);
       if (lane >= m) r = 0.0;
       double dw = 0.0;
 #pragma unroll
-      for (int k = 0; k < GM; ++k) dw = __builtin_fma(a[k], __shfl(r, k, 64), dw);
+      for (int k = 0; k < GM; ++k) dw = __builtin_fma(a[k], __shfl(r, k, SW), dw);
       w += dw;
     }
-    if (lane < m) W[(int64_t)c * ldm + lane] = w;
+    if (lane < m && c < sc) W[(int64_t)c * ldm + lane] = w;
   }
 }
 
@@ -943,9 +947,27 @@ __global__ __launch_bounds__(256) void cond_group_kernel(int64_t g_begin, int64_
   double* W = X + (int64_t)ldm * m + (int64_t)cond_ldim(sc) * m;
   if (m <= 4) cond_group_body<4>(m, sc, ldm, X, W, lane, status);
   else if (m <= 12) cond_group_body<12>(m, sc, ldm, X, W, lane, status);
+  else if (m <= 16) cond_group_body<16>(m, sc, ldm, X, W, lane, status);     // the 15-dof groups of [P2+FB]^3 vertex stars
   else if (m <= 24) cond_group_body<24>(m, sc, ldm, X, W, lane, status);
   else if (m <= 46) cond_group_body<46>(m, sc, ldm, X, W, lane, status);     // (48: the compiler gives up unrolling)
   else cond_group_body<COND_GMAX>(m, sc, ldm, X, W, lane, status);
+}
+
+// Levels whose groups all hold <= 16 entries (the 15-dof groups of [P2+FB]^3 vertex stars: 1.1 M of them on config 4's finest
+// level): four groups per wave, a group per 16 lanes.  With a wave per group 15 of 64 lanes held a row and this kernel was the
+// largest of the condensed factorisation (62 of 162 ms there).
+__global__ __launch_bounds__(256) void cond_group16_kernel(int64_t g_begin, int64_t g_end, CondDev cd, int* __restrict__ status) {
+  const int64_t g = g_begin + (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const bool have = g < g_end;
+  const int lane = threadIdx.x & 15;
+  const int m = have ? cd.g_m[g] : 0, sc = have ? cd.g_sc[g] : 0;      // (no group: identity rows, nothing loaded or stored)
+  const int ldm = cond_ldim(m);
+  double* X = cd.mat + (have ? cd.g_mat[g] : 0);
+  double* W = X + (int64_t)ldm * m + (int64_t)cond_ldim(sc) * m;
+  int scmax = sc;
+#pragma unroll
+  for (int o = 32; o >= 16; o >>= 1) scmax = max(scmax, __shfl_xor(scmax, o));
+  cond_group_body<16, 16>(m, sc, ldm, X, W, lane, status, scmax);
 }
 
 // RARE PATH (kernels_check.hip: cond_repair): the groups of a flagged patch by LU WITH PARTIAL PIVOTING -- what the reference's
@@ -1525,7 +1547,10 @@ struct BigSource {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cond_group_pivot_kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds);
         hipLaunchKernelGGL(cond_group_pivot_kernel, dim3((unsigned)(gb - ga)), dim3(64), glds, ctx->stream, ga, K->cd, K->status);
-      } else if (gb > ga)
+      } else if (gb > ga && K->cond_max_m <= 16)
+        hipLaunchKernelGGL(cond_group16_kernel, dim3((unsigned)((gb - ga + 15) / 16)), block, 0, ctx->stream, ga, gb, K->cd,
+                           K->status);
+      else if (gb > ga)
         hipLaunchKernelGGL(cond_group_kernel, dim3((unsigned)((gb - ga + 3) / 4)), block, 0, ctx->stream, ga, gb, K->cd,
                            K->status);
       hipLaunchKernelGGL(cond_schur_kernel, dim3((unsigned)nb), block, 0, ctx->stream, p0, K->cd, K->patch_ptr, d_scr_ptr, dst);
@@ -1699,7 +1724,10 @@ static int big_factor_core(alfi_ctx* ctx, const BigSource& src, int64_t npatch, 
       const int64_t n = h_patch_ptr[1] - h_patch_ptr[0];
       hipLaunchKernelGGL(dense_unpad_kernel, dim3(8192), block, 0, ctx->stream, n, (int64_t)B.Nmax, result, dense_out);
     } else {
-      hipLaunchKernelGGL(big_store_kernel, dim3(64, (unsigned)nb), block, 0, ctx->stream, p0, d_patch_ptr, d_inv_ptr,
+      // (a grid-stride loop over the entries: 4 passes per thread; 64 workgroups per patch left 48 of them without an entry
+      // for the 64 x 64 Schur complements of condensed vertex stars)
+      const unsigned sx = (unsigned)std::min<int64_t>(64, std::max<int64_t>(1, (int64_t)B.Nmax * B.Nmax / 1024));
+      hipLaunchKernelGGL(big_store_kernel, dim3(sx, (unsigned)nb), block, 0, ctx->stream, p0, d_patch_ptr, d_inv_ptr,
                          d_scr_ptr, result, inv);
     }
     e = hipGetLastError();
@@ -1822,7 +1850,17 @@ int launch_cond_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double*
     hipLaunchKernelGGL((cond_back_kernel<false, WV, 8>), dim3(grid.x), dim3(64 * WV), lds_b, ctx->stream, p0, p1, L->cd,  \
                        L->patch_ptr, L->stage_ptr, L->stage, ordered);                                                    \
   } while (0)
-  ALFI_COND_LAUNCH3(8);
+  // Waves per patch: a lane owns one row pair per phase, so a workgroup wider than the patch's row pairs is idle lanes.  Macro
+  // stars (config 5: > 1000 pairs of X / W) keep 8 waves; condensed vertex stars ([P2+FB]^3: 48 pairs of X / W, 84 of B) take
+  // 2 (128 lanes: one pass per phase), tiny patch sets 1.
+#ifdef ALFI_COND_WAVES_FORCE      // A/B builds only (scripts/build_variant.sh): every launch with this many waves per patch
+  ALFI_COND_LAUNCH3(ALFI_COND_WAVES_FORCE);
+#else
+  if (L->cond_max_pairs <= 64) ALFI_COND_LAUNCH3(1);
+  else if (L->cond_max_pairs <= 128) ALFI_COND_LAUNCH3(2);
+  else if (L->cond_max_pairs <= 256) ALFI_COND_LAUNCH3(4);
+  else ALFI_COND_LAUNCH3(8);
+#endif
 #undef ALFI_COND_LAUNCH3
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   return 0;

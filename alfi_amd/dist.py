@@ -890,8 +890,11 @@ class DistMultigrid(object):
                     self.halos[dl.id] = hb
                 if LL.level > 0:
                     dl.set_patches(LL.patch_ptr, LL.patch_dofs)
-                    if hip.condense_patches(LL):
+                    if getattr(LL, "patch_groups", None) is not None and env.condense():
                         dl.set_patch_groups(LL.patch_groups)
+                    elif not env.condense():
+                        dl.set_patch_groups(None)
+                    hip.note_patch_level(LL, dl)       # (a level that is not partitioned may find groups by itself)
                     if LL.A.vals is not None:          # (None: the operators are formed on the device first, the caller factors)
                         dl.factor_with_fallback()
                     decided = rule[LL.level] if use_rule else overlap_decision(p.splits, p.bs, p.distributed, overlap,

@@ -46,6 +46,12 @@ class Context(object):
         are taken in batches."""
         self.check(self.lib.alfi_ctx_set_assembly_scratch(self.h, int(max_bytes)))
 
+    def set_condense_min_bytes(self, min_bytes):
+        """A level without caller-supplied groups looks for condensable groups in its own sparsity at its first factorisation
+        when its dense patch inverses would take at least this many bytes (alfi_ctx_set_condense_min_bytes; default 1 GiB,
+        0 = every level, negative = never)."""
+        self.check(self.lib.alfi_ctx_set_condense_min_bytes(self.h, int(min_bytes)))
+
     def set_comm(self, callback, dred_ptr, dred_len):
         """callback: a ctypes function pointer of type alfi_amd.dist.CommFn (kept alive by the caller)."""
         self.check(self.lib.alfi_ctx_set_comm(self.h, ctypes.cast(callback, vp), None, vp(int(dred_ptr)), int(dred_len)))
@@ -377,6 +383,7 @@ class Level(object):
         s = np.ascontiguousarray(s, dtype=np.float64)
         self.ctx.check(self.ctx.lib.alfi_patches_set_facet_correction(self.h, int(nfacet), len(ptr) - 1, _ptr(ptr), _ptr(col),
                                                                       _ptr(fac), _ptr(s)))
+        self._record_storage()
 
     def set_facet_beta(self, beta, scale):
         """beta_F of every facet and adv * weight of host-assembled operator values (alfi_level_set_facet_beta)."""
@@ -417,6 +424,29 @@ class Level(object):
         entry belongs to, -1 = skeleton; None = dense inverses."""
         g = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
         self.ctx.check(self.ctx.lib.alfi_patches_set_groups(self.h, _ptr(g)))
+        self._record_storage()
+
+    host_level = None      # the host level these patches belong to (note_patch_level)
+
+    def _record_storage(self):
+        if self.host_level is not None and self.h:
+            self.host_level.patch_storage = self.condensed()
+
+    def find_patch_groups(self):
+        """Group labels found from the level's block sparsity (alfi_patches_find_groups): one per entry of patch_dofs, -1 =
+        skeleton; what the level uses by itself when its dense inverses would be large (Context.set_condense_min_bytes)."""
+        a, b, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        self.ctx.check(self.ctx.lib.alfi_patches_stats(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        g = np.empty(b.value, dtype=np.int32)
+        self.ctx.check(self.ctx.lib.alfi_patches_find_groups(self.h, _ptr(g)))
+        return g
+
+    def condensed(self):
+        """0: dense inverses, 1: condensed factors on the caller's groups, 2: on groups the library found itself
+        (alfi_patches_condensed; final after the first ``factor()`` of a patch set)."""
+        m = ctypes.c_int()
+        self.ctx.check(self.ctx.lib.alfi_patches_condensed(self.h, ctypes.byref(m)))
+        return m.value
 
     def factor_bytes(self):
         b = ctypes.c_int64()
@@ -431,12 +461,14 @@ class Level(object):
         dependency wavefronts one sweep was scheduled into."""
         it = np.ascontiguousarray(iterset if iterset is not None else [], dtype=np.int64)
         self.ctx.check(self.ctx.lib.alfi_patches_set_multiplicative(self.h, len(it), _ptr(it), 1 if symmetrise else 0))
+        self._record_storage()
         nw = ctypes.c_int64()
         self.ctx.check(self.ctx.lib.alfi_patches_multiplicative_levels(self.h, ctypes.byref(nw)))
         return nw.value
 
     def factor(self):
         self.ctx.check(self.ctx.lib.alfi_patches_factor(self.h))
+        self._record_storage()
 
     def factor_with_fallback(self):
         """factor(); condensed factors that fail the residual probe are repaired in place (pivoted LU of their Schur
@@ -660,10 +692,22 @@ def coarse_inverse(A_bsr):
     return np.linalg.inv(A)
 
 
+def note_patch_level(L, dl):
+    """``dl`` holds the patches of the host level ``L``: from now on the device level records on ``L`` what it stores
+    (``L.patch_storage`` = ``Level.condensed()``), whenever that can change -- factor(), set_patch_groups(),
+    set_multiplicative(), set_patch_facet_correction()."""
+    dl.host_level = L
+    dl._record_storage()
+
+
 def condense_patches(L):
     """Whether the level's patch factors are stored condensed: the generator supplied group labels (macro-star patches of
-    the Scott-Vogelius hierarchy, sv.macro_cell_groups) and ALFI_CONDENSE is not 0."""
-    return getattr(L, "patch_groups", None) is not None and env.condense()
+    the Scott-Vogelius hierarchy, sv.macro_cell_groups) and ALFI_CONDENSE is not 0 -- or the device level built from ``L``
+    found groups by itself when it factored (vertex stars whose dense inverses would be large) and still uses them
+    (``L.patch_storage == 2``, recorded by the device level: note_patch_level)."""
+    if not env.condense():
+        return False
+    return getattr(L, "patch_groups", None) is not None or getattr(L, "patch_storage", 0) == 2
 
 
 class Multigrid(object):
@@ -679,9 +723,12 @@ class Multigrid(object):
             dl = Level(ctx, L.A, L.bc_dofs)
             if L.level > 0:
                 dl.set_patches(L.patch_ptr, L.patch_dofs)
-                if condense_patches(L):
+                if getattr(L, "patch_groups", None) is not None and env.condense():
                     dl.set_patch_groups(L.patch_groups)
+                elif not env.condense():
+                    dl.set_patch_groups(None)              # dense inverses, also where the level would find groups itself
                 dl.factor_with_fallback()
+                note_patch_level(L, dl)
             elif coarse_inv is not None:
                 dl.set_coarse_inverse(coarse_inv)          # an inverse supplied by the caller (numpy array / device pointer)
             else:                                          # the library's own factorisation, dense or multifrontal

@@ -356,10 +356,15 @@ class HipPatchPC(object):
             from .sv import macro_cell_groups
             self.level.set_patch_groups(macro_cell_groups(L.V, dofs))
             self.condensed = True
+        elif self.multiplicative or not env.condense() or getattr(L, "facet_coupling", False):
+            # ... and no search for groups by the level itself either (large vertex-star levels, alfi_patches_find_groups):
+            # the sweeps and PCPATCH's facet rule need dense inverses, ALFI_CONDENSE=0 asks for them
+            self.level.set_patch_groups(None)
         # (operator values not there yet -- formed on the device by the caller, who then factors: problem.build_hierarchy
         # with operator_values=False)
         if L.A.vals is not None:
             self.level.factor()
+        hip.note_patch_level(L, self.level)
         if self.partition_of_unity:
             self.level.set_partition_of_unity(True)
         self.wavefronts = self.level.set_multiplicative(self.iterset, self.symmetrise) if self.multiplicative else 0

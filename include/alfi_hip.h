@@ -284,6 +284,23 @@ int alfi_patches_factor(alfi_level* lvl);
  * the factors of the level occupy (= the bytes one additive apply reads). */
 int alfi_patches_set_groups(alfi_level* lvl, const int32_t* group_host);
 int alfi_patches_factor_bytes(alfi_level* lvl, int64_t* bytes);
+/* Groups for alfi_patches_set_groups found from the level's block sparsity alone (after alfi_patches_set; host code, nothing
+ * changes on the level): group_out gets one label per entry of patch_dofs.  Per patch, on the node graph restricted to it:
+ * nodes coupled to every node of the patch (hubs) are skeleton; among the others, visited by ascending (degree, position), a
+ * seed takes the unassigned neighbours whose closed neighbourhood lies inside its own; such a set becomes a group if it has
+ * >= 2 nodes, <= 64 dofs, couples to <= 64 skeleton dofs and touches no earlier group; a patch keeps its groups only if its
+ * condensed factors take <= 0.75 of the dense inverse's doubles, otherwise (and for patches that are not whole nodes) every
+ * label is -1.  [P2+FB]^3 vertex stars of 153 dofs: 6 groups of 15 dofs (a face-centre edge node and the 4 face bubbles of
+ * its spokes) over a 63-dof skeleton, 0.435 of the dense doubles.  Deterministic.
+ * A level WITHOUT caller-supplied groups (alfi_patches_set_groups never called for the patch set, not partitioned, additive,
+ * no facet blocks and no facet correction: never a Burman level) does this itself at its first alfi_patches_factor if its dense inverses would take at least
+ * min_bytes (alfi_ctx_set_condense_min_bytes; default 1 GiB, negative = never) and stores condensed factors when groups were
+ * found.  On such a level alfi_patches_set_multiplicative and alfi_patches_set_facet_correction go back to dense inverses
+ * and factor again (multiplicative sweeps with the caller's groups are an error), and alfi_patch_get_inverse assembles the dense inverse from the factors on the host.
+ * alfi_patches_condensed: 0 = dense inverses, 1 = the caller's groups, 2 = groups the library found. */
+int alfi_patches_find_groups(alfi_level* lvl, int32_t* group_out_host);
+int alfi_ctx_set_condense_min_bytes(alfi_ctx* ctx, int64_t min_bytes);
+int alfi_patches_condensed(alfi_level* lvl, int* mode);
 /* Every alfi_patches_factor ends with a residual probe of every stored inverse, rho_p = || A_p (X_p e) - e ||_inf with a
  * fixed +-1 vector e, and re-inverts the patches with rho_p > 1e-6 (ALFI_PATCH_CHECK_TOL) -- or with a zero pivot -- by
  * LU with partial pivoting and triangular sweeps (the reference factors with pivoted LAPACK / UMFPACK LU, solver.py:599-602,
@@ -314,7 +331,8 @@ int alfi_patches_set_multiplicative(alfi_level* lvl, int64_t nit, const int64_t*
 int alfi_patches_multiplicative_levels(alfi_level* lvl, int64_t* nwave);
 /* sum_p n_p^2 (doubles held as inverses) and sum_p n_p, for roofline accounting */
 int alfi_patches_stats(alfi_level* lvl, int64_t* npatch, int64_t* sum_n, int64_t* sum_n2);
-/* debugging / parity tests: copy the dense inverse of patch p (row-major n_p x n_p) to the host */
+/* debugging / parity tests: copy the dense inverse of patch p (row-major n_p x n_p) to the host (condensed factors: assembled
+ * from them on the host, column by column in the operation order of the apply) */
 int alfi_patch_get_inverse(alfi_level* lvl, int64_t p, double* out_host);
 
 /* ---- level smoother: PETSc KSPFGMRES, k iterations, convergence_test skip [3P], alfi/solver.py:314-317 ----------- */
