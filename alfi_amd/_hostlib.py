@@ -47,6 +47,11 @@ def lib():
         _lib.alfi_host_gls.restype = ctypes.c_int
         _lib.alfi_host_burman.restype = ctypes.c_int
         _lib.alfi_host_find_groups.restype = ctypes.c_int64
+        for name in ("patch_layout", "condensed", "sweep"):
+            getattr(_lib, "alfi_host_plan_" + name).restype = ctypes.c_void_p
+        _lib.alfi_host_plan_status.restype = ctypes.c_int
+        _lib.alfi_host_plan_table.restype = ctypes.c_int
+        _lib.alfi_host_plan_free.restype = None
         nthr = env.host_threads() or cpu_share()
         _lib.alfi_host_set_num_threads(ctypes.c_int(nthr))
     return _lib
@@ -67,6 +72,77 @@ def find_groups(bs, rowptr, colidx, patch_ptr, patch_dofs):
     lib().alfi_host_find_groups(ctypes.c_int(bs), ctypes.c_int64(len(rp) - 1), ctypes.c_int64(len(pp) - 1), _p(pp), _p(pd),
                                 _p(rp), _p(ci), _p(out))
     return out
+
+
+class PlanError(ValueError):
+    """A planner of csrc/patch_plan.h refused its input: ``code`` is the ALFI_E_* code the device library returns for it, the
+    message its error text."""
+
+    def __init__(self, code, message):
+        ValueError.__init__(self, message)
+        self.code = code
+
+
+# CondChunk (csrc/cond_layout.h)
+COND_CHUNK = np.dtype([(k, np.int64) for k in ("off", "ubase", "sidx0", "stage_off")]
+                      + [(k, np.int32) for k in ("xq0", "xq1", "bq0", "bq1", "e0", "ne", "u0", "nu", "nI", "xp0", "bp0", "pad")])
+_PLAN_DTYPES = {4: np.dtype(np.int32), 8: np.dtype(np.int64), COND_CHUNK.itemsize: COND_CHUNK}
+
+
+def _plan_dict(handle):
+    """Every table (a copy, as an array) and scalar (an int) of a plan handle by its name; the handle is released."""
+    L = lib()
+    h = ctypes.c_void_p(handle)
+    try:
+        msg = ctypes.c_char_p()
+        rc = L.alfi_host_plan_status(h, ctypes.byref(msg))
+        if rc != 0:
+            raise PlanError(rc, msg.value.decode())
+        out, i = {}, 0
+        name, ptr, count, item = ctypes.c_char_p(), ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int()
+        while L.alfi_host_plan_table(h, ctypes.c_int64(i), ctypes.byref(name), ctypes.byref(ptr), ctypes.byref(count),
+                                     ctypes.byref(item)) == 0:
+            dt = _PLAN_DTYPES[item.value]
+            n = 1 if count.value < 0 else count.value
+            a = np.frombuffer(ctypes.string_at(ptr.value, n * dt.itemsize) if n else b"", dtype=dt).copy()
+            out[name.value.decode()] = int(a[0]) if count.value < 0 else a
+            i += 1
+        return out
+    finally:
+        L.alfi_host_plan_free(h)
+
+
+def _patch_args(patch_ptr, patch_dofs):
+    pp = np.ascontiguousarray(patch_ptr, dtype=np.int64)
+    pd = np.ascontiguousarray(patch_dofs, dtype=np.int32)
+    return pp, pd, ctypes.c_int64(len(pp) - 1)
+
+
+def plan_patch_layout(n, patch_ptr, patch_dofs):
+    """The tables alfi_patches_set builds for a level of n dofs (csrc/patch_plan.h: plan_patch_layout) as a dict."""
+    pp, pd, npatch = _patch_args(patch_ptr, patch_dofs)
+    return _plan_dict(lib().alfi_host_plan_patch_layout(ctypes.c_int64(n), npatch, _p(pp), _p(pd)))
+
+
+def plan_condensed(bs, rowptr, colidx, patch_ptr, patch_dofs, groups):
+    """The tables alfi_patches_set_groups builds from the labels ``groups`` (csrc/patch_plan.h: plan_condensed) as a dict."""
+    rp = np.ascontiguousarray(rowptr, dtype=np.int32)
+    ci = np.ascontiguousarray(colidx, dtype=np.int32)
+    pp, pd, npatch = _patch_args(patch_ptr, patch_dofs)
+    g = np.ascontiguousarray(groups, dtype=np.int32)
+    assert len(g) == len(pd)
+    return _plan_dict(lib().alfi_host_plan_condensed(ctypes.c_int(bs), ctypes.c_int64(len(rp) - 1), npatch, _p(pp), _p(pd), _p(g),
+                                                     _p(rp), _p(ci)))
+
+
+def plan_sweep(bs, rowptr, colidx, patch_ptr, patch_dofs, iterset, symmetrise):
+    """The schedule alfi_patches_set_multiplicative builds (csrc/patch_plan.h: check_sweep + plan_sweep) as a dict."""
+    rp = np.ascontiguousarray(rowptr, dtype=np.int32)
+    ci = np.ascontiguousarray(colidx, dtype=np.int32)
+    pp, pd, npatch = _patch_args(patch_ptr, patch_dofs)
+    it = np.ascontiguousarray(iterset, dtype=np.int64)
+    return _plan_dict(lib().alfi_host_plan_sweep(ctypes.c_int(bs), ctypes.c_int64(len(rp) - 1), npatch, _p(pp), _p(pd), _p(rp),
+                                                 _p(ci), ctypes.c_int64(len(it)), _p(it), ctypes.c_int(1 if symmetrise else 0)))
 
 
 def node_graph(cell_nodes, nnode):

@@ -72,7 +72,7 @@ def build_hip(force=False):
 
 def build_host(force=False):
     src = os.path.join(CSRC, "host_assemble.cpp")
-    if force or _newer(HOST_LIB, [src, os.path.join(CSRC, "find_groups.h")]):
+    if force or _newer(HOST_LIB, [src] + [os.path.join(CSRC, h) for h in ("find_groups.h", "patch_plan.h", "cond_layout.h")]):
         _run(["g++", "-O3", "-march=x86-64-v3", "-fopenmp", "-std=c++17", "-fPIC", "-shared", "-o", HOST_LIB, src])
     return HOST_LIB
 

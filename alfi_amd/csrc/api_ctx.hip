@@ -264,10 +264,7 @@ void free_cond(alfi_level* L) {
   L->cond_allocs.clear();
   L->cd = CondDev();
   L->cond = false;
-  L->h_sptr.clear();
-  L->h_cond_gptr.clear();
-  L->cond_ngroups = L->cond_mat_doubles = L->cond_sinv_doubles = 0;
-  L->cond_lds_bytes = L->cond_max_s = L->cond_umax = 0;
+  L->cplan = CondPlan();
 }
 
 // ---- context -------------------------------------------------------------------------------------------------------------

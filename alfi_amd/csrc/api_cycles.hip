@@ -576,7 +576,7 @@ static void cycle_signature(alfi_mg* mg, std::vector<uint64_t>* sig) {
     push(L->mult_seq);
     sig->push_back((uint64_t)L->npatch);
     sig->push_back((uint64_t)L->kmax);
-    sig->push_back((uint64_t)(L->mult ? 1 + (L->mult_symmetrise ? 1 : 0) + 4 * L->mult_wave_ptr.size() : 0));
+    sig->push_back((uint64_t)(L->mult ? 1 + (L->mult_symmetrise ? 1 : 0) + 4 * L->sweep.wave_ptr.size() : 0));
   }
   for (alfi_transfer* T : mg->transfers) {
     push(T->binv);

@@ -169,8 +169,8 @@ int alfi_level_set_overlap(alfi_level* L, int64_t nb_interior, int64_t npatch_in
         return alfi_set_error(ctx, ALFI_E_ARG, "an operator row declared interior holds a ghost column");
   }
   for (int64_t p = 0; p < npatch_interior; ++p)
-    for (int64_t q = L->h_patch_ptr[p]; q < L->h_patch_ptr[p + 1]; ++q)
-      if (L->h_patch_dofs[q] >= L->n_own)
+    for (int64_t q = L->lay.patch_ptr[p]; q < L->lay.patch_ptr[p + 1]; ++q)
+      if (L->lay.patch_dofs[q] >= L->n_own)
         return alfi_set_error(ctx, ALFI_E_ARG, "patch %lld declared interior holds a ghost dof", (long long)p);
   free_row_view(&L->A_int);
   free_row_view(&L->A_bnd);
@@ -198,6 +198,8 @@ int alfi_level_destroy(alfi_level* L) {
   dev_free(L->rev_nodes);
   dev_free(L->rev_ptr);
   dev_free(L->rev_pos);
+  dev_free(L->sum_send_nodes); dev_free(L->sum_nodes); dev_free(L->sum_ptr); dev_free(L->sum_src);   // alfi_level_set_sum_exchange
+  dev_free(L->sum_sendbuf); dev_free(L->sum_recvbuf);
   dev_free(L->fc_ptr); dev_free(L->fc_col); dev_free(L->fc_fac); dev_free(L->fc_s); dev_free(L->fc_beta);
   dev_free(L->patch_ptr);
   dev_free(L->patch_dofs);
@@ -706,11 +708,11 @@ int alfi_patches_set_facet_correction(alfi_level* L, int64_t nfacet, int64_t nro
   alfi_ctx* ctx = L->ctx;
   if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_set_facet_correction before alfi_patches_set");
   if (!ptr || nfacet < 0 || nrow < 0) return alfi_set_error(ctx, ALFI_E_ARG, "NULL argument");
-  if (L->h_patch_ptr[L->npatch] != nrow * L->bs) return alfi_set_error(ctx, ALFI_E_ARG, "facet correction rows != patch nodes");
+  if (L->lay.patch_ptr[L->npatch] != nrow * L->bs) return alfi_set_error(ctx, ALFI_E_ARG, "facet correction rows != patch nodes");
   const int64_t ne = ptr[nrow];
   if (ptr[0] != 0 || (ne > 0 && (!col || !fac || !s))) return alfi_set_error(ctx, ALFI_E_ARG, "bad facet correction lists");
   for (int64_t p = 0; p < L->npatch; ++p) {
-    const int64_t r0 = L->h_patch_ptr[p], r1 = L->h_patch_ptr[p + 1];
+    const int64_t r0 = L->lay.patch_ptr[p], r1 = L->lay.patch_ptr[p + 1];
     if (r0 % L->bs || r1 % L->bs) return alfi_set_error(ctx, ALFI_E_ARG, "facet correction needs patches of whole nodes");
     const int64_t nn = (r1 - r0) / L->bs;
     for (int64_t r = r0 / L->bs; r < r1 / L->bs; ++r) {
@@ -889,7 +891,7 @@ int level_patch_apply(alfi_level* L, const double* dx, double* dy, bool* ghosts_
     // iteration order and, with symmetrise_sweep, back again in reverse order
     if (L->distributed) ALFI_CHECK(halo_fwd(L, const_cast<double*>(dx)));
     ALFI_HIP_CHECK(ctx, hipMemsetAsync(dy, 0, sizeof(double) * L->n, ctx->stream));
-    const bool persistent = alfi_env_mult_persistent() && L->mult_nitems > 0;
+    const bool persistent = alfi_env_mult_persistent() && L->sweep.nitems > 0;
     {
       ProfScope prof(ctx, ALFI_EV_PATCH_APPLY);
       if (persistent) {
@@ -897,14 +899,14 @@ int level_patch_apply(alfi_level* L, const double* dx, double* dy, bool* ghosts_
         // synchronisation inside the smoother)
         ALFI_CHECK(launch_patch_mult_persistent(L, dx, dy));
       } else {   // one launch per dependency wavefront
-        const int64_t nw = (int64_t)L->mult_wave_ptr.size() - 1;
+        const int64_t nw = (int64_t)L->sweep.wave_ptr.size() - 1;
         for (int64_t w = 0; w < nw; ++w)
-          ALFI_CHECK(launch_patch_mult_wave(L, L->mult_seq + L->mult_wave_ptr[w], L->mult_wave_ptr[w + 1] - L->mult_wave_ptr[w],
+          ALFI_CHECK(launch_patch_mult_wave(L, L->mult_seq + L->sweep.wave_ptr[w], L->sweep.wave_ptr[w + 1] - L->sweep.wave_ptr[w],
                                             dx, dy));
         if (L->mult_symmetrise)
           for (int64_t w = nw - 1; w >= 0; --w)
-            ALFI_CHECK(launch_patch_mult_wave(L, L->mult_seq + L->mult_wave_ptr[w],
-                                              L->mult_wave_ptr[w + 1] - L->mult_wave_ptr[w], dx, dy));
+            ALFI_CHECK(launch_patch_mult_wave(L, L->mult_seq + L->sweep.wave_ptr[w],
+                                              L->sweep.wave_ptr[w + 1] - L->sweep.wave_ptr[w], dx, dy));
       }
     }
     if (L->distributed) ALFI_CHECK(halo_rev(L, dy));

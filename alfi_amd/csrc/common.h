@@ -9,6 +9,7 @@
 #include <vector>
 #include "alfi_hip.h"
 #include "env.h"   // every environment switch of the library
+#include "patch_plan.h"   // host planners of the patch tables; with cond_layout.h, the layout they share with the kernels
 
 // Every host <-> device copy the library makes is counted (alfi_transfer_stats): that a Newton step moves nothing but scalars
 // across PCIe is tested (tests/test_gpu_newton_state.py), not asserted.  Process-wide counters.
@@ -141,8 +142,7 @@ class ProfScope {
 
 constexpr int BURMAN_MAXQ = 32;        // points of a facet rule the Burman kernels take (3-D P3: 25 for the nonlinear rule)
 constexpr int BURMAN_MAXN = 20;        // nodes per cell the Burman kernels take ([P3]^3)
-constexpr int SMALL_PATCH_MAX = 160;   // register-resident inversion / one wave per patch up to here (kernels_patch.hip)
-constexpr int PATCH_MAX = 4096;        // blocked MFMA inversion / one workgroup per patch beyond (kernels_bigpatch.hip)
+// (SMALL_PATCH_MAX, PATCH_MAX: patch_plan.h)
 
 // ---- storage of one dense patch inverse (n x n, rows padded to ld = n rounded up to even) --------------------------------
 // Row pieces: as many 128-row pieces as fit, then the binary digits of the remainder (64, 32, ..., 2).  A piece of R rows
@@ -258,7 +258,7 @@ struct CondDev {
   double* sinv = nullptr;
   const int32_t* order = nullptr;  // (npatch) patches by descending factor bytes: dispatch order of a full-range apply
   // three-launch apply (cond_front / cond_sigma / cond_back): the rows of inv(Sigma) in chunks of COND_SIGMA_ROWS
-  const int32_t* ch_patch = nullptr;  // per chunk: its patch (natural order; the chunks of patch p: h_cond_chptr[p .. p + 1])
+  const int32_t* ch_patch = nullptr;  // per chunk: its patch (natural order; the chunks of patch p: CondPlan::chptr[p .. p + 1])
   const int32_t* ch_row = nullptr;    //            its first row
   double* tmp = nullptr;              // (sum_n) per patch [t_g ... | y_S] between the launches
   const int64_t* uptr = nullptr;      // (npatch+1) prefix sums of the patches' u buffer lengths
@@ -274,21 +274,8 @@ struct CondDev {
   // One descriptor per workgroup (CondChunk); a lane decodes its row pair from the per-pair group index and the group arrays
   // (cond_xpair / cond_bpair, kernels_bigpatch.hip).  Round 3 stored a 48 / 32-byte descriptor per LANE: 8 % more bytes than
   // the factors themselves on config 5's finest level.
-  const struct CondChunk* gc = nullptr;   // (nchunk)
+  const CondChunk* gc = nullptr;      // (nchunk; cond_layout.h)
   double* ubuf = nullptr;             // (sum of the u buffer lengths) u_g = B_g t_g in the row-sorted order of u_dst
-};
-struct CondChunk {
-  int64_t off;        // patch_ptr[p]
-  int64_t ubase;      // uptr[p]
-  int64_t sidx0;      // first entry of the chunk's S_g lists in CondDev::sidx
-  int64_t stage_off;  // stage_ptr[p]
-  int32_t xq0, xq1;   // the chunk's X / W row pairs in xpd
-  int32_t bq0, bq1;   // the chunk's B row pairs in bpd
-  int32_t e0, ne;     // its interior entries (adjacent in the condensed order)
-  int32_t u0, nu;     // its entries of the patch's u layout
-  int32_t nI;
-  int32_t xp0, bp0;   // first row pair of the PATCH in the X / W and in the B numbering (a pair's place inside its group)
-  int32_t pad;
 };
 // what a lane needs of its row pair (decoded in the kernel, never stored)
 struct CondXPair {
@@ -303,23 +290,6 @@ struct CondBPair {
   int32_t d0, d1;     // places of the two results in the row-sorted u buffer (-1: the row does not exist)
   int32_t pad;
 };
-
-// rows of inv(Sigma) per workgroup of the sigma kernels of the condensed apply (4 waves; kernels_bigpatch.hip, chunk table in
-// alfi_patches_set_groups)
-#ifndef ALFI_COND_SIGMA_ROWS
-#define ALFI_COND_SIGMA_ROWS 64
-#endif
-constexpr int COND_SIGMA_ROWS = ALFI_COND_SIGMA_ROWS;
-
-// storage of one group's matrices in CondDev::mat: [X (m x m) | B (sc x m) | W (m x sc)], column-major each, the leading
-// dimensions rounded up to EVEN (a lane streams two rows of a column with one 16-byte load; the pad row is never stored)
-// (Measured and dropped, round 5: leading dimensions of > 8 rows rounded up to whole 128-byte lines and every group on a line
-// boundary -- no column shares a line with its neighbour, +3.8 % bytes: config 5 24.13 against 23.60-23.68 ms per cycle, same box.)
-__host__ __device__ inline int cond_ldim(int rows) { return (rows + 1) & ~1; }
-__host__ __device__ inline int cond_pairs(int rows) { return (rows + 1) / 2; }     // row pairs a lane each
-__host__ __device__ inline int64_t cond_group_doubles(int m, int sc) {
-  return (int64_t)cond_ldim(m) * m + (int64_t)cond_ldim(sc) * m + (int64_t)cond_ldim(m) * sc;
-}
 
 // device-side data of the operator refresh (alfi_level_set_assembly, kernels_assemble.hip)
 struct AssemblyDev {
@@ -418,8 +388,8 @@ struct alfi_level {
   int64_t nbc = 0;
   uint8_t* bc_mask = nullptr;  // (n) 1 on Dirichlet dofs: the dof-wise sum of the patch results copies x there
   // patches
-  int64_t npatch = 0, sum_n = 0, sum_n2 = 0, inv_doubles = 0;
-  int max_np = 0;
+  PatchLayout lay;                // host side of the layout (patch_plan.h): patch_ptr, patch_dofs, inv_ptr
+  int64_t npatch = 0;
   int64_t* patch_ptr = nullptr;   // (npatch+1) offsets into patch_dofs / staging buffer
   // PCPATCH's interior-facet rule on a Burman level (alfi_patches_set_facet_correction): per patch-local row node (patches of
   // whole nodes, rows numbered patch_ptr[p] / bs + i), the entries (local column node, facet, s) of the K-side facet terms
@@ -443,7 +413,6 @@ struct alfi_level {
   int il_G = 0, il_nc = 0;        // lanes per patch (row pairs), columns stored per patch (= max_np)
   bool il_valid = false;
   double* stage = nullptr;        // (sum ld_p) staged patch results
-  int64_t stage_len = 0;
   int32_t* dof_ptr = nullptr;     // (n+1) CSR dof -> positions in stage
   int32_t* dof_pos = nullptr;     // (sum_n)
   bool factored = false;
@@ -468,27 +437,16 @@ struct alfi_level {
   bool cond_decided = false;             // this patch set has had its decision: groups of the caller, found ones, or dense
   CondDev cd;
   std::vector<void*> cond_allocs;        // every device array cd points to
-  std::vector<int64_t> h_sptr;           // host copy of cd.sptr (sizes of the Schur complements)
-  int64_t cond_ngroups = 0, cond_mat_doubles = 0, cond_sinv_doubles = 0;
-  int cond_lds_bytes = 0, cond_max_s = 0, cond_umax = 0, cond_lds_front = 0, cond_lds_back = 0;
-  std::vector<int64_t> h_cond_chptr;      // (npatch+1) chunks of the three-launch condensed apply
-  std::vector<int64_t> h_cond_gcptr;      // (npatch+1) group chunks of the patches
-  int cond_lds_gfront = 0, cond_lds_gback = 0;
-  int cond_max_m = 0;                     // largest group: <= 16 -> four groups per wave in the factorisation (cond_group16_kernel)
-  int cond_max_pairs = 0;                 // most row pairs of X / W or of B in one patch: waves per patch of cond_front / cond_back
-  std::vector<int64_t> h_cond_gptr;      // host copy of cd.gptr
+  CondPlan cplan;                        // host side of the plan cd was uploaded from (patch_plan.h): sptr, gptr, chptr, gcptr, limits
   // multiplicative sweeps: positions of the iteration sequence grouped into dependency wavefronts
   bool mult = false, mult_symmetrise = false;
-  bool mult_big = false;                // a patch holds more than 64 nodes: workgroup-per-patch sweep kernel
   int32_t* mult_seq = nullptr;          // (nit) patch ids, wavefront-major
-  std::vector<int64_t> mult_wave_ptr;   // (nwave+1) offsets into mult_seq
+  SweepPlan sweep;                      // host side of the schedule (patch_plan.h): wave_ptr, big, nitems
   // persistent schedule of the whole apply (forward sweep, then -- symmetrised -- the wavefronts in reverse): item -> patch,
   // predecessor counts (the last writers of the nodes an item reads), successor lists
-  int32_t mult_nitems = 0;
   int32_t *mult_items = nullptr, *mult_pred0 = nullptr, *mult_pred = nullptr, *mult_succ_ptr = nullptr, *mult_succ = nullptr;
   int32_t* mult_ctl = nullptr;          // [0] ticket counter (zeroed before every launch)
   int32_t* mult_rowtab = nullptr;       // (npatch, 64, 3) first block, block count, node of every patch node (zero-padded)
-  std::vector<int32_t> h_patch_dofs;    // host copy of the patch dofs (needed to build the wavefronts)
   // FGMRES workspace
   int kmax = 0;
   int64_t ldv = 0;       // stride of V and Z: n rounded up to even (16-byte aligned basis vectors)
@@ -509,8 +467,6 @@ struct alfi_level {
   double cinv_residual = -1.0;    // || A X e - e ||_inf of the inverse built by alfi_coarse_factor (-1: supplied by the caller)
   // multigrid work vectors (owned by alfi_mg but stored per level)
   double *mg_b = nullptr, *mg_x = nullptr, *mg_r = nullptr;
-  std::vector<int64_t> h_patch_ptr;  // host copy (for get_inverse)
-  std::vector<int64_t> h_inv_ptr;
 };
 
 struct alfi_transfer {

@@ -1,0 +1,43 @@
+// Layout of the condensed patch factors that the host planner (patch_plan.h) and the kernels (kernels_bigpatch.hip) share: the
+// chunk descriptor and the storage of one group's matrices.  Plain C++ for a host compiler, __host__ __device__ under hipcc.
+#pragma once
+#include <cstdint>
+
+#ifdef __HIPCC__
+#define ALFI_HD __host__ __device__
+#else
+#define ALFI_HD
+#endif
+
+// a chunk of consecutive groups of one patch (<= COND_CHUNK_PAIRS row pairs of X / W and of B): the work unit of cond_gfront /
+// cond_gback, one descriptor per workgroup
+struct CondChunk {
+  int64_t off;        // patch_ptr[p]
+  int64_t ubase;      // uptr[p]
+  int64_t sidx0;      // first entry of the chunk's S_g lists in CondDev::sidx
+  int64_t stage_off;  // stage_ptr[p]
+  int32_t xq0, xq1;   // the chunk's X / W row pairs in xpd
+  int32_t bq0, bq1;   // the chunk's B row pairs in bpd
+  int32_t e0, ne;     // its interior entries (adjacent in the condensed order)
+  int32_t u0, nu;     // its entries of the patch's u layout
+  int32_t nI;
+  int32_t xp0, bp0;   // first row pair of the PATCH in the X / W and in the B numbering (a pair's place inside its group)
+  int32_t pad;
+};
+
+// rows of inv(Sigma) per workgroup of the sigma kernels of the condensed apply (4 waves; kernels_bigpatch.hip, chunk table in
+// plan_condensed)
+#ifndef ALFI_COND_SIGMA_ROWS
+#define ALFI_COND_SIGMA_ROWS 64
+#endif
+constexpr int COND_SIGMA_ROWS = ALFI_COND_SIGMA_ROWS;
+
+// storage of one group's matrices in CondDev::mat: [X (m x m) | B (sc x m) | W (m x sc)], column-major each, the leading
+// dimensions rounded up to EVEN (a lane streams two rows of a column with one 16-byte load; the pad row is never stored)
+// (Measured and dropped, round 5: leading dimensions of > 8 rows rounded up to whole 128-byte lines and every group on a line
+// boundary -- no column shares a line with its neighbour, +3.8 % bytes: config 5 24.13 against 23.60-23.68 ms per cycle, same box.)
+ALFI_HD inline int cond_ldim(int rows) { return (rows + 1) & ~1; }
+ALFI_HD inline int cond_pairs(int rows) { return (rows + 1) / 2; }     // row pairs a lane each
+ALFI_HD inline int64_t cond_group_doubles(int m, int sc) {
+  return (int64_t)cond_ldim(m) * m + (int64_t)cond_ldim(sc) * m + (int64_t)cond_ldim(m) * sc;
+}

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <vector>
+#include "patch_plan.h"   // patch_of_whole_nodes
 
 // rowptr / colidx: block sparsity (nb block rows; the sign bit of a column index may carry the row-start mark of the flat
 // layout and is masked).  out: one label per entry of pdofs.  Returns the number of patches that got groups.
@@ -34,13 +35,9 @@ inline int64_t alfi_find_groups_host(int bs, int64_t nb, int64_t npatch, const i
     const int64_t off = pp[p];
     const int n = (int)(pp[p + 1] - off);
     for (int i = 0; i < n; ++i) out[off + i] = -1;
-    if (bs <= 0 || n % bs != 0) continue;
+    if (!patch_of_whole_nodes(bs, pd + off, n)) continue;
     const int nn = n / bs;
-    bool whole = true;
-    for (int i = 0; i < nn && whole; ++i)
-      for (int c = 0; c < bs; ++c)
-        if (pd[off + (int64_t)i * bs + c] != (pd[off + (int64_t)i * bs] / bs) * bs + c) whole = false;
-    if (!whole || nn < 3) continue;
+    if (nn < 3) continue;
     const int W = (nn + 63) / 64;
     adj.assign((size_t)nn * W, 0);
     for (int i = 0; i < nn; ++i) node_pos[pd[off + (int64_t)i * bs] / bs] = i;

@@ -19,6 +19,7 @@
 #include <omp.h>
 
 #include "find_groups.h"
+#include "patch_plan.h"
 
 extern "C" {
 
@@ -774,5 +775,96 @@ int64_t alfi_host_find_groups(int bs, int64_t nbrows, int64_t npatch, const int6
                               const int32_t* rowptr, const int32_t* colidx, int32_t* group_out) {
   return alfi_find_groups_host(bs, nbrows, npatch, patch_ptr, patch_dofs, rowptr, colidx, group_out);
 }
+
+}  // extern "C"
+
+// The planners of alfi_patches_set / _set_groups / _set_multiplicative (patch_plan.h) on host arrays: the CPU leg of their
+// tests.  Each returns a handle (never NULL); alfi_host_plan_status gives the planner's code and message, alfi_host_plan_table
+// enumerates what it built, alfi_host_plan_free releases it.
+struct alfi_host_plan {
+  PatchLayout lay;
+  CondPlan cond;
+  SweepPlan sweep;
+  int rc = 0;
+  std::string err;
+  struct Entry {
+    const char* name;
+    const void* ptr;
+    int64_t count;   // -1: a scalar (one int64, kept in value)
+    int item;
+    int64_t value;
+  };
+  std::vector<Entry> tab;
+  template <class T>
+  void table(const char* name, const std::vector<T>& v) { tab.push_back({name, v.data(), (int64_t)v.size(), (int)sizeof(T), 0}); }
+  void scalar(const char* name, int64_t v) { tab.push_back({name, nullptr, -1, 8, v}); }
+};
+#define ALFI_PLAN_TABLE(s, f) h->table(#f, h->s.f)
+#define ALFI_PLAN_SCALAR(s, f) h->scalar(#f, (int64_t)h->s.f)
+
+extern "C" {
+
+alfi_host_plan* alfi_host_plan_patch_layout(int64_t n, int64_t npatch, const int64_t* patch_ptr, const int32_t* patch_dofs) {
+  alfi_host_plan* h = new alfi_host_plan();
+  h->rc = plan_patch_layout(n, npatch, patch_ptr, patch_dofs, PATCH_MAX, &h->lay, &h->err);
+  if (h->rc != 0) return h;
+  ALFI_PLAN_TABLE(lay, inv_ptr); ALFI_PLAN_TABLE(lay, stage_ptr); ALFI_PLAN_TABLE(lay, dof_ptr); ALFI_PLAN_TABLE(lay, dof_pos);
+  ALFI_PLAN_SCALAR(lay, sum_n); ALFI_PLAN_SCALAR(lay, sum_n2); ALFI_PLAN_SCALAR(lay, inv_doubles);
+  ALFI_PLAN_SCALAR(lay, stage_len); ALFI_PLAN_SCALAR(lay, max_np);
+  return h;
+}
+
+alfi_host_plan* alfi_host_plan_condensed(int bs, int64_t nbrows, int64_t npatch, const int64_t* patch_ptr, const int32_t* patch_dofs,
+                                         const int32_t* group, const int32_t* rowptr, const int32_t* colidx) {
+  alfi_host_plan* h = new alfi_host_plan();
+  h->rc = plan_condensed(bs, nbrows, npatch, patch_ptr, patch_dofs, group, rowptr, colidx, COND_SIGMA_ROWS, &h->cond, &h->err);
+  if (h->rc != 0) return h;
+  ALFI_PLAN_TABLE(cond, dofs); ALFI_PLAN_TABLE(cond, slot); ALFI_PLAN_TABLE(cond, gptr); ALFI_PLAN_TABLE(cond, g_off);
+  ALFI_PLAN_TABLE(cond, g_m); ALFI_PLAN_TABLE(cond, g_sc); ALFI_PLAN_TABLE(cond, g_uoff); ALFI_PLAN_TABLE(cond, g_mat);
+  ALFI_PLAN_TABLE(cond, g_sidx); ALFI_PLAN_TABLE(cond, sidx); ALFI_PLAN_TABLE(cond, p_nI); ALFI_PLAN_TABLE(cond, sptr);
+  ALFI_PLAN_TABLE(cond, sinv_ptr); ALFI_PLAN_TABLE(cond, s_uptr); ALFI_PLAN_TABLE(cond, s_uidx); ALFI_PLAN_TABLE(cond, order);
+  ALFI_PLAN_TABLE(cond, chptr); ALFI_PLAN_TABLE(cond, ch_patch); ALFI_PLAN_TABLE(cond, ch_row); ALFI_PLAN_TABLE(cond, uptr);
+  ALFI_PLAN_TABLE(cond, u_dst); ALFI_PLAN_TABLE(cond, xp_ptr); ALFI_PLAN_TABLE(cond, xp_grp); ALFI_PLAN_TABLE(cond, g_xp);
+  ALFI_PLAN_TABLE(cond, bp_ptr); ALFI_PLAN_TABLE(cond, bp_grp); ALFI_PLAN_TABLE(cond, g_bp); ALFI_PLAN_TABLE(cond, gcptr);
+  ALFI_PLAN_TABLE(cond, gc);
+  ALFI_PLAN_SCALAR(cond, ngroups); ALFI_PLAN_SCALAR(cond, mat_doubles); ALFI_PLAN_SCALAR(cond, sinv_doubles);
+  ALFI_PLAN_SCALAR(cond, lds_bytes); ALFI_PLAN_SCALAR(cond, lds_front);
+  ALFI_PLAN_SCALAR(cond, lds_back); ALFI_PLAN_SCALAR(cond, lds_gfront); ALFI_PLAN_SCALAR(cond, lds_gback);
+  ALFI_PLAN_SCALAR(cond, max_s); ALFI_PLAN_SCALAR(cond, max_m); ALFI_PLAN_SCALAR(cond, max_pairs); ALFI_PLAN_SCALAR(cond, umax);
+  return h;
+}
+
+alfi_host_plan* alfi_host_plan_sweep(int bs, int64_t nbrows, int64_t npatch, const int64_t* patch_ptr, const int32_t* patch_dofs,
+                                     const int32_t* rowptr, const int32_t* colidx, int64_t nit, const int64_t* iterset,
+                                     int symmetrise) {
+  alfi_host_plan* h = new alfi_host_plan();
+  bool big = false;
+  h->rc = check_sweep(bs, npatch, patch_ptr, patch_dofs, SMALL_PATCH_MAX, nit, iterset, &big, &h->err);
+  if (h->rc == 0)
+    h->rc = plan_sweep(bs, nbrows, npatch, patch_ptr, patch_dofs, rowptr, colidx, nit, iterset, symmetrise != 0, big, &h->sweep,
+                       &h->err);
+  if (h->rc != 0) return h;
+  ALFI_PLAN_TABLE(sweep, seq); ALFI_PLAN_TABLE(sweep, wave_ptr); ALFI_PLAN_TABLE(sweep, items); ALFI_PLAN_TABLE(sweep, pred0);
+  ALFI_PLAN_TABLE(sweep, succ_ptr); ALFI_PLAN_TABLE(sweep, succ); ALFI_PLAN_TABLE(sweep, rowtab);
+  ALFI_PLAN_SCALAR(sweep, big); ALFI_PLAN_SCALAR(sweep, nitems);
+  return h;
+}
+#undef ALFI_PLAN_TABLE
+#undef ALFI_PLAN_SCALAR
+
+int alfi_host_plan_status(const alfi_host_plan* h, const char** message) {
+  if (message) *message = h->err.c_str();
+  return h->rc;
+}
+
+// table i of the plan: 0, or -1 past the last one
+int alfi_host_plan_table(const alfi_host_plan* h, int64_t i, const char** name, const void** ptr, int64_t* count, int* item_size) {
+  if (i < 0 || i >= (int64_t)h->tab.size()) return -1;
+  const alfi_host_plan::Entry& e = h->tab[(size_t)i];
+  *name = e.name; *ptr = e.count < 0 ? &e.value : e.ptr; *count = e.count; *item_size = e.item;
+  return 0;
+}
+
+void alfi_host_plan_free(alfi_host_plan* h) { delete h; }
 
 }  // extern "C"

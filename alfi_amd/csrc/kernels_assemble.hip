@@ -1231,7 +1231,7 @@ int launch_burman(alfi_level* L, double weight, const double* d_state, bool add_
 int launch_patch_facet_correct(alfi_level* L, int64_t p0, int64_t nb, const int64_t* mat_ptr, double* dst, int big) {
   alfi_ctx* ctx = L->ctx;
   if (nb <= 0) return 0;
-  const int64_t nn = (L->max_np / L->bs + 63) / 64;
+  const int64_t nn = (L->lay.max_np / L->bs + 63) / 64;
   for (int64_t b0 = 0; b0 < nb; b0 += 65535) {        // (grid y <= 65535)
     const int64_t nbb = std::min<int64_t>(65535, nb - b0);
     dim3 grid((unsigned)std::max<int64_t>(nn, 1), (unsigned)nbb), block(64);

@@ -688,9 +688,9 @@ int launch_big_mult_persistent(alfi_level* L, const double* x, double* y) {
     ctx->big_mult_ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 64;
   }
   const int pc = std::max(1, ctx->big_mult_per_cu[L->bs == 3 ? 1 : 0]);
-  dim3 grid((unsigned)std::min<int64_t>(L->mult_nitems, (int64_t)ctx->big_mult_ncu * pc)), block(256);
+  dim3 grid((unsigned)std::min<int64_t>(L->sweep.nitems, (int64_t)ctx->big_mult_ncu * pc)), block(256);
 #define ALFI_BPM(BSV)                                                                                                     \
-  hipLaunchKernelGGL((big_mult_persistent_kernel<BSV, true>), grid, block, 0, ctx->stream, L->mult_nitems, L->mult_items, \
+  hipLaunchKernelGGL((big_mult_persistent_kernel<BSV, true>), grid, block, 0, ctx->stream, L->sweep.nitems, L->mult_items, \
                      L->mult_pred, L->mult_succ_ptr, L->mult_succ, L->mult_ctl, ctx->dev_err, L->patch_ptr, L->patch_dofs, \
                      L->inv_ptr, L->inv, L->A.rowptr, L->A.colidx, L->A.vals, L->A.flat, x, y)
   if (L->bs == 2) ALFI_BPM(2);
@@ -736,7 +736,7 @@ int launch_big_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double* 
   alfi_ctx* ctx = L->ctx;
   if (p1 <= p0) return 0;
   constexpr bool nt = true;      // factors are read once per apply: nontemporal loads
-  const int split = big_split(p1 - p0, L->max_np);
+  const int split = big_split(p1 - p0, L->lay.max_np);
   dim3 grid((unsigned)((p1 - p0) * split)), block(256);
   if (nt)
     hipLaunchKernelGGL(big_apply_kernel<true>, grid, block, 0, ctx->stream, p0, p1, L->patch_ptr, L->patch_dofs, L->inv_ptr,
@@ -1533,7 +1533,7 @@ struct BigSource {
     if (M) {
       mf_fill_dispatch(M, ctx, p0, nb, d_scr_ptr, dst);
     } else if (K) {
-      const size_t lds = (size_t)(3 * K->max_np) * sizeof(int32_t);
+      const size_t lds = (size_t)(3 * K->lay.max_np) * sizeof(int32_t);
       if (K->bs == 2)
         hipLaunchKernelGGL(cond_fill_kernel<2>, dim3((unsigned)nb), block, lds, ctx->stream, p0, K->cd, K->patch_ptr,
                            K->patch_dofs, K->A.rowptr, K->A.colidx, K->A.vals, K->A.flat, d_scr_ptr, dst, K->status);
@@ -1541,13 +1541,13 @@ struct BigSource {
         hipLaunchKernelGGL(cond_fill_kernel<3>, dim3((unsigned)nb), block, lds, ctx->stream, p0, K->cd, K->patch_ptr,
                            K->patch_dofs, K->A.rowptr, K->A.colidx, K->A.vals, K->A.flat, d_scr_ptr, dst, K->status);
       // groups of the patches [p0, p0 + nb)
-      const int64_t ga = K->h_cond_gptr[p0], gb = K->h_cond_gptr[p0 + nb];
+      const int64_t ga = K->cplan.gptr[p0], gb = K->cplan.gptr[p0 + nb];
       if (gb > ga && pivot_groups) {
         const size_t glds = (size_t)(COND_GMAX * COND_GMAX + 64 * COND_GMAX) * sizeof(double) + COND_GMAX * sizeof(int);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cond_group_pivot_kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds);
         hipLaunchKernelGGL(cond_group_pivot_kernel, dim3((unsigned)(gb - ga)), dim3(64), glds, ctx->stream, ga, K->cd, K->status);
-      } else if (gb > ga && K->cond_max_m <= 16)
+      } else if (gb > ga && K->cplan.max_m <= 16)
         hipLaunchKernelGGL(cond_group16_kernel, dim3((unsigned)((gb - ga + 15) / 16)), block, 0, ctx->stream, ga, gb, K->cd,
                            K->status);
       else if (gb > ga)
@@ -1741,7 +1741,7 @@ static int big_factor_core(alfi_ctx* ctx, const BigSource& src, int64_t npatch, 
 int launch_big_factor(alfi_level* L) {
   BigSource src;
   src.L = L;
-  return big_factor_core(L->ctx, src, L->npatch, L->h_patch_ptr.data(), L->patch_ptr, L->inv_ptr, L->inv, L->status);
+  return big_factor_core(L->ctx, src, L->npatch, L->lay.patch_ptr.data(), L->patch_ptr, L->inv_ptr, L->inv, L->status);
 }
 
 // interior blocks of a transfer with 160 < m <= 4096 (macro-cell blocks of the 3-D Scott-Vogelius transfer, m = 390 for P3)
@@ -1780,7 +1780,7 @@ int launch_coarse_factor(alfi_level* L, double* out) {
 int launch_cond_factor(alfi_level* L) {
   BigSource src;
   src.K = L;
-  return big_factor_core(L->ctx, src, L->npatch, L->h_sptr.data(), L->cd.sptr, L->cd.sinv_ptr, L->cd.sinv, L->status);
+  return big_factor_core(L->ctx, src, L->npatch, L->cplan.sptr.data(), L->cd.sptr, L->cd.sinv_ptr, L->cd.sinv, L->status);
 }
 
 // the group matrices of ONE condensed patch again -- X_g, W_g by LU with partial pivoting -- and its Schur complement into scr
@@ -1816,11 +1816,11 @@ int launch_cond_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double*
   // full-range launches walk the patches largest first (workgroups are dispatched in index order: with ~7 patches per CU at
   // config 5's size the big patches must not come last); range launches (overlapped exchanges) keep the natural order
   const int ordered = p0 == 0 && p1 == L->npatch && L->cd.order ? 1 : 0;
-  const int64_t c0 = L->h_cond_chptr[p0], c1 = L->h_cond_chptr[p1];
+  const int64_t c0 = L->cplan.chptr[p0], c1 = L->cplan.chptr[p1];
   if (p1 - p0 < 1024) {
-    const int64_t k0 = L->h_cond_gcptr[p0], k1 = L->h_cond_gcptr[p1];
-    const size_t lds_f = (size_t)L->cond_lds_gfront, lds_b = (size_t)L->cond_lds_gback;
-    const size_t lds_s = (size_t)(L->cond_max_s + 2 + COND_SIGMA_ROWS) * sizeof(double);
+    const int64_t k0 = L->cplan.gcptr[p0], k1 = L->cplan.gcptr[p1];
+    const size_t lds_f = (size_t)L->cplan.lds_gfront, lds_b = (size_t)L->cplan.lds_gback;
+    const size_t lds_s = (size_t)(L->cplan.max_s + 2 + COND_SIGMA_ROWS) * sizeof(double);
     if (k1 > k0)
       hipLaunchKernelGGL((cond_gfront_kernel<false>), dim3((unsigned)(k1 - k0)), dim3(256), lds_f, ctx->stream, k0, L->cd, x);
     if (c1 > c0)
@@ -1832,8 +1832,8 @@ int launch_cond_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double*
     ALFI_HIP_CHECK(ctx, hipGetLastError());
     return 0;
   }
-  const size_t lds_f = (size_t)L->cond_lds_front, lds_s = (size_t)(L->cond_max_s + 2) * sizeof(double);
-  const size_t lds_b = (size_t)L->cond_lds_back;
+  const size_t lds_f = (size_t)L->cplan.lds_front, lds_s = (size_t)(L->cplan.max_s + 2) * sizeof(double);
+  const size_t lds_b = (size_t)L->cplan.lds_back;
 #define ALFI_COND_LAUNCH3(WV)                                                                                             \
   do {                                                                                                                    \
     if (lds_f > 64 * 1024)                                                                                                \
@@ -1856,9 +1856,9 @@ int launch_cond_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double*
 #ifdef ALFI_COND_WAVES_FORCE      // A/B builds only (scripts/build_variant.sh): every launch with this many waves per patch
   ALFI_COND_LAUNCH3(ALFI_COND_WAVES_FORCE);
 #else
-  if (L->cond_max_pairs <= 64) ALFI_COND_LAUNCH3(1);
-  else if (L->cond_max_pairs <= 128) ALFI_COND_LAUNCH3(2);
-  else if (L->cond_max_pairs <= 256) ALFI_COND_LAUNCH3(4);
+  if (L->cplan.max_pairs <= 64) ALFI_COND_LAUNCH3(1);
+  else if (L->cplan.max_pairs <= 128) ALFI_COND_LAUNCH3(2);
+  else if (L->cplan.max_pairs <= 256) ALFI_COND_LAUNCH3(4);
   else ALFI_COND_LAUNCH3(8);
 #endif
 #undef ALFI_COND_LAUNCH3

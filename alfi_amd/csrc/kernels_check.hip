@@ -293,7 +293,7 @@ static int launch_check(alfi_level* L, double tol) {
   hipLaunchKernelGGL(probe_fill_kernel, dim3(1024), dim3(256), 0, ctx->stream, e, L->n);
   int rc = launch_patch_apply_range(L, 0, L->npatch, e);
   if (rc == 0) {
-    const size_t lds = (size_t)L->max_np * (sizeof(double) + sizeof(int32_t));
+    const size_t lds = (size_t)L->lay.max_np * (sizeof(double) + sizeof(int32_t));
     unsigned long long* worst = reinterpret_cast<unsigned long long*>(L->chk);
     int* nflag = reinterpret_cast<int*>(L->chk + 1);
     dim3 grid((unsigned)L->npatch), block(256);
@@ -331,7 +331,7 @@ static int read_check(alfi_level* L, double* worst, int* nflag) {
 // round 3 repaired the Schur complement only, so a bad pivot inside one macro-cell group still did).
 static int cond_repair(alfi_level* L, double tol, int nflag, double worst) {
   alfi_ctx* ctx = L->ctx;
-  const int smax = L->cond_max_s;
+  const int smax = L->cplan.max_s;
   if (smax > 4096)
     return alfi_set_error(ctx, ALFI_E_SINGULAR, "%d condensed patch factors fail the residual probe (worst %.3e) and the "
                           "pivoted repair handles Schur complements of at most 4096 dofs", nflag, worst);
@@ -353,7 +353,7 @@ static int cond_repair(alfi_level* L, double tol, int nflag, double worst) {
   int rc = e == hipSuccess ? 0 : alfi_set_error(ctx, ALFI_E_HIP, "condensed repair: %s", hipGetErrorString(e));
   for (int i = 0; i < nflag && rc == 0; ++i) {
     const int64_t p = list[(size_t)i];
-    const int sp = (int)(L->h_sptr[p + 1] - L->h_sptr[p]);
+    const int sp = (int)(L->cplan.sptr[p + 1] - L->cplan.sptr[p]);
     if (sp == 0) continue;
     rc = launch_cond_schur_one(L, p, zero, sig);
     if (rc != 0) break;
@@ -419,16 +419,16 @@ int patch_verify_and_repair(alfi_level* L, int unpivoted_status) {
   // a Burman level: the repair subtracts the facet terms PCPATCH leaves out from the gathered matrix (RepairFacetRule)
   RepairFacetRule fc;
   if (L->fc_ptr && L->fc_scale != 0.0) fc = RepairFacetRule{L->fc_ptr, L->fc_col, L->fc_fac, L->fc_s, L->fc_beta, L->fc_scale};
-  if (L->max_np > REPAIR_MAX_NP)
+  if (L->lay.max_np > REPAIR_MAX_NP)
     return alfi_set_error(ctx, ALFI_E_SINGULAR, "%d patch inverses fail the residual probe (worst %.3e) and the pivoted "
                           "repair handles patches of at most %d dofs", nflag, worst, (int)REPAIR_MAX_NP);
   // pivoted re-inversion of the flagged patches, in batches bounded by 1 GiB of scratch
-  const int64_t stride = 2 * (int64_t)L->max_np * L->max_np;      // L \ U and the inverse being built
+  const int64_t stride = 2 * (int64_t)L->lay.max_np * L->lay.max_np;      // L \ U and the inverse being built
   const int64_t per_batch = std::max<int64_t>(1, ((int64_t)1 << 27) / stride);
   double* scratch = nullptr;
   ALFI_HIP_CHECK(ctx, hipMalloc((void**)&scratch, sizeof(double) * (size_t)(std::min<int64_t>(per_batch, nflag) * stride)));
   ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->status, 0, sizeof(int), ctx->stream));
-  const size_t lds = (size_t)L->max_np * (2 * sizeof(double) + 2 * sizeof(int32_t));
+  const size_t lds = (size_t)L->lay.max_np * (2 * sizeof(double) + 2 * sizeof(int32_t));
   int rc = 0;
   if (lds > 64 * 1024) {     // beyond the default dynamic LDS limit (gfx950: 160 KB per CU)
     hipError_t ea = L->bs == 2 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_repair_kernel<2, false>),

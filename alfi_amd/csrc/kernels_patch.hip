@@ -921,7 +921,7 @@ int launch_patch_invert_arrays(alfi_ctx* ctx, int64_t npatch, int max_np, const 
 }
 
 int launch_patch_invert(alfi_level* L) {
-  return launch_patch_invert_arrays(L->ctx, L->npatch, L->max_np, L->patch_ptr, L->inv_ptr, L->inv, L->status);
+  return launch_patch_invert_arrays(L->ctx, L->npatch, L->lay.max_np, L->patch_ptr, L->inv_ptr, L->inv, L->status);
 }
 
 // stage[stage_ptr[p] + r] = sum_c inv_p[r][c] x[patch_dofs[patch_ptr[p] + c]] for npatch row-piece inverses of size <= 160
@@ -938,7 +938,7 @@ int launch_patch_apply_arrays(alfi_ctx* ctx, int64_t npatch, const int64_t* patc
 int launch_patch_mult_wave(alfi_level* L, const int32_t* seq, int64_t count, const double* x, double* y) {
   alfi_ctx* ctx = L->ctx;
   if (count == 0) return 0;
-  if (L->mult_big) return launch_big_mult_wave(L, seq, count, x, y);
+  if (L->sweep.big) return launch_big_mult_wave(L, seq, count, x, y);
   dim3 grid((unsigned)count), block(MULT_NTHR);
 #define ALFI_MULT(BSV, NTV)                                                                                           \
   hipLaunchKernelGGL((patch_mult_kernel<BSV, NTV>), grid, block, 0, ctx->stream, count, seq, L->patch_ptr,            \
@@ -968,12 +968,12 @@ extern "C" int64_t alfi_debug_mult_stamps(int64_t* out, int64_t nitems) {
 
 int launch_patch_mult_persistent(alfi_level* L, const double* x, double* y) {
   alfi_ctx* ctx = L->ctx;
-  if (L->mult_nitems == 0) return 0;
+  if (L->sweep.nitems == 0) return 0;
   // fresh counters for this apply: predecessor counts and the ticket (the error word is the ctx's, sticky)
-  ALFI_HIP_CHECK(ctx, hipMemcpyAsync(L->mult_pred, L->mult_pred0, sizeof(int32_t) * (size_t)L->mult_nitems,
+  ALFI_HIP_CHECK(ctx, hipMemcpyAsync(L->mult_pred, L->mult_pred0, sizeof(int32_t) * (size_t)L->sweep.nitems,
                                      hipMemcpyDeviceToDevice, ctx->stream));
   ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->mult_ctl, 0, 4 * sizeof(int32_t), ctx->stream));
-  if (L->mult_big) return launch_big_mult_persistent(L, x, y);      // macro stars: a workgroup per item (kernels_bigpatch.hip)
+  if (L->sweep.big) return launch_big_mult_persistent(L, x, y);      // macro stars: a workgroup per item (kernels_bigpatch.hip)
   // a resident grid: as many workgroups per CU as the kernel's registers and LDS admit (every ticket holder must be running;
   // more workgroups in flight = more of the next wavefronts' independent patches started early)
   // (per ctx -- ADVICE r4: function-local statics sized every later ctx's grid from the first ctx's device)
@@ -987,19 +987,19 @@ int launch_patch_mult_persistent(alfi_level* L, const double* x, double* y) {
     ctx->mult_ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 64;
   }
   const int pc = std::max(1, std::min(ctx->mult_per_cu[L->bs == 3 ? 1 : 0], ALFI_MULT_WG_PER_CU));
-  dim3 grid((unsigned)std::min<int64_t>(L->mult_nitems, (int64_t)ctx->mult_ncu * pc)), block(MULT_NTHR);
+  dim3 grid((unsigned)std::min<int64_t>(L->sweep.nitems, (int64_t)ctx->mult_ncu * pc)), block(MULT_NTHR);
 #ifdef ALFI_MULT_TIMING
-  if (g_mult_stamps_n < L->mult_nitems) {
+  if (g_mult_stamps_n < L->sweep.nitems) {
     if (g_mult_stamps) (void)hipFree(g_mult_stamps);
-    ALFI_HIP_CHECK(ctx, hipMalloc(&g_mult_stamps, sizeof(int64_t) * 8 * (size_t)L->mult_nitems));
-    g_mult_stamps_n = L->mult_nitems;
+    ALFI_HIP_CHECK(ctx, hipMalloc(&g_mult_stamps, sizeof(int64_t) * 8 * (size_t)L->sweep.nitems));
+    g_mult_stamps_n = L->sweep.nitems;
   }
 #define ALFI_PMULT_STAMPS , g_mult_stamps
 #else
 #define ALFI_PMULT_STAMPS
 #endif
 #define ALFI_PMULT(BSV)                                                                                                   \
-  hipLaunchKernelGGL((patch_mult_persistent_kernel<BSV, true>), grid, block, 0, ctx->stream, L->mult_nitems, L->mult_items, \
+  hipLaunchKernelGGL((patch_mult_persistent_kernel<BSV, true>), grid, block, 0, ctx->stream, L->sweep.nitems, L->mult_items, \
                      L->mult_pred, L->mult_succ_ptr, L->mult_succ, L->mult_ctl, ctx->dev_err, L->patch_ptr,               \
                      L->patch_dofs, L->inv_ptr, L->inv, L->mult_rowtab, L->A.colidx, L->A.vals, L->A.flat, x, y ALFI_PMULT_STAMPS)
   if (L->bs == 2) ALFI_PMULT(2);
@@ -1027,7 +1027,7 @@ int launch_patch_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double
   // against 8.6 us).  Config 3: 17.27 -> 17.1 ms per cycle, same box.
   // (ALFI_TEST_LARGE_PATHS: no level counts as small, so that test hierarchies take the kernels of the large levels)
   const int64_t few = alfi_test_large_paths() ? 0 : 1000, fewer = alfi_test_large_paths() ? 0 : 256;
-  if (L->max_np > SMALL_PATCH_MAX || (L->max_np > 64 && L->npatch <= fewer)) {     // kernels_bigpatch.hip
+  if (L->lay.max_np > SMALL_PATCH_MAX || (L->lay.max_np > 64 && L->npatch <= fewer)) {     // kernels_bigpatch.hip
     ALFI_CHECK(launch_big_apply_range(L, p0, p1, x));
     return 0;
   }
@@ -1050,10 +1050,10 @@ int launch_patch_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double
     }
 #undef ALFI_IL
   } else {
-    if (L->max_np > 128 || (L->max_np > 64 && L->npatch <= few))
+    if (L->lay.max_np > 128 || (L->lay.max_np > 64 && L->npatch <= few))
       hipLaunchKernelGGL((patch_apply_kernel<true, 2 * APPLY_W>), dim3((unsigned)cnt), dim3(128 * APPLY_W), 0, ctx->stream, p0,
                          p1, L->patch_ptr, L->patch_dofs, L->inv_ptr, L->stage_ptr, L->inv, x, L->stage);
-    else if (L->max_np > 64)
+    else if (L->lay.max_np > 64)
       hipLaunchKernelGGL((patch_apply_kernel<true, APPLY_W>), dim3((unsigned)cnt), dim3(64 * APPLY_W), 0, ctx->stream, p0, p1,
                          L->patch_ptr, L->patch_dofs, L->inv_ptr, L->stage_ptr, L->inv, x, L->stage);
     else
@@ -1083,10 +1083,10 @@ int launch_patch_sum(alfi_level* L, const double* x, double* y) { return launch_
 int build_patch_il(alfi_level* L) {
   alfi_ctx* ctx = L->ctx;
   L->il_valid = false;
-  if (L->cond || L->npatch == 0 || L->max_np > 32 || L->inv_shrunk) return 0;
-  const int need = (L->max_np + 1) / 2;
+  if (L->cond || L->npatch == 0 || L->lay.max_np > 32 || L->inv_shrunk) return 0;
+  const int need = (L->lay.max_np + 1) / 2;
   const int G = need <= 4 ? 4 : need <= 7 ? 7 : need <= 8 ? 8 : need <= 12 ? 12 : 16;
-  const int PW = 64 / G, LW = PW * G, nc = L->max_np;
+  const int PW = 64 / G, LW = PW * G, nc = L->lay.max_np;
   const int64_t ngroups = (L->npatch + PW - 1) / PW;
   const int64_t total = ngroups * nc * LW;          // 16-byte entries
   if (!L->inv_il || L->il_doubles != 2 * total) {

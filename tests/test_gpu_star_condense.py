@@ -91,6 +91,22 @@ def test_find_groups_on_the_device_level(cctx, dctx, hier):
     assert out["condensed"] <= 0.46 * out["dense"]
 
 
+@pytest.mark.parametrize("name", ["b", "a"])
+def test_the_device_level_plans_with_the_code_the_host_library_exports(dctx, name):
+    """csrc/patch_plan.h once in each library: the level's factor bytes and wavefront count are those of the host plan of the
+    same inputs (tests/patch_plan_cases.py: b = this file's N = 4 level as a hierarchy of its own, a = 2-D Scott-Vogelius)."""
+    from tests.patch_plan_cases import case, plans
+    L, groups, iterset = case(name)
+    pl = plans(name)
+    dl = _level(dctx, L)
+    dl.set_patch_groups(groups)
+    assert dl.condensed() == 1
+    assert dl.factor_bytes() == 8 * (pl["cond"]["mat_doubles"] + pl["cond"]["sinv_doubles"])
+    dl.set_patch_groups(None)                                                  # sweeps read dense inverses
+    assert dl.set_multiplicative(iterset, True) == len(pl["sweep"]["wave_ptr"]) - 1
+    dl.close()
+
+
 @pytest.mark.parametrize("shape", ["N4", "N8", "N8-twice"])
 def test_condensed_apply_equals_dense_apply(cctx, dctx, hier, shape):
     from oracle import alfi_oracle as O
