@@ -274,16 +274,17 @@ int alfi_patches_factor(alfi_level* L) {
   alfi_ctx* ctx = L->ctx;
   if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_factor before alfi_patches_set");
   if (!L->cond_decided) {
-    // first factorisation of a patch set the caller gave no groups for: a serial, additive level whose dense inverses would take
+    // first factorisation of a patch set the caller gave no groups for: an additive level whose dense inverses would take
     // condense_min_bytes or more looks for groups in its own sparsity (find_groups.h) and stores condensed factors if it finds
-    // any.
+    // any.  On a partitioned level all of this is the rank's own business: its patches (ghost dofs included: the local operator
+    // holds their rows over the local columns), its sparsity, its inverse bytes against the threshold -- no collective, and
+    // ranks of one level may decide differently (the block factorisation is exact for any valid grouping).
     L->cond_decided = true;
     const int64_t thr = ctx->condense_min_bytes;
-    const bool serial = L->n_own == L->n && !L->distributed && !L->has_halo;
     // (never a Burman level: its sparsity couples cells across facets, alfi_level_set_facet_blocks, and PCPATCH's facet rule,
     // alfi_patches_set_facet_correction, changes the patch matrices)
     const bool facets = L->facet_blocks || L->fc_ptr;
-    if (thr >= 0 && !L->cond && !L->mult && serial && !facets && L->npatch > 0 && 8 * L->lay.inv_doubles >= thr) {
+    if (thr >= 0 && !L->cond && !L->mult && !facets && L->npatch > 0 && 8 * L->lay.inv_doubles >= thr) {
       std::vector<int32_t> group((size_t)L->lay.sum_n), rowptr, colidx;
       int64_t grouped = 0;
       ALFI_CHECK(find_groups(L, group.data(), &grouped, &rowptr, &colidx));

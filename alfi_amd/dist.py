@@ -780,12 +780,16 @@ class DistMultigrid(object):
 
     def __init__(self, levels, transfers, k, robust_restriction=False, group=None, device=None, min_dofs=400000,
                  coarse_inverse=None, verbose=False, force_distributed=False, overlap=None, overlap_min_dofs=None,
-                 transport=None, on_stage=None, use_overlap_rule=True, solo=None, full_cycle=False):
+                 transport=None, on_stage=None, use_overlap_rule=True, solo=None, full_cycle=False,
+                 condense_min_bytes=None):
         """transport: "rccl" -- the library's own RCCL communicator serves every exchange point of a cycle (no Python
         between the kernels; the default whenever the process group's backend is nccl) -- or "callback": the library
         calls back into this module, which exchanges through torch.distributed (the test transport: gloo, ranks sharing
         a GPU).  ALFI_DIST_TRANSPORT overrides.  on_stage(name): called at "partition", "localize", "comm_init",
-        "upload_factor" (bench.py's per-rank stage markers); ``setup_s`` holds the seconds each took."""
+        "upload_factor" (bench.py's per-rank stage markers); ``setup_s`` holds the seconds each took.
+        condense_min_bytes: a level whose RANK-LOCAL dense star inverses would take at least this many bytes finds groups in its
+        own sparsity and stores condensed factors (Context.set_condense_min_bytes, set before the first factorisation; None: the
+        library's default, 0: wherever groups are found, < 0: never).  ``patch_storage()`` reports what every local level decided."""
         import time
         import torch
         from . import hip
@@ -833,6 +837,8 @@ class DistMultigrid(object):
         self.k = k
         with torch.cuda.stream(self.stream):
             self.ctx = ctx = hip.Context(device.index or 0, stream=self.stream.cuda_stream)
+            if condense_min_bytes is not None:
+                ctx.set_condense_min_bytes(condense_min_bytes)
             if transport == "rccl":
                 from . import _lib
                 stage("comm_init")
@@ -864,6 +870,7 @@ class DistMultigrid(object):
                     inner = float("inf")
                     if LL is not None and LL.level > 0 and p.nb_own > 0:
                         sizes = np.diff(np.asarray(LL.patch_ptr[:LL.npatch_int + 1], dtype=np.int64)).astype(np.float64)
+                        # (the bytes of DENSE inverses: an overestimate by about 2 on a level that condenses itself)
                         inner = 8.0 * float((sizes * sizes).sum())
                     mine.append((msg, inner))
                 every = self.comm.all_gather_object(mine)
@@ -892,9 +899,14 @@ class DistMultigrid(object):
                     dl.set_patches(LL.patch_ptr, LL.patch_dofs)
                     if getattr(LL, "patch_groups", None) is not None and env.condense():
                         dl.set_patch_groups(LL.patch_groups)
-                    elif not env.condense():
+                    elif not env.condense() or getattr(levels[LL.level], "facet_coupling", False):
+                        # dense inverses, also where the level would find groups itself (ALFI_CONDENSE=0; Burman levels:
+                        # PCPATCH's facet rule changes the patch matrices)
                         dl.set_patch_groups(None)
-                    hip.note_patch_level(LL, dl)       # (a level that is not partitioned may find groups by itself)
+                    # From here on the device level records on LL what it stores, after every factorisation: a level whose
+                    # rank-local dense inverses reach the context's threshold finds groups by itself at its first one (here,
+                    # or the caller's first refactor() when the operators are formed on the device), partitioned or not.
+                    hip.note_patch_level(LL, dl)
                     if LL.A.vals is not None:          # (None: the operators are formed on the device first, the caller factors)
                         dl.factor_with_fallback()
                     decided = rule[LL.level] if use_rule else overlap_decision(p.splits, p.bs, p.distributed, overlap,
@@ -991,6 +1003,13 @@ class DistMultigrid(object):
                         dl.factor_with_fallback()
                 elif LL.part.nb_own > 0:
                     self._coarse(dl, levels[0].A if levels is not None else None, coarse_inverse)
+
+    def patch_storage(self):
+        """Per local level (``local_levels``; the coarsest and levels without owned patches: None) the pair (mode, factor bytes):
+        mode 0 dense inverses, 1 condensed factors on the generator's groups, 2 on groups the level found itself
+        (hip.Level.condensed(), final after the first factorisation of the level)."""
+        return [(dl.condensed(), dl.factor_bytes()) if LL.level > 0 and len(LL.patch_ptr) > 1 else None
+                for dl, LL in zip(self.levels, self.local_levels)]
 
     def local_vec(self, global_array=None):
         """Device vector of the finest level in local numbering (owned + ghost slots), filled from a global array."""

@@ -148,10 +148,12 @@ class DistNavierStokesSolver(HipNavierStokesSolver):
 
     _partitioned = True
 
-    def __init__(self, *args, min_dofs=400000, group=None, device_state=True, **kwargs):
+    def __init__(self, *args, min_dofs=400000, group=None, device_state=True, condense_min_bytes=None, **kwargs):
         """device_state False: the Newton state replicated on the hosts, every level's state formed there (``_winds``) and
-        uploaded, residual and update gathered after every step (the loop of round 4; kept for comparisons)."""
+        uploaded, residual and update gathered after every step (the loop of round 4; kept for comparisons).
+        condense_min_bytes: DistMultigrid's (None: the library's default threshold for condensing vertex-star factors)."""
         self._min_dofs, self._group, self._want_device_state = min_dofs, group, bool(device_state)
+        self._condense_min_bytes = condense_min_bytes
         super().__init__(*args, **kwargs)
 
     def _device_state_resident(self):
@@ -174,7 +176,8 @@ class DistNavierStokesSolver(HipNavierStokesSolver):
     def _create_device(self, restriction):
         self.dmg = DistMultigrid(self.levels, self.transfers, self.params["fieldsplit_0"]["mg_levels"]["ksp_max_it"],
                                  robust_restriction=restriction, group=self._group, min_dofs=self._min_dofs,
-                                 full_cycle=self.params["fieldsplit_0"].get("pc_mg_type") == "full")
+                                 full_cycle=self.params["fieldsplit_0"].get("pc_mg_type") == "full",
+                                 condense_min_bytes=self._condense_min_bytes)
         self.ctx = self.dmg.ctx
         L = self.levels[-1]
         self.saddle = sad = DistSaddle(self.dmg, self.B, self.vol, L.V.cell_nodes, self.nu, self.gamma,

@@ -431,6 +431,7 @@ class Level(object):
     def _record_storage(self):
         if self.host_level is not None and self.h:
             self.host_level.patch_storage = self.condensed()
+            self.host_level.patch_factor_bytes = self.factor_bytes()
 
     def find_patch_groups(self):
         """Group labels found from the level's block sparsity (alfi_patches_find_groups): one per entry of patch_dofs, -1 =
@@ -693,9 +694,11 @@ def coarse_inverse(A_bsr):
 
 
 def note_patch_level(L, dl):
-    """``dl`` holds the patches of the host level ``L``: from now on the device level records on ``L`` what it stores
-    (``L.patch_storage`` = ``Level.condensed()``), whenever that can change -- factor(), set_patch_groups(),
-    set_multiplicative(), set_patch_facet_correction()."""
+    """``dl`` holds the patches of the host level ``L`` (a level of the hierarchy, or a rank's dist.LocalLevel): from now on the
+    device level records on ``L`` what it stores (``L.patch_storage`` = ``Level.condensed()``, ``L.patch_factor_bytes`` =
+    ``Level.factor_bytes()``), whenever that can change -- factor(), set_patch_groups(), set_multiplicative(),
+    set_patch_facet_correction().  A level decides at its first factorisation: where the caller factors later (operators formed
+    on the device first), the record follows then."""
     dl.host_level = L
     dl._record_storage()
 
@@ -704,7 +707,8 @@ def condense_patches(L):
     """Whether the level's patch factors are stored condensed: the generator supplied group labels (macro-star patches of
     the Scott-Vogelius hierarchy, sv.macro_cell_groups) and ALFI_CONDENSE is not 0 -- or the device level built from ``L``
     found groups by itself when it factored (vertex stars whose dense inverses would be large) and still uses them
-    (``L.patch_storage == 2``, recorded by the device level: note_patch_level)."""
+    (``L.patch_storage == 2``, recorded by the device level: note_patch_level).  ``L`` may be a rank's local level of a
+    partitioned hierarchy (dist.DistMultigrid.local_levels): the decision is the rank's own."""
     if not env.condense():
         return False
     return getattr(L, "patch_groups", None) is not None or getattr(L, "patch_storage", 0) == 2

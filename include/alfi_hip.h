@@ -292,10 +292,11 @@ int alfi_patches_factor_bytes(alfi_level* lvl, int64_t* bytes);
  * condensed factors take <= 0.75 of the dense inverse's doubles, otherwise (and for patches that are not whole nodes) every
  * label is -1.  [P2+FB]^3 vertex stars of 153 dofs: 6 groups of 15 dofs (a face-centre edge node and the 4 face bubbles of
  * its spokes) over a 63-dof skeleton, 0.435 of the dense doubles.  Deterministic.
- * A level WITHOUT caller-supplied groups (alfi_patches_set_groups never called for the patch set, not partitioned, additive,
+ * A level WITHOUT caller-supplied groups (alfi_patches_set_groups never called for the patch set, additive,
  * no facet blocks and no facet correction: never a Burman level) does this itself at its first alfi_patches_factor if its dense inverses would take at least
  * min_bytes (alfi_ctx_set_condense_min_bytes; default 1 GiB, negative = never) and stores condensed factors when groups were
- * found.  On such a level alfi_patches_set_multiplicative and alfi_patches_set_facet_correction go back to dense inverses
+ * found.  A partitioned level (alfi_level_set_partition) does the same for ITS patches, ghost dofs included, in its local
+ * sparsity and with its own dense bytes against min_bytes: no collective, and the ranks of one level may decide differently.  On such a level alfi_patches_set_multiplicative and alfi_patches_set_facet_correction go back to dense inverses
  * and factor again (multiplicative sweeps with the caller's groups are an error), and alfi_patch_get_inverse assembles the dense inverse from the factors on the host.
  * alfi_patches_condensed: 0 = dense inverses, 1 = the caller's groups, 2 = groups the library found. */
 int alfi_patches_find_groups(alfi_level* lvl, int32_t* group_out_host);

@@ -4,6 +4,12 @@ ghosts, whom it would exchange with and how many bytes per exchange -- the plan 
 
     python scripts/partition_report.py cfg4 --world 8 > profiles/r03_partition_plan_cfg4_8ranks.json
 
+Per rank and smoothed level also what the rank would STORE for its patches: every rank decides for itself at its first
+factorisation (alfi_patches_factor) -- dense inverses below --condense-min-bytes of rank-local dense bytes (default: the library's
+1 GiB, csrc/env.h), else the groups the finder (csrc/find_groups.h) sees in the rank's localised sparsity and the condensed factors
+the planner (csrc/patch_plan.h) lays out for them; both run here on the host through libalfi_host.so.  Levels with generator
+groups or facet coupling are reported as the device path treats them (mode 1 / dense).
+
 (Eight processes cannot share the one GPU of the build box -- the pool allows six -- so the 8-way split of the full-size
 configuration is recorded from the partitioner itself; the 4- and 6-rank runs through tests/mock_rccl execute the same code.)"""
 import argparse
@@ -17,11 +23,36 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def patch_storage(L, part, min_bytes):
+    """(mode, factor bytes, dense bytes) of the rank ``part`` on level ``L``: the decision of alfi_patches_factor on the host."""
+    import copy
+    from alfi_amd import _hostlib, dist as D, env
+    from alfi_amd.problem import BSR
+    Ls = copy.copy(L)
+    Ls.A = BSR(L.A.nbrows, L.A.nbcols, L.bs, L.A.rowptr, L.A.colidx, None)           # the sparsity is all this needs
+    LL = D.localize_level(Ls, part)
+    n = np.diff(LL.patch_ptr)
+    dense = int(8 * ((n * ((n + 1) & ~1) + 15) & ~15).sum())
+    groups, mode = getattr(LL, "patch_groups", None), 1
+    if not env.condense() or getattr(L, "facet_coupling", False) or len(n) == 0:
+        return 0, dense, dense
+    if groups is None:
+        if min_bytes < 0 or dense < min_bytes:
+            return 0, dense, dense
+        groups, mode = _hostlib.find_groups(LL.bs, LL.A.rowptr, LL.A.colidx, LL.patch_ptr, LL.patch_dofs), 2
+        if not (groups >= 0).any():
+            return 0, dense, dense
+    plan = _hostlib.plan_condensed(LL.bs, LL.A.rowptr, LL.A.colidx, LL.patch_ptr, LL.patch_dofs, groups)
+    return mode, int(8 * (plan["mat_doubles"] + plan["sinv_doubles"])), dense
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("config")
     ap.add_argument("--world", type=int, default=8)
     ap.add_argument("--min-dofs", type=int, default=400000)
+    ap.add_argument("--condense-min-bytes", type=int, default=1 << 30, help="rank-local dense bytes from which a level condenses "
+                    "its vertex-star factors itself (default: the library's)")
     args = ap.parse_args()
     import bench
     from alfi_amd import dist as D
@@ -54,7 +85,12 @@ def main():
             nbr = np.flatnonzero((recv > 0) | (send > 0))
             lo, hi = int(s[r]), int(s[r + 1])
             npatch = int(len(D.owned_patches(L, lo, hi))) if l > 0 else 0
-            per.append({"rank": r, "owned_dofs": int((hi - lo) * bs), "ghost_dofs": int(len(g) * bs),
+            store = {}
+            if npatch > 0:
+                mode, fbytes, dense = patch_storage(L, D.LevelPart(l, bs, s, r, g), args.condense_min_bytes)
+                store = {"patch_storage_mode": mode, "patch_factor_GB": round(fbytes / 1e9, 3),
+                         "dense_inverse_GB": round(dense / 1e9, 3)}
+            per.append({"rank": r, "owned_dofs": int((hi - lo) * bs), "ghost_dofs": int(len(g) * bs), **store,
                         "ghost_fraction": round(len(g) / max(hi - lo, 1), 4), "patches": npatch,
                         "neighbours": [int(q) for q in nbr], "n_neighbours": int(len(nbr)),
                         "forward_halo_KB_sent": round(8e-3 * bs * int(send.sum()), 1),
@@ -64,6 +100,9 @@ def main():
         row["neighbours_max"] = max(p["n_neighbours"] for p in per)
         row["owned_dofs_min_max"] = [min(p["owned_dofs"] for p in per), max(p["owned_dofs"] for p in per)]
         row["ghost_fraction_max"] = max(p["ghost_fraction"] for p in per)
+        if l > 0:
+            row["patch_storage_modes"] = [p.get("patch_storage_mode") for p in per]
+            row["patch_factor_GB_total"] = round(sum(p.get("patch_factor_GB", 0.0) for p in per), 3)
         levels.append(row)
     out = {"config": args.config, "workload": bench.describe(args.config), "world": world, "min_dofs": args.min_dofs,
            "host_generation_s": round(t_gen, 1), "ghost_lists_all_ranks_s": round(t_ghost, 1),
