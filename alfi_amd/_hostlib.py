@@ -47,8 +47,11 @@ def lib():
         _lib.alfi_host_gls.restype = ctypes.c_int
         _lib.alfi_host_burman.restype = ctypes.c_int
         _lib.alfi_host_find_groups.restype = ctypes.c_int64
-        for name in ("patch_layout", "condensed", "sweep"):
+        for name in ("patch_layout", "condensed", "sweep", "f32_layout"):
             getattr(_lib, "alfi_host_plan_" + name).restype = ctypes.c_void_p
+        _lib.alfi_host_f32_index.restype = ctypes.c_int64
+        _lib.alfi_host_f32_ld.restype = ctypes.c_int
+        _lib.alfi_host_f32_patch_floats.restype = ctypes.c_int64
         _lib.alfi_host_plan_status.restype = ctypes.c_int
         _lib.alfi_host_plan_table.restype = ctypes.c_int
         _lib.alfi_host_plan_free.restype = None
@@ -122,6 +125,24 @@ def plan_patch_layout(n, patch_ptr, patch_dofs):
     """The tables alfi_patches_set builds for a level of n dofs (csrc/patch_plan.h: plan_patch_layout) as a dict."""
     pp, pd, npatch = _patch_args(patch_ptr, patch_dofs)
     return _plan_dict(lib().alfi_host_plan_patch_layout(ctypes.c_int64(n), npatch, _p(pp), _p(pd)))
+
+
+def plan_f32_layout(patch_ptr):
+    """The single-precision storage of a level's dense inverses (csrc/patch_plan.h: plan_f32_offsets) as a dict: ``f32_ptr``
+    (offsets of the patches in floats), ``inv32_floats``, ``rows_per_load`` (rows of a column one lane loads) and
+    ``align_floats`` (every offset is a multiple)."""
+    pp = np.ascontiguousarray(patch_ptr, dtype=np.int64)
+    return _plan_dict(lib().alfi_host_plan_f32_layout(ctypes.c_int64(len(pp) - 1), _p(pp)))
+
+
+def f32_index(n):
+    """(ld, floats, index): the padded row count of an n x n inverse in the single-precision storage, the floats the patch
+    occupies and the (ld, n) array of the offsets of its entries (r, c), pad rows r >= n included (f32_inv_index)."""
+    L = lib()
+    ld = L.alfi_host_f32_ld(ctypes.c_int(n))
+    idx = np.array([[L.alfi_host_f32_index(ctypes.c_int(r), ctypes.c_int(c), ctypes.c_int(n)) for c in range(n)]
+                    for r in range(ld)], dtype=np.int64).reshape(ld, n)
+    return ld, L.alfi_host_f32_patch_floats(ctypes.c_int(n)), idx
 
 
 def plan_condensed(bs, rowptr, colidx, patch_ptr, patch_dofs, groups):

@@ -98,6 +98,10 @@ SIGNATURES = {
     "alfi_patches_find_groups": (ctypes.c_int, [vp, vp]),
     "alfi_ctx_set_condense_min_bytes": (ctypes.c_int, [vp, ctypes.c_int64]),
     "alfi_patches_condensed": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int)]),
+    "alfi_patches_set_storage": (ctypes.c_int, [vp, ctypes.c_int]),
+    "alfi_patches_storage": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int)]),
+    "alfi_patches_set_canonical_order": (ctypes.c_int, [vp, vp]),
+    "alfi_patch_apply_split": (ctypes.c_int, [vp, ctypes.c_int64, vp, vp]),
     "alfi_patches_check": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
                                           ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]),
     "alfi_patches_set_partition_of_unity": (ctypes.c_int, [vp, ctypes.c_int]),

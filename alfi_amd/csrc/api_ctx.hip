@@ -316,6 +316,7 @@ int alfi_ctx_destroy(alfi_ctx* ctx) {
   dev_free(ctx->dev_err);
   (void)hipFree(ctx->big_arena);
   (void)hipFree(ctx->asm_scratch);
+  dev_free(ctx->f32_work);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return 0;

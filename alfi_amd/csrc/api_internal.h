@@ -42,6 +42,7 @@ int build_chunk_tables(alfi_ctx* ctx, DevBSR* d, const int32_t* rowptr, int64_t 
 int upload_bsr(alfi_ctx* ctx, DevBSR* d, const alfi_bsr_host* h, int bs);
 void free_bsr(DevBSR* d);
 void free_cond(alfi_level* L);
+void free_f32(alfi_level* L);     // api_patches.hip: the single-precision copy of a level's inverses
 int comm_allreduce(alfi_level* L, int64_t offset, int64_t count);
 int halo_fwd(alfi_level* L, double* v);
 int halo_fwd_begin(alfi_level* L, const double* v);

@@ -207,6 +207,8 @@ int alfi_level_destroy(alfi_level* L) {
   dev_free(L->stage_ptr);
   dev_free(L->inv);
   dev_free(L->inv_il);
+  free_f32(L);
+  dev_free(L->canon_rank);
   dev_free(L->stage);
   dev_free(L->dof_ptr);
   dev_free(L->dof_pos);
@@ -707,6 +709,9 @@ int alfi_patches_set_facet_correction(alfi_level* L, int64_t nfacet, int64_t nro
                                       const int32_t* fac, const double* s) {
   alfi_ctx* ctx = L->ctx;
   if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_set_facet_correction before alfi_patches_set");
+  if (L->f32_req || L->f32)
+    return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_set_facet_correction on a level with FP32 patch storage "
+                                             "(alfi_patches_set_storage(lvl, 0) first)");
   if (!ptr || nfacet < 0 || nrow < 0) return alfi_set_error(ctx, ALFI_E_ARG, "NULL argument");
   if (L->lay.patch_ptr[L->npatch] != nrow * L->bs) return alfi_set_error(ctx, ALFI_E_ARG, "facet correction rows != patch nodes");
   const int64_t ne = ptr[nrow];

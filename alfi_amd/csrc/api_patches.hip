@@ -6,6 +6,23 @@
 
 static_assert(PLAN_E_ARG == ALFI_E_ARG, "the planners (patch_plan.h) return the C ABI's code");
 
+// the single-precision copy of the inverses and its offsets
+void free_f32(alfi_level* L) {
+  // the last FP32 level of the ctx takes the FP64 work buffer with it (callers have synchronised the stream)
+  if (L->inv32 && --L->ctx->f32_levels == 0) {
+    dev_free(L->ctx->f32_work);
+    L->ctx->f32_work = nullptr;
+    L->ctx->f32_work_doubles = 0;
+  }
+  dev_free(L->inv32);
+  dev_free(L->inv32_ptr);
+  L->inv32 = nullptr;
+  L->inv32_ptr = nullptr;
+  L->inv32_floats = 0;
+  std::vector<int64_t>().swap(L->f32_ptr);
+  L->f32 = false;
+}
+
 // ---- patches -------------------------------------------------------------------------------------------------------------
 int alfi_patches_set(alfi_level* L, int64_t npatch, const int64_t* pptr, const int32_t* pdofs) {
   alfi_ctx* ctx = L->ctx;
@@ -19,6 +36,10 @@ int alfi_patches_set(alfi_level* L, int64_t npatch, const int64_t* pptr, const i
   dev_free(L->inv_ptr);
   dev_free(L->stage_ptr);
   dev_free(L->inv);
+  free_f32(L);                                    // a new patch set starts in FP64 (alfi_patches_set_storage)
+  dev_free(L->canon_rank);
+  L->canon_rank = nullptr;
+  L->f32_req = false;
   dev_free(L->inv_il);
   L->inv_il = nullptr;
   L->il_doubles = 0;
@@ -65,6 +86,63 @@ int alfi_patches_set(alfi_level* L, int64_t npatch, const int64_t* pptr, const i
   // caller declares the new one
   L->overlap = false;
   L->npatch_int = 0;
+  return 0;
+}
+
+int alfi_patches_set_storage(alfi_level* L, int dtype) {
+  alfi_ctx* ctx = L->ctx;
+  if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_set_storage before alfi_patches_set");
+  if (dtype != ALFI_STORAGE_F64 && dtype != ALFI_STORAGE_F32)
+    return alfi_set_error(ctx, ALFI_E_ARG, "alfi_patches_set_storage: dtype %d (0: FP64, 1: FP32)", dtype);
+  if (dtype == ALFI_STORAGE_F32) {
+    // what has no single-precision form is refused here, before any device work: the request is explicit, so nothing falls
+    // back to FP64 behind the caller's back
+    if (L->npatch == 0) return alfi_set_error(ctx, ALFI_E_ARG, "FP32 patch storage: the level has no patches");
+    if (L->lay.max_np <= 32)
+      return alfi_set_error(ctx, ALFI_E_ARG, "FP32 patch storage: every patch has <= 32 dofs and the level applies the "
+                                             "interleaved small-patch copy, which has no FP32 form");
+    if (L->lay.max_np > SMALL_PATCH_MAX)
+      return alfi_set_error(ctx, ALFI_E_ARG, "FP32 patch storage: a patch has %d dofs; the FP32 apply handles at most %d "
+                                             "(macro stars keep FP64)", L->lay.max_np, SMALL_PATCH_MAX);
+    if (L->cond && !L->cond_auto)
+      return alfi_set_error(ctx, ALFI_E_ARG, "FP32 patch storage: the level has caller-supplied groups; condensed factors cancel "
+                                             "in single precision and stay FP64 (alfi_patches_set_groups(NULL) first)");
+    if (L->mult) return alfi_set_error(ctx, ALFI_E_ARG, "FP32 patch storage: multiplicative sweeps read FP64 inverses");
+    if (L->fc_ptr)
+      return alfi_set_error(ctx, ALFI_E_ARG, "FP32 patch storage: the level has a facet correction (Burman); its patch "
+                                             "matrices are factored and repaired in FP64 only");
+  }
+  // (the level keeps what it holds, and works with it, until the next alfi_patches_factor)
+  L->f32_req = dtype == ALFI_STORAGE_F32;
+  return 0;
+}
+
+int alfi_patches_set_canonical_order(alfi_level* L, const int32_t* rank) {
+  alfi_ctx* ctx = L->ctx;
+  if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_set_canonical_order before alfi_patches_set");
+  if (rank) {                                      // per patch a permutation of 0 .. n_p - 1
+    std::vector<char> seen;
+    for (int64_t p = 0; p < L->npatch; ++p) {
+      const int64_t a = L->lay.patch_ptr[p], n = L->lay.patch_ptr[p + 1] - a;
+      seen.assign((size_t)n, 0);
+      for (int64_t q = 0; q < n; ++q) {
+        if (rank[a + q] < 0 || rank[a + q] >= n || seen[(size_t)rank[a + q]])
+          return alfi_set_error(ctx, ALFI_E_ARG, "patch %lld: the canonical order is not a permutation of its entries", (long long)p);
+        seen[(size_t)rank[a + q]] = 1;
+      }
+    }
+  }
+  ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  dev_free(L->canon_rank);
+  L->canon_rank = nullptr;
+  if (rank) ALFI_CHECK(dev_upload(ctx, &L->canon_rank, rank, L->lay.sum_n));
+  if (L->f32_req || L->f32) L->factored = false;   // the stored inverses belong to the old order
+  return 0;
+}
+
+int alfi_patches_storage(alfi_level* L, int* dtype) {
+  if (dtype) *dtype = L->f32 ? ALFI_STORAGE_F32 : ALFI_STORAGE_F64;
   return 0;
 }
 
@@ -133,6 +211,9 @@ static int set_groups_impl(alfi_level* L, const int32_t* group, const std::vecto
 }
 
 int alfi_patches_set_groups(alfi_level* L, const int32_t* group) {
+  if (group && (L->f32_req || L->f32))
+    return alfi_set_error(L->ctx, ALFI_E_STATE, "alfi_patches_set_groups on a level with FP32 patch storage: condensed factors "
+                                                "stay FP64 (alfi_patches_set_storage(lvl, 0) first)");
   const int rc = set_groups_impl(L, group);
   // the caller has decided for this patch set, NULL (dense inverses) included: no search for groups at the factorisation
   L->cond_auto = false;
@@ -173,7 +254,14 @@ int alfi_patches_condensed(alfi_level* L, int* mode) {
 }
 
 int alfi_patches_factor_bytes(alfi_level* L, int64_t* bytes) {
-  *bytes = L->cond ? 8 * (L->cplan.mat_doubles + L->cplan.sinv_doubles) : 8 * L->lay.inv_doubles;
+  if (L->f32) {
+    *bytes = 4 * L->inv32_floats;
+  } else if (L->f32_req) {                            // not factored yet: what the factorisation will store
+    std::vector<int64_t> ptr;
+    *bytes = 4 * plan_f32_offsets(L->npatch, L->lay.patch_ptr.data(), &ptr);
+  } else {
+    *bytes = L->cond ? 8 * (L->cplan.mat_doubles + L->cplan.sinv_doubles) : 8 * L->lay.inv_doubles;
+  }
   return 0;
 }
 
@@ -215,6 +303,9 @@ int alfi_patches_set_multiplicative(alfi_level* L, int64_t nit, const int64_t* i
   if (ctx->dev_err) ALFI_HIP_CHECK(ctx, hipMemset(ctx->dev_err, 0, 16));
   if (nit == 0) return 0;
   if (nit < 0 || !iterset) return alfi_set_error(ctx, ALFI_E_ARG, "bad iteration set");
+  if (L->f32_req || L->f32)
+    return alfi_set_error(ctx, ALFI_E_STATE, "multiplicative sweeps on a level with FP32 patch storage: the sweeps read FP64 "
+                                             "inverses (alfi_patches_set_storage(lvl, 0) first)");
   if (L->cond && !L->cond_auto)
     return alfi_set_error(ctx, ALFI_E_STATE, "multiplicative sweeps need dense patch inverses (alfi_patches_set_groups(NULL))");
   // (groups the library found itself are its own business: the sweeps read dense inverses, so such a level goes back to them
@@ -273,6 +364,15 @@ int alfi_patches_multiplicative_levels(alfi_level* L, int64_t* nwave) {
 int alfi_patches_factor(alfi_level* L) {
   alfi_ctx* ctx = L->ctx;
   if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_factor before alfi_patches_set");
+  if (L->f32_req) {
+    // an FP32 level does not condense, whatever its dense bytes and the threshold: it counts as decided (groups the library
+    // found at an earlier FP64 factorisation go)
+    if (L->cond && L->cond_auto) {
+      free_cond(L);
+      L->cond_auto = false;
+    }
+    L->cond_decided = true;
+  }
   if (!L->cond_decided) {
     // first factorisation of a patch set the caller gave no groups for: an additive level whose dense inverses would take
     // condense_min_bytes or more looks for groups in its own sparsity (find_groups.h) and stores condensed factors if it finds
@@ -302,7 +402,45 @@ int alfi_patches_factor(alfi_level* L) {
   }
   ProfScope prof(ctx, ALFI_EV_PATCH_FACTOR);
   ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->status, 0, sizeof(int), ctx->stream));
-  if (!L->cond && L->inv_shrunk) {                 // first dense factorisation of this patch set
+  // FP32 storage: the factorisation below -- gather, Gauss-Jordan, probe, repair -- runs unchanged on the ctx's FP64 work buffer
+  // (L->inv points there until this function returns); the level keeps the single-precision copy made at the end
+  struct InvGuard {
+    alfi_level* L;
+    double* keep;
+    ~InvGuard() { if (keep) L->inv = keep; }
+  } guard{L, nullptr};
+  if (L->f32_req) {
+    ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    L->factored = false;                           // from here to the end of this call the level holds nothing an apply may read
+    if (!L->inv_shrunk) {                          // FP64 inverses of an earlier factorisation
+      dev_free(L->inv);
+      L->inv = nullptr;
+      ALFI_CHECK(dev_alloc(ctx, &L->inv, 16));
+      L->inv_shrunk = true;
+    }
+    L->f32 = false;                                // until the copy is written the FP64 kernels apply (the probe)
+    if (!L->inv32) {
+      L->inv32_floats = plan_f32_offsets(L->npatch, L->lay.patch_ptr.data(), &L->f32_ptr);
+      ALFI_CHECK(dev_upload(ctx, &L->inv32_ptr, L->f32_ptr.data(), L->npatch + 1));
+      ALFI_CHECK(dev_alloc(ctx, &L->inv32, L->inv32_floats));
+      ++ctx->f32_levels;
+      ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->inv32, 0, sizeof(float) * (size_t)std::max<int64_t>(L->inv32_floats, 1), ctx->stream));
+    }
+    if (ctx->f32_work_doubles < L->lay.inv_doubles) {
+      dev_free(ctx->f32_work);
+      ctx->f32_work = nullptr;
+      ctx->f32_work_doubles = 0;
+      ALFI_CHECK(dev_alloc(ctx, &ctx->f32_work, L->lay.inv_doubles));
+      ctx->f32_work_doubles = L->lay.inv_doubles;
+    }
+    guard.keep = L->inv;
+    L->inv = ctx->f32_work;
+  } else if (L->inv32) {                           // back to FP64
+    ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    L->factored = false;
+    free_f32(L);
+  }
+  if (!L->cond && L->inv_shrunk && !L->f32_req) {  // first dense factorisation of this patch set
     ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     dev_free(L->inv);
     L->inv = nullptr;
@@ -316,9 +454,12 @@ int alfi_patches_factor(alfi_level* L) {
   } else if (L->lay.max_np > SMALL_PATCH_MAX) {
     ALFI_CHECK(launch_big_factor(L));             // macro-star sized patches: blocked Gauss-Jordan on the matrix cores
   } else {
-    ALFI_CHECK(launch_patch_gather_dense(L));
+    // (an FP32 level with a canonical order eliminates in that order and turns the inverses back: the rest sees patch_dofs' order)
+    const bool ranked = L->f32_req && L->canon_rank;
+    ALFI_CHECK(ranked ? launch_patch_gather_ranked(L) : launch_patch_gather_dense(L));
     if (L->fc_ptr && L->fc_scale != 0.0) ALFI_CHECK(launch_patch_facet_correct(L, 0, L->npatch, L->inv_ptr, L->inv, 0));
     ALFI_CHECK(launch_patch_invert(L));
+    if (ranked) ALFI_CHECK(launch_patch_unrank(L));
   }
   ALFI_CHECK(build_patch_il(L));                  // small-patch levels: the wave-contiguous copy the apply streams
   prof.close();
@@ -328,6 +469,10 @@ int alfi_patches_factor(alfi_level* L) {
   // every stored inverse is probed (|| A_p X_p e - e ||); the ones that fail -- an unpivoted elimination met a zero or
   // tiny pivot -- are re-inverted with partial pivoting, as the reference's LAPACK / UMFPACK factorisations would
   ALFI_CHECK(patch_verify_and_repair(L, st));
+  if (L->f32_req) {                                // the probed (and repaired) FP64 inverses, rounded to nearest
+    ALFI_CHECK(launch_patch_f32_convert(L, L->inv));
+    L->f32 = true;
+  }
   L->factored = true;
   return 0;
 }
@@ -346,6 +491,21 @@ int alfi_patch_apply(alfi_level* L, const double* dx, double* dy) {
   if (dx == dy) return alfi_set_error(L->ctx, ALFI_E_ARG, "alfi_patch_apply: x and y must not alias");
   L->ctx->cur_tag = L->id;
   return level_patch_apply(L, dx, dy);
+}
+
+// TEST HOOK: the additive apply as two range launches, [0, split) and [split, npatch), then the dof-wise sum -- what the
+// overlapped exchange of a partitioned level does with its patch ranges, on a serial level
+int alfi_patch_apply_split(alfi_level* L, int64_t split, const double* dx, double* dy) {
+  alfi_ctx* ctx = L->ctx;
+  if (!L->factored) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patch_apply_split before alfi_patches_factor");
+  if (dx == dy) return alfi_set_error(ctx, ALFI_E_ARG, "alfi_patch_apply_split: x and y must not alias");
+  if (L->mult || L->jacobi || level_is_partitioned(L))
+    return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patch_apply_split: additive patch solves on a serial level only");
+  if (split < 0 || split > L->npatch) return alfi_set_error(ctx, ALFI_E_ARG, "alfi_patch_apply_split: split out of range");
+  ctx->cur_tag = L->id;
+  ALFI_CHECK(launch_patch_apply_range(L, 0, split, dx));
+  ALFI_CHECK(launch_patch_apply_range(L, split, L->npatch, dx));
+  return launch_patch_sum(L, dx, dy);
 }
 
 int alfi_patches_stats(alfi_level* L, int64_t* npatch, int64_t* sum_n, int64_t* sum_n2) {
@@ -435,6 +595,14 @@ int alfi_patch_get_inverse(alfi_level* L, int64_t p, double* out) {
   if (p < 0 || p >= L->npatch) return alfi_set_error(ctx, ALFI_E_ARG, "patch index out of range");
   if (L->cond) return cond_get_inverse(L, p, out);
   const int64_t n = L->lay.patch_ptr[p + 1] - L->lay.patch_ptr[p];
+  if (L->f32) {                                    // the stored floats, widened
+    std::vector<float> tmp32((size_t)(n * f32_ld((int)n)));
+    ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    ALFI_HIP_CHECK(ctx, hipMemcpy(tmp32.data(), L->inv32 + L->f32_ptr[(size_t)p], tmp32.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i)
+      for (int64_t j = 0; j < n; ++j) out[i * n + j] = (double)tmp32[(size_t)f32_inv_index((int)i, (int)j, (int)n)];
+    return 0;
+  }
   const int64_t ld = (n + 1) & ~(int64_t)1;
   std::vector<double> tmp(n * ld);
   ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));

@@ -62,6 +62,9 @@ struct alfi_ctx {
   size_t big_arena_bytes = 0;
   void* asm_scratch = nullptr;      // element blocks / element vectors of the operator refresh (kernels_assemble.hip), grow-only
   size_t asm_scratch_bytes = 0;
+  double* f32_work = nullptr;       // FP64 work buffer the FP32 levels of this ctx factor in (alfi_patches_set_storage), grow-only
+  int64_t f32_work_doubles = 0;
+  int f32_levels = 0;               // levels of this ctx that hold a single-precision copy: the last one to go releases f32_work
   int64_t asm_scratch_limit = (int64_t)24 << 30;   // bytes of element blocks per batch of cells (alfi_ctx_set_assembly_scratch)
   // a level without caller-supplied groups whose dense inverses would take at least this many bytes looks for groups itself when
   // it factors (alfi_ctx_set_condense_min_bytes; negative: never)
@@ -438,6 +441,15 @@ struct alfi_level {
   CondDev cd;
   std::vector<void*> cond_allocs;        // every device array cd points to
   CondPlan cplan;                        // host side of the plan cd was uploaded from (patch_plan.h): sptr, gptr, chptr, gcptr, limits
+  // single-precision storage of the dense inverses (alfi_patches_set_storage; layout: patch_plan.h, f32_inv_index)
+  bool f32_req = false;                  // what the next alfi_patches_factor stores
+  bool f32 = false;                      // what the level holds: inv32 is what the additive apply streams, inv is a placeholder
+  float* inv32 = nullptr;
+  int64_t* inv32_ptr = nullptr;          // (npatch+1) offsets (floats) into inv32
+  std::vector<int64_t> f32_ptr;          // the same on the host
+  int64_t inv32_floats = 0;
+  int32_t* canon_rank = nullptr;         // (sum_n) alfi_patches_set_canonical_order: place of every patch entry in the caller's
+                                         // canonical order of its patch (FP32 levels eliminate in that order), or NULL
   // multiplicative sweeps: positions of the iteration sequence grouped into dependency wavefronts
   bool mult = false, mult_symmetrise = false;
   int32_t* mult_seq = nullptr;          // (nit) patch ids, wavefront-major
@@ -595,6 +607,10 @@ int launch_big_factor(alfi_level* lvl);
 int launch_cond_factor(alfi_level* lvl);
 int launch_cond_apply_range(alfi_level* lvl, int64_t p0, int64_t p1, const double* x);
 int launch_cond_schur_one(alfi_level* lvl, int64_t p, const int64_t* d_zero, double* scr);   // repair path (kernels_check.hip)                                                    // gather + blocked MFMA inversion
+// FP32 levels: inv32 <- the FP64 inverses at src (row-piece layout, offsets lvl->inv_ptr), rounded to nearest, pad rows zero
+int launch_patch_f32_convert(alfi_level* lvl, const double* src);
+int launch_patch_gather_ranked(alfi_level* lvl);   // FP32 levels with a canonical order: gather in that order ...
+int launch_patch_unrank(alfi_level* lvl);          // ... and the inverses back into the order of patch_dofs
 int build_patch_il(alfi_level* lvl);   // small-patch levels: (re)build the interleaved copy of the inverses from lvl->inv
 int launch_patch_sum(alfi_level* lvl, const double* x, double* y);             // stage 2
 int launch_patch_sum_range(alfi_level* lvl, int64_t i0, int64_t i1, const double* x, double* y);   // stage 2, dofs [i0, i1)

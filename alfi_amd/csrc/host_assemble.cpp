@@ -785,6 +785,7 @@ struct alfi_host_plan {
   PatchLayout lay;
   CondPlan cond;
   SweepPlan sweep;
+  std::vector<int64_t> f32_ptr;
   int rc = 0;
   std::string err;
   struct Entry {
@@ -813,6 +814,28 @@ alfi_host_plan* alfi_host_plan_patch_layout(int64_t n, int64_t npatch, const int
   ALFI_PLAN_SCALAR(lay, stage_len); ALFI_PLAN_SCALAR(lay, max_np);
   return h;
 }
+
+// the single-precision storage of a level's dense inverses (patch_plan.h): the offsets of the patches (floats, npatch + 1) and
+// the scalars of the layout
+alfi_host_plan* alfi_host_plan_f32_layout(int64_t npatch, const int64_t* patch_ptr) {
+  alfi_host_plan* h = new alfi_host_plan();
+  for (int64_t p = 0; p < npatch; ++p)
+    if (patch_ptr[p + 1] - patch_ptr[p] <= 0 || patch_ptr[p + 1] - patch_ptr[p] > SMALL_PATCH_MAX) {
+      h->rc = plan_fail(&h->err, "patch %lld has %lld dofs; FP32 storage holds patches of 1..%d", (long long)p,
+                        (long long)(patch_ptr[p + 1] - patch_ptr[p]), SMALL_PATCH_MAX);
+      return h;
+    }
+  const int64_t total = plan_f32_offsets(npatch, patch_ptr, &h->f32_ptr);
+  h->table("f32_ptr", h->f32_ptr);
+  h->scalar("inv32_floats", total);
+  h->scalar("rows_per_load", F32_ROWS);
+  h->scalar("align_floats", F32_ALIGN);
+  return h;
+}
+// entry (r, c) of an n x n inverse in that storage, r < alfi_host_f32_ld(n) (pad rows included), c < n; floats a patch occupies
+int64_t alfi_host_f32_index(int r, int c, int n) { return f32_inv_index(r, c, n); }
+int alfi_host_f32_ld(int n) { return f32_ld(n); }
+int64_t alfi_host_f32_patch_floats(int n) { return f32_patch_floats(n); }
 
 alfi_host_plan* alfi_host_plan_condensed(int bs, int64_t nbrows, int64_t npatch, const int64_t* patch_ptr, const int32_t* patch_dofs,
                                          const int32_t* group, const int32_t* rowptr, const int32_t* colidx) {

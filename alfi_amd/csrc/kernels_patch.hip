@@ -330,6 +330,210 @@ __global__ __launch_bounds__(64 * W) void patch_apply_kernel(int64_t p0, int64_t
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// 3f. the additive apply of a level that stores its inverses in SINGLE precision (alfi_patches_set_storage; layout: patch_plan.h,
+//     f32_inv_index): the structure of patch_apply_kernel -- a workgroup of W waves per patch, wave w takes the w-th share of
+//     the columns of every row piece, partial sums added in the order of the waves, ascending columns inside a wave -- with
+//     float loads of the same 16 bytes per lane (F32_ROWS = 4 rows of a column), widened in registers: every product and every
+//     sum is FP64, the stored values are the only single-precision quantity.
+// ---------------------------------------------------------------------------------------------------------------------
+typedef float alfi_fv __attribute__((ext_vector_type(F32_ROWS)));
+// one row piece of F32_ROWS * G rows, stored [column][rows of the piece]: G lanes per column, 64 / G columns per wave instruction
+template <int G, bool NT, int U>
+__device__ __forceinline__ void apply_piece_f32(const float* __restrict__ T, int n, const double* __restrict__ xs, int lane,
+                                                double* __restrict__ out) {
+  constexpr int C = 64 / G, V = F32_ROWS;
+  const int cg = lane / G, l = lane % G;
+  const float* base = T + V * l;
+  double acc[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) acc[k] = 0.0;
+  const alfi_fv zero = {};
+  int j = cg;
+  for (; j + (U - 1) * C < n; j += U * C) {
+    alfi_fv v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const alfi_fv* q = reinterpret_cast<const alfi_fv*>(base + (int64_t)(j + u * C) * (V * G));
+      v[u] = NT ? __builtin_nontemporal_load(q) : *q;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const double xj = xs[j + u * C];
+#pragma unroll
+      for (int k = 0; k < V; ++k) acc[k] = __builtin_fma((double)v[u][k], xj, acc[k]);
+    }
+  }
+  if (j < n) {       // the last, partial group: its loads are requested together too (same summation order: ascending columns)
+    alfi_fv v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const alfi_fv* q = reinterpret_cast<const alfi_fv*>(base + (int64_t)(j + u * C) * (V * G));
+      v[u] = j + u * C < n ? (NT ? __builtin_nontemporal_load(q) : *q) : zero;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (j + u * C < n) {
+        const double xj = xs[j + u * C];
+#pragma unroll
+        for (int k = 0; k < V; ++k) acc[k] = __builtin_fma((double)v[u][k], xj, acc[k]);
+      }
+  }
+  if (C > 1) {
+#pragma unroll
+    for (int o = G; o < 64; o <<= 1) {
+#pragma unroll
+      for (int k = 0; k < V; ++k) acc[k] += __shfl_xor(acc[k], o);
+    }
+  }
+  // the pad rows of the inverse are zero, so storing all rows of the lane is always valid (part has f32_ld(n) <= MAX_NP slots)
+  if (cg == 0) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) out[V * l + k] = acc[k];
+  }
+}
+
+constexpr int F32_APPLY_U = ALFI_APPLY_U * 4 / F32_ROWS;      // the bytes in flight per lane of the FP64 apply
+template <bool NT, int W>
+__global__ __launch_bounds__(64 * W) void patch_apply_f32_kernel(int64_t p0, int64_t p1, const int64_t* __restrict__ patch_ptr,
+                                                                  const int32_t* __restrict__ patch_dofs,
+                                                                  const int64_t* __restrict__ inv32_ptr,
+                                                                  const int64_t* __restrict__ stage_ptr,
+                                                                  const float* __restrict__ inv32, const double* __restrict__ x,
+                                                                  double* __restrict__ stage) {
+  static_assert(MAX_NP % F32_ROWS == 0, "the partial sums of the pad rows have slots");
+  __shared__ double xs[MAX_NP];
+  __shared__ double part[W][MAX_NP];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t p = p0 + blockIdx.x;
+  if (p >= p1) return;
+  const int64_t off = patch_ptr[p];
+  const int n = (int)(patch_ptr[p + 1] - off);
+  for (int i = threadIdx.x; i < n; i += 64 * W) xs[i] = x[patch_dofs[off + i]];
+  __syncthreads();
+  const int ld = f32_ld(n);
+  const float* T = inv32 + inv32_ptr[p];
+  const int ca = (int)(((int64_t)wave * n) / W), cn = (int)(((int64_t)(wave + 1) * n) / W) - ca;
+  double* out = part[wave];
+  int row0 = 0;
+  for (; row0 + 128 <= ld; row0 += 128)
+    apply_piece_f32<128 / F32_ROWS, NT, F32_APPLY_U>(T + (int64_t)row0 * n + (int64_t)ca * 128, cn, xs + ca, lane, out + row0);
+  const int rem = ld - row0;  // a multiple of F32_ROWS, < 128: one piece per binary digit
+#define ALFI_PIECE(R)                                                                                                      \
+  if (R >= F32_ROWS && (rem & R)) {                                                                                        \
+    apply_piece_f32<(R >= F32_ROWS ? R / F32_ROWS : 1), NT, F32_APPLY_U>(T + (int64_t)row0 * n + (int64_t)ca * R, cn, xs + ca, \
+                                                                         lane, out + row0);                                \
+    row0 += R;                                                                                                             \
+  }
+  ALFI_PIECE(64)
+  ALFI_PIECE(32)
+  ALFI_PIECE(16)
+  ALFI_PIECE(8)
+  ALFI_PIECE(4)
+  ALFI_PIECE(2)
+#undef ALFI_PIECE
+  __syncthreads();
+  // the staging buffer has the FP64 layout's slots: n rounded up to even (a pad row's sum is zero)
+  double* dst = stage + stage_ptr[p];
+  const int lds = (n + 1) & ~1;
+  for (int i = threadIdx.x; i < lds; i += 64 * W) {
+    double d = part[0][i];
+#pragma unroll
+    for (int w = 1; w < W; ++w) d += part[w][i];
+    dst[i] = d;
+  }
+}
+
+// FP32 levels with a canonical order (alfi_patches_set_canonical_order): the gather of section 1 with row / column a of the patch
+// written at position rank[a], so that the unpivoted elimination runs in the caller's canonical order -- a partitioned level
+// then eliminates in the order of the unpartitioned one and gets the same FP64 inverse bit for bit, whatever its local numbering
+template <int BS>
+__global__ __launch_bounds__(256) void patch_gather_ranked_kernel(const int32_t* __restrict__ rowptr,
+                                                                   const int32_t* __restrict__ colidx,
+                                                                   const double* __restrict__ vals,
+                                                                   const int64_t* __restrict__ patch_ptr,
+                                                                   const int32_t* __restrict__ patch_dofs,
+                                                                   const int32_t* __restrict__ rank,
+                                                                   const int64_t* __restrict__ inv_ptr,
+                                                                   double* __restrict__ inv, int flat) {
+  __shared__ int32_t dofs_s[MAX_NP];
+  __shared__ int32_t rank_s[MAX_NP];
+  __shared__ double rowbuf[4][MAX_NP];
+  const int64_t p = blockIdx.x;
+  const int64_t off = patch_ptr[p];
+  const int n = (int)(patch_ptr[p + 1] - off);
+  const int ld = (n + 1) & ~1;
+  double* S = inv + inv_ptr[p];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    dofs_s[i] = patch_dofs[off + i];
+    rank_s[i] = rank[off + i];
+  }
+  __syncthreads();
+  for (int r = wave; r < n; r += 4) {
+    for (int c = lane; c < ld; c += 64) rowbuf[wave][c] = 0.0;
+    ALFI_WAVE_LDS_ORDER_GATHER();
+    const int gr = dofs_s[r];
+    const int brow = gr / BS, rr = gr % BS;
+    const int32_t lo = rowptr[brow], hi = rowptr[brow + 1];
+    const int nent = (hi - lo) * BS;
+    for (int e = lane; e < nent; e += 64) {
+      const int blk = e / BS, cc = e % BS;
+      const int gcol = (colidx[lo + blk] & 0x7fffffff) * BS + cc;  // sign bit = row-start mark (flat layout)
+      int a = 0, b = n;
+      while (a < b) {
+        const int mid = (a + b) >> 1;
+        if (dofs_s[mid] < gcol) a = mid + 1; else b = mid;
+      }
+      if (a < n && dofs_s[a] == gcol) rowbuf[wave][rank_s[a]] = vals[bsr_val_index(flat, lo + blk, rr * BS + cc, BS * BS)];
+    }
+    ALFI_WAVE_LDS_ORDER_GATHER();
+    for (int c = lane; c < ld; c += 64) S[(int64_t)rank_s[r] * ld + c] = rowbuf[wave][c];
+    ALFI_WAVE_LDS_ORDER_GATHER();
+  }
+}
+
+// ... and the inverse back into the order of patch_dofs, out of place through a scratch of `stride` doubles per patch:
+// (1) scratch[(r, c)] = inverse[(rank[r], rank[c])], pad row zero; (2) the copy back
+__global__ __launch_bounds__(256) void patch_unrank_kernel(int64_t p0, const int64_t* __restrict__ patch_ptr,
+                                                            const int32_t* __restrict__ rank, const int64_t* __restrict__ inv_ptr,
+                                                            double* __restrict__ inv, double* __restrict__ scratch, int64_t stride,
+                                                            int back) {
+  __shared__ int32_t rank_s[MAX_NP];
+  const int64_t p = p0 + blockIdx.x;
+  const int64_t off = patch_ptr[p];
+  const int n = (int)(patch_ptr[p + 1] - off);
+  const int ld = (n + 1) & ~1;
+  double* S = inv + inv_ptr[p];
+  double* T = scratch + (int64_t)blockIdx.x * stride;
+  if (back) {
+    for (int e = threadIdx.x; e < ld * n; e += 256) S[e] = T[e];
+    return;
+  }
+  for (int i = threadIdx.x; i < n; i += 256) rank_s[i] = rank[off + i];
+  __syncthreads();
+  for (int e = threadIdx.x; e < ld * n; e += 256) {
+    const int r = e % ld, c = e / ld;
+    T[patch_inv_index(r, c, n, ld)] = r < n ? S[patch_inv_index(rank_s[r], rank_s[c], n, ld)] : 0.0;
+  }
+}
+
+// the single-precision copy <- the FP64 row-piece storage: a workgroup per patch, a thread per stored float (pad rows included)
+__global__ __launch_bounds__(256) void patch_f32_convert_kernel(const int64_t* __restrict__ patch_ptr,
+                                                                 const int64_t* __restrict__ inv_ptr,
+                                                                 const int64_t* __restrict__ inv32_ptr,
+                                                                 const double* __restrict__ inv, float* __restrict__ inv32) {
+  const int64_t p = blockIdx.x;
+  const int n = (int)(patch_ptr[p + 1] - patch_ptr[p]);
+  const int ld = (n + 1) & ~1, ld32 = f32_ld(n);
+  const double* S = inv + inv_ptr[p];
+  float* D = inv32 + inv32_ptr[p];
+  for (int e = threadIdx.x; e < ld32 * n; e += 256) {
+    const int r = e % ld32, c = e / ld32;
+    D[f32_inv_index(r, c, n)] = r < n ? (float)S[patch_inv_index(r, c, n, ld)] : 0.0f;     // (float): round to nearest even
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // 3a. additive apply for levels of SMALL patches (every n_p <= 32: the 2-D stars with n_p = 14) from the INTERLEAVED copy of
 //     the inverses (patch_il_index, common.h).  A wave per patch would stream 1.5 KB per wave, so G lanes share a patch
 //     (lane l owns the row pair 2l, 2l + 1), PW = 64 / G patches share a wave, and column c of the wave's PW patches is ONE
@@ -1020,6 +1224,18 @@ int launch_patch_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double
     ALFI_CHECK(launch_cond_apply_range(L, p0, p1, x));
     return 0;
   }
+  if (L->f32) {                                 // single-precision storage: its own kernel whatever the patch count
+    const int64_t cnt = p1 - p0;
+#define ALFI_F32_APPLY(WV)                                                                                                  \
+  hipLaunchKernelGGL((patch_apply_f32_kernel<true, WV>), dim3((unsigned)cnt), dim3(64 * WV), 0, ctx->stream, p0, p1, L->patch_ptr, \
+                     L->patch_dofs, L->inv32_ptr, L->stage_ptr, L->inv32, x, L->stage)
+    if (L->lay.max_np > 128) ALFI_F32_APPLY(2 * APPLY_W);
+    else if (L->lay.max_np > 64) ALFI_F32_APPLY(APPLY_W);
+    else ALFI_F32_APPLY(1);
+#undef ALFI_F32_APPLY
+    ALFI_HIP_CHECK(ctx, hipGetLastError());
+    return 0;
+  }
   // levels with FEW star patches of 3-D size (the lower levels of a hierarchy: 125 and 729 patches under config 3's 35 937)
   // leave most CUs empty: up to 1000 patches each patch gets 8 waves whatever its size (729 patches: 13.8 us against 15.6 us
   // through the macro stars' kernel, whose row pieces -- 64 + 32 + 8 + 4 + 2 rows for 111 dofs -- are dealt unevenly to 4
@@ -1077,6 +1293,53 @@ int launch_patch_sum_range(alfi_level* L, int64_t i0, int64_t i1, const double* 
 }
 
 int launch_patch_sum(alfi_level* L, const double* x, double* y) { return launch_patch_sum_range(L, 0, L->n, x, y); }
+
+// gather of a level with a canonical order (max_np <= SMALL_PATCH_MAX), and its inverses back into the order of patch_dofs
+int launch_patch_gather_ranked(alfi_level* L) {
+  alfi_ctx* ctx = L->ctx;
+  if (L->npatch == 0) return 0;
+  dim3 grid((unsigned)L->npatch), block(256);
+  if (L->bs == 2)
+    hipLaunchKernelGGL(patch_gather_ranked_kernel<2>, grid, block, 0, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals,
+                       L->patch_ptr, L->patch_dofs, L->canon_rank, L->inv_ptr, L->inv, L->A.flat);
+  else if (L->bs == 3)
+    hipLaunchKernelGGL(patch_gather_ranked_kernel<3>, grid, block, 0, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals,
+                       L->patch_ptr, L->patch_dofs, L->canon_rank, L->inv_ptr, L->inv, L->A.flat);
+  else
+    return alfi_set_error(ctx, ALFI_E_ARG, "unsupported block size %d", L->bs);
+  ALFI_HIP_CHECK(ctx, hipGetLastError());
+  return 0;
+}
+
+int launch_patch_unrank(alfi_level* L) {
+  alfi_ctx* ctx = L->ctx;
+  if (L->npatch == 0) return 0;
+  const int64_t ldmax = (L->lay.max_np + 1) & ~1;
+  const int64_t stride = ldmax * L->lay.max_np;
+  const int64_t batch = std::min<int64_t>(L->npatch, std::max<int64_t>(1, ((int64_t)1 << 27) / stride));   // <= 1 GiB of scratch
+  double* scratch = nullptr;
+  ALFI_HIP_CHECK(ctx, hipMalloc((void**)&scratch, sizeof(double) * (size_t)(batch * stride)));
+  int rc = 0;
+  for (int64_t p0 = 0; p0 < L->npatch && rc == 0; p0 += batch) {
+    const int64_t nb = std::min<int64_t>(batch, L->npatch - p0);
+    for (int back = 0; back < 2; ++back)
+      hipLaunchKernelGGL(patch_unrank_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, p0, L->patch_ptr, L->canon_rank,
+                         L->inv_ptr, L->inv, scratch, stride, back);
+    if (hipGetLastError() != hipSuccess) rc = alfi_set_error(ctx, ALFI_E_HIP, "patch_unrank_kernel launch failed");
+  }
+  (void)hipStreamSynchronize(ctx->stream);
+  (void)hipFree(scratch);
+  return rc;
+}
+
+int launch_patch_f32_convert(alfi_level* L, const double* src) {
+  alfi_ctx* ctx = L->ctx;
+  if (L->npatch == 0) return 0;
+  hipLaunchKernelGGL(patch_f32_convert_kernel, dim3((unsigned)L->npatch), dim3(256), 0, ctx->stream, L->patch_ptr, L->inv_ptr,
+                     L->inv32_ptr, src, L->inv32);
+  ALFI_HIP_CHECK(ctx, hipGetLastError());
+  return 0;
+}
 
 // Small-patch levels (every n_p <= 32, dense inverses): (re)build the interleaved copy the additive apply streams.  Called
 // at the end of every factorisation and after a pivoted repair has rewritten some inverses.

@@ -556,6 +556,9 @@ def localize_level(L, part):
         cnt = np.diff(nptr)[porder]
         out.patch_ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
         out.patch_dofs = ld[order].astype(np.int32)
+        # the place of every entry in the GLOBAL patch (ascending global dofs): the elimination order of the unpartitioned level,
+        # which an FP32 level follows (hip.Level.set_patch_canonical_order)
+        out.patch_rank = (np.arange(len(gd)) - nptr[pid])[order].astype(np.int32)
         if getattr(L, "patch_groups", None) is not None:        # labels of condensed patch factors follow their dofs
             out.patch_groups = np.asarray(L.patch_groups)[idx][order].astype(np.int32)
         out.patch_ids = sel[porder]
@@ -781,7 +784,7 @@ class DistMultigrid(object):
     def __init__(self, levels, transfers, k, robust_restriction=False, group=None, device=None, min_dofs=400000,
                  coarse_inverse=None, verbose=False, force_distributed=False, overlap=None, overlap_min_dofs=None,
                  transport=None, on_stage=None, use_overlap_rule=True, solo=None, full_cycle=False,
-                 condense_min_bytes=None):
+                 condense_min_bytes=None, patch_factor_dtype=None):
         """transport: "rccl" -- the library's own RCCL communicator serves every exchange point of a cycle (no Python
         between the kernels; the default whenever the process group's backend is nccl) -- or "callback": the library
         calls back into this module, which exchanges through torch.distributed (the test transport: gloo, ranks sharing
@@ -789,7 +792,9 @@ class DistMultigrid(object):
         "upload_factor" (bench.py's per-rank stage markers); ``setup_s`` holds the seconds each took.
         condense_min_bytes: a level whose RANK-LOCAL dense star inverses would take at least this many bytes finds groups in its
         own sparsity and stores condensed factors (Context.set_condense_min_bytes, set before the first factorisation; None: the
-        library's default, 0: wherever groups are found, < 0: never).  ``patch_storage()`` reports what every local level decided."""
+        library's default, 0: wherever groups are found, < 0: never).  ``patch_storage()`` reports what every local level decided.
+        patch_factor_dtype: None, or "f32": every rank asks its own smoothed levels to store their dense patch inverses in single
+        precision (hip.ask_patch_storage; no collective: a level without an FP32 form keeps FP64 on that rank)."""
         import time
         import torch
         from . import hip
@@ -906,6 +911,14 @@ class DistMultigrid(object):
                     # From here on the device level records on LL what it stores, after every factorisation: a level whose
                     # rank-local dense inverses reach the context's threshold finds groups by itself at its first one (here,
                     # or the caller's first refactor() when the operators are formed on the device), partitioned or not.
+                    if not getattr(levels[LL.level], "facet_coupling", False) and len(LL.patch_ptr) > 1:
+                        hip.ask_patch_storage(dl, patch_factor_dtype)
+                        # the unpartitioned level's elimination order, where it buys the unpartitioned level's float32 values: the
+                        # operator values are cut from the global operator (formed per rank on the device they differ from the
+                        # serial ones already, and every Newton step would pay for the extra passes)
+                        if (patch_factor_dtype is not None and LL.A.vals is not None
+                                and getattr(LL, "patch_rank", None) is not None):
+                            dl.set_patch_canonical_order(LL.patch_rank)
                     hip.note_patch_level(LL, dl)
                     if LL.A.vals is not None:          # (None: the operators are formed on the device first, the caller factors)
                         dl.factor_with_fallback()
@@ -1007,8 +1020,13 @@ class DistMultigrid(object):
     def patch_storage(self):
         """Per local level (``local_levels``; the coarsest and levels without owned patches: None) the pair (mode, factor bytes):
         mode 0 dense inverses, 1 condensed factors on the generator's groups, 2 on groups the level found itself
-        (hip.Level.condensed(), final after the first factorisation of the level)."""
+        (hip.Level.condensed(), final after the first factorisation of the level).  ``patch_storage_dtypes()``: "f64" / "f32"."""
         return [(dl.condensed(), dl.factor_bytes()) if LL.level > 0 and len(LL.patch_ptr) > 1 else None
+                for dl, LL in zip(self.levels, self.local_levels)]
+
+    def patch_storage_dtypes(self):
+        """Per local level what its patch factors are stored in, "f64" or "f32" (None where ``patch_storage()`` has None)."""
+        return [dl.patch_storage_dtype() if LL.level > 0 and len(LL.patch_ptr) > 1 else None
                 for dl, LL in zip(self.levels, self.local_levels)]
 
     def local_vec(self, global_array=None):

@@ -11,7 +11,10 @@ from ._lib import BsrHost, CsrHost, vp
 
 
 class AlfiHipError(RuntimeError):
-    pass
+    code = None        # the library's error code (ALFI_E_*), where the error came from one of its calls
+
+
+E_ARG, E_STATE = -2, -3        # ALFI_E_ARG, ALFI_E_STATE
 
 
 def _ptr(a):
@@ -31,7 +34,9 @@ class Context(object):
 
     def check(self, rc):
         if rc != 0:
-            raise AlfiHipError("libalfi_hip error %d: %s" % (rc, self.lib.alfi_last_error(self.h).decode()))
+            e = AlfiHipError("libalfi_hip error %d: %s" % (rc, self.lib.alfi_last_error(self.h).decode()))
+            e.code = rc
+            raise e
 
     def sync(self):
         self.check(self.lib.alfi_ctx_sync(self.h))
@@ -432,6 +437,31 @@ class Level(object):
         if self.host_level is not None and self.h:
             self.host_level.patch_storage = self.condensed()
             self.host_level.patch_factor_bytes = self.factor_bytes()
+            self.host_level.patch_factor_dtype = self.patch_storage_dtype()
+
+    STORAGE_DTYPES = {"f64": 0, "f32": 1}          # ALFI_STORAGE_F64 / ALFI_STORAGE_F32
+
+    def set_patch_storage(self, dtype):
+        """Storage of the level's dense patch inverses from its next ``factor()`` on (alfi_patches_set_storage): "f64" or "f32"
+        -- single precision in device memory, every product and sum of the apply still FP64.  AlfiHipError with ``code ==
+        E_ARG`` where no FP32 form exists (small 2-D stars, macro stars, caller-supplied groups, multiplicative sweeps, a facet
+        correction); the level stays as it was."""
+        if dtype not in self.STORAGE_DTYPES:
+            raise ValueError("patch storage %r (f64 or f32)" % (dtype,))
+        self.ctx.check(self.ctx.lib.alfi_patches_set_storage(self.h, self.STORAGE_DTYPES[dtype]))
+
+    def set_patch_canonical_order(self, rank):
+        """FP32 levels (alfi_patches_set_canonical_order): ``rank[q]`` = the place of entry q of patch_dofs in a canonical
+        order of its patch -- for a rank's local level the order of the unpartitioned patch (dist.localize_level: ``patch_rank``),
+        so that the stored float32 values do not depend on the partition; None: the order of patch_dofs."""
+        r = None if rank is None else np.ascontiguousarray(rank, dtype=np.int32)
+        self.ctx.check(self.ctx.lib.alfi_patches_set_canonical_order(self.h, _ptr(r)))
+
+    def patch_storage_dtype(self):
+        """"f64" or "f32": what the level holds now (alfi_patches_storage; a request takes effect at the next ``factor()``)."""
+        d = ctypes.c_int()
+        self.ctx.check(self.ctx.lib.alfi_patches_storage(self.h, ctypes.byref(d)))
+        return "f32" if d.value == 1 else "f64"
 
     def find_patch_groups(self):
         """Group labels found from the level's block sparsity (alfi_patches_find_groups): one per entry of patch_dofs, -1 =
@@ -520,6 +550,10 @@ class Level(object):
 
     def patch_apply(self, x, y):
         self.ctx.check(self.ctx.lib.alfi_patch_apply(self.h, x.ptr, y.ptr))
+
+    def patch_apply_split(self, split, x, y):
+        """TEST HOOK (alfi_patch_apply_split): the additive apply as the range launches [0, split) and [split, npatch)."""
+        self.ctx.check(self.ctx.lib.alfi_patch_apply_split(self.h, int(split), x.ptr, y.ptr))
 
     def spmv(self, x, y):
         self.ctx.check(self.ctx.lib.alfi_spmv(self.h, x.ptr, y.ptr))
@@ -696,11 +730,27 @@ def coarse_inverse(A_bsr):
 def note_patch_level(L, dl):
     """``dl`` holds the patches of the host level ``L`` (a level of the hierarchy, or a rank's dist.LocalLevel): from now on the
     device level records on ``L`` what it stores (``L.patch_storage`` = ``Level.condensed()``, ``L.patch_factor_bytes`` =
-    ``Level.factor_bytes()``), whenever that can change -- factor(), set_patch_groups(), set_multiplicative(),
+    ``Level.factor_bytes()``, ``L.patch_factor_dtype`` = ``Level.patch_storage_dtype()``), whenever that can change -- factor(), set_patch_groups(), set_multiplicative(),
     set_patch_facet_correction().  A level decides at its first factorisation: where the caller factors later (operators formed
     on the device first), the record follows then."""
     dl.host_level = L
     dl._record_storage()
+
+
+def ask_patch_storage(dl, dtype):
+    """The front ends' ``patch_factor_dtype`` keyword on one device level: None asks nothing; "f32" asks the level
+    (``Level.set_patch_storage``), and a level the library refuses with ALFI_E_ARG -- it has no FP32 form: the small 2-D stars,
+    macro stars, caller-supplied groups -- keeps FP64, which ``L.patch_factor_dtype`` of its host level then records
+    (note_patch_level).  Any other error propagates."""
+    if dtype is None:
+        return
+    if dtype != "f32":
+        raise ValueError("patch_factor_dtype %r (None or \"f32\")" % (dtype,))
+    try:
+        dl.set_patch_storage(dtype)
+    except AlfiHipError as e:
+        if e.code != E_ARG:
+            raise
 
 
 def condense_patches(L):
@@ -717,9 +767,12 @@ def condense_patches(L):
 class Multigrid(object):
     """Device-resident PCMG (solver.py:359-379) built from alfi_amd.problem.build_hierarchy output."""
 
-    def __init__(self, ctx, levels, transfers, k, robust_restriction=False, coarse_inv=None, verbose=False, coarse="auto"):
+    def __init__(self, ctx, levels, transfers, k, robust_restriction=False, coarse_inv=None, verbose=False, coarse="auto",
+                 patch_factor_dtype=None):
         """coarse: "dense" (explicit inverse, alfi_coarse_factor), "sparse" (multifrontal factors, alfi_coarse_factor_sparse)
-        or "auto": sparse from COARSE_SPARSE_MIN dofs on (env ALFI_COARSE_SPARSE_MIN)."""
+        or "auto": sparse from COARSE_SPARSE_MIN dofs on (env ALFI_COARSE_SPARSE_MIN).
+        patch_factor_dtype: None, or "f32": every smoothed level is asked to store its dense patch inverses in single precision
+        (ask_patch_storage: a level without an FP32 form keeps FP64; ``L.patch_factor_dtype`` records what each one holds)."""
         import time
         t0 = time.time()
         dlevels = []
@@ -731,6 +784,7 @@ class Multigrid(object):
                     dl.set_patch_groups(L.patch_groups)
                 elif not env.condense():
                     dl.set_patch_groups(None)              # dense inverses, also where the level would find groups itself
+                ask_patch_storage(dl, patch_factor_dtype)
                 dl.factor_with_fallback()
                 note_patch_level(L, dl)
             elif coarse_inv is not None:

@@ -362,6 +362,10 @@ class HipPatchPC(object):
             self.level.set_patch_groups(None)
         # (operator values not there yet -- formed on the device by the caller, who then factors: problem.build_hierarchy
         # with operator_values=False)
+        # the front end's patch_factor_dtype (HipMG hands it over as an attribute of the PC).  Not asked where this class sets
+        # multiplicative sweeps or the caller a facet correction afterwards: neither has an FP32 form, the level keeps FP64
+        if not self.multiplicative and not getattr(L, "facet_coupling", False):
+            hip.ask_patch_storage(self.level, getattr(pc, "patch_factor_dtype", None))
         if L.A.vals is not None:
             self.level.factor()
         hip.note_patch_level(L, self.level)
@@ -397,7 +401,9 @@ class HipMG(object):
     ``ksp_chebyshev_eigenvalues`` ("emin,emax": no estimate is run); ``pc_type`` python (``pc_python_type``) | jacobi.
     ``pc_mg_cycle_type`` v | w.  The Chebyshev intervals are estimated at construction and again by ``update``."""
 
-    def __init__(self, ctx, levels, transfers, params, restriction=False, coarse_inv=None):
+    def __init__(self, ctx, levels, transfers, params, restriction=False, coarse_inv=None, patch_factor_dtype=None):
+        """patch_factor_dtype: None, or "f32": every smoothed level is asked to store its dense patch inverses in single
+        precision (hip.ask_patch_storage; a keyword, not an option: the dictionaries mirror the reference's)."""
         self.opts = o = parse_mg_options(params)
         mgl = params["mg_levels"]
         self.k = o["k"]
@@ -421,6 +427,7 @@ class HipMG(object):
                 self.pc_objs.append(None)
                 continue
             pc = PC(ctx, L, options=mgl)
+            pc.patch_factor_dtype = patch_factor_dtype
             obj = HipJacobiPC() if jacobi else pc_cls()
             obj.initialize(pc)
             self.pcs.append(pc)
@@ -591,7 +598,8 @@ class HipOuterSolver(object):
     only the finest level is uploaded), fieldsplit_1 = ``DGMassInv``.  ``solve(f, g)`` returns (u, p, iterations, true
     residual norm)."""
 
-    def __init__(self, ctx, levels, transfers, params, restriction=False, coarse_inv=None):
+    def __init__(self, ctx, levels, transfers, params, restriction=False, coarse_inv=None, patch_factor_dtype=None):
+        """patch_factor_dtype: HipMG's (None, or "f32": single-precision storage of the dense patch inverses where it exists)."""
         from .problem import build_pressure_coupling
         if params.get("ksp_type") != "fgmres" or params.get("pc_type") != "fieldsplit" \
                 or params.get("pc_fieldsplit_type") != "schur" \
@@ -613,7 +621,8 @@ class HipOuterSolver(object):
             hip.Multigrid._from_device_levels(mg, ctx, [dl], [], 1, False)
             self.mg = mg
         else:
-            self.hmg = HipMG(ctx, levels, transfers, fs0, restriction=restriction, coarse_inv=coarse_inv)
+            self.hmg = HipMG(ctx, levels, transfers, fs0, restriction=restriction, coarse_inv=coarse_inv,
+                             patch_factor_dtype=patch_factor_dtype)
             if not self.hmg.full:
                 raise NotImplementedError("fieldsplit_0 must use pc_mg_type full (solver.py:366)")
             self.mg = self.hmg.mg

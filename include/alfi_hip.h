@@ -302,6 +302,35 @@ int alfi_patches_factor_bytes(alfi_level* lvl, int64_t* bytes);
 int alfi_patches_find_groups(alfi_level* lvl, int32_t* group_out_host);
 int alfi_ctx_set_condense_min_bytes(alfi_ctx* ctx, int64_t min_bytes);
 int alfi_patches_condensed(alfi_level* lvl, int* mode);
+/* Storage of a level's DENSE patch inverses: ALFI_STORAGE_F64 (the default) or ALFI_STORAGE_F32 -- single precision in device
+ * memory, half the bytes an additive apply streams, widened in registers: every product and every sum of the apply stays FP64,
+ * so the apply differs from the FP64 one by at most 2^-24 (|inv(A_p)| |x|)_i per patch row plus FP64 round-off.  Legal after
+ * alfi_patches_set, before or between factorisations; the next alfi_patches_factor obeys it (the level keeps working with what
+ * it holds until then).  The factorisation itself is unchanged -- gather, FP64 Gauss-Jordan, residual probe and pivoted repair
+ * run on an FP64 work buffer that belongs to the ctx (grow-only, shared by its FP32 levels, not counted in
+ * alfi_patches_factor_bytes) and alfi_patches_check reports the figures of the FP64 inverse --, then the inverses are rounded
+ * to nearest into the level's own copy.  An FP32 level never condenses itself, whatever alfi_ctx_set_condense_min_bytes says.
+ * alfi_patches_factor_bytes counts the floats; alfi_patch_get_inverse returns the stored values widened.
+ * ALFI_E_ARG (the level stays as it was) where no FP32 form exists: a level whose every patch has <= 32 dofs (the interleaved
+ * small-patch copy), patches above 160 dofs (macro stars), caller-supplied groups, multiplicative sweeps, a facet correction.
+ * On an FP32 level alfi_patches_set_multiplicative, alfi_patches_set_groups (non-NULL) and alfi_patches_set_facet_correction
+ * return ALFI_E_STATE: the request was explicit, nothing goes back to FP64 by itself.  alfi_patches_set starts a patch set in
+ * FP64 again.  alfi_patches_storage: what the level holds now. */
+#define ALFI_STORAGE_F64 0
+#define ALFI_STORAGE_F32 1
+int alfi_patches_set_storage(alfi_level* lvl, int dtype);
+int alfi_patches_storage(alfi_level* lvl, int* dtype);
+/* FP32 levels only (FP64 levels ignore it): rank_host[q] = the place of entry q of patch_dofs in a canonical order of its patch
+ * (per patch a permutation of 0 .. n_p - 1, else ALFI_E_ARG; NULL: none).  The unpivoted elimination of the next
+ * alfi_patches_factor then runs in that order instead of the order of patch_dofs, and the inverses are turned back before the
+ * probe.  For partitioned levels, whose local numbering lists ghost dofs last: with the order of the unpartitioned level's
+ * patch a rank computes the FP64 inverse of the unpartitioned level bit for bit, so the values rounded to float32 are the same
+ * on any partition (two roundings of inverses that differ by FP64 round-off differ by a whole float32 ulp wherever an entry
+ * crosses a rounding boundary).  After alfi_patches_set. */
+int alfi_patches_set_canonical_order(alfi_level* lvl, const int32_t* rank_host);
+/* TEST HOOK: alfi_patch_apply on a serial additive level as two range launches, patches [0, split) and [split, npatch), then the
+ * dof-wise sum: the range launches of a partitioned level's overlapped exchange, reachable without a partition. */
+int alfi_patch_apply_split(alfi_level* lvl, int64_t split, const double* x_dev, double* y_dev);
 /* Every alfi_patches_factor ends with a residual probe of every stored inverse, rho_p = || A_p (X_p e) - e ||_inf with a
  * fixed +-1 vector e, and re-inverts the patches with rho_p > 1e-6 (ALFI_PATCH_CHECK_TOL) -- or with a zero pivot -- by
  * LU with partial pivoting and triangular sweeps (the reference factors with pivoted LAPACK / UMFPACK LU, solver.py:599-602,

@@ -23,8 +23,10 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def patch_storage(L, part, min_bytes):
-    """(mode, factor bytes, dense bytes) of the rank ``part`` on level ``L``: the decision of alfi_patches_factor on the host."""
+def patch_storage(L, part, min_bytes, dtype=None):
+    """(mode, factor bytes, dense bytes, dtype) of the rank ``part`` on level ``L``: the decision of alfi_patches_factor on the
+    host.  dtype "f32": the rank asked for single-precision storage (alfi_patches_set_storage); a level that has an FP32 form --
+    its largest patch has 33 .. 160 dofs, no generator groups, no facet coupling -- stores floats and does not condense."""
     import copy
     from alfi_amd import _hostlib, dist as D, env
     from alfi_amd.problem import BSR
@@ -34,16 +36,19 @@ def patch_storage(L, part, min_bytes):
     n = np.diff(LL.patch_ptr)
     dense = int(8 * ((n * ((n + 1) & ~1) + 15) & ~15).sum())
     groups, mode = getattr(LL, "patch_groups", None), 1
+    if (dtype == "f32" and len(n) and 32 < n.max() <= 160 and not getattr(L, "facet_coupling", False)
+            and (groups is None or not env.condense())):
+        return 0, int(4 * _hostlib.plan_f32_layout(LL.patch_ptr)["inv32_floats"]), dense, "f32"
     if not env.condense() or getattr(L, "facet_coupling", False) or len(n) == 0:
-        return 0, dense, dense
+        return 0, dense, dense, "f64"
     if groups is None:
         if min_bytes < 0 or dense < min_bytes:
-            return 0, dense, dense
+            return 0, dense, dense, "f64"
         groups, mode = _hostlib.find_groups(LL.bs, LL.A.rowptr, LL.A.colidx, LL.patch_ptr, LL.patch_dofs), 2
         if not (groups >= 0).any():
-            return 0, dense, dense
+            return 0, dense, dense, "f64"
     plan = _hostlib.plan_condensed(LL.bs, LL.A.rowptr, LL.A.colidx, LL.patch_ptr, LL.patch_dofs, groups)
-    return mode, int(8 * (plan["mat_doubles"] + plan["sinv_doubles"])), dense
+    return mode, int(8 * (plan["mat_doubles"] + plan["sinv_doubles"])), dense, "f64"
 
 
 def main():
@@ -53,6 +58,8 @@ def main():
     ap.add_argument("--min-dofs", type=int, default=400000)
     ap.add_argument("--condense-min-bytes", type=int, default=1 << 30, help="rank-local dense bytes from which a level condenses "
                     "its vertex-star factors itself (default: the library's)")
+    ap.add_argument("--patch-factor-dtype", choices=["f32"], default=None, help="the ranks ask their levels for single-precision "
+                    "storage of the dense patch inverses (patch_factor_dtype of DistMultigrid)")
     args = ap.parse_args()
     import bench
     from alfi_amd import dist as D
@@ -87,8 +94,9 @@ def main():
             npatch = int(len(D.owned_patches(L, lo, hi))) if l > 0 else 0
             store = {}
             if npatch > 0:
-                mode, fbytes, dense = patch_storage(L, D.LevelPart(l, bs, s, r, g), args.condense_min_bytes)
-                store = {"patch_storage_mode": mode, "patch_factor_GB": round(fbytes / 1e9, 3),
+                mode, fbytes, dense, dtype = patch_storage(L, D.LevelPart(l, bs, s, r, g), args.condense_min_bytes,
+                                                           args.patch_factor_dtype)
+                store = {"patch_storage_mode": mode, "patch_factor_dtype": dtype, "patch_factor_GB": round(fbytes / 1e9, 3),
                          "dense_inverse_GB": round(dense / 1e9, 3)}
             per.append({"rank": r, "owned_dofs": int((hi - lo) * bs), "ghost_dofs": int(len(g) * bs), **store,
                         "ghost_fraction": round(len(g) / max(hi - lo, 1), 4), "patches": npatch,
@@ -102,6 +110,7 @@ def main():
         row["ghost_fraction_max"] = max(p["ghost_fraction"] for p in per)
         if l > 0:
             row["patch_storage_modes"] = [p.get("patch_storage_mode") for p in per]
+            row["patch_factor_dtypes"] = [p.get("patch_factor_dtype") for p in per]
             row["patch_factor_GB_total"] = round(sum(p.get("patch_factor_GB", 0.0) for p in per), 3)
         levels.append(row)
     out = {"config": args.config, "workload": bench.describe(args.config), "world": world, "min_dofs": args.min_dofs,

@@ -32,6 +32,8 @@ def main():
                     "solves apply) with the partition balanced for them")
     ap.add_argument("--condense-min-bytes", type=int, default=None, help="DistMultigrid(condense_min_bytes=...): the rank-local "
                     "dense bytes from which a level condenses its vertex-star factors itself (default: the library's, 1 GiB)")
+    ap.add_argument("--patch-factor-dtype", choices=["f32"], default=None, help="DistMultigrid(patch_factor_dtype=...): the ranks "
+                    "ask their levels for single-precision storage of the dense patch inverses")
     args = ap.parse_args()
     import torch
     import bench
@@ -48,7 +50,7 @@ def main():
         for r in ranks:
             t0 = time.time()
             dmg = DistMultigrid(lv, tr, k, solo=(r, world), min_dofs=args.min_dofs, full_cycle=args.cycle == "f",
-                                condense_min_bytes=args.condense_min_bytes)
+                                condense_min_bytes=args.condense_min_bytes, patch_factor_dtype=args.patch_factor_dtype)
             cycle = dmg.fcycle if args.cycle == "f" else dmg.vcycle
             dmg.sync()
             t_setup = time.time() - t0
@@ -69,9 +71,11 @@ def main():
             compute = sum(v for name, v in ev.items() if name != "COMM")
             own = [int(p.nb_own) * p.bs for p in dmg.parts]
             storage = {LL.level: st for LL, st in zip(dmg.local_levels, dmg.patch_storage()) if st is not None}
+            dtypes = {LL.level: dt for LL, dt in zip(dmg.local_levels, dmg.patch_storage_dtypes()) if dt is not None}
             row = {"world": world, "rank": r, "compute_ms": round(compute, 3), "wall_ms_with_host_callbacks": round(wall, 2),
                    "setup_s": round(t_setup, 1), "owned_dofs_by_level": own,
                    "patch_storage_mode_by_level": {str(l): st[0] for l, st in sorted(storage.items())},
+                   "patch_factor_dtype_by_level": {str(l): dt for l, dt in sorted(dtypes.items())},
                    "patch_factor_GB_by_level": {str(l): round(st[1] / 1e9, 3) for l, st in sorted(storage.items())},
                    "events_ms": {name: round(v, 3) for name, v in ev.items()}}
             rows.append(row)
@@ -82,8 +86,9 @@ def main():
     for world in (1, args.world):
         mine = [x for x in rows if x["world"] == world]
         gb = [sum(x["patch_factor_GB_by_level"].values()) for x in mine]
-        print("%d rank(s): patch factors %.2f GB over the ranks (per rank max %.2f / min %.2f), storage modes of the finest level %s"
-              % (world, sum(gb), max(gb), min(gb), [x["patch_storage_mode_by_level"].get(str(len(lv) - 1)) for x in mine]))
+        print("%d rank(s): patch factors %.2f GB over the ranks (per rank max %.2f / min %.2f), storage modes of the finest level %s, dtypes %s"
+              % (world, sum(gb), max(gb), min(gb), [x["patch_storage_mode_by_level"].get(str(len(lv) - 1)) for x in mine],
+                 [x["patch_factor_dtype_by_level"].get(str(len(lv) - 1)) for x in mine]))
     one = rows[0]["compute_ms"]
     many = [x["compute_ms"] for x in rows[1:]]
     print("device time of the kernels per %s-cycle: 1 rank %.2f ms; %d ranks: max %.2f / mean %.2f / min %.2f ms "
