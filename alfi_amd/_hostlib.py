@@ -47,7 +47,8 @@ def lib():
         _lib.alfi_host_gls.restype = ctypes.c_int
         _lib.alfi_host_burman.restype = ctypes.c_int
         _lib.alfi_host_find_groups.restype = ctypes.c_int64
-        for name in ("patch_layout", "condensed", "sweep", "f32_layout"):
+        _lib.alfi_host_f32_index_table.restype = None
+        for name in ("patch_layout", "condensed", "sweep", "f32_layout", "macro_f32_layout"):
             getattr(_lib, "alfi_host_plan_" + name).restype = ctypes.c_void_p
         _lib.alfi_host_f32_index.restype = ctypes.c_int64
         _lib.alfi_host_f32_ld.restype = ctypes.c_int
@@ -133,6 +134,21 @@ def plan_f32_layout(patch_ptr):
     ``align_floats`` (every offset is a multiple)."""
     pp = np.ascontiguousarray(patch_ptr, dtype=np.int64)
     return _plan_dict(lib().alfi_host_plan_f32_layout(ctypes.c_int64(len(pp) - 1), _p(pp)))
+
+
+def plan_macro_f32_layout(patch_ptr):
+    """plan_f32_layout for the levels of alfi_patches_set_macro_storage: patches of up to 4096 dofs, same layout."""
+    pp = np.ascontiguousarray(patch_ptr, dtype=np.int64)
+    return _plan_dict(lib().alfi_host_plan_macro_f32_layout(ctypes.c_int64(len(pp) - 1), _p(pp)))
+
+
+def f32_index_table(n):
+    """f32_index(n) computed in one call (macro stars: up to 4096 x 4096 offsets)."""
+    L = lib()
+    ld = L.alfi_host_f32_ld(ctypes.c_int(n))
+    idx = np.empty((ld, n), dtype=np.int64)
+    L.alfi_host_f32_index_table(ctypes.c_int(n), _p(idx))
+    return ld, L.alfi_host_f32_patch_floats(ctypes.c_int(n)), idx
 
 
 def f32_index(n):

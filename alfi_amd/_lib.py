@@ -100,6 +100,9 @@ SIGNATURES = {
     "alfi_patches_condensed": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int)]),
     "alfi_patches_set_storage": (ctypes.c_int, [vp, ctypes.c_int]),
     "alfi_patches_storage": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int)]),
+    "alfi_patches_set_macro_storage": (ctypes.c_int, [vp, ctypes.c_int]),
+    "alfi_ctx_set_f32_work_bytes": (ctypes.c_int, [vp, ctypes.c_int64]),
+    "alfi_ctx_f32_work_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64)]),
     "alfi_patches_set_canonical_order": (ctypes.c_int, [vp, vp]),
     "alfi_patch_apply_split": (ctypes.c_int, [vp, ctypes.c_int64, vp, vp]),
     "alfi_patches_check": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),

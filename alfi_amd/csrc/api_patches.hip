@@ -21,6 +21,7 @@ void free_f32(alfi_level* L) {
   L->inv32_floats = 0;
   std::vector<int64_t>().swap(L->f32_ptr);
   L->f32 = false;
+  if (!L->f32_req) L->f32_macro = false;
 }
 
 // ---- patches -------------------------------------------------------------------------------------------------------------
@@ -36,10 +37,10 @@ int alfi_patches_set(alfi_level* L, int64_t npatch, const int64_t* pptr, const i
   dev_free(L->inv_ptr);
   dev_free(L->stage_ptr);
   dev_free(L->inv);
+  L->f32_req = false;
   free_f32(L);                                    // a new patch set starts in FP64 (alfi_patches_set_storage)
   dev_free(L->canon_rank);
   L->canon_rank = nullptr;
-  L->f32_req = false;
   dev_free(L->inv_il);
   L->inv_il = nullptr;
   L->il_doubles = 0;
@@ -114,6 +115,41 @@ int alfi_patches_set_storage(alfi_level* L, int dtype) {
   }
   // (the level keeps what it holds, and works with it, until the next alfi_patches_factor)
   L->f32_req = dtype == ALFI_STORAGE_F32;
+  if (L->f32_req) L->f32_macro = false;
+  return 0;
+}
+
+// The second, separate request for FP32 storage: the one macro stars and Burman levels can make.  What alfi_patches_set_storage
+// refuses for want of a kernel (patches above 160 dofs) or of a place for the facet rule (a facet correction) is accepted here;
+// what has no single-precision form at all is refused as there.
+int alfi_patches_set_macro_storage(alfi_level* L, int dtype) {
+  alfi_ctx* ctx = L->ctx;
+  if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_set_macro_storage before alfi_patches_set");
+  if (dtype != ALFI_STORAGE_F64 && dtype != ALFI_STORAGE_F32)
+    return alfi_set_error(ctx, ALFI_E_ARG, "alfi_patches_set_macro_storage: dtype %d (0: FP64, 1: FP32)", dtype);
+  if (dtype == ALFI_STORAGE_F32) {
+    if (L->npatch == 0) return alfi_set_error(ctx, ALFI_E_ARG, "FP32 macro-star storage: the level has no patches");
+    if (L->lay.max_np <= 32)
+      return alfi_set_error(ctx, ALFI_E_ARG, "FP32 macro-star storage: every patch has <= 32 dofs and the level applies the "
+                                             "interleaved small-patch copy, which has no FP32 form");
+    if (L->cond && !L->cond_auto)
+      return alfi_set_error(ctx, ALFI_E_ARG, "FP32 macro-star storage: the level has caller-supplied groups; condensed factors "
+                                             "cancel in single precision and stay FP64 (alfi_patches_set_groups(NULL) first)");
+    if (L->mult) return alfi_set_error(ctx, ALFI_E_ARG, "FP32 macro-star storage: multiplicative sweeps read FP64 inverses");
+  }
+  L->f32_req = dtype == ALFI_STORAGE_F32;
+  if (L->f32_req) L->f32_macro = true;
+  return 0;
+}
+
+int alfi_ctx_set_f32_work_bytes(alfi_ctx* ctx, int64_t bytes) {
+  if (bytes <= 0) return alfi_set_error(ctx, ALFI_E_ARG, "alfi_ctx_set_f32_work_bytes: %lld bytes", (long long)bytes);
+  ctx->f32_work_cap = bytes;
+  return 0;
+}
+
+int alfi_ctx_f32_work_bytes(alfi_ctx* ctx, int64_t* bytes) {
+  if (bytes) *bytes = 8 * ctx->f32_work_doubles;
   return 0;
 }
 
@@ -409,6 +445,7 @@ int alfi_patches_factor(alfi_level* L) {
     double* keep;
     ~InvGuard() { if (keep) L->inv = keep; }
   } guard{L, nullptr};
+  std::vector<int64_t> ranges;                     // FP32 storage of big patches: the boundaries of the ranges it is factored in
   if (L->f32_req) {
     ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     L->factored = false;                           // from here to the end of this call the level holds nothing an apply may read
@@ -426,12 +463,28 @@ int alfi_patches_factor(alfi_level* L) {
       ++ctx->f32_levels;
       ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->inv32, 0, sizeof(float) * (size_t)std::max<int64_t>(L->inv32_floats, 1), ctx->stream));
     }
-    if (ctx->f32_work_doubles < L->lay.inv_doubles) {
+    // big patches pass through the work buffer range by range: the longest runs of consecutive patches whose FP64 row pieces
+    // fit alfi_ctx_set_f32_work_bytes (one patch above it is a range of its own); the rest needs the whole level there
+    int64_t work = L->lay.inv_doubles;
+    if (L->lay.max_np > SMALL_PATCH_MAX) {
+      const int64_t cap = std::max<int64_t>(ctx->f32_work_cap / 8, 1);
+      const std::vector<int64_t>& ip = L->lay.inv_ptr;
+      ranges.push_back(0);
+      work = 0;
+      for (int64_t p0 = 0; p0 < L->npatch;) {
+        int64_t p1 = p0 + 1;
+        while (p1 < L->npatch && ip[(size_t)p1 + 1] - ip[(size_t)p0] <= cap) ++p1;
+        work = std::max(work, ip[(size_t)p1] - ip[(size_t)p0]);
+        ranges.push_back(p1);
+        p0 = p1;
+      }
+    }
+    if (ctx->f32_work_doubles < work) {
       dev_free(ctx->f32_work);
       ctx->f32_work = nullptr;
       ctx->f32_work_doubles = 0;
-      ALFI_CHECK(dev_alloc(ctx, &ctx->f32_work, L->lay.inv_doubles));
-      ctx->f32_work_doubles = L->lay.inv_doubles;
+      ALFI_CHECK(dev_alloc(ctx, &ctx->f32_work, work));
+      ctx->f32_work_doubles = work;
     }
     guard.keep = L->inv;
     L->inv = ctx->f32_work;
@@ -449,6 +502,34 @@ int alfi_patches_factor(alfi_level* L) {
   }
   if (L->cond && L->fc_ptr && L->fc_scale != 0.0)
     return alfi_set_error(ctx, ALFI_E_STATE, "condensed patch factors on a Burman level (the facet rule couples macro interiors)");
+  if (!ranges.empty()) {
+    // Range by range: blocked inversion (facet rule and polish as for an FP64 level), probe, pivoted repair and second probe
+    // with the FP64 kernels on the work buffer, then the rounding into the level's copy.  The kernels address patch p at
+    // inv + inv_ptr[p]: the work buffer is handed to them biased by the range's first offset (only the range's patches are
+    // touched).  A patch's elimination reads its own scratch only, so what is stored does not depend on the ranges.
+    double* probe_vec = nullptr;
+    ALFI_CHECK(patch_probe_vector(L, &probe_vec));
+    PatchCheckAcc acc;
+    int rc = 0;
+    for (size_t r = 0; r + 1 < ranges.size() && rc == 0; ++r) {
+      const int64_t p0 = ranges[r], p1 = ranges[r + 1];
+      L->inv = ctx->f32_work - L->lay.inv_ptr[(size_t)p0];
+      rc = launch_big_factor_range(L, p0, p1);
+      int st = 0;
+      if (rc == 0 && hipMemcpy(&st, L->status, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = alfi_set_error(ctx, ALFI_E_HIP, "reading the factorisation status failed");
+      if (rc == 0) rc = patch_verify_and_repair_range(L, st, p0, p1, probe_vec, &acc);
+      if (rc == 0) rc = launch_patch_f32_convert_range(L, L->inv, p0, p1);
+    }
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(probe_vec);
+    prof.close();
+    patch_check_finish(L, acc);
+    ALFI_CHECK(rc);
+    L->f32 = true;
+    L->factored = true;
+    return 0;
+  }
   if (L->cond) {
     ALFI_CHECK(launch_cond_factor(L));            // condensed factors: group inverses + Schur complements
   } else if (L->lay.max_np > SMALL_PATCH_MAX) {

@@ -65,6 +65,8 @@ struct alfi_ctx {
   double* f32_work = nullptr;       // FP64 work buffer the FP32 levels of this ctx factor in (alfi_patches_set_storage), grow-only
   int64_t f32_work_doubles = 0;
   int f32_levels = 0;               // levels of this ctx that hold a single-precision copy: the last one to go releases f32_work
+  int64_t f32_work_cap = (int64_t)1 << 30;   // bytes of f32_work a big-patch FP32 level is factored through, range by range
+                                             // (alfi_ctx_set_f32_work_bytes); one patch above it is a range of its own
   int64_t asm_scratch_limit = (int64_t)24 << 30;   // bytes of element blocks per batch of cells (alfi_ctx_set_assembly_scratch)
   // a level without caller-supplied groups whose dense inverses would take at least this many bytes looks for groups itself when
   // it factors (alfi_ctx_set_condense_min_bytes; negative: never)
@@ -444,6 +446,8 @@ struct alfi_level {
   // single-precision storage of the dense inverses (alfi_patches_set_storage; layout: patch_plan.h, f32_inv_index)
   bool f32_req = false;                  // what the next alfi_patches_factor stores
   bool f32 = false;                      // what the level holds: inv32 is what the additive apply streams, inv is a placeholder
+  bool f32_macro = false;                // the FP32 request came through alfi_patches_set_macro_storage: patches above 160 dofs and
+                                         // a facet correction are accepted (cleared with the single-precision copy)
   float* inv32 = nullptr;
   int64_t* inv32_ptr = nullptr;          // (npatch+1) offsets (floats) into inv32
   std::vector<int64_t> f32_ptr;          // the same on the host
@@ -581,6 +585,17 @@ int launch_patch_gather_dense(alfi_level* lvl);
 int launch_patch_invert(alfi_level* lvl);
 // kernels_check.hip: probe || A_p X_p e - e || of every stored inverse, pivoted re-inversion of the patches that fail
 int patch_verify_and_repair(alfi_level* lvl, int unpivoted_status);
+// the same for the patches [p0, p1) of a level that is factored range by range (FP32 storage of big patches): probe_vec is the
+// level's +-1 vector (patch_probe_vector, made once per factorisation); the figures accumulate in *acc, which
+// patch_check_finish turns into what alfi_patches_check reports -- the figures of one probe of the whole level
+struct PatchCheckAcc {
+  double worst = -1.0, worst_after = -1.0;
+  int64_t flagged = 0, repaired = 0;
+};
+int patch_probe_vector(alfi_level* lvl, double** probe_vec);
+int patch_verify_and_repair_range(alfi_level* lvl, int unpivoted_status, int64_t p0, int64_t p1, const double* probe_vec,
+                                  PatchCheckAcc* acc);
+int patch_check_finish(alfi_level* lvl, const PatchCheckAcc& acc);
 int launch_patch_invert_arrays(alfi_ctx* ctx, int64_t npatch, int max_np, const int64_t* patch_ptr,
                                const int64_t* inv_ptr, double* inv, int* status);
 int launch_patch_apply_arrays(alfi_ctx* ctx, int64_t npatch, const int64_t* patch_ptr, const int32_t* patch_dofs,
@@ -603,12 +618,15 @@ void mf_free(struct MfDev* m);
 int64_t mf_bytes(const struct MfDev* m);
 int launch_coarse_factor(alfi_level* lvl, double* out);                                   // dense inverse of the whole level operator
 int launch_big_factor(alfi_level* lvl);
+int launch_big_factor_range(alfi_level* lvl, int64_t p0, int64_t p1);      // the patches [p0, p1) only
+int launch_big_apply_f32_range(alfi_level* lvl, int64_t p0, int64_t p1, const double* x);   // FP32 levels with n_p > 160
 // condensed patches (kernels_bigpatch.hip): block factorisation / its apply for the patches [p0, p1)
 int launch_cond_factor(alfi_level* lvl);
 int launch_cond_apply_range(alfi_level* lvl, int64_t p0, int64_t p1, const double* x);
 int launch_cond_schur_one(alfi_level* lvl, int64_t p, const int64_t* d_zero, double* scr);   // repair path (kernels_check.hip)                                                    // gather + blocked MFMA inversion
 // FP32 levels: inv32 <- the FP64 inverses at src (row-piece layout, offsets lvl->inv_ptr), rounded to nearest, pad rows zero
 int launch_patch_f32_convert(alfi_level* lvl, const double* src);
+int launch_patch_f32_convert_range(alfi_level* lvl, const double* src, int64_t p0, int64_t p1);
 int launch_patch_gather_ranked(alfi_level* lvl);   // FP32 levels with a canonical order: gather in that order ...
 int launch_patch_unrank(alfi_level* lvl);          // ... and the inverses back into the order of patch_dofs
 int build_patch_il(alfi_level* lvl);   // small-patch levels: (re)build the interleaved copy of the inverses from lvl->inv

@@ -832,6 +832,28 @@ alfi_host_plan* alfi_host_plan_f32_layout(int64_t npatch, const int64_t* patch_p
   h->scalar("align_floats", F32_ALIGN);
   return h;
 }
+// the same for the levels of alfi_patches_set_macro_storage: patches of up to PATCH_MAX dofs
+alfi_host_plan* alfi_host_plan_macro_f32_layout(int64_t npatch, const int64_t* patch_ptr) {
+  alfi_host_plan* h = new alfi_host_plan();
+  for (int64_t p = 0; p < npatch; ++p)
+    if (patch_ptr[p + 1] - patch_ptr[p] <= 0 || patch_ptr[p + 1] - patch_ptr[p] > PATCH_MAX) {
+      h->rc = plan_fail(&h->err, "patch %lld has %lld dofs; FP32 macro-star storage holds patches of 1..%d", (long long)p,
+                        (long long)(patch_ptr[p + 1] - patch_ptr[p]), PATCH_MAX);
+      return h;
+    }
+  const int64_t total = plan_f32_offsets(npatch, patch_ptr, &h->f32_ptr);
+  h->table("f32_ptr", h->f32_ptr);
+  h->scalar("inv32_floats", total);
+  h->scalar("rows_per_load", F32_ROWS);
+  h->scalar("align_floats", F32_ALIGN);
+  return h;
+}
+// all offsets of an n x n inverse at once: out[r * n + c] = f32_inv_index(r, c, n), r < f32_ld(n) (big patches: 16 M entries)
+void alfi_host_f32_index_table(int n, int64_t* out) {
+  const int ld = f32_ld(n);
+  for (int r = 0; r < ld; ++r)
+    for (int c = 0; c < n; ++c) out[(int64_t)r * n + c] = f32_inv_index(r, c, n);
+}
 // entry (r, c) of an n x n inverse in that storage, r < alfi_host_f32_ld(n) (pad rows included), c < n; floats a patch occupies
 int64_t alfi_host_f32_index(int r, int c, int n) { return f32_inv_index(r, c, n); }
 int alfi_host_f32_ld(int n) { return f32_ld(n); }

@@ -540,6 +540,107 @@ __global__ __launch_bounds__(256) void big_apply_kernel(int64_t p0, int64_t npat
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// 3'. the same apply for a level that stores its inverses in SINGLE precision (alfi_patches_set_macro_storage; layout:
+//     patch_plan.h, f32_inv_index: rows padded to a multiple of 4, pieces of 128 rows and then the binary digits of the rest down
+//     to 4, a piece stored [column][rows of the piece]).  The work split is big_apply_kernel's -- a workgroup of 4 waves per
+//     patch, ``split`` workgroups per patch on launches of few patches, whole pieces dealt round-robin to the 4 split waves --
+//     and a lane loads the same 16 bytes: its four rows of a column as one float4, widened in registers.  Every product and
+//     every sum is an FP64 fma; a row's sum is the ascending columns of its column group, then the groups by shuffles in a
+//     fixed order: it depends on the patch alone, not on the launch, the range or ``split``.
+// ---------------------------------------------------------------------------------------------------------------------
+typedef float big_f4 __attribute__((ext_vector_type(4)));
+// one stored piece of 4 G rows: G lanes per column, 64 / G columns per wave instruction.  lim: rows of the piece that exist.
+// A patch has (n + 1) & ~1 staging slots, not f32_ld(n): the sums of the pad rows (zeros) are NOT stored -- for n = 1, 2 mod 4
+// they would land in the next patch's slots, or behind the staging buffer for the last patch.
+template <int G, bool NT>
+__device__ __forceinline__ void big_piece_f32(const float* __restrict__ T, int n, const double* __restrict__ xs, int lane,
+                                              double* __restrict__ out, int lim) {
+  constexpr int C = 64 / G, U = 8;
+  const int cg = lane / G, l = lane % G;
+  const float* base = T + 4 * l;
+  double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
+  int j = cg;
+  for (; j + (U - 1) * C < n; j += U * C) {
+    big_f4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const big_f4* q = reinterpret_cast<const big_f4*>(base + (int64_t)(j + u * C) * (4 * G));
+      v[u] = NT ? __builtin_nontemporal_load(q) : *q;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const double xj = xs[j + u * C];
+      acc0 = __builtin_fma((double)v[u].x, xj, acc0);
+      acc1 = __builtin_fma((double)v[u].y, xj, acc1);
+      acc2 = __builtin_fma((double)v[u].z, xj, acc2);
+      acc3 = __builtin_fma((double)v[u].w, xj, acc3);
+    }
+  }
+  for (; j < n; j += C) {
+    const big_f4* q = reinterpret_cast<const big_f4*>(base + (int64_t)j * (4 * G));
+    const big_f4 v = NT ? __builtin_nontemporal_load(q) : *q;
+    const double xj = xs[j];
+    acc0 = __builtin_fma((double)v.x, xj, acc0);
+    acc1 = __builtin_fma((double)v.y, xj, acc1);
+    acc2 = __builtin_fma((double)v.z, xj, acc2);
+    acc3 = __builtin_fma((double)v.w, xj, acc3);
+  }
+  if (C > 1) {
+#pragma unroll
+    for (int o = G; o < 64; o <<= 1) {
+      acc0 += __shfl_xor(acc0, o);
+      acc1 += __shfl_xor(acc1, o);
+      acc2 += __shfl_xor(acc2, o);
+      acc3 += __shfl_xor(acc3, o);
+    }
+  }
+  if (cg == 0) {
+    const int r = 4 * l;
+    if (r < lim) out[r] = acc0;
+    if (r + 1 < lim) out[r + 1] = acc1;
+    if (r + 2 < lim) out[r + 2] = acc2;
+    if (r + 3 < lim) out[r + 3] = acc3;
+  }
+}
+
+template <bool NT>
+__global__ __launch_bounds__(256) void big_apply_f32_kernel(int64_t p0, int64_t npatch, const int64_t* __restrict__ patch_ptr,
+                                                             const int32_t* __restrict__ patch_dofs,
+                                                             const int64_t* __restrict__ inv32_ptr,
+                                                             const int64_t* __restrict__ stage_ptr,
+                                                             const float* __restrict__ inv32, const double* __restrict__ x,
+                                                             double* __restrict__ stage, int split) {
+  __shared__ double xs[BIG_MAX_NP];
+  const int64_t p = p0 + blockIdx.x / split;
+  const int part = blockIdx.x % split, nwave = 4 * split;
+  if (p >= npatch) return;
+  const int64_t off = patch_ptr[p];
+  const int n = (int)(patch_ptr[p + 1] - off);
+  for (int i = threadIdx.x; i < n; i += 256) xs[i] = x[patch_dofs[off + i]];
+  __syncthreads();
+  const int wave = part * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int ld = f32_ld(n);
+  const float* T = inv32 + inv32_ptr[p];
+  double* out = stage + stage_ptr[p];
+  int piece = 0, row0 = 0;
+  for (; row0 + 128 <= ld; row0 += 128, ++piece)
+    if (piece % nwave == wave) big_piece_f32<32, NT>(T + (int64_t)row0 * n, n, xs, lane, out + row0, n - row0);
+  const int rem = ld - row0;          // a multiple of 4, < 128: one piece per binary digit
+#define ALFI_BIG_PIECE_F32(R)                                                                                      \
+  if (rem & R) {                                                                                                   \
+    if (piece % nwave == wave) big_piece_f32<R / 4, NT>(T + (int64_t)row0 * n, n, xs, lane, out + row0, n - row0); \
+    row0 += R;                                                                                                     \
+    ++piece;                                                                                                       \
+  }
+  ALFI_BIG_PIECE_F32(64)
+  ALFI_BIG_PIECE_F32(32)
+  ALFI_BIG_PIECE_F32(16)
+  ALFI_BIG_PIECE_F32(8)
+  ALFI_BIG_PIECE_F32(4)
+#undef ALFI_BIG_PIECE_F32
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // 3b. multiplicative sweep over large patches (macro stars, alfi/solver.py:322-324 with 339-342: --patch macro
 //     --patch-composition multiplicative): one dependency wavefront per launch as in kernels_patch.hip, but a WORKGROUP per
 //     patch.  r_p = x_p - (A y)_p: a wave per patch node, lanes over the blocks of its operator row (coalesced value
@@ -744,6 +845,18 @@ int launch_big_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double* 
   else
     hipLaunchKernelGGL(big_apply_kernel<false>, grid, block, 0, ctx->stream, p0, p1, L->patch_ptr, L->patch_dofs, L->inv_ptr,
                        L->stage_ptr, L->inv, x, L->stage, split);
+  ALFI_HIP_CHECK(ctx, hipGetLastError());
+  return 0;
+}
+
+// FP32 levels with a patch above 160 dofs (alfi_patches_set_macro_storage): the same split, the single-precision copy
+int launch_big_apply_f32_range(alfi_level* L, int64_t p0, int64_t p1, const double* x) {
+  alfi_ctx* ctx = L->ctx;
+  if (p1 <= p0) return 0;
+  const int split = big_split(p1 - p0, L->lay.max_np);
+  dim3 grid((unsigned)((p1 - p0) * split)), block(256);
+  hipLaunchKernelGGL(big_apply_f32_kernel<true>, grid, block, 0, ctx->stream, p0, p1, L->patch_ptr, L->patch_dofs, L->inv32_ptr,
+                     L->stage_ptr, L->inv32, x, L->stage, split);
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   return 0;
 }
@@ -1611,12 +1724,15 @@ __global__ __launch_bounds__(64) void big_offsets_kernel(int64_t p0, int64_t nb,
   }
 }
 
-// fill + blocked inversion of npatch matrices, in batches bounded by the scratch budget
+// fill + blocked inversion of the matrices [pfirst, plast), in batches bounded by the scratch budget.  A matrix's elimination
+// reads its own scratch only and a batch's composition sets grid extents only: what is stored for a matrix does not depend on
+// the range it is factored in.
 // dense_out != nullptr (one matrix): the inverse is delivered row-major n x n there instead of the row-piece layout
-static int big_factor_core(alfi_ctx* ctx, const BigSource& src, int64_t npatch, const int64_t* h_patch_ptr,
+static int big_factor_core(alfi_ctx* ctx, const BigSource& src, int64_t pfirst, int64_t plast, const int64_t* h_patch_ptr,
                            const int64_t* d_patch_ptr, const int64_t* d_inv_ptr, double* inv, int* status,
                            double* dense_out = nullptr) {
-  if (npatch == 0) return 0;
+  const int64_t npatch = plast;
+  if (plast <= pfirst) return 0;
   const int64_t limit = alfi_env_big_scratch_bytes();   // scratch (matrices + panels) per batch
   constexpr bool polish = true;   // one Newton-Schulz step after the blocked elimination (explicit pivot-block inverses lose
                                   // cond * eps: 2e-5 against LAPACK without it, 1e-8 with)
@@ -1628,7 +1744,7 @@ static int big_factor_core(alfi_ctx* ctx, const BigSource& src, int64_t npatch, 
   };
   std::vector<Batch> batches;
   int64_t smax = 0, pmax = 0, nbmax = 0;
-  for (int64_t p0 = 0; p0 < npatch;) {
+  for (int64_t p0 = pfirst; p0 < npatch;) {
     Batch B;
     B.p0 = p0;
     B.sdoubles = B.pdoubles = 0;
@@ -1741,7 +1857,15 @@ static int big_factor_core(alfi_ctx* ctx, const BigSource& src, int64_t npatch, 
 int launch_big_factor(alfi_level* L) {
   BigSource src;
   src.L = L;
-  return big_factor_core(L->ctx, src, L->npatch, L->lay.patch_ptr.data(), L->patch_ptr, L->inv_ptr, L->inv, L->status);
+  return big_factor_core(L->ctx, src, 0, L->npatch, L->lay.patch_ptr.data(), L->patch_ptr, L->inv_ptr, L->inv, L->status);
+}
+
+// the patches [p0, p1) of a level that is factored range by range (FP32 storage: L->inv is the ctx's work area, biased so that
+// L->inv + inv_ptr[p0] is its start)
+int launch_big_factor_range(alfi_level* L, int64_t p0, int64_t p1) {
+  BigSource src;
+  src.L = L;
+  return big_factor_core(L->ctx, src, p0, p1, L->lay.patch_ptr.data(), L->patch_ptr, L->inv_ptr, L->inv, L->status);
 }
 
 // interior blocks of a transfer with 160 < m <= 4096 (macro-cell blocks of the 3-D Scott-Vogelius transfer, m = 390 for P3)
@@ -1750,7 +1874,7 @@ int launch_big_factor_transfer(alfi_transfer* T) {
   src.T = T;
   std::vector<int64_t> hptr(T->nblk + 1);
   for (int64_t b = 0; b <= T->nblk; ++b) hptr[b] = b * T->m;
-  return big_factor_core(T->ctx, src, T->nblk, hptr.data(), T->pm_ptr, T->pm_inv_ptr, T->binv, T->status);
+  return big_factor_core(T->ctx, src, 0, T->nblk, hptr.data(), T->pm_ptr, T->pm_inv_ptr, T->binv, T->status);
 }
 
 // Dense inverse of a whole level operator (the coarse grid: AssembledPC + LU in the reference, alfi/solver.py:369-378) with
@@ -1764,7 +1888,7 @@ int launch_coarse_factor(alfi_level* L, double* out) {
   int64_t* dptr = nullptr;
   ALFI_HIP_CHECK(ctx, hipMalloc((void**)&dptr, sizeof(hptr)));
   hipError_t e = hipMemcpy(dptr, hptr, sizeof(hptr), hipMemcpyHostToDevice);
-  int rc = e == hipSuccess ? big_factor_core(ctx, src, 1, hptr, dptr, nullptr, nullptr, L->status, out)
+  int rc = e == hipSuccess ? big_factor_core(ctx, src, 0, 1, hptr, dptr, nullptr, nullptr, L->status, out)
                            : alfi_set_error(ctx, ALFI_E_HIP, "hipMemcpy: %s", hipGetErrorString(e));
   (void)hipFree(dptr);
   // the 3 N^2 scratch arena of a large coarse grid is not needed again (patch re-factorisations are far smaller)
@@ -1780,7 +1904,7 @@ int launch_coarse_factor(alfi_level* L, double* out) {
 int launch_cond_factor(alfi_level* L) {
   BigSource src;
   src.K = L;
-  return big_factor_core(L->ctx, src, L->npatch, L->cplan.sptr.data(), L->cd.sptr, L->cd.sinv_ptr, L->cd.sinv, L->status);
+  return big_factor_core(L->ctx, src, 0, L->npatch, L->cplan.sptr.data(), L->cd.sptr, L->cd.sinv_ptr, L->cd.sinv, L->status);
 }
 
 // the group matrices of ONE condensed patch again -- X_g, W_g by LU with partial pivoting -- and its Schur complement into scr

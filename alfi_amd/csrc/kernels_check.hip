@@ -50,11 +50,12 @@ __global__ void probe_fill_kernel(double* __restrict__ e, int64_t n) {
     e[i] = probe_entry(i);
 }
 
-// one workgroup per patch.  The level's own apply kernels (whatever the storage of the factors: row pieces, large
+// one workgroup per patch of [p0, p0 + gridDim.x).  The level's own apply kernels (whatever the storage of the factors: row pieces, large
 // patches, condensed) have put y_p = X_p e_p into the staging buffer; this kernel forms A_p y_p - e_p from the
 // operator rows.  Dynamic LDS: n int32 + n doubles.
 template <int BS>
-__global__ __launch_bounds__(256) void patch_check_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
+__global__ __launch_bounds__(256) void patch_check_kernel(int64_t p0, const int32_t* __restrict__ rowptr,
+                                                           const int32_t* __restrict__ colidx,
                                                            const double* __restrict__ vals, int flat,
                                                            const int64_t* __restrict__ patch_ptr,
                                                            const int32_t* __restrict__ patch_dofs,
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(256) void patch_check_kernel(const int32_t* __restr
                                                            const int32_t* __restrict__ fc_fac, const double* __restrict__ fc_s,
                                                            const double* __restrict__ fc_beta, double fc_scale) {
   extern __shared__ unsigned char smem[];
-  const int64_t p = blockIdx.x;
+  const int64_t p = p0 + blockIdx.x;
   const int64_t off = patch_ptr[p];
   const int n = (int)(patch_ptr[p + 1] - off);
   double* y_s = reinterpret_cast<double*>(smem);
@@ -283,32 +284,35 @@ __global__ __launch_bounds__(256) void patch_repair_kernel(const int32_t* __rest
 
 }  // namespace
 
-// probe all patches: e = +-1 by dof, the level's stage-1 apply, residual per patch; results accumulate in L->chk (device)
-static int launch_check(alfi_level* L, double tol) {
+// probe the patches [p0, p1): e = +-1 by dof (probe_vec, or made here), the level's stage-1 apply, residual per patch; results
+// accumulate in L->chk (device)
+static int launch_check(alfi_level* L, double tol, int64_t p0, int64_t p1, const double* probe_vec = nullptr) {
   alfi_ctx* ctx = L->ctx;
-  if (L->npatch == 0) return 0;
+  if (p1 <= p0) return 0;
   const bool fc = L->fc_ptr && L->fc_scale != 0.0;
-  double* e = nullptr;
-  ALFI_HIP_CHECK(ctx, hipMalloc((void**)&e, sizeof(double) * (size_t)std::max<int64_t>(L->n, 1)));
-  hipLaunchKernelGGL(probe_fill_kernel, dim3(1024), dim3(256), 0, ctx->stream, e, L->n);
-  int rc = launch_patch_apply_range(L, 0, L->npatch, e);
+  double* own = nullptr;
+  if (!probe_vec) {
+    ALFI_CHECK(patch_probe_vector(L, &own));
+    probe_vec = own;
+  }
+  int rc = launch_patch_apply_range(L, p0, p1, probe_vec);
   if (rc == 0) {
     const size_t lds = (size_t)L->lay.max_np * (sizeof(double) + sizeof(int32_t));
     unsigned long long* worst = reinterpret_cast<unsigned long long*>(L->chk);
     int* nflag = reinterpret_cast<int*>(L->chk + 1);
-    dim3 grid((unsigned)L->npatch), block(256);
+    dim3 grid((unsigned)(p1 - p0)), block(256);
     if (L->bs == 2)
-      hipLaunchKernelGGL(patch_check_kernel<2>, grid, block, lds, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals, L->A.flat,
+      hipLaunchKernelGGL(patch_check_kernel<2>, grid, block, lds, ctx->stream, p0, L->A.rowptr, L->A.colidx, L->A.vals, L->A.flat,
                          L->patch_ptr, L->patch_dofs, L->stage_ptr, L->stage, tol, worst, L->chk_list, nflag, L->chk_cap,
                          fc ? L->fc_ptr : nullptr, L->fc_col, L->fc_fac, L->fc_s, L->fc_beta, L->fc_scale);
     else
-      hipLaunchKernelGGL(patch_check_kernel<3>, grid, block, lds, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals, L->A.flat,
+      hipLaunchKernelGGL(patch_check_kernel<3>, grid, block, lds, ctx->stream, p0, L->A.rowptr, L->A.colidx, L->A.vals, L->A.flat,
                          L->patch_ptr, L->patch_dofs, L->stage_ptr, L->stage, tol, worst, L->chk_list, nflag, L->chk_cap,
                          fc ? L->fc_ptr : nullptr, L->fc_col, L->fc_fac, L->fc_s, L->fc_beta, L->fc_scale);
     if (hipGetLastError() != hipSuccess) rc = alfi_set_error(ctx, ALFI_E_HIP, "patch_check_kernel launch failed");
   }
   (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(e);
+  if (own) (void)hipFree(own);
   return rc;
 }
 
@@ -372,7 +376,7 @@ static int cond_repair(alfi_level* L, double tol, int nflag, double worst) {
   if (rc != 0) return rc;
   if (st != 0) return alfi_set_error(ctx, ALFI_E_SINGULAR, "a condensed patch operator is singular to working precision (pivoted inversion)");
   ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->chk, 0, 2 * sizeof(double), ctx->stream));
-  rc = launch_check(L, tol);
+  rc = launch_check(L, tol, 0, L->npatch);
   double worst2 = 0.0;
   int nflag2 = 0;
   if (rc == 0) rc = read_check(L, &worst2, &nflag2);
@@ -386,15 +390,47 @@ static int cond_repair(alfi_level* L, double tol, int nflag, double worst) {
   return 0;
 }
 
+// the level's probe vector e (+-1 by dof) on the device; the caller frees it (hipFree)
+int patch_probe_vector(alfi_level* L, double** probe_vec) {
+  alfi_ctx* ctx = L->ctx;
+  double* e = nullptr;
+  ALFI_HIP_CHECK(ctx, hipMalloc((void**)&e, sizeof(double) * (size_t)std::max<int64_t>(L->n, 1)));
+  hipLaunchKernelGGL(probe_fill_kernel, dim3(1024), dim3(256), 0, ctx->stream, e, L->n);
+  if (hipGetLastError() != hipSuccess) {
+    (void)hipFree(e);
+    return alfi_set_error(ctx, ALFI_E_HIP, "probe_fill_kernel launch failed");
+  }
+  *probe_vec = e;
+  return 0;
+}
+
+// what alfi_patches_check reports, from the figures of the ranges (one range: the whole level)
+int patch_check_finish(alfi_level* L, const PatchCheckAcc& acc) {
+  L->chk_worst = acc.worst;
+  L->chk_flagged = acc.flagged;
+  L->chk_repaired = acc.repaired;
+  L->chk_worst_after = acc.worst_after;
+  return 0;
+}
+
 // Called by alfi_patches_factor after the fast inversion.  unpivoted_status: the zero-pivot flag of that inversion (a
 // patch that met one holds non-finite entries and is caught by the probe).
 int patch_verify_and_repair(alfi_level* L, int unpivoted_status) {
+  PatchCheckAcc acc;
+  const int rc = patch_verify_and_repair_range(L, unpivoted_status, 0, L->npatch, nullptr, &acc);
+  patch_check_finish(L, acc);
+  return rc;
+}
+
+// The probe, the repair and the second probe for the patches [p0, p1) (dense inverses; condensed levels: the whole level only).
+// A level factored range by range sees in *acc what one pass over all its patches would have reported: the worst first residual,
+// the flagged and repaired counts, and the worst residual of the inverses it ends up with.
+int patch_verify_and_repair_range(alfi_level* L, int unpivoted_status, int64_t p0, int64_t p1, const double* probe_vec,
+                                  PatchCheckAcc* acc) {
   alfi_ctx* ctx = L->ctx;
   const bool enabled = alfi_env_patch_check();
   const double tol = alfi_env_patch_check_tol();
-  L->chk_worst = -1.0;
-  L->chk_flagged = L->chk_repaired = 0;
-  if (!enabled || L->npatch == 0) {
+  if (!enabled || p1 <= p0) {
     if (unpivoted_status != 0) return alfi_set_error(ctx, ALFI_E_SINGULAR, "zero pivot while inverting a patch operator");
     return 0;
   }
@@ -404,18 +440,27 @@ int patch_verify_and_repair(alfi_level* L, int unpivoted_status) {
     ALFI_HIP_CHECK(ctx, hipMalloc((void**)&L->chk_list, sizeof(int32_t) * (size_t)L->chk_cap));
   }
   ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->chk, 0, 2 * sizeof(double), ctx->stream));
-  ALFI_CHECK(launch_check(L, tol));
+  ALFI_CHECK(launch_check(L, tol, p0, p1, probe_vec));
   double worst = 0.0;
   int nflag = 0;
   ALFI_CHECK(read_check(L, &worst, &nflag));
-  L->chk_worst = worst;
-  L->chk_flagged = nflag;
-  if (nflag == 0) return 0;
+  acc->worst = std::max(acc->worst, worst);
+  acc->flagged += nflag;
+  if (nflag == 0) {
+    acc->worst_after = std::max(acc->worst_after, worst);
+    return 0;
+  }
   if (nflag > L->chk_cap)
     return alfi_set_error(ctx, ALFI_E_SINGULAR, "%d of %lld patch inverses fail the residual probe (worst %.3e)", nflag,
-                          (long long)L->npatch, worst);
+                          (long long)(p1 - p0), worst);
   constexpr int REPAIR_MAX_NP = PATCH_MAX;     // (a 2000-dof patch takes ~0.5 s of one workgroup: a rare-path safety net)
-  if (L->cond) return cond_repair(L, tol, nflag, worst);
+  if (L->cond) {
+    L->chk_repaired = 0;
+    const int rc = cond_repair(L, tol, nflag, worst);
+    acc->repaired += L->chk_repaired;
+    if (rc == 0) acc->worst_after = L->chk_worst_after;
+    return rc;
+  }
   // a Burman level: the repair subtracts the facet terms PCPATCH leaves out from the gathered matrix (RepairFacetRule)
   RepairFacetRule fc;
   if (L->fc_ptr && L->fc_scale != 0.0) fc = RepairFacetRule{L->fc_ptr, L->fc_col, L->fc_fac, L->fc_s, L->fc_beta, L->fc_scale};
@@ -457,15 +502,15 @@ int patch_verify_and_repair(alfi_level* L, int unpivoted_status) {
   if (rc != 0) return rc;
   if (st != 0) return alfi_set_error(ctx, ALFI_E_SINGULAR, "a patch operator is singular to working precision (pivoted inversion)");
   ALFI_CHECK(build_patch_il(L));      // small-patch levels: the repaired inverses into the interleaved copy the apply streams
-  // probe again (all patches: the apply kernels work on whole levels)
+  // probe again (every patch of the range, the untouched ones included)
   ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->chk, 0, 2 * sizeof(double), ctx->stream));
-  rc = launch_check(L, tol);
+  rc = launch_check(L, tol, p0, p1, probe_vec);
   double worst2 = 0.0;
   int nflag2 = 0;
   if (rc == 0) rc = read_check(L, &worst2, &nflag2);
   if (rc != 0) return rc;
-  L->chk_repaired = nflag - nflag2;
-  L->chk_worst_after = worst2;
+  acc->repaired += nflag - nflag2;
+  acc->worst_after = std::max(acc->worst_after, worst2);
   // A patch that stays above the tolerance after a pivoted LU inversion is ill-conditioned, not mis-factored: the probe
   // residual of a backward-stable inverse scales like cond(A_p) eps (gamma / nu h^-2 eps: 5e-8 at Re 5000 on the shipped
   // meshes, more on finer levels at Re 10 000).  LAPACK -- the reference's patch solver -- would hand back the same

@@ -517,12 +517,13 @@ __global__ __launch_bounds__(256) void patch_unrank_kernel(int64_t p0, const int
   }
 }
 
-// the single-precision copy <- the FP64 row-piece storage: a workgroup per patch, a thread per stored float (pad rows included)
-__global__ __launch_bounds__(256) void patch_f32_convert_kernel(const int64_t* __restrict__ patch_ptr,
+// the single-precision copy <- the FP64 row-piece storage: a workgroup per patch of [p0, p0 + gridDim.x), a thread per stored float
+// (pad rows included)
+__global__ __launch_bounds__(256) void patch_f32_convert_kernel(int64_t p0, const int64_t* __restrict__ patch_ptr,
                                                                  const int64_t* __restrict__ inv_ptr,
                                                                  const int64_t* __restrict__ inv32_ptr,
                                                                  const double* __restrict__ inv, float* __restrict__ inv32) {
-  const int64_t p = blockIdx.x;
+  const int64_t p = p0 + blockIdx.x;
   const int n = (int)(patch_ptr[p + 1] - patch_ptr[p]);
   const int ld = (n + 1) & ~1, ld32 = f32_ld(n);
   const double* S = inv + inv_ptr[p];
@@ -1224,6 +1225,10 @@ int launch_patch_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double
     ALFI_CHECK(launch_cond_apply_range(L, p0, p1, x));
     return 0;
   }
+  if (L->f32 && L->lay.max_np > SMALL_PATCH_MAX) {   // single-precision macro stars (kernels_bigpatch.hip)
+    ALFI_CHECK(launch_big_apply_f32_range(L, p0, p1, x));
+    return 0;
+  }
   if (L->f32) {                                 // single-precision storage: its own kernel whatever the patch count
     const int64_t cnt = p1 - p0;
 #define ALFI_F32_APPLY(WV)                                                                                                  \
@@ -1332,10 +1337,13 @@ int launch_patch_unrank(alfi_level* L) {
   return rc;
 }
 
-int launch_patch_f32_convert(alfi_level* L, const double* src) {
+int launch_patch_f32_convert(alfi_level* L, const double* src) { return launch_patch_f32_convert_range(L, src, 0, L->npatch); }
+
+// the patches [p0, p1): src + inv_ptr[p] holds patch p's FP64 inverse
+int launch_patch_f32_convert_range(alfi_level* L, const double* src, int64_t p0, int64_t p1) {
   alfi_ctx* ctx = L->ctx;
-  if (L->npatch == 0) return 0;
-  hipLaunchKernelGGL(patch_f32_convert_kernel, dim3((unsigned)L->npatch), dim3(256), 0, ctx->stream, L->patch_ptr, L->inv_ptr,
+  if (p1 <= p0) return 0;
+  hipLaunchKernelGGL(patch_f32_convert_kernel, dim3((unsigned)(p1 - p0)), dim3(256), 0, ctx->stream, p0, L->patch_ptr, L->inv_ptr,
                      L->inv32_ptr, src, L->inv32);
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   return 0;

@@ -793,7 +793,7 @@ static int mf_numeric(alfi_level* L, MfDev* m) {
     fill.xoff = m->xoff;
     fill.fac = m->fac;
     src.M = &fill;
-    rc = big_factor_core(ctx, src, cnt, hptr.data(), dptr, nullptr, nullptr, L->status);
+    rc = big_factor_core(ctx, src, 0, cnt, hptr.data(), dptr, nullptr, nullptr, L->status);
     (void)hipFree(dptr);
     if (rc != 0) break;
     // W = X F_sb and L = F_bs X, each with one residual correction (the entries of X are large and those of the products

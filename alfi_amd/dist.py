@@ -784,7 +784,7 @@ class DistMultigrid(object):
     def __init__(self, levels, transfers, k, robust_restriction=False, group=None, device=None, min_dofs=400000,
                  coarse_inverse=None, verbose=False, force_distributed=False, overlap=None, overlap_min_dofs=None,
                  transport=None, on_stage=None, use_overlap_rule=True, solo=None, full_cycle=False,
-                 condense_min_bytes=None, patch_factor_dtype=None):
+                 condense_min_bytes=None, patch_factor_dtype=None, macro_factor_dtype=None):
         """transport: "rccl" -- the library's own RCCL communicator serves every exchange point of a cycle (no Python
         between the kernels; the default whenever the process group's backend is nccl) -- or "callback": the library
         calls back into this module, which exchanges through torch.distributed (the test transport: gloo, ranks sharing
@@ -794,10 +794,15 @@ class DistMultigrid(object):
         own sparsity and stores condensed factors (Context.set_condense_min_bytes, set before the first factorisation; None: the
         library's default, 0: wherever groups are found, < 0: never).  ``patch_storage()`` reports what every local level decided.
         patch_factor_dtype: None, or "f32": every rank asks its own smoothed levels to store their dense patch inverses in single
-        precision (hip.ask_patch_storage; no collective: a level without an FP32 form keeps FP64 on that rank)."""
+        precision (hip.ask_patch_storage; no collective: a level without an FP32 form keeps FP64 on that rank).
+        macro_factor_dtype: None, or "f32": the request macro stars and Burman levels can take (hip.ask_macro_patch_storage),
+        asked of every rank's local levels, facet-coupled ones included; a level with the generator's groups stays condensed
+        FP64.  The big-patch path has no canonical elimination order: a rank's float32 values are those of ITS numbering, no
+        bitwise agreement with the serial level is promised.  One of the two keywords at most (ValueError)."""
         import time
         import torch
         from . import hip
+        hip.check_factor_dtypes(patch_factor_dtype, macro_factor_dtype)
         stage = on_stage or (lambda name: None)
         self.setup_s = {}
         # solo = (rank, world): that rank of a world-rank job alone in this process, exchange points stubbed (SoloComm: timing only)
@@ -919,6 +924,8 @@ class DistMultigrid(object):
                         if (patch_factor_dtype is not None and LL.A.vals is not None
                                 and getattr(LL, "patch_rank", None) is not None):
                             dl.set_patch_canonical_order(LL.patch_rank)
+                    if len(LL.patch_ptr) > 1:
+                        hip.ask_macro_patch_storage(dl, macro_factor_dtype)
                     hip.note_patch_level(LL, dl)
                     if LL.A.vals is not None:          # (None: the operators are formed on the device first, the caller factors)
                         dl.factor_with_fallback()

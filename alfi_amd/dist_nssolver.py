@@ -177,7 +177,8 @@ class DistNavierStokesSolver(HipNavierStokesSolver):
         self.dmg = DistMultigrid(self.levels, self.transfers, self.params["fieldsplit_0"]["mg_levels"]["ksp_max_it"],
                                  robust_restriction=restriction, group=self._group, min_dofs=self._min_dofs,
                                  full_cycle=self.params["fieldsplit_0"].get("pc_mg_type") == "full",
-                                 condense_min_bytes=self._condense_min_bytes, patch_factor_dtype=self._patch_factor_dtype)
+                                 condense_min_bytes=self._condense_min_bytes, patch_factor_dtype=self._patch_factor_dtype,
+                                 macro_factor_dtype=self._macro_factor_dtype)
         self.ctx = self.dmg.ctx
         L = self.levels[-1]
         self.saddle = sad = DistSaddle(self.dmg, self.B, self.vol, L.V.cell_nodes, self.nu, self.gamma,

@@ -51,6 +51,17 @@ class Context(object):
         are taken in batches."""
         self.check(self.lib.alfi_ctx_set_assembly_scratch(self.h, int(max_bytes)))
 
+    def set_f32_work_bytes(self, n):
+        """Cap in bytes on the FP64 work buffer that FP32 levels of big patches are factored through, range by range
+        (alfi_ctx_set_f32_work_bytes; default 1 GiB; n <= 0: AlfiHipError with E_ARG)."""
+        self.check(self.lib.alfi_ctx_set_f32_work_bytes(self.h, int(n)))
+
+    def f32_work_bytes(self):
+        """Bytes of the FP64 work buffer the context holds for its FP32 levels now (alfi_ctx_f32_work_bytes)."""
+        b = ctypes.c_int64()
+        self.check(self.lib.alfi_ctx_f32_work_bytes(self.h, ctypes.byref(b)))
+        return b.value
+
     def set_condense_min_bytes(self, min_bytes):
         """A level without caller-supplied groups looks for condensable groups in its own sparsity at its first factorisation
         when its dense patch inverses would take at least this many bytes (alfi_ctx_set_condense_min_bytes; default 1 GiB,
@@ -450,6 +461,16 @@ class Level(object):
             raise ValueError("patch storage %r (f64 or f32)" % (dtype,))
         self.ctx.check(self.ctx.lib.alfi_patches_set_storage(self.h, self.STORAGE_DTYPES[dtype]))
 
+    def set_macro_patch_storage(self, dtype):
+        """The FP32 request of macro stars and Burman levels (alfi_patches_set_macro_storage): "f64" or "f32" from the next
+        ``factor()`` on.  Accepts what ``set_patch_storage`` refuses -- a patch above 160 dofs (the level is then factored in
+        patch ranges through the context's work buffer, ``Context.set_f32_work_bytes``) and a facet correction, set before or
+        after.  AlfiHipError with ``code == E_ARG`` where no FP32 form exists (no patches, every patch <= 32 dofs,
+        caller-supplied groups, multiplicative sweeps); the level stays as it was."""
+        if dtype not in self.STORAGE_DTYPES:
+            raise ValueError("patch storage %r (f64 or f32)" % (dtype,))
+        self.ctx.check(self.ctx.lib.alfi_patches_set_macro_storage(self.h, self.STORAGE_DTYPES[dtype]))
+
     def set_patch_canonical_order(self, rank):
         """FP32 levels (alfi_patches_set_canonical_order): ``rank[q]`` = the place of entry q of patch_dofs in a canonical
         order of its patch -- for a rank's local level the order of the unpartitioned patch (dist.localize_level: ``patch_rank``),
@@ -751,6 +772,30 @@ def ask_patch_storage(dl, dtype):
     except AlfiHipError as e:
         if e.code != E_ARG:
             raise
+
+
+def ask_macro_patch_storage(dl, dtype):
+    """The front ends' ``macro_factor_dtype`` keyword on one device level, as ask_patch_storage: None asks nothing; "f32" asks
+    the level through ``Level.set_macro_patch_storage``, and a level the library refuses with ALFI_E_ARG (caller-supplied
+    groups: the condensed Scott-Vogelius levels; small 2-D stars; multiplicative sweeps) keeps FP64.  Any other error
+    propagates."""
+    if dtype is None:
+        return
+    if dtype != "f32":
+        raise ValueError("macro_factor_dtype %r (None or \"f32\")" % (dtype,))
+    try:
+        dl.set_macro_patch_storage(dtype)
+    except AlfiHipError as e:
+        if e.code != E_ARG:
+            raise
+
+
+def check_factor_dtypes(patch_factor_dtype, macro_factor_dtype):
+    """One FP32 request per level: the two keywords of the front ends exclude each other."""
+    if patch_factor_dtype is not None and macro_factor_dtype is not None:
+        raise ValueError("patch_factor_dtype and macro_factor_dtype are two requests for the same levels: give one")
+    if macro_factor_dtype not in (None, "f32"):
+        raise ValueError("macro_factor_dtype %r (None or \"f32\")" % (macro_factor_dtype,))
 
 
 def condense_patches(L):

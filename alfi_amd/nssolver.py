@@ -65,7 +65,7 @@ class HipNavierStokesSolver(object):
     def __init__(self, problem, nref, k, gamma=1e4, smoothing=None, restriction=False, ctx=None, verbose=False,
                  snes_rtol=None, snes_atol=None, snes_stol=1e-6, snes_max_it=20, discretisation="pkp0", stabilisation_type=None,
                  stabilisation_weight=None, supg_magic=9.0, device_assembly=None, solver_type="almg", direct_max_bytes=0,
-                 patch_factor_dtype=None):
+                 patch_factor_dtype=None, macro_factor_dtype=None):
         """discretisation: "pkp0" ([P_k(+FB)]^d - P0 on the uniform hierarchy, ConstantPressureSolver solver.py:561-602) or
         "sv" ([P_k]^d - P_{k-1}^dg on the barycentric hierarchy with macro-star patches, ScottVogeliusSolver :604-662).
         stabilisation_type: None / "none", "supg" or "gls" (P0-pressure pairs; GLS's wind is the velocity at the start of each
@@ -80,8 +80,11 @@ class HipNavierStokesSolver(object):
         ignored, as on the reference's idealal lines); "lu", "simple", "lsc", "alamg": NotImplementedError.
         direct_max_bytes: allu only -- cap on the factors + front storage in bytes (0: the free device memory).
         patch_factor_dtype: None, or "f32": the smoothed levels store their dense patch inverses in single precision where that
-        form exists (hip.ask_patch_storage); every refactorisation of a Newton step converts again."""
-        self._patch_factor_dtype = patch_factor_dtype
+        form exists (hip.ask_patch_storage); every refactorisation of a Newton step converts again.
+        macro_factor_dtype: None, or "f32": the same for macro stars and Burman levels (hip.ask_macro_patch_storage; levels that
+        store condensed factors on the generator's groups keep them in FP64).  One of the two keywords at most (ValueError)."""
+        hip.check_factor_dtypes(patch_factor_dtype, macro_factor_dtype)
+        self._patch_factor_dtype, self._macro_factor_dtype = patch_factor_dtype, macro_factor_dtype
         check_solver_type(solver_type, self._partitioned)
         self.solver_type = solver_type
         self.allu = solver_type == "allu"
@@ -230,7 +233,7 @@ class HipNavierStokesSolver(object):
     def _create_device(self, restriction):
         self.ctx = self._ctx_arg or hip.Context(0)
         self.hmg = HipMG(self.ctx, self.levels, self.transfers, self._fieldsplit_0_mg, restriction=restriction,
-                         patch_factor_dtype=self._patch_factor_dtype)
+                         patch_factor_dtype=self._patch_factor_dtype, macro_factor_dtype=self._macro_factor_dtype)
         self.saddle = hip.Saddle(self.hmg.mg, self.B, None if self.sv else self.vol, self.nu, self.gamma,
                                  remove_constant_nullspace=self.nullspace, mass_inv=self.Minv)
         self._ksp, self._device_transfers = self.saddle, list(zip(self.transfers, self.hmg.mg.transfers))

@@ -366,6 +366,10 @@ class HipPatchPC(object):
         # multiplicative sweeps or the caller a facet correction afterwards: neither has an FP32 form, the level keeps FP64
         if not self.multiplicative and not getattr(L, "facet_coupling", False):
             hip.ask_patch_storage(self.level, getattr(pc, "patch_factor_dtype", None))
+        # the front end's macro_factor_dtype: asked after the groups decision, facet-coupled levels included (the request takes a
+        # facet correction set afterwards).  A level that got the caller's groups above is refused and stays condensed FP64.
+        if not self.multiplicative:
+            hip.ask_macro_patch_storage(self.level, getattr(pc, "macro_factor_dtype", None))
         if L.A.vals is not None:
             self.level.factor()
         hip.note_patch_level(L, self.level)
@@ -401,9 +405,13 @@ class HipMG(object):
     ``ksp_chebyshev_eigenvalues`` ("emin,emax": no estimate is run); ``pc_type`` python (``pc_python_type``) | jacobi.
     ``pc_mg_cycle_type`` v | w.  The Chebyshev intervals are estimated at construction and again by ``update``."""
 
-    def __init__(self, ctx, levels, transfers, params, restriction=False, coarse_inv=None, patch_factor_dtype=None):
+    def __init__(self, ctx, levels, transfers, params, restriction=False, coarse_inv=None, patch_factor_dtype=None,
+                 macro_factor_dtype=None):
         """patch_factor_dtype: None, or "f32": every smoothed level is asked to store its dense patch inverses in single
-        precision (hip.ask_patch_storage; a keyword, not an option: the dictionaries mirror the reference's)."""
+        precision (hip.ask_patch_storage; a keyword, not an option: the dictionaries mirror the reference's).
+        macro_factor_dtype: None, or "f32": the same request in the form macro stars and Burman levels can take
+        (hip.ask_macro_patch_storage: levels with the caller's groups stay condensed FP64).  One of the two at most."""
+        hip.check_factor_dtypes(patch_factor_dtype, macro_factor_dtype)
         self.opts = o = parse_mg_options(params)
         mgl = params["mg_levels"]
         self.k = o["k"]
@@ -428,6 +436,7 @@ class HipMG(object):
                 continue
             pc = PC(ctx, L, options=mgl)
             pc.patch_factor_dtype = patch_factor_dtype
+            pc.macro_factor_dtype = macro_factor_dtype
             obj = HipJacobiPC() if jacobi else pc_cls()
             obj.initialize(pc)
             self.pcs.append(pc)

@@ -320,6 +320,34 @@ int alfi_patches_condensed(alfi_level* lvl, int* mode);
 #define ALFI_STORAGE_F32 1
 int alfi_patches_set_storage(alfi_level* lvl, int dtype);
 int alfi_patches_storage(alfi_level* lvl, int* dtype);
+/* The FP32 request of the levels alfi_patches_set_storage refuses for want of a kernel or of a place for the facet rule: macro
+ * stars (a patch above 160 dofs, up to 4096) and Burman levels (a facet correction, set before OR after this call).  A second,
+ * separate request: nothing alfi_patches_set_storage does changes.  Same dtypes, same timing (after alfi_patches_set; the next
+ * alfi_patches_factor obeys it), same error model: the apply differs from the FP64 one by at most 2^-24 (|inv(A_p)| |x|)_i per
+ * patch row plus FP64 round-off, every product and sum being FP64.
+ *   - A level with a patch above 160 dofs is FACTORED IN PATCH RANGES: the longest runs of consecutive patches whose FP64 row
+ *     pieces fit alfi_ctx_set_f32_work_bytes (one larger patch is a range of its own) pass, one after the other, through the
+ *     ctx's FP64 work buffer -- blocked inversion with the facet rule and the polish, residual probe, pivoted repair, second
+ *     probe, rounding to nearest into the level's float32 copy.  The level holds sum 4 n_p^2 bytes (padded) and the ctx the work
+ *     buffer; the FP64 inverses of the whole level never exist at once.  The stored values do not depend on the ranges, and
+ *     alfi_patches_check reports the figures of the FP64 inverses before rounding, accumulated over the ranges: those of an FP64
+ *     level.  big_apply_f32_kernel applies them (a workgroup per patch, float4 loads, FP64 fma).
+ *   - A level whose every patch has <= 160 dofs takes the path of alfi_patches_set_storage (whole-level work buffer), with the
+ *     facet rule applied on the work buffer.
+ * ALFI_E_ARG, before any device work and with the level left as it was: no patches; every patch <= 32 dofs (the interleaved
+ * copy); caller-supplied groups (condensed factors cancel in single precision); multiplicative sweeps.  On a level asked through
+ * this call alfi_patches_set_multiplicative and alfi_patches_set_groups (non-NULL) return ALFI_E_STATE;
+ * alfi_patches_set_facet_correction is accepted and marks the level unfactored.  Such a level never condenses itself.
+ * alfi_patches_set starts a patch set in FP64 again; alfi_patches_storage, alfi_patches_factor_bytes and alfi_patch_get_inverse
+ * report the single-precision copy as for alfi_patches_set_storage. */
+int alfi_patches_set_macro_storage(alfi_level* lvl, int dtype);
+/* Cap in bytes on the FP64 work buffer the levels of alfi_patches_set_macro_storage with a patch above 160 dofs are factored
+ * through, range by range (default 1 GiB; bytes <= 0: ALFI_E_ARG).  The buffer belongs to the ctx, is shared with the
+ * whole-level buffer of the levels of small patches (which this cap does not bound), grows only -- for big-patch levels to
+ * max(cap, their largest patch: at most 134 MB) --, is not counted in alfi_patches_factor_bytes and is released with the
+ * ctx's last FP32 level.  alfi_ctx_f32_work_bytes: what the ctx holds now. */
+int alfi_ctx_set_f32_work_bytes(alfi_ctx* ctx, int64_t bytes);
+int alfi_ctx_f32_work_bytes(alfi_ctx* ctx, int64_t* bytes);
 /* FP32 levels only (FP64 levels ignore it): rank_host[q] = the place of entry q of patch_dofs in a canonical order of its patch
  * (per patch a permutation of 0 .. n_p - 1, else ALFI_E_ARG; NULL: none).  The unpivoted elimination of the next
  * alfi_patches_factor then runs in that order instead of the order of patch_dofs, and the inverses are turned back before the
