@@ -48,6 +48,8 @@ def lib():
         _lib.alfi_host_burman.restype = ctypes.c_int
         _lib.alfi_host_find_groups.restype = ctypes.c_int64
         _lib.alfi_host_f32_index_table.restype = None
+        _lib.alfi_host_piece_index_table.restype = None
+        _lib.alfi_host_patch_index_table.restype = None
         for name in ("patch_layout", "condensed", "sweep", "f32_layout", "macro_f32_layout"):
             getattr(_lib, "alfi_host_plan_" + name).restype = ctypes.c_void_p
         _lib.alfi_host_f32_index.restype = ctypes.c_int64
@@ -149,6 +151,21 @@ def f32_index_table(n):
     idx = np.empty((ld, n), dtype=np.int64)
     L.alfi_host_f32_index_table(ctypes.c_int(n), _p(idx))
     return ld, L.alfi_host_f32_patch_floats(ctypes.c_int(n)), idx
+
+
+def piece_index_table(n, ld, min_rows):
+    """(ld, n) offsets of the row-piece storage of an n x n inverse with rows padded to ld (csrc/patch_plan.h: piece_index)."""
+    idx = np.empty((ld, n), dtype=np.int64)
+    lib().alfi_host_piece_index_table(ctypes.c_int(n), ctypes.c_int(ld), ctypes.c_int(min_rows), _p(idx))
+    return idx
+
+
+def patch_index_table(n):
+    """The same through the FP64 wrapper (patch_inv_index): rows padded to even."""
+    ld = (n + 1) // 2 * 2
+    idx = np.empty((ld, n), dtype=np.int64)
+    lib().alfi_host_patch_index_table(ctypes.c_int(n), ctypes.c_int(ld), _p(idx))
+    return idx
 
 
 def f32_index(n):

@@ -537,7 +537,7 @@ int alfi_patches_factor(alfi_level* L) {
   } else {
     // (an FP32 level with a canonical order eliminates in that order and turns the inverses back: the rest sees patch_dofs' order)
     const bool ranked = L->f32_req && L->canon_rank;
-    ALFI_CHECK(ranked ? launch_patch_gather_ranked(L) : launch_patch_gather_dense(L));
+    ALFI_CHECK(launch_patch_gather_dense(L, ranked));
     if (L->fc_ptr && L->fc_scale != 0.0) ALFI_CHECK(launch_patch_facet_correct(L, 0, L->npatch, L->inv_ptr, L->inv, 0));
     ALFI_CHECK(launch_patch_invert(L));
     if (ranked) ALFI_CHECK(launch_patch_unrank(L));

@@ -149,29 +149,7 @@ constexpr int BURMAN_MAXQ = 32;        // points of a facet rule the Burman kern
 constexpr int BURMAN_MAXN = 20;        // nodes per cell the Burman kernels take ([P3]^3)
 // (SMALL_PATCH_MAX, PATCH_MAX: patch_plan.h)
 
-// ---- storage of one dense patch inverse (n x n, rows padded to ld = n rounded up to even) --------------------------------
-// Row pieces: as many 128-row pieces as fit, then the binary digits of the remainder (64, 32, ..., 2).  A piece of R rows
-// is stored [column][R] contiguously, pieces follow each other, so the whole inverse is ld * n contiguous doubles that
-// the apply kernel streams front to back exactly once, every wave instruction reading 1 KiB of consecutive bytes
-// (64 / (R/2) columns at a time).  Offset of entry (r, c):
-__host__ __device__ inline int64_t patch_inv_index(int r, int c, int n, int ld) {
-  int row0 = r & ~127, rows = 128;
-  if (row0 + 128 > ld) {
-    const int rem = ld - row0;
-    int rr = r - row0;
-    for (int bit = 64; bit >= 2; bit >>= 1) {
-      if (rem & bit) {
-        if (rr < bit) {
-          rows = bit;
-          break;
-        }
-        rr -= bit;
-        row0 += bit;
-      }
-    }
-  }
-  return (int64_t)row0 * n + (int64_t)c * rows + (r - row0);
-}
+// (storage of one dense patch inverse -- row pieces; patch_inv_index, f32_inv_index: patch_plan.h)
 
 // Interleaved storage of SMALL patch inverses (every n_p <= 2 G <= 32): G lanes share a patch (lane l owns the row pair
 // 2l, 2l + 1), PW = 64 / G patches share a wave, and the wave's PW patches are stored column by column,
@@ -581,7 +559,9 @@ int launch_bsr_spmv(alfi_ctx* ctx, const DevBSR& A, const double* x, double* y, 
 // host (nnzb, bs, bs) values -> d->vals in d's layout (staged through a bounded device buffer)
 int upload_bsr_values(alfi_ctx* ctx, DevBSR* d, const double* host_vals);
 int build_spmv_dedup(alfi_ctx* ctx, DevBSR* d);     // column de-duplication tables of the flat product (kernels_vec.hip)
-int launch_patch_gather_dense(alfi_level* lvl);
+// A_p into the row-major scratch of the inversion; ranked (FP32 levels with a canonical order): row / column a of a patch at
+// position canon_rank[a]
+int launch_patch_gather_dense(alfi_level* lvl, bool ranked = false);
 int launch_patch_invert(alfi_level* lvl);
 // kernels_check.hip: probe || A_p X_p e - e || of every stored inverse, pivoted re-inversion of the patches that fail
 int patch_verify_and_repair(alfi_level* lvl, int unpivoted_status);
@@ -627,8 +607,7 @@ int launch_cond_schur_one(alfi_level* lvl, int64_t p, const int64_t* d_zero, dou
 // FP32 levels: inv32 <- the FP64 inverses at src (row-piece layout, offsets lvl->inv_ptr), rounded to nearest, pad rows zero
 int launch_patch_f32_convert(alfi_level* lvl, const double* src);
 int launch_patch_f32_convert_range(alfi_level* lvl, const double* src, int64_t p0, int64_t p1);
-int launch_patch_gather_ranked(alfi_level* lvl);   // FP32 levels with a canonical order: gather in that order ...
-int launch_patch_unrank(alfi_level* lvl);          // ... and the inverses back into the order of patch_dofs
+int launch_patch_unrank(alfi_level* lvl);          // a ranked gather's inverses back into the order of patch_dofs
 int build_patch_il(alfi_level* lvl);   // small-patch levels: (re)build the interleaved copy of the inverses from lvl->inv
 int launch_patch_sum(alfi_level* lvl, const double* x, double* y);             // stage 2
 int launch_patch_sum_range(alfi_level* lvl, int64_t i0, int64_t i1, const double* x, double* y);   // stage 2, dofs [i0, i1)

@@ -854,6 +854,16 @@ void alfi_host_f32_index_table(int n, int64_t* out) {
   for (int r = 0; r < ld; ++r)
     for (int c = 0; c < n; ++c) out[(int64_t)r * n + c] = f32_inv_index(r, c, n);
 }
+// the row-piece storage itself and its FP64 wrapper: out[r * n + c] = piece_index(r, c, n, ld, min_rows) / patch_inv_index(r, c, n,
+// ld), r < ld
+void alfi_host_piece_index_table(int n, int ld, int min_rows, int64_t* out) {
+  for (int r = 0; r < ld; ++r)
+    for (int c = 0; c < n; ++c) out[(int64_t)r * n + c] = piece_index(r, c, n, ld, min_rows);
+}
+void alfi_host_patch_index_table(int n, int ld, int64_t* out) {
+  for (int r = 0; r < ld; ++r)
+    for (int c = 0; c < n; ++c) out[(int64_t)r * n + c] = patch_inv_index(r, c, n, ld);
+}
 // entry (r, c) of an n x n inverse in that storage, r < alfi_host_f32_ld(n) (pad rows included), c < n; floats a patch occupies
 int64_t alfi_host_f32_index(int r, int c, int n) { return f32_inv_index(r, c, n); }
 int alfi_host_f32_ld(int n) { return f32_ld(n); }

@@ -8,12 +8,13 @@
 //    64 x 64 pivot block in LDS, the scaled pivot row panel R = D^-1 S[K,:], the saved column panel F = S[:,K] and
 //    S[:,K] <- -F D^-1) and the rank-64 trailing update S -= F R on the FP64 matrix cores
 //    (v_mfma_f64_16x16x4_f64: 95 % of the flops).  No pivoting across blocks, like the register kernel for small patches.
-//  * apply: one WORKGROUP per patch; the row pieces of the inverse (same storage as for small patches,
-//    patch_inv_index) are dealt round-robin to the four waves, x_p sits in LDS.
+//  * apply: one WORKGROUP per patch; the row pieces of the inverse (same storage as for small patches, piece_index in
+//    patch_plan.h; the loop that streams a piece: row_piece.h) are dealt round-robin to the four waves, x_p sits in LDS.
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
 #include "common.h"
+#include "row_piece.h"
 
 constexpr int BIG_NB = 64;          // pivot block / GEMM k-extent
 constexpr int BIG_MAX_NP = PATCH_MAX;
@@ -376,92 +377,13 @@ __global__ __launch_bounds__(256) void big_store_kernel(int64_t p0, const int64_
 // 3. additive apply, stage 1: one workgroup per patch, row pieces dealt to the four waves
 // ---------------------------------------------------------------------------------------------------------------------
 typedef double big_d2 __attribute__((ext_vector_type(2)));
-template <int G, bool NT>
-__device__ __forceinline__ void big_piece(const double* __restrict__ T, int n, const double* __restrict__ xs, int lane,
-                                          double* __restrict__ out) {
-  constexpr int C = 64 / G, U = 8;
-  const int cg = lane / G, l = lane % G;
-  const double* base = T + 2 * l;
-  double acc0 = 0.0, acc1 = 0.0;
-  int j = cg;
-  for (; j + (U - 1) * C < n; j += U * C) {
-    big_d2 v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const big_d2* q = reinterpret_cast<const big_d2*>(base + (int64_t)(j + u * C) * (2 * G));
-      v[u] = NT ? __builtin_nontemporal_load(q) : *q;
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const double xj = xs[j + u * C];
-      acc0 = __builtin_fma(v[u].x, xj, acc0);
-      acc1 = __builtin_fma(v[u].y, xj, acc1);
-    }
-  }
-  for (; j < n; j += C) {
-    const big_d2* q = reinterpret_cast<const big_d2*>(base + (int64_t)j * (2 * G));
-    const big_d2 v = NT ? __builtin_nontemporal_load(q) : *q;
-    const double xj = xs[j];
-    acc0 = __builtin_fma(v.x, xj, acc0);
-    acc1 = __builtin_fma(v.y, xj, acc1);
-  }
-  if (C > 1) {
-#pragma unroll
-    for (int o = G; o < 64; o <<= 1) {
-      acc0 += __shfl_xor(acc0, o);
-      acc1 += __shfl_xor(acc1, o);
-    }
-  }
-  if (cg == 0) *reinterpret_cast<double2*>(out + 2 * l) = make_double2(acc0, acc1);
-}
+constexpr int BIG_U = 8;            // 16-byte loads in flight per lane (piece_dot, row_piece.h); the tail a column at a time
 
 // Rows [r0, r1) of y = T x for a wave, T in the row-piece layout (pieces of 128 rows, then the binary digits of the rest;
 // piece (row0, P rows): entry (r, c) at T[row0 * n + c * P + (r - row0)]).  The range is cut into aligned power-of-two
 // blocks of rows inside the stored pieces: a block of 2 G rows takes G lanes per column and 64 / G columns per load
 // instruction.  Used where whole pieces dealt round-robin leave waves idle (a Schur complement of 312 rows is
 // 2 x 128 + 32 + 16 + 8: two of eight waves would stream 82 % of it).
-template <int G, bool NT>
-__device__ __forceinline__ void big_block(const double* __restrict__ Tp, int P, int n, const double* __restrict__ xs, int lane,
-                                          double* __restrict__ out, int lim) {
-  constexpr int C = 64 / G, U = 8;
-  const int cg = lane / G, l = lane % G;
-  const double* base = Tp + 2 * l;
-  double acc0 = 0.0, acc1 = 0.0;
-  int j = cg;
-  for (; j + (U - 1) * C < n; j += U * C) {
-    big_d2 v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const big_d2* q = reinterpret_cast<const big_d2*>(base + (int64_t)(j + u * C) * P);
-      v[u] = NT ? __builtin_nontemporal_load(q) : *q;
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const double xj = xs[j + u * C];
-      acc0 = __builtin_fma(v[u].x, xj, acc0);
-      acc1 = __builtin_fma(v[u].y, xj, acc1);
-    }
-  }
-  for (; j < n; j += C) {
-    const big_d2* q = reinterpret_cast<const big_d2*>(base + (int64_t)j * P);
-    const big_d2 v = NT ? __builtin_nontemporal_load(q) : *q;
-    const double xj = xs[j];
-    acc0 = __builtin_fma(v.x, xj, acc0);
-    acc1 = __builtin_fma(v.y, xj, acc1);
-  }
-  if (C > 1) {
-#pragma unroll
-    for (int o = G; o < 64; o <<= 1) {
-      acc0 += __shfl_xor(acc0, o);
-      acc1 += __shfl_xor(acc1, o);
-    }
-  }
-  if (cg == 0) {                       // lim: rows of the range that exist (the pad row of an odd n is not written)
-    if (2 * l < lim) out[2 * l] = acc0;
-    if (2 * l + 1 < lim) out[2 * l + 1] = acc1;
-  }
-}
-
 template <bool NT>
 __device__ __forceinline__ void big_rows(const double* __restrict__ T, int n, int ld, int r0, int r1,
                                          const double* __restrict__ xs, int lane, double* __restrict__ ys) {
@@ -487,26 +409,36 @@ __device__ __forceinline__ void big_rows(const double* __restrict__ T, int n, in
     int R = P;                         // the largest aligned power-of-two block at o that ends inside the piece and the range
     while (R > 2 && ((o & (R - 1)) != 0 || o + R > P || r + R > r1)) R >>= 1;
     const double* Tp = T + (int64_t)row0 * n + o;
+    // (lim = n - r: the pad row of an odd n is not written)
+#define ALFI_BIG_BLOCK(RV) \
+  case RV: piece_apply<double, RV / 2, NT, BIG_U, false, PieceStore::GUARDED>(Tp, P, n, xs, lane, ys + r, n - r); break;
     switch (R) {
-      case 128: big_block<64, NT>(Tp, P, n, xs, lane, ys + r, n - r); break;
-      case 64: big_block<32, NT>(Tp, P, n, xs, lane, ys + r, n - r); break;
-      case 32: big_block<16, NT>(Tp, P, n, xs, lane, ys + r, n - r); break;
-      case 16: big_block<8, NT>(Tp, P, n, xs, lane, ys + r, n - r); break;
-      case 8: big_block<4, NT>(Tp, P, n, xs, lane, ys + r, n - r); break;
-      case 4: big_block<2, NT>(Tp, P, n, xs, lane, ys + r, n - r); break;
-      default: big_block<1, NT>(Tp, P, n, xs, lane, ys + r, n - r); break;
+      ALFI_BIG_BLOCK(128) ALFI_BIG_BLOCK(64) ALFI_BIG_BLOCK(32) ALFI_BIG_BLOCK(16) ALFI_BIG_BLOCK(8) ALFI_BIG_BLOCK(4)
+      default: piece_apply<double, 1, NT, BIG_U, false, PieceStore::GUARDED>(Tp, P, n, xs, lane, ys + r, n - r); break;
     }
+#undef ALFI_BIG_BLOCK
     r += R;
   }
 }
 
-template <bool NT>
+// One workgroup of 4 waves per patch (``split`` workgroups on launches of few patches): x_p into LDS, the stored row pieces of
+// the inverse dealt round-robin to the 4 split waves, every wave streaming its pieces whole (piece_apply, row_piece.h) and
+// writing their rows of the staged result.  S is the storage scalar of the inverse; the arithmetic is FP64 for both.
+// S = float (alfi_patches_set_macro_storage): the same work split over the single-precision copy.  A patch has (n + 1) & ~1
+// staging slots, not RowPiece<float>::ld(n): the sums of its pad rows (zeros) are NOT stored -- for n = 1, 2 mod 4 they would
+// land in the next patch's slots, or behind the staging buffer for the last patch.  A row's sum is the ascending columns of its
+// column group, then the groups by shuffles in a fixed order: it depends on the patch alone, not on the launch, the range or
+// ``split``.
+template <typename S, bool NT>
 __global__ __launch_bounds__(256) void big_apply_kernel(int64_t p0, int64_t npatch, const int64_t* __restrict__ patch_ptr,
                                                          const int32_t* __restrict__ patch_dofs,
                                                          const int64_t* __restrict__ inv_ptr,
                                                          const int64_t* __restrict__ stage_ptr,
-                                                         const double* __restrict__ inv, const double* __restrict__ x,
+                                                         const S* __restrict__ inv, const double* __restrict__ x,
                                                          double* __restrict__ stage, int split) {
+  constexpr int V = RowPiece<S>::V;
+  // a pair leaves as one store (the pad row of an odd n is zero and has a slot); of four rows those that exist
+  constexpr PieceStore ST = V == 2 ? PieceStore::PAIR : PieceStore::GUARDED;
   __shared__ double xs[BIG_MAX_NP];
   // ``split`` consecutive workgroups share a patch (levels with few patches: 303 macro stars would leave half the CUs idle)
   const int64_t p = p0 + blockIdx.x / split;
@@ -517,128 +449,14 @@ __global__ __launch_bounds__(256) void big_apply_kernel(int64_t p0, int64_t npat
   for (int i = threadIdx.x; i < n; i += 256) xs[i] = x[patch_dofs[off + i]];
   __syncthreads();
   const int wave = part * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int ld = (n + 1) & ~1;
-  const double* T = inv + inv_ptr[p];
+  const S* T = inv + inv_ptr[p];
   double* out = stage + stage_ptr[p];
-  int piece = 0, row0 = 0;
-  for (; row0 + 128 <= ld; row0 += 128, ++piece)
-    if (piece % nwave == wave) big_piece<64, NT>(T + (int64_t)row0 * n, n, xs, lane, out + row0);
-  const int rem = ld - row0;
-#define ALFI_BIG_PIECE(R)                                                                   \
-  if (rem & R) {                                                                            \
-    if (piece % nwave == wave) big_piece<R / 2, NT>(T + (int64_t)row0 * n, n, xs, lane, out + row0); \
-    row0 += R;                                                                              \
-    ++piece;                                                                                \
-  }
-  ALFI_BIG_PIECE(64)
-  ALFI_BIG_PIECE(32)
-  ALFI_BIG_PIECE(16)
-  ALFI_BIG_PIECE(8)
-  ALFI_BIG_PIECE(4)
-  ALFI_BIG_PIECE(2)
-#undef ALFI_BIG_PIECE
+  walk_pieces<V>(RowPiece<S>::ld(n), [=](auto R, int row0, int piece) {
+    if (piece % nwave == wave)
+      piece_apply<S, R / V, NT, BIG_U, false, ST>(T + (int64_t)row0 * n, R, n, xs, lane, out + row0, n - row0);
+  });
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// 3'. the same apply for a level that stores its inverses in SINGLE precision (alfi_patches_set_macro_storage; layout:
-//     patch_plan.h, f32_inv_index: rows padded to a multiple of 4, pieces of 128 rows and then the binary digits of the rest down
-//     to 4, a piece stored [column][rows of the piece]).  The work split is big_apply_kernel's -- a workgroup of 4 waves per
-//     patch, ``split`` workgroups per patch on launches of few patches, whole pieces dealt round-robin to the 4 split waves --
-//     and a lane loads the same 16 bytes: its four rows of a column as one float4, widened in registers.  Every product and
-//     every sum is an FP64 fma; a row's sum is the ascending columns of its column group, then the groups by shuffles in a
-//     fixed order: it depends on the patch alone, not on the launch, the range or ``split``.
-// ---------------------------------------------------------------------------------------------------------------------
-typedef float big_f4 __attribute__((ext_vector_type(4)));
-// one stored piece of 4 G rows: G lanes per column, 64 / G columns per wave instruction.  lim: rows of the piece that exist.
-// A patch has (n + 1) & ~1 staging slots, not f32_ld(n): the sums of the pad rows (zeros) are NOT stored -- for n = 1, 2 mod 4
-// they would land in the next patch's slots, or behind the staging buffer for the last patch.
-template <int G, bool NT>
-__device__ __forceinline__ void big_piece_f32(const float* __restrict__ T, int n, const double* __restrict__ xs, int lane,
-                                              double* __restrict__ out, int lim) {
-  constexpr int C = 64 / G, U = 8;
-  const int cg = lane / G, l = lane % G;
-  const float* base = T + 4 * l;
-  double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-  int j = cg;
-  for (; j + (U - 1) * C < n; j += U * C) {
-    big_f4 v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const big_f4* q = reinterpret_cast<const big_f4*>(base + (int64_t)(j + u * C) * (4 * G));
-      v[u] = NT ? __builtin_nontemporal_load(q) : *q;
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const double xj = xs[j + u * C];
-      acc0 = __builtin_fma((double)v[u].x, xj, acc0);
-      acc1 = __builtin_fma((double)v[u].y, xj, acc1);
-      acc2 = __builtin_fma((double)v[u].z, xj, acc2);
-      acc3 = __builtin_fma((double)v[u].w, xj, acc3);
-    }
-  }
-  for (; j < n; j += C) {
-    const big_f4* q = reinterpret_cast<const big_f4*>(base + (int64_t)j * (4 * G));
-    const big_f4 v = NT ? __builtin_nontemporal_load(q) : *q;
-    const double xj = xs[j];
-    acc0 = __builtin_fma((double)v.x, xj, acc0);
-    acc1 = __builtin_fma((double)v.y, xj, acc1);
-    acc2 = __builtin_fma((double)v.z, xj, acc2);
-    acc3 = __builtin_fma((double)v.w, xj, acc3);
-  }
-  if (C > 1) {
-#pragma unroll
-    for (int o = G; o < 64; o <<= 1) {
-      acc0 += __shfl_xor(acc0, o);
-      acc1 += __shfl_xor(acc1, o);
-      acc2 += __shfl_xor(acc2, o);
-      acc3 += __shfl_xor(acc3, o);
-    }
-  }
-  if (cg == 0) {
-    const int r = 4 * l;
-    if (r < lim) out[r] = acc0;
-    if (r + 1 < lim) out[r + 1] = acc1;
-    if (r + 2 < lim) out[r + 2] = acc2;
-    if (r + 3 < lim) out[r + 3] = acc3;
-  }
-}
-
-template <bool NT>
-__global__ __launch_bounds__(256) void big_apply_f32_kernel(int64_t p0, int64_t npatch, const int64_t* __restrict__ patch_ptr,
-                                                             const int32_t* __restrict__ patch_dofs,
-                                                             const int64_t* __restrict__ inv32_ptr,
-                                                             const int64_t* __restrict__ stage_ptr,
-                                                             const float* __restrict__ inv32, const double* __restrict__ x,
-                                                             double* __restrict__ stage, int split) {
-  __shared__ double xs[BIG_MAX_NP];
-  const int64_t p = p0 + blockIdx.x / split;
-  const int part = blockIdx.x % split, nwave = 4 * split;
-  if (p >= npatch) return;
-  const int64_t off = patch_ptr[p];
-  const int n = (int)(patch_ptr[p + 1] - off);
-  for (int i = threadIdx.x; i < n; i += 256) xs[i] = x[patch_dofs[off + i]];
-  __syncthreads();
-  const int wave = part * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int ld = f32_ld(n);
-  const float* T = inv32 + inv32_ptr[p];
-  double* out = stage + stage_ptr[p];
-  int piece = 0, row0 = 0;
-  for (; row0 + 128 <= ld; row0 += 128, ++piece)
-    if (piece % nwave == wave) big_piece_f32<32, NT>(T + (int64_t)row0 * n, n, xs, lane, out + row0, n - row0);
-  const int rem = ld - row0;          // a multiple of 4, < 128: one piece per binary digit
-#define ALFI_BIG_PIECE_F32(R)                                                                                      \
-  if (rem & R) {                                                                                                   \
-    if (piece % nwave == wave) big_piece_f32<R / 4, NT>(T + (int64_t)row0 * n, n, xs, lane, out + row0, n - row0); \
-    row0 += R;                                                                                                     \
-    ++piece;                                                                                                       \
-  }
-  ALFI_BIG_PIECE_F32(64)
-  ALFI_BIG_PIECE_F32(32)
-  ALFI_BIG_PIECE_F32(16)
-  ALFI_BIG_PIECE_F32(8)
-  ALFI_BIG_PIECE_F32(4)
-#undef ALFI_BIG_PIECE_F32
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 3b. multiplicative sweep over large patches (macro stars, alfi/solver.py:322-324 with 339-342: --patch macro
@@ -694,25 +512,11 @@ __device__ __forceinline__ void big_mult_patch(int64_t p, double* __restrict__ r
     }
   }
   __syncthreads();
-  const int ld = (n + 1) & ~1;
   const double* T = inv + inv_ptr[p];
-  int piece = 0, row0 = 0;
-  for (; row0 + 128 <= ld; row0 += 128, ++piece)
-    if (piece % 4 == wave) big_piece<64, NT>(T + (int64_t)row0 * n, n, rs, lane, ys + row0);
-  const int rem = ld - row0;
-#define ALFI_BIG_PIECE(R)                                                                      \
-  if (rem & R) {                                                                               \
-    if (piece % 4 == wave) big_piece<R / 2, NT>(T + (int64_t)row0 * n, n, rs, lane, ys + row0); \
-    row0 += R;                                                                                 \
-    ++piece;                                                                                   \
-  }
-  ALFI_BIG_PIECE(64)
-  ALFI_BIG_PIECE(32)
-  ALFI_BIG_PIECE(16)
-  ALFI_BIG_PIECE(8)
-  ALFI_BIG_PIECE(4)
-  ALFI_BIG_PIECE(2)
-#undef ALFI_BIG_PIECE
+  walk_pieces<2>(RowPiece<double>::ld(n), [=](auto R, int row0, int piece) {
+    if (piece % 4 == wave)
+      piece_apply<double, R / 2, NT, BIG_U, false, PieceStore::PAIR>(T + (int64_t)row0 * n, R, n, rs, lane, ys + row0, 0);
+  });
   __syncthreads();
   for (int i = threadIdx.x; i < n; i += 256) y[patch_dofs[off + i]] += ys[i];
 }
@@ -805,18 +609,14 @@ int launch_big_mult_persistent(alfi_level* L, const double* x, double* y) {
 int launch_big_mult_wave(alfi_level* L, const int32_t* seq, int64_t count, const double* x, double* y) {
   alfi_ctx* ctx = L->ctx;
   if (count == 0) return 0;
-  constexpr bool nt = true;      // factors are read once per apply: nontemporal loads
   dim3 grid((unsigned)count), block(256);
-#define ALFI_BMULT(BSV, NTV)                                                                                          \
-  hipLaunchKernelGGL((big_mult_kernel<BSV, NTV>), grid, block, 0, ctx->stream, count, seq, L->patch_ptr, L->patch_dofs, \
+  // (factors are read once per apply: nontemporal loads)
+#define ALFI_BMULT(BSV)                                                                                                \
+  hipLaunchKernelGGL((big_mult_kernel<BSV, true>), grid, block, 0, ctx->stream, count, seq, L->patch_ptr, L->patch_dofs, \
                      L->inv_ptr, L->inv, L->A.rowptr, L->A.colidx, L->A.vals, L->A.flat, x, y)
-  if (L->bs == 2) {
-    if (nt) ALFI_BMULT(2, true); else ALFI_BMULT(2, false);
-  } else if (L->bs == 3) {
-    if (nt) ALFI_BMULT(3, true); else ALFI_BMULT(3, false);
-  } else {
-    return alfi_set_error(ctx, ALFI_E_ARG, "unsupported block size %d", L->bs);
-  }
+  if (L->bs == 2) ALFI_BMULT(2);
+  else if (L->bs == 3) ALFI_BMULT(3);
+  else return alfi_set_error(ctx, ALFI_E_ARG, "unsupported block size %d", L->bs);
 #undef ALFI_BMULT
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   return 0;
@@ -833,32 +633,27 @@ static int big_split(int64_t npatch, int max_np) {
   return (int)(want < 1 ? 1 : (want > cap ? cap : want));
 }
 
-int launch_big_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double* x) {
-  alfi_ctx* ctx = L->ctx;
+// the patches [p0, p1) of either storage (factors are read once per apply: nontemporal loads)
+template <typename S>
+static int launch_big_apply(alfi_ctx* ctx, int64_t p0, int64_t p1, int max_np, const int64_t* patch_ptr, const int32_t* patch_dofs,
+                            const int64_t* inv_ptr, const int64_t* stage_ptr, const S* inv, const double* x, double* stage) {
   if (p1 <= p0) return 0;
-  constexpr bool nt = true;      // factors are read once per apply: nontemporal loads
-  const int split = big_split(p1 - p0, L->lay.max_np);
+  const int split = big_split(p1 - p0, max_np);
   dim3 grid((unsigned)((p1 - p0) * split)), block(256);
-  if (nt)
-    hipLaunchKernelGGL(big_apply_kernel<true>, grid, block, 0, ctx->stream, p0, p1, L->patch_ptr, L->patch_dofs, L->inv_ptr,
-                       L->stage_ptr, L->inv, x, L->stage, split);
-  else
-    hipLaunchKernelGGL(big_apply_kernel<false>, grid, block, 0, ctx->stream, p0, p1, L->patch_ptr, L->patch_dofs, L->inv_ptr,
-                       L->stage_ptr, L->inv, x, L->stage, split);
+  hipLaunchKernelGGL((big_apply_kernel<S, true>), grid, block, 0, ctx->stream, p0, p1, patch_ptr, patch_dofs, inv_ptr, stage_ptr,
+                     inv, x, stage, split);
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   return 0;
 }
 
+int launch_big_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double* x) {
+  return launch_big_apply(L->ctx, p0, p1, L->lay.max_np, L->patch_ptr, L->patch_dofs, L->inv_ptr, L->stage_ptr, L->inv, x, L->stage);
+}
+
 // FP32 levels with a patch above 160 dofs (alfi_patches_set_macro_storage): the same split, the single-precision copy
 int launch_big_apply_f32_range(alfi_level* L, int64_t p0, int64_t p1, const double* x) {
-  alfi_ctx* ctx = L->ctx;
-  if (p1 <= p0) return 0;
-  const int split = big_split(p1 - p0, L->lay.max_np);
-  dim3 grid((unsigned)((p1 - p0) * split)), block(256);
-  hipLaunchKernelGGL(big_apply_f32_kernel<true>, grid, block, 0, ctx->stream, p0, p1, L->patch_ptr, L->patch_dofs, L->inv32_ptr,
-                     L->stage_ptr, L->inv32, x, L->stage, split);
-  ALFI_HIP_CHECK(ctx, hipGetLastError());
-  return 0;
+  return launch_big_apply(L->ctx, p0, p1, L->lay.max_np, L->patch_ptr, L->patch_dofs, L->inv32_ptr, L->stage_ptr, L->inv32, x,
+                          L->stage);
 }
 
 // nu K + gamma D of the interior blocks of a Schoeberl transfer (dense m x m inputs, transfer.py:186-232) into the scratch
@@ -879,18 +674,7 @@ __global__ __launch_bounds__(256) void big_dense_fill_kernel(int64_t p0, int m, 
 int launch_big_apply_arrays(alfi_ctx* ctx, int64_t npatch, int max_np, const int64_t* patch_ptr,
                             const int32_t* patch_dofs, const int64_t* inv_ptr, const int64_t* stage_ptr, const double* inv,
                             const double* x, double* stage) {
-  if (npatch == 0) return 0;
-  constexpr bool nt = true;      // factors are read once per apply: nontemporal loads
-  const int split = big_split(npatch, max_np);
-  dim3 grid((unsigned)(npatch * split)), block(256);
-  if (nt)
-    hipLaunchKernelGGL(big_apply_kernel<true>, grid, block, 0, ctx->stream, (int64_t)0, npatch, patch_ptr, patch_dofs,
-                       inv_ptr, stage_ptr, inv, x, stage, split);
-  else
-    hipLaunchKernelGGL(big_apply_kernel<false>, grid, block, 0, ctx->stream, (int64_t)0, npatch, patch_ptr, patch_dofs,
-                       inv_ptr, stage_ptr, inv, x, stage, split);
-  ALFI_HIP_CHECK(ctx, hipGetLastError());
-  return 0;
+  return launch_big_apply(ctx, 0, npatch, max_np, patch_ptr, patch_dofs, inv_ptr, stage_ptr, inv, x, stage);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

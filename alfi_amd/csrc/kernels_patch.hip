@@ -1,12 +1,13 @@
 // Patch smoother kernels for gfx950 (wave64): PCPATCH setup (gather + dense inversion) and additive apply.
 //
-// Storage of the inverses (owned layout, chosen for the apply kernel; patch_inv_index in common.h): patch p holds an
-// n_p x n_p inverse at inv + inv_ptr[p] (a multiple of 16 doubles = 128 B) as row pieces of 128, 64, ..., 2 rows, each
-// piece stored [column][rows of the piece].  Lane l of a wave reads a row pair of one column as one aligned 16-byte load,
-// a wave instruction covers 1 KiB of consecutive bytes, and consecutive instructions continue where the previous one
-// stopped: every 128-B line of the inverse is fetched exactly once and fully used.  (Round 1 stored plain column-major
+// Storage of the inverses (owned layout, chosen for the apply kernel; piece_index in patch_plan.h, the loop that streams it in
+// row_piece.h): patch p holds an n_p x n_p inverse at inv + inv_ptr[p] (a multiple of 16 doubles = 128 B) as row pieces of 128,
+// 64, ..., 2 rows, each piece stored [column][rows of the piece].  Lane l of a wave reads a row pair of one column as one aligned
+// 16-byte load, a wave instruction covers 1 KiB of consecutive bytes, and consecutive instructions continue where the previous
+// one stopped: every 128-B line of the inverse is fetched exactly once and fully used.  (Round 1 stored plain column-major
 // with ld = 154: the 26-row tail of each column was read in a second pass through lines shared with the next column,
-// FETCH_SIZE showed 1.19 x the algorithmic bytes -- profiles/pmc_patch_apply_cfg4.json.)
+// FETCH_SIZE showed 1.19 x the algorithmic bytes -- profiles/pmc_patch_apply_cfg4.json.)  A level may hold a single-precision
+// copy instead (alfi_patches_set_storage): four rows per lane, the same 16 bytes.
 //
 // Roofline: apply is a GEMV streaming every inverse once (0.25 flop/B) -> HBM-bound; algorithmic bytes per patch
 // 8 n_p^2 + 28 n_p.  Inversion is 2 n_p^3 flops per patch in FP64; gfx950's FP64 MFMA rate
@@ -14,6 +15,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include "common.h"
+#include "row_piece.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 1. gather A_p = A[dofs_p, dofs_p] from the BSR operator into row-major dense storage (ld_p columns per row)
@@ -27,23 +29,35 @@ constexpr int MAX_NP = 160;
     __builtin_amdgcn_wave_barrier();                           \
   } while (0)
 
-template <int BS>
+// RANKED (FP32 levels with a canonical order, alfi_patches_set_canonical_order): row / column a of the patch is written at
+// position rank[a], so that the unpivoted elimination runs in the caller's canonical order -- a partitioned level then eliminates
+// in the order of the unpartitioned one and gets the same FP64 inverse bit for bit, whatever its local numbering
+template <int BS, bool RANKED>
 __global__ __launch_bounds__(256) void patch_gather_dense_kernel(const int32_t* __restrict__ rowptr,
                                                                   const int32_t* __restrict__ colidx,
                                                                   const double* __restrict__ vals,
                                                                   const int64_t* __restrict__ patch_ptr,
                                                                   const int32_t* __restrict__ patch_dofs,
+                                                                  const int32_t* __restrict__ rank,
                                                                   const int64_t* __restrict__ inv_ptr,
                                                                   double* __restrict__ inv, int flat) {
   __shared__ int32_t dofs_s[MAX_NP];
+  __shared__ int32_t rank_s[RANKED ? MAX_NP : 1];      // !RANKED: never referenced, so never allocated
   __shared__ double rowbuf[4][MAX_NP];
+  const auto place = [&](int a) {
+    if constexpr (RANKED) return (int)rank_s[a];
+    else return a;
+  };
   const int64_t p = blockIdx.x;
   const int64_t off = patch_ptr[p];
   const int n = (int)(patch_ptr[p + 1] - off);
   const int ld = (n + 1) & ~1;
   double* S = inv + inv_ptr[p];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int i = threadIdx.x; i < n; i += 256) dofs_s[i] = patch_dofs[off + i];
+  for (int i = threadIdx.x; i < n; i += 256) {
+    dofs_s[i] = patch_dofs[off + i];
+    if constexpr (RANKED) rank_s[i] = rank[off + i];
+  }
   __syncthreads();
   // every wave takes rows of its own through its own row buffer: no workgroup barrier inside the loop (the LDS serves a wave's
   // accesses in order; until round 5 the four waves met at two barriers per four rows, 76 per patch of 153 dofs)
@@ -63,10 +77,10 @@ __global__ __launch_bounds__(256) void patch_gather_dense_kernel(const int32_t* 
         const int mid = (a + b) >> 1;
         if (dofs_s[mid] < gcol) a = mid + 1; else b = mid;
       }
-      if (a < n && dofs_s[a] == gcol) rowbuf[wave][a] = vals[bsr_val_index(flat, lo + blk, rr * BS + cc, BS * BS)];
+      if (a < n && dofs_s[a] == gcol) rowbuf[wave][place(a)] = vals[bsr_val_index(flat, lo + blk, rr * BS + cc, BS * BS)];
     }
     ALFI_WAVE_LDS_ORDER_GATHER();
-    for (int c = lane; c < ld; c += 64) S[(int64_t)r * ld + c] = rowbuf[wave][c];
+    for (int c = lane; c < ld; c += 64) S[(int64_t)place(r) * ld + c] = rowbuf[wave][c];
     ALFI_WAVE_LDS_ORDER_GATHER();        // the copy out has read the buffer before the next row clears it
   }
 }
@@ -211,7 +225,7 @@ __global__ __launch_bounds__(256) void invert_small_kernel(int64_t nmat, const i
 // ---------------------------------------------------------------------------------------------------------------------
 // 3. additive apply, stage 1: one wave per patch.  stage[patch_ptr[p] + r] = sum_c inv_p[r][c] * x[dofs_p[c]]
 // ---------------------------------------------------------------------------------------------------------------------
-// one row piece of 2G rows, stored [column][2G]: G lanes per column, 64/G columns per wave instruction
+// (one row piece: piece_apply, row_piece.h; load_pair serves the interleaved copy of section 3a)
 typedef double alfi_d2 __attribute__((ext_vector_type(2)));
 template <bool NT>
 __device__ __forceinline__ double2 load_pair(const double* p) {   // one aligned 16-byte load
@@ -223,51 +237,10 @@ __device__ __forceinline__ double2 load_pair(const double* p) {   // one aligned
 #ifndef ALFI_APPLY_U
 #define ALFI_APPLY_U 8                    // tuning builds: -DALFI_APPLY_U=16
 #endif
-// U = loads kept in flight per lane.  8 for the additive apply (a CU holds 16-32 waves there: 8 KiB in flight per wave fill the
-// memory pipeline); the multiplicative sweep runs ONE wave per patch with ~2 waves per CU, where the wave's own bytes in flight
-// bound it (8 KiB / ~2 us of loaded latency = 4 GB/s per wave: the 46 us per wavefront of round 3) -- it asks for 32.
-template <int G, bool NT, int U = ALFI_APPLY_U>
-__device__ __forceinline__ void apply_piece(const double* __restrict__ T, int n, const double* __restrict__ xs,
-                                            int lane, double* __restrict__ out) {
-  constexpr int C = 64 / G;  // columns handled per wave instruction
-  const int cg = lane / G, l = lane % G;
-  const double* base = T + 2 * l;
-  double acc0 = 0.0, acc1 = 0.0;
-  int j = cg;
-  for (; j + (U - 1) * C < n; j += U * C) {
-    double2 v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = load_pair<NT>(base + (int64_t)(j + u * C) * (2 * G));
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const double xj = xs[j + u * C];
-      acc0 = __builtin_fma(v[u].x, xj, acc0);
-      acc1 = __builtin_fma(v[u].y, xj, acc1);
-    }
-  }
-  if (j < n) {       // the last, partial group: its loads are requested together too (same summation order: ascending columns)
-    double2 v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      v[u] = j + u * C < n ? load_pair<NT>(base + (int64_t)(j + u * C) * (2 * G)) : make_double2(0.0, 0.0);
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (j + u * C < n) {
-        const double xj = xs[j + u * C];
-        acc0 = __builtin_fma(v[u].x, xj, acc0);
-        acc1 = __builtin_fma(v[u].y, xj, acc1);
-      }
-  }
-  if (C > 1) {
-#pragma unroll
-    for (int o = G; o < 64; o <<= 1) {
-      acc0 += __shfl_xor(acc0, o);
-      acc1 += __shfl_xor(acc1, o);
-    }
-  }
-  // the padding row (n odd) of the inverse is zero, so storing both rows is always valid (stage has ld slots)
-  if (cg == 0) *reinterpret_cast<double2*>(out + 2 * l) = make_double2(acc0, acc1);
-}
+// U = 16-byte loads kept in flight per lane (piece_dot, row_piece.h).  8 for the additive apply (a CU holds 16-32 waves there:
+// 8 KiB in flight per wave fill the memory pipeline); the multiplicative sweep runs ONE wave per patch with ~2 waves per CU,
+// where the wave's own bytes in flight bound it (8 KiB / ~2 us of loaded latency = 4 GB/s per wave: the 46 us per wavefront of
+// round 3) -- it asks for 32.
 
 // A WORKGROUP of APPLY_W waves per patch: wave w takes the w-th share of the columns of every row piece, the partial results
 // are added in the order of the waves (deterministic).  Rounds 1-3 gave a patch to ONE wave, four patches to a workgroup: a
@@ -282,14 +255,20 @@ __device__ __forceinline__ void apply_piece(const double* __restrict__ T, int n,
 #define ALFI_APPLY_W 4
 #endif
 constexpr int APPLY_W = ALFI_APPLY_W;     // waves per patch of 65 .. 128 dofs (twice as many above, one wave below)
-template <bool NT, int W>
+// S = float (alfi_patches_set_storage): the same kernel over the single-precision copy -- the stored values are the only
+// single-precision quantity.  Its staging slots are the FP64 layout's, n rounded up to even, not RowPiece<float>::ld(n).
+template <typename S, bool NT, int W>
 __global__ __launch_bounds__(64 * W) void patch_apply_kernel(int64_t p0, int64_t p1,
                                                                     const int64_t* __restrict__ patch_ptr,
                                                                     const int32_t* __restrict__ patch_dofs,
                                                                     const int64_t* __restrict__ inv_ptr,
                                                                     const int64_t* __restrict__ stage_ptr,
-                                                                    const double* __restrict__ inv,
+                                                                    const S* __restrict__ inv,
                                                                     const double* __restrict__ x, double* __restrict__ stage) {
+  constexpr int V = RowPiece<S>::V;
+  // a pair leaves as one store (the pad row of an odd n is zero); four rows as scalars into the slots of the padded rows
+  constexpr PieceStore ST = V == 2 ? PieceStore::PAIR : PieceStore::ALL;
+  static_assert(MAX_NP % V == 0, "the partial sums of the pad rows have slots");
   __shared__ double xs[MAX_NP];
   __shared__ double part[W][MAX_NP];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -299,140 +278,13 @@ __global__ __launch_bounds__(64 * W) void patch_apply_kernel(int64_t p0, int64_t
   const int n = (int)(patch_ptr[p + 1] - off);
   for (int i = threadIdx.x; i < n; i += 64 * W) xs[i] = x[patch_dofs[off + i]];
   __syncthreads();
-  const int ld = (n + 1) & ~1;
-  const double* T = inv + inv_ptr[p];
+  const S* T = inv + inv_ptr[p];
   const int ca = (int)(((int64_t)wave * n) / W), cn = (int)(((int64_t)(wave + 1) * n) / W) - ca;
   double* out = part[wave];
-  int row0 = 0;
-  for (; row0 + 128 <= ld; row0 += 128)
-    apply_piece<64, NT>(T + (int64_t)row0 * n + (int64_t)ca * 128, cn, xs + ca, lane, out + row0);
-  const int rem = ld - row0;  // even, < 128: one piece per binary digit
-#define ALFI_PIECE(R)                                                                             \
-  if (rem & R) {                                                                                  \
-    apply_piece<R / 2, NT>(T + (int64_t)row0 * n + (int64_t)ca * R, cn, xs + ca, lane, out + row0); \
-    row0 += R;                                                                                    \
-  }
-  ALFI_PIECE(64)
-  ALFI_PIECE(32)
-  ALFI_PIECE(16)
-  ALFI_PIECE(8)
-  ALFI_PIECE(4)
-  ALFI_PIECE(2)
-#undef ALFI_PIECE
+  walk_pieces<V>(RowPiece<S>::ld(n), [=](auto R, int row0, int) {
+    piece_apply<S, R / V, NT, ALFI_APPLY_U, true, ST>(T + (int64_t)row0 * n + (int64_t)ca * R, R, cn, xs + ca, lane, out + row0, 0);
+  });
   __syncthreads();
-  double* dst = stage + stage_ptr[p];
-  for (int i = threadIdx.x; i < ld; i += 64 * W) {
-    double d = part[0][i];
-#pragma unroll
-    for (int w = 1; w < W; ++w) d += part[w][i];
-    dst[i] = d;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// 3f. the additive apply of a level that stores its inverses in SINGLE precision (alfi_patches_set_storage; layout: patch_plan.h,
-//     f32_inv_index): the structure of patch_apply_kernel -- a workgroup of W waves per patch, wave w takes the w-th share of
-//     the columns of every row piece, partial sums added in the order of the waves, ascending columns inside a wave -- with
-//     float loads of the same 16 bytes per lane (F32_ROWS = 4 rows of a column), widened in registers: every product and every
-//     sum is FP64, the stored values are the only single-precision quantity.
-// ---------------------------------------------------------------------------------------------------------------------
-typedef float alfi_fv __attribute__((ext_vector_type(F32_ROWS)));
-// one row piece of F32_ROWS * G rows, stored [column][rows of the piece]: G lanes per column, 64 / G columns per wave instruction
-template <int G, bool NT, int U>
-__device__ __forceinline__ void apply_piece_f32(const float* __restrict__ T, int n, const double* __restrict__ xs, int lane,
-                                                double* __restrict__ out) {
-  constexpr int C = 64 / G, V = F32_ROWS;
-  const int cg = lane / G, l = lane % G;
-  const float* base = T + V * l;
-  double acc[V];
-#pragma unroll
-  for (int k = 0; k < V; ++k) acc[k] = 0.0;
-  const alfi_fv zero = {};
-  int j = cg;
-  for (; j + (U - 1) * C < n; j += U * C) {
-    alfi_fv v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const alfi_fv* q = reinterpret_cast<const alfi_fv*>(base + (int64_t)(j + u * C) * (V * G));
-      v[u] = NT ? __builtin_nontemporal_load(q) : *q;
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const double xj = xs[j + u * C];
-#pragma unroll
-      for (int k = 0; k < V; ++k) acc[k] = __builtin_fma((double)v[u][k], xj, acc[k]);
-    }
-  }
-  if (j < n) {       // the last, partial group: its loads are requested together too (same summation order: ascending columns)
-    alfi_fv v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const alfi_fv* q = reinterpret_cast<const alfi_fv*>(base + (int64_t)(j + u * C) * (V * G));
-      v[u] = j + u * C < n ? (NT ? __builtin_nontemporal_load(q) : *q) : zero;
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (j + u * C < n) {
-        const double xj = xs[j + u * C];
-#pragma unroll
-        for (int k = 0; k < V; ++k) acc[k] = __builtin_fma((double)v[u][k], xj, acc[k]);
-      }
-  }
-  if (C > 1) {
-#pragma unroll
-    for (int o = G; o < 64; o <<= 1) {
-#pragma unroll
-      for (int k = 0; k < V; ++k) acc[k] += __shfl_xor(acc[k], o);
-    }
-  }
-  // the pad rows of the inverse are zero, so storing all rows of the lane is always valid (part has f32_ld(n) <= MAX_NP slots)
-  if (cg == 0) {
-#pragma unroll
-    for (int k = 0; k < V; ++k) out[V * l + k] = acc[k];
-  }
-}
-
-constexpr int F32_APPLY_U = ALFI_APPLY_U * 4 / F32_ROWS;      // the bytes in flight per lane of the FP64 apply
-template <bool NT, int W>
-__global__ __launch_bounds__(64 * W) void patch_apply_f32_kernel(int64_t p0, int64_t p1, const int64_t* __restrict__ patch_ptr,
-                                                                  const int32_t* __restrict__ patch_dofs,
-                                                                  const int64_t* __restrict__ inv32_ptr,
-                                                                  const int64_t* __restrict__ stage_ptr,
-                                                                  const float* __restrict__ inv32, const double* __restrict__ x,
-                                                                  double* __restrict__ stage) {
-  static_assert(MAX_NP % F32_ROWS == 0, "the partial sums of the pad rows have slots");
-  __shared__ double xs[MAX_NP];
-  __shared__ double part[W][MAX_NP];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t p = p0 + blockIdx.x;
-  if (p >= p1) return;
-  const int64_t off = patch_ptr[p];
-  const int n = (int)(patch_ptr[p + 1] - off);
-  for (int i = threadIdx.x; i < n; i += 64 * W) xs[i] = x[patch_dofs[off + i]];
-  __syncthreads();
-  const int ld = f32_ld(n);
-  const float* T = inv32 + inv32_ptr[p];
-  const int ca = (int)(((int64_t)wave * n) / W), cn = (int)(((int64_t)(wave + 1) * n) / W) - ca;
-  double* out = part[wave];
-  int row0 = 0;
-  for (; row0 + 128 <= ld; row0 += 128)
-    apply_piece_f32<128 / F32_ROWS, NT, F32_APPLY_U>(T + (int64_t)row0 * n + (int64_t)ca * 128, cn, xs + ca, lane, out + row0);
-  const int rem = ld - row0;  // a multiple of F32_ROWS, < 128: one piece per binary digit
-#define ALFI_PIECE(R)                                                                                                      \
-  if (R >= F32_ROWS && (rem & R)) {                                                                                        \
-    apply_piece_f32<(R >= F32_ROWS ? R / F32_ROWS : 1), NT, F32_APPLY_U>(T + (int64_t)row0 * n + (int64_t)ca * R, cn, xs + ca, \
-                                                                         lane, out + row0);                                \
-    row0 += R;                                                                                                             \
-  }
-  ALFI_PIECE(64)
-  ALFI_PIECE(32)
-  ALFI_PIECE(16)
-  ALFI_PIECE(8)
-  ALFI_PIECE(4)
-  ALFI_PIECE(2)
-#undef ALFI_PIECE
-  __syncthreads();
-  // the staging buffer has the FP64 layout's slots: n rounded up to even (a pad row's sum is zero)
   double* dst = stage + stage_ptr[p];
   const int lds = (n + 1) & ~1;
   for (int i = threadIdx.x; i < lds; i += 64 * W) {
@@ -443,56 +295,7 @@ __global__ __launch_bounds__(64 * W) void patch_apply_f32_kernel(int64_t p0, int
   }
 }
 
-// FP32 levels with a canonical order (alfi_patches_set_canonical_order): the gather of section 1 with row / column a of the patch
-// written at position rank[a], so that the unpivoted elimination runs in the caller's canonical order -- a partitioned level
-// then eliminates in the order of the unpartitioned one and gets the same FP64 inverse bit for bit, whatever its local numbering
-template <int BS>
-__global__ __launch_bounds__(256) void patch_gather_ranked_kernel(const int32_t* __restrict__ rowptr,
-                                                                   const int32_t* __restrict__ colidx,
-                                                                   const double* __restrict__ vals,
-                                                                   const int64_t* __restrict__ patch_ptr,
-                                                                   const int32_t* __restrict__ patch_dofs,
-                                                                   const int32_t* __restrict__ rank,
-                                                                   const int64_t* __restrict__ inv_ptr,
-                                                                   double* __restrict__ inv, int flat) {
-  __shared__ int32_t dofs_s[MAX_NP];
-  __shared__ int32_t rank_s[MAX_NP];
-  __shared__ double rowbuf[4][MAX_NP];
-  const int64_t p = blockIdx.x;
-  const int64_t off = patch_ptr[p];
-  const int n = (int)(patch_ptr[p + 1] - off);
-  const int ld = (n + 1) & ~1;
-  double* S = inv + inv_ptr[p];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    dofs_s[i] = patch_dofs[off + i];
-    rank_s[i] = rank[off + i];
-  }
-  __syncthreads();
-  for (int r = wave; r < n; r += 4) {
-    for (int c = lane; c < ld; c += 64) rowbuf[wave][c] = 0.0;
-    ALFI_WAVE_LDS_ORDER_GATHER();
-    const int gr = dofs_s[r];
-    const int brow = gr / BS, rr = gr % BS;
-    const int32_t lo = rowptr[brow], hi = rowptr[brow + 1];
-    const int nent = (hi - lo) * BS;
-    for (int e = lane; e < nent; e += 64) {
-      const int blk = e / BS, cc = e % BS;
-      const int gcol = (colidx[lo + blk] & 0x7fffffff) * BS + cc;  // sign bit = row-start mark (flat layout)
-      int a = 0, b = n;
-      while (a < b) {
-        const int mid = (a + b) >> 1;
-        if (dofs_s[mid] < gcol) a = mid + 1; else b = mid;
-      }
-      if (a < n && dofs_s[a] == gcol) rowbuf[wave][rank_s[a]] = vals[bsr_val_index(flat, lo + blk, rr * BS + cc, BS * BS)];
-    }
-    ALFI_WAVE_LDS_ORDER_GATHER();
-    for (int c = lane; c < ld; c += 64) S[(int64_t)rank_s[r] * ld + c] = rowbuf[wave][c];
-    ALFI_WAVE_LDS_ORDER_GATHER();
-  }
-}
-
-// ... and the inverse back into the order of patch_dofs, out of place through a scratch of `stride` doubles per patch:
+// the inverses of a ranked gather back into the order of patch_dofs, out of place through a scratch of `stride` doubles per patch:
 // (1) scratch[(r, c)] = inverse[(rank[r], rank[c])], pad row zero; (2) the copy back
 __global__ __launch_bounds__(256) void patch_unrank_kernel(int64_t p0, const int64_t* __restrict__ patch_ptr,
                                                             const int32_t* __restrict__ rank, const int64_t* __restrict__ inv_ptr,
@@ -661,7 +464,7 @@ constexpr int MAX_PNODES = 64;
 constexpr int MULT_W = ALFI_MULT_W;         // waves per patch
 constexpr int MULT_NTHR = 64 * MULT_W;
 static_assert(MULT_NTHR >= MAX_NP, "one thread per row entry of a patch in the residual");
-constexpr int MULT_U = ALFI_MULT_U;         // 16-byte loads in flight per lane in the sweep's inverse apply (see apply_piece)
+constexpr int MULT_U = ALFI_MULT_U;         // 16-byte loads in flight per lane in the sweep's inverse apply (piece_dot, row_piece.h)
 constexpr int MULT_G = ALFI_MULT_G;         // operator blocks per thread whose loads leave together (one group)
 constexpr int MULT_NG = ALFI_MULT_NG;       // groups per round (G x NG blocks per thread: 2560 blocks per round at 4 waves)
 constexpr int MULT_MAXU = MULT_G * MULT_NG;
@@ -845,26 +648,30 @@ __device__ __forceinline__ void mult_wg_apply(int64_t p, MultLds& S, const int64
                                               const int64_t* __restrict__ inv_ptr, const double* __restrict__ inv) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int n = (int)(patch_ptr[p + 1] - patch_ptr[p]);
-  const int ld = (n + 1) & ~1;
   const double* T = inv + inv_ptr[p];
   double* out = S.part[wave];
+  const int ca = (int)(((int64_t)wave * n) / MULT_W), cn = (int)(((int64_t)(wave + 1) * n) / MULT_W) - ca;
+  // (the piece walk stays written out here: through walk_pieces the persistent sweep of bs = 2 takes 209 VGPRs instead of 207)
+  const int ld = RowPiece<double>::ld(n);
   int row0 = 0;
   // pieces of >= 64 rows: column shares
-  const int ca = (int)(((int64_t)wave * n) / MULT_W), cn = (int)(((int64_t)(wave + 1) * n) / MULT_W) - ca;
   for (; row0 + 128 <= ld; row0 += 128)
-    apply_piece<64, NT, MULT_U>(T + (int64_t)row0 * n + (int64_t)ca * 128, cn, S.rs + ca, lane, out + row0);
+    piece_apply<double, 64, NT, MULT_U, true, PieceStore::PAIR>(T + (int64_t)row0 * n + (int64_t)ca * 128, 128, cn, S.rs + ca, lane,
+                                                                out + row0, 0);
   const int rem = ld - row0;
   if (rem & 64) {
-    apply_piece<32, NT, MULT_U>(T + (int64_t)row0 * n + (int64_t)ca * 64, cn, S.rs + ca, lane, out + row0);
+    piece_apply<double, 32, NT, MULT_U, true, PieceStore::PAIR>(T + (int64_t)row0 * n + (int64_t)ca * 64, 64, cn, S.rs + ca, lane,
+                                                                out + row0, 0);
     row0 += 64;
   }
   // smaller pieces: a wave each, all columns
   int piece = 0;
-#define ALFI_PIECE(R)                                                                    \
-  if (rem & R) {                                                                         \
-    if (piece % MULT_W == wave) apply_piece<R / 2, NT, MULT_U>(T + (int64_t)row0 * n, n, S.rs, lane, out + row0); \
-    row0 += R;                                                                           \
-    ++piece;                                                                             \
+#define ALFI_PIECE(R)                                                                                                         \
+  if (rem & R) {                                                                                                              \
+    if (piece % MULT_W == wave)                                                                                               \
+      piece_apply<double, R / 2, NT, MULT_U, true, PieceStore::PAIR>(T + (int64_t)row0 * n, R, n, S.rs, lane, out + row0, 0); \
+    row0 += R;                                                                                                                \
+    ++piece;                                                                                                                  \
   }
   ALFI_PIECE(32)
   ALFI_PIECE(16)
@@ -1062,18 +869,21 @@ __global__ __launch_bounds__(256) void patch_sum_kernel(int64_t i0, int64_t n, c
 // ---------------------------------------------------------------------------------------------------------------------
 // launch wrappers
 // ---------------------------------------------------------------------------------------------------------------------
-int launch_patch_gather_dense(alfi_level* L) {
+int launch_patch_gather_dense(alfi_level* L, bool ranked) {
   alfi_ctx* ctx = L->ctx;
   if (L->npatch == 0) return 0;
   dim3 grid((unsigned)L->npatch), block(256);
-  if (L->bs == 2)
-    hipLaunchKernelGGL(patch_gather_dense_kernel<2>, grid, block, 0, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals,
-                       L->patch_ptr, L->patch_dofs, L->inv_ptr, L->inv, L->A.flat);
-  else if (L->bs == 3)
-    hipLaunchKernelGGL(patch_gather_dense_kernel<3>, grid, block, 0, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals,
-                       L->patch_ptr, L->patch_dofs, L->inv_ptr, L->inv, L->A.flat);
-  else
+#define ALFI_GATHER(BSV, RV)                                                                                              \
+  hipLaunchKernelGGL((patch_gather_dense_kernel<BSV, RV>), grid, block, 0, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals, \
+                     L->patch_ptr, L->patch_dofs, L->canon_rank, L->inv_ptr, L->inv, L->A.flat)
+  if (L->bs == 2) {
+    if (ranked) ALFI_GATHER(2, true); else ALFI_GATHER(2, false);
+  } else if (L->bs == 3) {
+    if (ranked) ALFI_GATHER(3, true); else ALFI_GATHER(3, false);
+  } else {
     return alfi_set_error(ctx, ALFI_E_ARG, "unsupported block size %d", L->bs);
+  }
+#undef ALFI_GATHER
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   return 0;
 }
@@ -1129,13 +939,26 @@ int launch_patch_invert(alfi_level* L) {
   return launch_patch_invert_arrays(L->ctx, L->npatch, L->lay.max_np, L->patch_ptr, L->inv_ptr, L->inv, L->status);
 }
 
+// stage 1 of the patches [p0, p1) with W waves per patch, either storage
+template <typename S>
+static void launch_patch_apply_w(alfi_ctx* ctx, int W, int64_t p0, int64_t p1, const int64_t* patch_ptr, const int32_t* patch_dofs,
+                                 const int64_t* inv_ptr, const int64_t* stage_ptr, const S* inv, const double* x, double* stage) {
+  const dim3 grid((unsigned)(p1 - p0));
+#define ALFI_APPLY(WV)                                                                                                  \
+  hipLaunchKernelGGL((patch_apply_kernel<S, true, WV>), grid, dim3(64 * WV), 0, ctx->stream, p0, p1, patch_ptr, patch_dofs, \
+                     inv_ptr, stage_ptr, inv, x, stage)
+  if (W == 2 * APPLY_W) ALFI_APPLY(2 * APPLY_W);
+  else if (W == APPLY_W) ALFI_APPLY(APPLY_W);
+  else ALFI_APPLY(1);
+#undef ALFI_APPLY
+}
+
 // stage[stage_ptr[p] + r] = sum_c inv_p[r][c] x[patch_dofs[patch_ptr[p] + c]] for npatch row-piece inverses of size <= 160
 int launch_patch_apply_arrays(alfi_ctx* ctx, int64_t npatch, const int64_t* patch_ptr, const int32_t* patch_dofs,
                               const int64_t* inv_ptr, const int64_t* stage_ptr, const double* inv, const double* x,
                               double* stage) {
   if (npatch == 0) return 0;
-  hipLaunchKernelGGL((patch_apply_kernel<true, APPLY_W>), dim3((unsigned)npatch), dim3(64 * APPLY_W), 0, ctx->stream, (int64_t)0,
-                     npatch, patch_ptr, patch_dofs, inv_ptr, stage_ptr, inv, x, stage);
+  launch_patch_apply_w(ctx, APPLY_W, 0, npatch, patch_ptr, patch_dofs, inv_ptr, stage_ptr, inv, x, stage);
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   return 0;
 }
@@ -1225,41 +1048,28 @@ int launch_patch_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double
     ALFI_CHECK(launch_cond_apply_range(L, p0, p1, x));
     return 0;
   }
-  if (L->f32 && L->lay.max_np > SMALL_PATCH_MAX) {   // single-precision macro stars (kernels_bigpatch.hip)
-    ALFI_CHECK(launch_big_apply_f32_range(L, p0, p1, x));
-    return 0;
-  }
-  if (L->f32) {                                 // single-precision storage: its own kernel whatever the patch count
-    const int64_t cnt = p1 - p0;
-#define ALFI_F32_APPLY(WV)                                                                                                  \
-  hipLaunchKernelGGL((patch_apply_f32_kernel<true, WV>), dim3((unsigned)cnt), dim3(64 * WV), 0, ctx->stream, p0, p1, L->patch_ptr, \
-                     L->patch_dofs, L->inv32_ptr, L->stage_ptr, L->inv32, x, L->stage)
-    if (L->lay.max_np > 128) ALFI_F32_APPLY(2 * APPLY_W);
-    else if (L->lay.max_np > 64) ALFI_F32_APPLY(APPLY_W);
-    else ALFI_F32_APPLY(1);
-#undef ALFI_F32_APPLY
-    ALFI_HIP_CHECK(ctx, hipGetLastError());
+  if (L->lay.max_np > SMALL_PATCH_MAX) {         // macro stars, either storage (kernels_bigpatch.hip)
+    ALFI_CHECK(L->f32 ? launch_big_apply_f32_range(L, p0, p1, x) : launch_big_apply_range(L, p0, p1, x));
     return 0;
   }
   // levels with FEW star patches of 3-D size (the lower levels of a hierarchy: 125 and 729 patches under config 3's 35 937)
   // leave most CUs empty: up to 1000 patches each patch gets 8 waves whatever its size (729 patches: 13.8 us against 15.6 us
   // through the macro stars' kernel, whose row pieces -- 64 + 32 + 8 + 4 + 2 rows for 111 dofs -- are dealt unevenly to 4
   // waves); with fewer patches than CUs the macro stars' kernel and its several workgroups per patch win (125 patches: 7.5
-  // against 8.6 us).  Config 3: 17.27 -> 17.1 ms per cycle, same box.
+  // against 8.6 us).  Config 3: 17.27 -> 17.1 ms per cycle, same box.  A level with single-precision storage takes its waves
+  // from the patch size alone.
   // (ALFI_TEST_LARGE_PATHS: no level counts as small, so that test hierarchies take the kernels of the large levels)
   const int64_t few = alfi_test_large_paths() ? 0 : 1000, fewer = alfi_test_large_paths() ? 0 : 256;
-  if (L->lay.max_np > SMALL_PATCH_MAX || (L->lay.max_np > 64 && L->npatch <= fewer)) {     // kernels_bigpatch.hip
+  if (!L->f32 && L->lay.max_np > 64 && L->npatch <= fewer) {     // kernels_bigpatch.hip
     ALFI_CHECK(launch_big_apply_range(L, p0, p1, x));
     return 0;
   }
-  const int64_t cnt = p1 - p0;
-  dim3 grid((unsigned)((cnt + 3) / 4)), block(256);
   // (the inverses are read once per apply: nontemporal loads keep x, the staging buffer and the index arrays in cache)
-  if (L->il_valid) {
+  if (L->il_valid && !L->f32) {
     // small patches, interleaved copy of the inverses: G lanes per patch, 64 / G patches per wave
     const int PW = 64 / L->il_G;
     const int64_t nwave = (p1 - 1) / PW - p0 / PW + 1;
-    dim3 igrid((unsigned)((nwave + 3) / 4));
+    dim3 igrid((unsigned)((nwave + 3) / 4)), block(256);
 #define ALFI_IL(GV)                                                                                                      \
   case GV:                                                                                                               \
     hipLaunchKernelGGL((patch_apply_il_kernel<GV, true>), igrid, block, 0, ctx->stream, p0, p1, L->il_nc, L->patch_ptr,  \
@@ -1271,15 +1081,13 @@ int launch_patch_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double
     }
 #undef ALFI_IL
   } else {
-    if (L->lay.max_np > 128 || (L->lay.max_np > 64 && L->npatch <= few))
-      hipLaunchKernelGGL((patch_apply_kernel<true, 2 * APPLY_W>), dim3((unsigned)cnt), dim3(128 * APPLY_W), 0, ctx->stream, p0,
-                         p1, L->patch_ptr, L->patch_dofs, L->inv_ptr, L->stage_ptr, L->inv, x, L->stage);
-    else if (L->lay.max_np > 64)
-      hipLaunchKernelGGL((patch_apply_kernel<true, APPLY_W>), dim3((unsigned)cnt), dim3(64 * APPLY_W), 0, ctx->stream, p0, p1,
-                         L->patch_ptr, L->patch_dofs, L->inv_ptr, L->stage_ptr, L->inv, x, L->stage);
+    // waves per patch: eight above 128 dofs (and on FP64 levels of few patches above 64), four above 64, one below
+    const int W = L->lay.max_np > 128 || (!L->f32 && L->lay.max_np > 64 && L->npatch <= few) ? 2 * APPLY_W
+                  : L->lay.max_np > 64 ? APPLY_W : 1;
+    if (L->f32)
+      launch_patch_apply_w(ctx, W, p0, p1, L->patch_ptr, L->patch_dofs, L->inv32_ptr, L->stage_ptr, L->inv32, x, L->stage);
     else
-      hipLaunchKernelGGL((patch_apply_kernel<true, 1>), dim3((unsigned)cnt), dim3(64), 0, ctx->stream, p0, p1, L->patch_ptr,
-                         L->patch_dofs, L->inv_ptr, L->stage_ptr, L->inv, x, L->stage);
+      launch_patch_apply_w(ctx, W, p0, p1, L->patch_ptr, L->patch_dofs, L->inv_ptr, L->stage_ptr, L->inv, x, L->stage);
   }
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   return 0;
@@ -1298,23 +1106,6 @@ int launch_patch_sum_range(alfi_level* L, int64_t i0, int64_t i1, const double* 
 }
 
 int launch_patch_sum(alfi_level* L, const double* x, double* y) { return launch_patch_sum_range(L, 0, L->n, x, y); }
-
-// gather of a level with a canonical order (max_np <= SMALL_PATCH_MAX), and its inverses back into the order of patch_dofs
-int launch_patch_gather_ranked(alfi_level* L) {
-  alfi_ctx* ctx = L->ctx;
-  if (L->npatch == 0) return 0;
-  dim3 grid((unsigned)L->npatch), block(256);
-  if (L->bs == 2)
-    hipLaunchKernelGGL(patch_gather_ranked_kernel<2>, grid, block, 0, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals,
-                       L->patch_ptr, L->patch_dofs, L->canon_rank, L->inv_ptr, L->inv, L->A.flat);
-  else if (L->bs == 3)
-    hipLaunchKernelGGL(patch_gather_ranked_kernel<3>, grid, block, 0, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals,
-                       L->patch_ptr, L->patch_dofs, L->canon_rank, L->inv_ptr, L->inv, L->A.flat);
-  else
-    return alfi_set_error(ctx, ALFI_E_ARG, "unsupported block size %d", L->bs);
-  ALFI_HIP_CHECK(ctx, hipGetLastError());
-  return 0;
-}
 
 int launch_patch_unrank(alfi_level* L) {
   alfi_ctx* ctx = L->ctx;

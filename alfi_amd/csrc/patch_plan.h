@@ -112,26 +112,18 @@ inline int plan_patch_layout(int64_t n, int64_t npatch, const int64_t* pptr, con
   return 0;
 }
 
-// ---- the single-precision storage of a level's dense inverses (alfi_patches_set_storage) ------------------------------------
-// Patch p holds its n_p x n_p inverse as floats at inv32 + f32_ptr[p]: rows padded to ld = n_p rounded up to F32_ROWS, cut
-// into row pieces of 128, 64, ..., F32_ROWS rows (as many 128-row pieces as fit, then the binary digits of the remainder), a
-// piece of R rows stored [column][R].  A lane of the apply reads F32_ROWS rows of one column with one aligned load of
-// 4 * F32_ROWS bytes -- the 16 bytes per lane of the FP64 layout (patch_inv_index, common.h) --, a wave instruction 1 KiB of
-// consecutive bytes.  Pad rows are stored as zeros; every patch starts on a 128-byte line.
-constexpr int F32_ROWS = 4;               // rows of a column per lane: one 16-byte load
-constexpr int F32_ALIGN = 32;             // floats: a patch's storage starts on a 128-byte line
-
-ALFI_HD inline int f32_ld(int n) { return (n + F32_ROWS - 1) & ~(F32_ROWS - 1); }
-// floats patch p occupies (its padded rows, rounded up to whole 128-byte lines)
-ALFI_HD inline int64_t f32_patch_floats(int n) { return ((int64_t)n * f32_ld(n) + F32_ALIGN - 1) & ~(int64_t)(F32_ALIGN - 1); }
-// offset of entry (r, c), r < f32_ld(n), c < n
-ALFI_HD inline int64_t f32_inv_index(int r, int c, int n) {
-  const int ld = f32_ld(n);
+// ---- storage of one dense inverse: row pieces (the kernels that stream it: row_piece.h) --------------------------------------
+// An n x n inverse with its rows padded to ld (n rounded up to min_rows, pad rows stored as zeros) is cut into row pieces: as
+// many 128-row pieces as fit, then the binary digits of the remainder (64, 32, ..., min_rows).  A piece of R rows is stored
+// [column][R] contiguously and the pieces follow each other, so the inverse is ld * n contiguous values that the apply streams
+// front to back exactly once, a lane reading min_rows rows of one column as one aligned 16-byte load and a wave instruction
+// 1 KiB of consecutive bytes.  Offset of entry (r, c), r < ld, c < n:
+ALFI_HD inline int64_t piece_index(int r, int c, int n, int ld, int min_rows) {
   int row0 = r & ~127, rows = 128;
   if (row0 + 128 > ld) {
     const int rem = ld - row0;
     int rr = r - row0;
-    for (int bit = 64; bit >= F32_ROWS; bit >>= 1) {
+    for (int bit = 64; bit >= min_rows; bit >>= 1) {
       if (rem & bit) {
         if (rr < bit) {
           rows = bit;
@@ -144,6 +136,19 @@ ALFI_HD inline int64_t f32_inv_index(int r, int c, int n) {
   }
   return (int64_t)row0 * n + (int64_t)c * rows + (r - row0);
 }
+// FP64 storage: min_rows = 2, ld = n rounded up to even (the caller passes it), patch p at inv + inv_ptr[p] (a multiple of 16
+// doubles = 128 B)
+ALFI_HD inline int64_t patch_inv_index(int r, int c, int n, int ld) { return piece_index(r, c, n, ld, 2); }
+
+// FP32 storage (alfi_patches_set_storage, alfi_patches_set_macro_storage): min_rows = F32_ROWS -- the same 16 bytes per lane --,
+// patch p at inv32 + f32_ptr[p], every patch on a 128-byte line
+constexpr int F32_ROWS = 4;               // rows of a column per lane: one 16-byte load
+constexpr int F32_ALIGN = 32;             // floats: a patch's storage starts on a 128-byte line
+
+ALFI_HD inline int f32_ld(int n) { return (n + F32_ROWS - 1) & ~(F32_ROWS - 1); }
+// floats patch p occupies (its padded rows, rounded up to whole 128-byte lines)
+ALFI_HD inline int64_t f32_patch_floats(int n) { return ((int64_t)n * f32_ld(n) + F32_ALIGN - 1) & ~(int64_t)(F32_ALIGN - 1); }
+ALFI_HD inline int64_t f32_inv_index(int r, int c, int n) { return piece_index(r, c, n, f32_ld(n), F32_ROWS); }
 // (npatch + 1) offsets in floats; returns the floats of the level
 inline int64_t plan_f32_offsets(int64_t npatch, const int64_t* pptr, std::vector<int64_t>* f32_ptr) {
   f32_ptr->resize((size_t)npatch + 1);

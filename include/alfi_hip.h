@@ -331,7 +331,7 @@ int alfi_patches_storage(alfi_level* lvl, int* dtype);
  *     probe, rounding to nearest into the level's float32 copy.  The level holds sum 4 n_p^2 bytes (padded) and the ctx the work
  *     buffer; the FP64 inverses of the whole level never exist at once.  The stored values do not depend on the ranges, and
  *     alfi_patches_check reports the figures of the FP64 inverses before rounding, accumulated over the ranges: those of an FP64
- *     level.  big_apply_f32_kernel applies them (a workgroup per patch, float4 loads, FP64 fma).
+ *     level.  big_apply_kernel<float, NT> applies them (a workgroup per patch, float4 loads, FP64 fma).
  *   - A level whose every patch has <= 160 dofs takes the path of alfi_patches_set_storage (whole-level work buffer), with the
  *     facet rule applied on the work buffer.
  * ALFI_E_ARG, before any device work and with the level left as it was: no patches; every patch <= 32 dofs (the interleaved

@@ -1,5 +1,5 @@
 """Single-precision storage of dense MACRO-STAR inverses, Burman levels included (alfi_patches_set_macro_storage;
-hip.Level.set_macro_patch_storage and the front ends' macro_factor_dtype="f32"): big_apply_f32_kernel, the factorisation in patch
+hip.Level.set_macro_patch_storage and the front ends' macro_factor_dtype="f32"): big_apply_kernel<float, NT>, the factorisation in patch
 ranges through the context's work buffer (alfi_ctx_set_f32_work_bytes), and the facet rule on FP32 levels.  -m gpu.
 
 Error model (tests/test_gpu_patch_storage.py): for stored values fl32(inv(A_p)) and FP64 arithmetic,

@@ -1,5 +1,5 @@
 """CPU checks of the single-precision storage of dense MACRO-STAR inverses (alfi_patches_set_macro_storage) through
-libalfi_host.so: the layout of csrc/patch_plan.h (f32_inv_index, plan_f32_offsets) beyond 160 dofs, where big_apply_f32_kernel
+libalfi_host.so: the layout of csrc/patch_plan.h (f32_inv_index, plan_f32_offsets) beyond 160 dofs, where big_apply_kernel<float, NT>
 reads it -- the assertions tests/test_patch_storage_layout.py makes up to 160."""
 import numpy as np
 import pytest

@@ -90,3 +90,34 @@ def test_a_rank_knows_the_order_of_the_unpartitioned_patch():
             assert np.array_equal(got, want)
             permuted += int(not np.array_equal(rank, np.arange(b - a)))
     assert permuted > 0          # ghosts are numbered last: some patch's local order is not the global one
+
+
+def _documented_layout(n, ld, min_rows):
+    """(ld, n) offsets of the row-piece storage as patch_plan.h documents it: as many 128-row pieces as fit, then the binary
+    digits of the remainder down to min_rows, a piece of R rows stored [column][R], the pieces one after the other"""
+    pieces = [128] * (ld // 128) + [b for b in (64, 32, 16, 8, 4, 2) if b >= min_rows and (ld % 128) & b]
+    assert sum(pieces) == ld
+    idx = np.empty((ld, n), dtype=np.int64)
+    row0 = 0
+    for rows in pieces:
+        r, c = np.meshgrid(np.arange(rows), np.arange(n), indexing="ij")
+        idx[row0:row0 + rows] = row0 * n + c * rows + r
+        row0 += rows
+    return idx
+
+
+@pytest.mark.parametrize("min_rows", [2, 4])
+def test_the_unified_index_is_the_documented_layout_and_the_wrappers_are_it(min_rows):
+    """piece_index (csrc/patch_plan.h), the one loop over the binary digits: a bijection onto [0, ld n) that equals the documented
+    layout, for every n the FP64 / FP32 kernels of small patches see and well into the macro stars; patch_inv_index (min_rows 2)
+    and f32_inv_index (min_rows 4) are it."""
+    for n in range(1, 601):
+        ld = (n + min_rows - 1) // min_rows * min_rows
+        idx = _hostlib.piece_index_table(n, ld, min_rows)
+        assert idx.min() == 0 and np.array_equal(np.bincount(idx.ravel(), minlength=ld * n), np.ones(ld * n, dtype=np.int64)), n
+        assert np.array_equal(idx, _documented_layout(n, ld, min_rows)), n
+        if min_rows == 2:
+            assert np.array_equal(_hostlib.patch_index_table(n), idx), n
+        else:
+            wld, _, widx = _hostlib.f32_index_table(n)
+            assert wld == ld and np.array_equal(widx, idx), n
