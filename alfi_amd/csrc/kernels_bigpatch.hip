@@ -384,30 +384,36 @@ constexpr int BIG_U = 8;            // 16-byte loads in flight per lane (piece_d
 // blocks of rows inside the stored pieces: a block of 2 G rows takes G lanes per column and 64 / G columns per load
 // instruction.  Used where whole pieces dealt round-robin leave waves idle (a Schur complement of 312 rows is
 // 2 x 128 + 32 + 16 + 8: two of eight waves would stream 82 % of it).
+// the next block of a range of rows [r, r1): the stored piece (row0, P rows) that holds row r and R, the rows of the block
+__device__ __forceinline__ void big_block(int ld, int r, int r1, int& row0, int& P, int& R) {
+  const int full = ld & ~127;
+  if (r < full) {
+    row0 = r & ~127;
+    P = 128;
+  } else {
+    row0 = full;
+    P = 64;
+    const int rem = ld - full;
+    for (; P >= 2; P >>= 1)
+      if (rem & P) {
+        if (r < row0 + P) break;
+        row0 += P;
+      }
+  }
+  const int o = r - row0;
+  R = P;                               // the largest aligned power-of-two block at o that ends inside the piece and the range
+  while (R > 2 && ((o & (R - 1)) != 0 || o + R > P || r + R > r1)) R >>= 1;
+}
+
 template <bool NT>
 __device__ __forceinline__ void big_rows(const double* __restrict__ T, int n, int ld, int r0, int r1,
                                          const double* __restrict__ xs, int lane, double* __restrict__ ys) {
   // ys: n doubles (LDS or global); rows >= n (the zero pad row) are not stored
-  const int full = ld & ~127;
   int r = r0;
   while (r < r1) {
-    int row0, P;                       // the stored piece that holds row r
-    if (r < full) {
-      row0 = r & ~127;
-      P = 128;
-    } else {
-      row0 = full;
-      P = 64;
-      const int rem = ld - full;
-      for (; P >= 2; P >>= 1)
-        if (rem & P) {
-          if (r < row0 + P) break;
-          row0 += P;
-        }
-    }
+    int row0, P, R;
+    big_block(ld, r, r1, row0, P, R);
     const int o = r - row0;
-    int R = P;                         // the largest aligned power-of-two block at o that ends inside the piece and the range
-    while (R > 2 && ((o & (R - 1)) != 0 || o + R > P || r + R > r1)) R >>= 1;
     const double* Tp = T + (int64_t)row0 * n + o;
     // (lim = n - r: the pad row of an odd n is not written)
 #define ALFI_BIG_BLOCK(RV) \
@@ -419,6 +425,41 @@ __device__ __forceinline__ void big_rows(const double* __restrict__ T, int n, in
 #undef ALFI_BIG_BLOCK
     r += R;
   }
+}
+
+// One block of big_rows in two halves, for a kernel that requests the block before its operand exists: the loads of a block of
+// R = 2 << lg <= 16 rows over n <= BIG_U * 64 / (R / 2) columns -- every column group of the lane, BIG_U 16-byte loads held in
+// registers -- and, later, the sums.  The sums are those of piece_apply<double, R / 2, ., BIG_U, false, GUARDED> to the bit: a
+// lane's columns ascending, then the column groups by shuffles (row_piece.h).  Tp: (first row of the block, column 0), P: the
+// rows of the stored piece.
+template <bool NT>
+__device__ __forceinline__ void big_block_prefetch(const double* __restrict__ Tp, int P, int n, int lg, int lane,
+                                                   big_d2 (&v)[BIG_U]) {
+  const int C = 64 >> lg, cg = lane >> lg, l = lane & ((1 << lg) - 1);
+#pragma unroll
+  for (int u = 0; u < BIG_U; ++u) {
+    const big_d2 z = {0.0, 0.0};
+    v[u] = cg + u * C < n ? piece_load<double, NT>(Tp + 2 * l + (int64_t)(cg + u * C) * P) : z;
+  }
+}
+__device__ __forceinline__ void big_block_finish(const big_d2 (&v)[BIG_U], int n, int lg, const double* __restrict__ xs, int lane,
+                                                 double* __restrict__ out, int lim) {
+  const int G = 1 << lg, C = 64 >> lg, cg = lane >> lg, l = lane & (G - 1);
+  double acc0 = 0.0, acc1 = 0.0;
+#pragma unroll
+  for (int u = 0; u < BIG_U; ++u)
+    if (cg + u * C < n) {
+      const double xj = xs[cg + u * C];
+      acc0 = __builtin_fma(v[u].x, xj, acc0);
+      acc1 = __builtin_fma(v[u].y, xj, acc1);
+    }
+  for (int o = G; o < 64; o <<= 1) {
+    acc0 += __shfl_xor(acc0, o);
+    acc1 += __shfl_xor(acc1, o);
+  }
+  if (cg != 0) return;
+  if (2 * l < lim) out[2 * l] = acc0;
+  if (2 * l + 1 < lim) out[2 * l + 1] = acc1;
 }
 
 // One workgroup of 4 waves per patch (``split`` workgroups on launches of few patches): x_p into LDS, the stored row pieces of
@@ -1135,13 +1176,28 @@ __global__ __launch_bounds__(256) void cond_sigma_kernel(int64_t c0, CondDev cd,
   const int s = n - nI;
   const int ld = (s + 1) & ~1;
   const double* rhs = stage + stage_ptr[p] + nI;
-  for (int i = threadIdx.x; i < s; i += 256) cond_dsmem[i] = rhs[i];
-  __syncthreads();
   const int r1 = min(ld, r0 + COND_SIGMA_ROWS);
   const int share = (((r1 - r0) + 3) / 4 + 15) & ~15;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int a = r0 + wave * share, b = min(r1, a + share);
-  if (a < b) big_rows<NT>(cd.sinv + cd.sinv_ptr[p], s, ld, a, b, cond_dsmem, lane, cd.tmp + off + nI);
+  // A small skeleton (vertex stars: s = 63, 27): the first block of the wave's share is requested WHOLE, before the right-hand side
+  // is in LDS -- the loads depend on the tables alone.  (big_rows after the barrier: one batch of BIG_U loads, then, for the lanes
+  // whose column group misses the last batch -- 8 of 64 at s = 63 --, a column at a time with the whole wave waiting.)
+  int row0 = 0, P = 2, R = 2;
+  if (a < b) big_block(ld, a, b, row0, P, R);
+  const int lg = __builtin_ctz(R) - 1;
+  const bool ahead = a < b && s <= BIG_U * (64 >> lg);      // wave-uniform
+  big_d2 sv[BIG_U];
+  if (ahead) big_block_prefetch<NT>(cd.sinv + cd.sinv_ptr[p] + (int64_t)row0 * s + (a - row0), P, s, lg, lane, sv);
+  for (int i = threadIdx.x; i < s; i += 256) cond_dsmem[i] = rhs[i];
+  __syncthreads();
+  double* ys = cd.tmp + off + nI;
+  if (ahead) {
+    big_block_finish(sv, s, lg, cond_dsmem, lane, ys + a, s - a);
+    if (a + R < b) big_rows<NT>(cd.sinv + cd.sinv_ptr[p], s, ld, a + R, b, cond_dsmem, lane, ys);
+  } else if (a < b) {
+    big_rows<NT>(cd.sinv + cd.sinv_ptr[p], s, ld, a, b, cond_dsmem, lane, ys);
+  }
 }
 
 template <bool NT, int COND_WAVES, int RU>
@@ -1716,6 +1772,11 @@ int launch_cond_schur_one(alfi_level* L, int64_t p, const int64_t* d_zero, doubl
 // Measured and dropped (rounds 2-3, profiles/r03_cond_apply_ab_cfg5.txt): the whole apply as ONE launch per patch (941 against
 // 860 us on config 5's finest level), 4 or 16 waves per patch on large launches, 16 columns in flight per lane, nontemporal
 // loads for the group matrices (a column of 45 doubles shares its first and last line with its neighbours: 218 against 208 us).
+// Condensed vertex stars (config 4: 185 193 patches of <= 153 dofs, a skeleton of <= 63): the sigma launch asks for a wave's block of
+// inv(Sigma) before the right-hand side is in LDS (big_block_prefetch: 1395 -> 956 us per launch, the apply 3340 -> 2940-3020 us).
+// Measured and dropped there (profiles/star_fused_cfg4.txt): the whole apply as one launch of resident workgroups, the group
+// matrices of a patch through LDS and the next patch's requested meanwhile -- bitwise equal, 5000 us per apply (one patch per
+// workgroup: 5830 us): 2 workgroups per CU do not cover the descriptor chain of a patch.
 int launch_cond_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double* x) {
   alfi_ctx* ctx = L->ctx;
   if (p1 <= p0) return 0;
