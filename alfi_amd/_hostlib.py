@@ -50,7 +50,7 @@ def lib():
         _lib.alfi_host_f32_index_table.restype = None
         _lib.alfi_host_piece_index_table.restype = None
         _lib.alfi_host_patch_index_table.restype = None
-        for name in ("patch_layout", "condensed", "sweep", "f32_layout", "macro_f32_layout"):
+        for name in ("patch_layout", "condensed", "sweep", "f32_layout", "macro_f32_layout", "f32_ranges"):
             getattr(_lib, "alfi_host_plan_" + name).restype = ctypes.c_void_p
         _lib.alfi_host_f32_index.restype = ctypes.c_int64
         _lib.alfi_host_f32_ld.restype = ctypes.c_int
@@ -142,6 +142,14 @@ def plan_macro_f32_layout(patch_ptr):
     """plan_f32_layout for the levels of alfi_patches_set_macro_storage: patches of up to 4096 dofs, same layout."""
     pp = np.ascontiguousarray(patch_ptr, dtype=np.int64)
     return _plan_dict(lib().alfi_host_plan_macro_f32_layout(ctypes.c_int64(len(pp) - 1), _p(pp)))
+
+
+def plan_f32_ranges(inv_ptr, cap_doubles):
+    """The patch ranges an FP32 level of big patches is factored in through a work buffer of ``cap_doubles`` doubles
+    (csrc/patch_plan.h: plan_f32_ranges) as a dict: ``ranges`` (the boundaries, 0 .. npatch) and ``work_doubles`` (the largest
+    range).  ``inv_ptr``: the offsets of the FP64 inverses, as ``plan_patch_layout`` returns them."""
+    ip = np.ascontiguousarray(inv_ptr, dtype=np.int64)
+    return _plan_dict(lib().alfi_host_plan_f32_ranges(ctypes.c_int64(len(ip) - 1), _p(ip), ctypes.c_int64(cap_doubles)))
 
 
 def f32_index_table(n):

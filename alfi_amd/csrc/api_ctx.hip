@@ -263,7 +263,7 @@ void free_cond(alfi_level* L) {
   for (void* q : L->cond_allocs) dev_free(q);
   L->cond_allocs.clear();
   L->cd = CondDev();
-  L->cond = false;
+  if (L->held == HELD_COND) set_held(L, HELD_NONE);   // (the placeholder is all the level holds now)
   L->cplan = CondPlan();
 }
 

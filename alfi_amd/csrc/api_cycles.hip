@@ -567,7 +567,7 @@ static void cycle_signature(alfi_mg* mg, std::vector<uint64_t>* sig) {
     push(L->A.vals);
     push(L->inv);
     push(L->inv32);
-    sig->push_back((uint64_t)(L->f32 ? 1 : 0));
+    sig->push_back((uint64_t)(L->held == HELD_F32 ? 1 : 0));
     push(L->cd.mat);
     push(L->cd.sinv);
     push(L->patch_ptr);

@@ -42,7 +42,6 @@ int build_chunk_tables(alfi_ctx* ctx, DevBSR* d, const int32_t* rowptr, int64_t 
 int upload_bsr(alfi_ctx* ctx, DevBSR* d, const alfi_bsr_host* h, int bs);
 void free_bsr(DevBSR* d);
 void free_cond(alfi_level* L);
-void free_f32(alfi_level* L);     // api_patches.hip: the single-precision copy of a level's inverses
 int comm_allreduce(alfi_level* L, int64_t offset, int64_t count);
 int halo_fwd(alfi_level* L, double* v);
 int halo_fwd_begin(alfi_level* L, const double* v);
@@ -59,7 +58,22 @@ int level_patch_apply(alfi_level* L, const double* dx, double* dy, bool* ghosts_
 inline bool level_pc_ready(const alfi_level* L) { return L->factored || L->jacobi; }
 // the entry points that exist on serial levels only (Chebyshev smoother, W-cycle, CG, Arnoldi, point Jacobi)
 inline bool level_is_partitioned(const alfi_level* L) { return L->distributed || L->has_halo || L->n_own != L->n; }
+// ---- the state of a level's patch factors (common.h: store_req, held, cond_by) ------------------------------------------------
+// the only writer of `held`, and of `cond` with it
+inline void set_held(alfi_level* L, PatchStoreHeld h) {
+  L->held = h;
+  L->cond = h == HELD_COND;
+}
+inline bool wants_f32(const alfi_level* L) { return L->store_req != STORE_REQ_F64; }               // the next factorisation
+inline bool is_or_will_be_f32(const alfi_level* L) { return wants_f32(L) || L->held == HELD_F32; }
+inline bool cond_by_caller(const alfi_level* L) { return L->cond && L->cond_by == COND_BY_CALLER; }
+inline bool cond_by_own_choice(const alfi_level* L) { return L->cond && L->cond_by == COND_BY_LIBRARY; }
+// PCPATCH's facet rule changes the patch matrices of this level
+inline bool facet_rule_active(const alfi_level* L) { return L->fc_ptr && L->fc_scale != 0.0; }
 // api_patches.hip
+// every factor storage of the level -- dense FP64, interleaved copy, FP32, condensed -- and the requests that go with a patch
+// set; the ctx's FP64 work buffer goes with its last FP32 level.  Callers have synchronised the stream.
+void free_patch_factors(alfi_level* L);
 void free_mult_schedule(alfi_level* L);
 // a level that condensed itself goes back to dense inverses for good (api_patches.hip); true: it was factored, factor it again
 bool auto_cond_to_dense(alfi_level* L);

@@ -205,9 +205,7 @@ int alfi_level_destroy(alfi_level* L) {
   dev_free(L->patch_dofs);
   dev_free(L->inv_ptr);
   dev_free(L->stage_ptr);
-  dev_free(L->inv);
-  dev_free(L->inv_il);
-  free_f32(L);
+  free_patch_factors(L);
   dev_free(L->canon_rank);
   dev_free(L->stage);
   dev_free(L->dof_ptr);
@@ -218,7 +216,6 @@ int alfi_level_destroy(alfi_level* L) {
   dev_free(L->tr_mirror);
   dev_free(L->chk);
   dev_free(L->chk_list);
-  free_cond(L);
   dev_free(L->V);
   dev_free(L->Z);
   dev_free(L->w);
@@ -709,8 +706,9 @@ int alfi_patches_set_facet_correction(alfi_level* L, int64_t nfacet, int64_t nro
                                       const int32_t* fac, const double* s) {
   alfi_ctx* ctx = L->ctx;
   if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_set_facet_correction before alfi_patches_set");
-  // (a level asked through alfi_patches_set_macro_storage takes a facet correction like an FP64 level)
-  if ((L->f32_req || L->f32) && !L->f32_macro)
+  // refused while the star request for FP32 stands (a level asked through alfi_patches_set_macro_storage takes a facet
+  // correction like an FP64 level)
+  if (L->store_req == STORE_REQ_F32_STAR)
     return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_set_facet_correction on a level with FP32 patch storage "
                                              "(alfi_patches_set_storage(lvl, 0) first)");
   if (!ptr || nfacet < 0 || nrow < 0) return alfi_set_error(ctx, ALFI_E_ARG, "NULL argument");
@@ -744,7 +742,7 @@ int alfi_patches_set_facet_correction(alfi_level* L, int64_t nfacet, int64_t nro
   ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->fc_beta, 0, sizeof(double) * (size_t)std::max<int64_t>(nfacet, 1), ctx->stream));
   L->fc_nfacet = nfacet;
   L->fc_scale = 0.0;
-  if (L->f32_req || L->f32) L->factored = false;   // (alfi_patches_set_macro_storage: the stored floats belong to the old matrices)
+  if (is_or_will_be_f32(L)) L->factored = false;   // (alfi_patches_set_macro_storage: the stored floats belong to the old matrices)
   if (refactor) ALFI_CHECK(alfi_patches_factor(L));
   return rc;
 }

@@ -1,14 +1,17 @@
 // C ABI of libalfi_hip.so (include/alfi_hip.h), PCPATCH: patch sets, condensed factors, multiplicative schedules, factorisation, apply.
 // (One file per concern since round 5: api_ctx / api_level / api_patches / api_smoother / api_cycles / api_saddle; the helpers they
 // share are declared in api_internal.h.)
+#include <optional>
 #include "api_internal.h"
 #include "find_groups.h"
 
 static_assert(PLAN_E_ARG == ALFI_E_ARG, "the planners (patch_plan.h) return the C ABI's code");
 
-// the single-precision copy of the inverses and its offsets
-void free_f32(alfi_level* L) {
-  // the last FP32 level of the ctx takes the FP64 work buffer with it (callers have synchronised the stream)
+// ---- the storage of a level's patch factors (state: common.h, questions: api_internal.h) ---------------------------------------
+// Every function here expects the stream synchronised by its caller.
+
+// the single-precision copy of the inverses and its offsets; the last FP32 level of the ctx takes the FP64 work buffer with it
+static void free_f32(alfi_level* L) {
   if (L->inv32 && --L->ctx->f32_levels == 0) {
     dev_free(L->ctx->f32_work);
     L->ctx->f32_work = nullptr;
@@ -20,8 +23,31 @@ void free_f32(alfi_level* L) {
   L->inv32_ptr = nullptr;
   L->inv32_floats = 0;
   std::vector<int64_t>().swap(L->f32_ptr);
-  L->f32 = false;
-  if (!L->f32_req) L->f32_macro = false;
+  if (L->held == HELD_F32) set_held(L, HELD_NONE);
+}
+
+// `inv` as the 16-double placeholder: all a level has of dense FP64 inverses before its first dense factorisation, with condensed
+// factors and with FP32 storage (never NULL once the patches are set: a kernel argument and part of the cycle graphs' signature)
+static int inv_to_placeholder(alfi_level* L) {
+  dev_free(L->inv);
+  L->inv = nullptr;
+  if (L->held == HELD_F64) set_held(L, HELD_NONE);
+  return dev_alloc(L->ctx, &L->inv, 16);
+}
+
+void free_patch_factors(alfi_level* L) {
+  dev_free(L->inv);
+  L->inv = nullptr;
+  dev_free(L->inv_il);
+  L->inv_il = nullptr;
+  L->il_doubles = 0;
+  L->il_valid = false;
+  free_f32(L);
+  free_cond(L);
+  set_held(L, HELD_NONE);
+  L->store_req = STORE_REQ_F64;                   // a new patch set starts in FP64 and undecided about condensation
+  L->cond_by = COND_UNDECIDED;
+  L->factored = false;
 }
 
 // ---- patches -------------------------------------------------------------------------------------------------------------
@@ -36,25 +62,14 @@ int alfi_patches_set(alfi_level* L, int64_t npatch, const int64_t* pptr, const i
   dev_free(L->patch_dofs);
   dev_free(L->inv_ptr);
   dev_free(L->stage_ptr);
-  dev_free(L->inv);
-  L->f32_req = false;
-  free_f32(L);                                    // a new patch set starts in FP64 (alfi_patches_set_storage)
+  free_patch_factors(L);
   dev_free(L->canon_rank);
   L->canon_rank = nullptr;
-  dev_free(L->inv_il);
-  L->inv_il = nullptr;
-  L->il_doubles = 0;
-  L->il_valid = false;
   dev_free(L->stage);
   dev_free(L->dof_ptr);
   dev_free(L->dof_pos);
   L->patch_ptr = nullptr; L->patch_dofs = nullptr; L->inv_ptr = nullptr; L->stage_ptr = nullptr;
-  L->inv = nullptr; L->stage = nullptr; L->dof_ptr = nullptr; L->dof_pos = nullptr;
-  L->factored = false;
-  free_cond(L);
-  L->cond_auto = false;
-  L->cond_decided = false;
-  L->inv_shrunk = false;
+  L->stage = nullptr; L->dof_ptr = nullptr; L->dof_pos = nullptr;
   L->npatch = npatch;
   PatchLayout lay;
   std::string err;
@@ -68,8 +83,7 @@ int alfi_patches_set(alfi_level* L, int64_t npatch, const int64_t* pptr, const i
   ALFI_CHECK(dev_upload(ctx, &L->dof_pos, lay.dof_pos.data(), lay.sum_n));
   // the dense inverses (8 sum n_p^2 bytes) are allocated by the first alfi_patches_factor that needs them: a level that
   // gets condensed factors (alfi_patches_set_groups) never holds them -- 265 GB for the 3.4 M-dof Scott-Vogelius level
-  ALFI_CHECK(dev_alloc(ctx, &L->inv, 16));
-  L->inv_shrunk = true;
+  ALFI_CHECK(inv_to_placeholder(L));
   ALFI_CHECK(dev_alloc(ctx, &L->stage, lay.stage_len));
   ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->stage, 0, (size_t)std::max<int64_t>(lay.stage_len, 1) * sizeof(double), ctx->stream));
   // later calls read patch_ptr, patch_dofs and inv_ptr on the host (copied here, while the device clears the staging buffer);
@@ -90,57 +104,40 @@ int alfi_patches_set(alfi_level* L, int64_t npatch, const int64_t* pptr, const i
   return 0;
 }
 
-int alfi_patches_set_storage(alfi_level* L, int dtype) {
+// The two requests for FP32 storage.  What has no single-precision form is refused here, before any device work: the request
+// is explicit, so nothing falls back to FP64 behind the caller's back.  The star request (alfi_patches_set_storage) also refuses
+// what it has no kernel for (patches above 160 dofs) and no place for the facet rule for (a facet correction); the macro request
+// (alfi_patches_set_macro_storage), the one macro stars and Burman levels can make, accepts both.
+static int set_storage_request(alfi_level* L, int dtype, bool macro) {
   alfi_ctx* ctx = L->ctx;
-  if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_set_storage before alfi_patches_set");
+  const char* fn = macro ? "alfi_patches_set_macro_storage" : "alfi_patches_set_storage";
+  const char* what = macro ? "FP32 macro-star storage" : "FP32 patch storage";
+  if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "%s before alfi_patches_set", fn);
   if (dtype != ALFI_STORAGE_F64 && dtype != ALFI_STORAGE_F32)
-    return alfi_set_error(ctx, ALFI_E_ARG, "alfi_patches_set_storage: dtype %d (0: FP64, 1: FP32)", dtype);
+    return alfi_set_error(ctx, ALFI_E_ARG, "%s: dtype %d (0: FP64, 1: FP32)", fn, dtype);
   if (dtype == ALFI_STORAGE_F32) {
-    // what has no single-precision form is refused here, before any device work: the request is explicit, so nothing falls
-    // back to FP64 behind the caller's back
-    if (L->npatch == 0) return alfi_set_error(ctx, ALFI_E_ARG, "FP32 patch storage: the level has no patches");
+    if (L->npatch == 0) return alfi_set_error(ctx, ALFI_E_ARG, "%s: the level has no patches", what);
     if (L->lay.max_np <= 32)
-      return alfi_set_error(ctx, ALFI_E_ARG, "FP32 patch storage: every patch has <= 32 dofs and the level applies the "
-                                             "interleaved small-patch copy, which has no FP32 form");
-    if (L->lay.max_np > SMALL_PATCH_MAX)
-      return alfi_set_error(ctx, ALFI_E_ARG, "FP32 patch storage: a patch has %d dofs; the FP32 apply handles at most %d "
-                                             "(macro stars keep FP64)", L->lay.max_np, SMALL_PATCH_MAX);
-    if (L->cond && !L->cond_auto)
-      return alfi_set_error(ctx, ALFI_E_ARG, "FP32 patch storage: the level has caller-supplied groups; condensed factors cancel "
-                                             "in single precision and stay FP64 (alfi_patches_set_groups(NULL) first)");
-    if (L->mult) return alfi_set_error(ctx, ALFI_E_ARG, "FP32 patch storage: multiplicative sweeps read FP64 inverses");
-    if (L->fc_ptr)
-      return alfi_set_error(ctx, ALFI_E_ARG, "FP32 patch storage: the level has a facet correction (Burman); its patch "
-                                             "matrices are factored and repaired in FP64 only");
+      return alfi_set_error(ctx, ALFI_E_ARG, "%s: every patch has <= 32 dofs and the level applies the interleaved small-patch "
+                                             "copy, which has no FP32 form", what);
+    if (!macro && L->lay.max_np > SMALL_PATCH_MAX)
+      return alfi_set_error(ctx, ALFI_E_ARG, "%s: a patch has %d dofs; the FP32 apply handles at most %d (macro stars keep FP64)",
+                            what, L->lay.max_np, SMALL_PATCH_MAX);
+    if (cond_by_caller(L))
+      return alfi_set_error(ctx, ALFI_E_ARG, "%s: the level has caller-supplied groups; condensed factors cancel in single "
+                                             "precision and stay FP64 (alfi_patches_set_groups(NULL) first)", what);
+    if (L->mult) return alfi_set_error(ctx, ALFI_E_ARG, "%s: multiplicative sweeps read FP64 inverses", what);
+    if (!macro && L->fc_ptr)
+      return alfi_set_error(ctx, ALFI_E_ARG, "%s: the level has a facet correction (Burman); its patch matrices are factored "
+                                             "and repaired in FP64 only", what);
   }
   // (the level keeps what it holds, and works with it, until the next alfi_patches_factor)
-  L->f32_req = dtype == ALFI_STORAGE_F32;
-  if (L->f32_req) L->f32_macro = false;
+  L->store_req = dtype != ALFI_STORAGE_F32 ? STORE_REQ_F64 : macro ? STORE_REQ_F32_MACRO : STORE_REQ_F32_STAR;
   return 0;
 }
 
-// The second, separate request for FP32 storage: the one macro stars and Burman levels can make.  What alfi_patches_set_storage
-// refuses for want of a kernel (patches above 160 dofs) or of a place for the facet rule (a facet correction) is accepted here;
-// what has no single-precision form at all is refused as there.
-int alfi_patches_set_macro_storage(alfi_level* L, int dtype) {
-  alfi_ctx* ctx = L->ctx;
-  if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_set_macro_storage before alfi_patches_set");
-  if (dtype != ALFI_STORAGE_F64 && dtype != ALFI_STORAGE_F32)
-    return alfi_set_error(ctx, ALFI_E_ARG, "alfi_patches_set_macro_storage: dtype %d (0: FP64, 1: FP32)", dtype);
-  if (dtype == ALFI_STORAGE_F32) {
-    if (L->npatch == 0) return alfi_set_error(ctx, ALFI_E_ARG, "FP32 macro-star storage: the level has no patches");
-    if (L->lay.max_np <= 32)
-      return alfi_set_error(ctx, ALFI_E_ARG, "FP32 macro-star storage: every patch has <= 32 dofs and the level applies the "
-                                             "interleaved small-patch copy, which has no FP32 form");
-    if (L->cond && !L->cond_auto)
-      return alfi_set_error(ctx, ALFI_E_ARG, "FP32 macro-star storage: the level has caller-supplied groups; condensed factors "
-                                             "cancel in single precision and stay FP64 (alfi_patches_set_groups(NULL) first)");
-    if (L->mult) return alfi_set_error(ctx, ALFI_E_ARG, "FP32 macro-star storage: multiplicative sweeps read FP64 inverses");
-  }
-  L->f32_req = dtype == ALFI_STORAGE_F32;
-  if (L->f32_req) L->f32_macro = true;
-  return 0;
-}
+int alfi_patches_set_storage(alfi_level* L, int dtype) { return set_storage_request(L, dtype, false); }
+int alfi_patches_set_macro_storage(alfi_level* L, int dtype) { return set_storage_request(L, dtype, true); }
 
 int alfi_ctx_set_f32_work_bytes(alfi_ctx* ctx, int64_t bytes) {
   if (bytes <= 0) return alfi_set_error(ctx, ALFI_E_ARG, "alfi_ctx_set_f32_work_bytes: %lld bytes", (long long)bytes);
@@ -173,12 +170,12 @@ int alfi_patches_set_canonical_order(alfi_level* L, const int32_t* rank) {
   dev_free(L->canon_rank);
   L->canon_rank = nullptr;
   if (rank) ALFI_CHECK(dev_upload(ctx, &L->canon_rank, rank, L->lay.sum_n));
-  if (L->f32_req || L->f32) L->factored = false;   // the stored inverses belong to the old order
+  if (is_or_will_be_f32(L)) L->factored = false;   // the stored inverses belong to the old order
   return 0;
 }
 
 int alfi_patches_storage(alfi_level* L, int* dtype) {
-  if (dtype) *dtype = L->f32 ? ALFI_STORAGE_F32 : ALFI_STORAGE_F64;
+  if (dtype) *dtype = L->held == HELD_F32 ? ALFI_STORAGE_F32 : ALFI_STORAGE_F64;
   return 0;
 }
 
@@ -232,14 +229,9 @@ static int set_groups_impl(alfi_level* L, const int32_t* group, const std::vecto
   ALFI_CHECK(dev_alloc(ctx, &cd.sinv, pl.sinv_doubles));
   L->cond_allocs.push_back(cd.sinv);
   // the dense inverses are not needed any more
-  if (!L->inv_shrunk) {
-    dev_free(L->inv);
-    L->inv = nullptr;
-    ALFI_CHECK(dev_alloc(ctx, &L->inv, 16));
-    L->inv_shrunk = true;
-  }
+  if (L->held == HELD_F64) ALFI_CHECK(inv_to_placeholder(L));
   L->cd = cd;
-  L->cond = true;
+  set_held(L, HELD_COND);
   L->il_valid = false;
   pl.release_tables();                                   // the host keeps sptr, gptr, chptr, gcptr and the limits
   L->cplan = std::move(pl);
@@ -247,13 +239,12 @@ static int set_groups_impl(alfi_level* L, const int32_t* group, const std::vecto
 }
 
 int alfi_patches_set_groups(alfi_level* L, const int32_t* group) {
-  if (group && (L->f32_req || L->f32))
+  if (group && is_or_will_be_f32(L))
     return alfi_set_error(L->ctx, ALFI_E_STATE, "alfi_patches_set_groups on a level with FP32 patch storage: condensed factors "
                                                 "stay FP64 (alfi_patches_set_storage(lvl, 0) first)");
   const int rc = set_groups_impl(L, group);
   // the caller has decided for this patch set, NULL (dense inverses) included: no search for groups at the factorisation
-  L->cond_auto = false;
-  L->cond_decided = rc == 0;
+  L->cond_by = rc != 0 ? COND_UNDECIDED : group ? COND_BY_CALLER : COND_DENSE;
   return rc;
 }
 
@@ -285,14 +276,14 @@ int alfi_ctx_set_condense_min_bytes(alfi_ctx* ctx, int64_t min_bytes) {
 }
 
 int alfi_patches_condensed(alfi_level* L, int* mode) {
-  if (mode) *mode = !L->cond ? 0 : (L->cond_auto ? 2 : 1);
+  if (mode) *mode = !L->cond ? 0 : (cond_by_own_choice(L) ? 2 : 1);
   return 0;
 }
 
 int alfi_patches_factor_bytes(alfi_level* L, int64_t* bytes) {
-  if (L->f32) {
+  if (L->held == HELD_F32) {
     *bytes = 4 * L->inv32_floats;
-  } else if (L->f32_req) {                            // not factored yet: what the factorisation will store
+  } else if (wants_f32(L)) {                          // not factored yet: what the factorisation will store
     std::vector<int64_t> ptr;
     *bytes = 4 * plan_f32_offsets(L->npatch, L->lay.patch_ptr.data(), &ptr);
   } else {
@@ -302,17 +293,17 @@ int alfi_patches_factor_bytes(alfi_level* L, int64_t* bytes) {
 }
 
 // A level that condensed itself (or has not decided yet) and now gets something the condensed factors do not support --
-// multiplicative sweeps, PCPATCH's facet rule -- goes back to dense inverses for good.  The condensed storage is released here
-// (the two are never held together); returns whether the level was factored: the caller factors it again.
+// multiplicative sweeps, PCPATCH's facet rule, FP32 storage -- goes back to dense inverses for good.  The condensed storage is
+// released here (the two are never held together); returns whether the level was factored: the caller factors it again.
+// (Groups of the caller's are the caller's to withdraw: such a level stays as it is.)
 bool auto_cond_to_dense(alfi_level* L) {
   bool refactor = false;
-  if (L->cond && L->cond_auto) {
+  if (cond_by_own_choice(L)) {
     refactor = L->factored;
     free_cond(L);
-    L->cond_auto = false;
     L->factored = false;
   }
-  L->cond_decided = true;
+  if (L->cond_by != COND_BY_CALLER) L->cond_by = COND_DENSE;
   return refactor;
 }
 
@@ -339,10 +330,10 @@ int alfi_patches_set_multiplicative(alfi_level* L, int64_t nit, const int64_t* i
   if (ctx->dev_err) ALFI_HIP_CHECK(ctx, hipMemset(ctx->dev_err, 0, 16));
   if (nit == 0) return 0;
   if (nit < 0 || !iterset) return alfi_set_error(ctx, ALFI_E_ARG, "bad iteration set");
-  if (L->f32_req || L->f32)
+  if (is_or_will_be_f32(L))
     return alfi_set_error(ctx, ALFI_E_STATE, "multiplicative sweeps on a level with FP32 patch storage: the sweeps read FP64 "
                                              "inverses (alfi_patches_set_storage(lvl, 0) first)");
-  if (L->cond && !L->cond_auto)
+  if (cond_by_caller(L))
     return alfi_set_error(ctx, ALFI_E_STATE, "multiplicative sweeps need dense patch inverses (alfi_patches_set_groups(NULL))");
   // (groups the library found itself are its own business: the sweeps read dense inverses, so such a level goes back to them
   // below, once the arguments have been checked, and is factored again at the end)
@@ -397,65 +388,52 @@ int alfi_patches_multiplicative_levels(alfi_level* L, int64_t* nwave) {
   return 0;
 }
 
-int alfi_patches_factor(alfi_level* L) {
+// ---- the factorisation: decide (condensation, storage), prepare the storage, one pass per range of patches -----------------------
+
+// Who decides about condensation, if nobody has for this patch set.
+static int decide_condensation(alfi_level* L) {
   alfi_ctx* ctx = L->ctx;
-  if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_factor before alfi_patches_set");
-  if (L->f32_req) {
-    // an FP32 level does not condense, whatever its dense bytes and the threshold: it counts as decided (groups the library
-    // found at an earlier FP64 factorisation go)
-    if (L->cond && L->cond_auto) {
-      free_cond(L);
-      L->cond_auto = false;
-    }
-    L->cond_decided = true;
+  // an FP32 level does not condense, whatever its dense bytes and the threshold: it counts as decided (groups the library found
+  // at an earlier FP64 factorisation go)
+  if (wants_f32(L)) (void)auto_cond_to_dense(L);
+  if (L->cond_by != COND_UNDECIDED) return 0;
+  // first factorisation of a patch set the caller gave no groups for: an additive level whose dense inverses would take
+  // condense_min_bytes or more looks for groups in its own sparsity (find_groups.h) and stores condensed factors if it finds
+  // any.  On a partitioned level all of this is the rank's own business: its patches (ghost dofs included: the local operator
+  // holds their rows over the local columns), its sparsity, its inverse bytes against the threshold -- no collective, and
+  // ranks of one level may decide differently (the block factorisation is exact for any valid grouping).
+  L->cond_by = COND_DENSE;
+  const int64_t thr = ctx->condense_min_bytes;
+  // (never a Burman level: its sparsity couples cells across facets, alfi_level_set_facet_blocks, and PCPATCH's facet rule,
+  // alfi_patches_set_facet_correction, changes the patch matrices)
+  const bool facets = L->facet_blocks || L->fc_ptr;
+  if (thr < 0 || L->mult || facets || L->npatch == 0 || 8 * L->lay.inv_doubles < thr) return 0;
+  std::vector<int32_t> group((size_t)L->lay.sum_n), rowptr, colidx;
+  int64_t grouped = 0;
+  ALFI_CHECK(find_groups(L, group.data(), &grouped, &rowptr, &colidx));
+  if (grouped == 0) return 0;
+  // (the finder keeps to the limits of the format; a failure here is an error like any other, and leaves no condensed storage)
+  const std::vector<int32_t>* sparsity[2] = {&rowptr, &colidx};
+  const int rc = set_groups_impl(L, group.data(), sparsity);
+  if (rc != 0) {
+    free_cond(L);
+    return rc;
   }
-  if (!L->cond_decided) {
-    // first factorisation of a patch set the caller gave no groups for: an additive level whose dense inverses would take
-    // condense_min_bytes or more looks for groups in its own sparsity (find_groups.h) and stores condensed factors if it finds
-    // any.  On a partitioned level all of this is the rank's own business: its patches (ghost dofs included: the local operator
-    // holds their rows over the local columns), its sparsity, its inverse bytes against the threshold -- no collective, and
-    // ranks of one level may decide differently (the block factorisation is exact for any valid grouping).
-    L->cond_decided = true;
-    const int64_t thr = ctx->condense_min_bytes;
-    // (never a Burman level: its sparsity couples cells across facets, alfi_level_set_facet_blocks, and PCPATCH's facet rule,
-    // alfi_patches_set_facet_correction, changes the patch matrices)
-    const bool facets = L->facet_blocks || L->fc_ptr;
-    if (thr >= 0 && !L->cond && !L->mult && !facets && L->npatch > 0 && 8 * L->lay.inv_doubles >= thr) {
-      std::vector<int32_t> group((size_t)L->lay.sum_n), rowptr, colidx;
-      int64_t grouped = 0;
-      ALFI_CHECK(find_groups(L, group.data(), &grouped, &rowptr, &colidx));
-      if (grouped > 0) {
-        // (the finder keeps to the limits of the format; a failure here is an error like any other)
-        const std::vector<int32_t>* sparsity[2] = {&rowptr, &colidx};
-        const int rc = set_groups_impl(L, group.data(), sparsity);
-        if (rc != 0) {
-          free_cond(L);
-          return rc;
-        }
-        L->cond_auto = true;
-      }
-    }
-  }
-  ProfScope prof(ctx, ALFI_EV_PATCH_FACTOR);
-  ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->status, 0, sizeof(int), ctx->stream));
-  // FP32 storage: the factorisation below -- gather, Gauss-Jordan, probe, repair -- runs unchanged on the ctx's FP64 work buffer
-  // (L->inv points there until this function returns); the level keeps the single-precision copy made at the end
-  struct InvGuard {
-    alfi_level* L;
-    double* keep;
-    ~InvGuard() { if (keep) L->inv = keep; }
-  } guard{L, nullptr};
-  std::vector<int64_t> ranges;                     // FP32 storage of big patches: the boundaries of the ranges it is factored in
-  if (L->f32_req) {
+  L->cond_by = COND_BY_LIBRARY;
+  return 0;
+}
+
+// The storage the factorisation writes to, and the ranges of patches it runs in: one, [0, npatch), except for an FP32 level of
+// big patches.  An FP32 level is factored -- gather, Gauss-Jordan, probe, repair, all unchanged -- in the ctx's FP64 work buffer
+// and keeps the single-precision copy made from it; small patches need the whole level there, big patches pass through range by
+// range (plan_f32_ranges, alfi_ctx_set_f32_work_bytes).
+static int prepare_factor_storage(alfi_level* L, PatchStoreHeld target, std::vector<int64_t>* ranges) {
+  alfi_ctx* ctx = L->ctx;
+  ranges->assign({0, L->npatch});
+  if (target == HELD_F32) {
     ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    L->factored = false;                           // from here to the end of this call the level holds nothing an apply may read
-    if (!L->inv_shrunk) {                          // FP64 inverses of an earlier factorisation
-      dev_free(L->inv);
-      L->inv = nullptr;
-      ALFI_CHECK(dev_alloc(ctx, &L->inv, 16));
-      L->inv_shrunk = true;
-    }
-    L->f32 = false;                                // until the copy is written the FP64 kernels apply (the probe)
+    L->factored = false;                           // from here to the end of the factorisation the level holds nothing an apply may read
+    if (L->held == HELD_F64) ALFI_CHECK(inv_to_placeholder(L));   // FP64 inverses of an earlier factorisation
     if (!L->inv32) {
       L->inv32_floats = plan_f32_offsets(L->npatch, L->lay.patch_ptr.data(), &L->f32_ptr);
       ALFI_CHECK(dev_upload(ctx, &L->inv32_ptr, L->f32_ptr.data(), L->npatch + 1));
@@ -463,22 +441,9 @@ int alfi_patches_factor(alfi_level* L) {
       ++ctx->f32_levels;
       ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->inv32, 0, sizeof(float) * (size_t)std::max<int64_t>(L->inv32_floats, 1), ctx->stream));
     }
-    // big patches pass through the work buffer range by range: the longest runs of consecutive patches whose FP64 row pieces
-    // fit alfi_ctx_set_f32_work_bytes (one patch above it is a range of its own); the rest needs the whole level there
     int64_t work = L->lay.inv_doubles;
-    if (L->lay.max_np > SMALL_PATCH_MAX) {
-      const int64_t cap = std::max<int64_t>(ctx->f32_work_cap / 8, 1);
-      const std::vector<int64_t>& ip = L->lay.inv_ptr;
-      ranges.push_back(0);
-      work = 0;
-      for (int64_t p0 = 0; p0 < L->npatch;) {
-        int64_t p1 = p0 + 1;
-        while (p1 < L->npatch && ip[(size_t)p1 + 1] - ip[(size_t)p0] <= cap) ++p1;
-        work = std::max(work, ip[(size_t)p1] - ip[(size_t)p0]);
-        ranges.push_back(p1);
-        p0 = p1;
-      }
-    }
+    if (L->lay.max_np > SMALL_PATCH_MAX)
+      work = plan_f32_ranges(L->npatch, L->lay.inv_ptr.data(), std::max<int64_t>(ctx->f32_work_cap / 8, 1), ranges);
     if (ctx->f32_work_doubles < work) {
       dev_free(ctx->f32_work);
       ctx->f32_work = nullptr;
@@ -486,77 +451,95 @@ int alfi_patches_factor(alfi_level* L) {
       ALFI_CHECK(dev_alloc(ctx, &ctx->f32_work, work));
       ctx->f32_work_doubles = work;
     }
-    guard.keep = L->inv;
-    L->inv = ctx->f32_work;
-  } else if (L->inv32) {                           // back to FP64
+    return 0;
+  }
+  if (L->inv32) {                                  // back to FP64
     ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     L->factored = false;
     free_f32(L);
   }
-  if (!L->cond && L->inv_shrunk && !L->f32_req) {  // first dense factorisation of this patch set
+  if (target == HELD_F64 && L->held != HELD_F64) { // first dense factorisation of this patch set
     ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     dev_free(L->inv);
     L->inv = nullptr;
     ALFI_CHECK(dev_alloc(ctx, &L->inv, L->lay.inv_doubles));
-    L->inv_shrunk = false;
+    set_held(L, HELD_F64);
   }
-  if (L->cond && L->fc_ptr && L->fc_scale != 0.0)
-    return alfi_set_error(ctx, ALFI_E_STATE, "condensed patch factors on a Burman level (the facet rule couples macro interiors)");
-  if (!ranges.empty()) {
-    // Range by range: blocked inversion (facet rule and polish as for an FP64 level), probe, pivoted repair and second probe
-    // with the FP64 kernels on the work buffer, then the rounding into the level's copy.  The kernels address patch p at
-    // inv + inv_ptr[p]: the work buffer is handed to them biased by the range's first offset (only the range's patches are
-    // touched).  A patch's elimination reads its own scratch only, so what is stored does not depend on the ranges.
-    double* probe_vec = nullptr;
-    ALFI_CHECK(patch_probe_vector(L, &probe_vec));
-    PatchCheckAcc acc;
-    int rc = 0;
-    for (size_t r = 0; r + 1 < ranges.size() && rc == 0; ++r) {
-      const int64_t p0 = ranges[r], p1 = ranges[r + 1];
-      L->inv = ctx->f32_work - L->lay.inv_ptr[(size_t)p0];
-      rc = launch_big_factor_range(L, p0, p1);
-      int st = 0;
-      if (rc == 0 && hipMemcpy(&st, L->status, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = alfi_set_error(ctx, ALFI_E_HIP, "reading the factorisation status failed");
-      if (rc == 0) rc = patch_verify_and_repair_range(L, st, p0, p1, probe_vec, &acc);
-      if (rc == 0) rc = launch_patch_f32_convert_range(L, L->inv, p0, p1);
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(probe_vec);
-    prof.close();
-    patch_check_finish(L, acc);
-    ALFI_CHECK(rc);
-    L->f32 = true;
-    L->factored = true;
-    return 0;
-  }
-  if (L->cond) {
-    ALFI_CHECK(launch_cond_factor(L));            // condensed factors: group inverses + Schur complements
-  } else if (L->lay.max_np > SMALL_PATCH_MAX) {
-    ALFI_CHECK(launch_big_factor(L));             // macro-star sized patches: blocked Gauss-Jordan on the matrix cores
+  return 0;
+}
+
+// Where the kernels of the pass that starts at patch p0 find the dense FP64 inverses they work on: they address patch p at
+// base + inv_ptr[p].  An FP64 level is factored in place.  An FP32 level is factored in the ctx's work buffer, which holds the
+// range's patches from its own start: the base is the buffer's address less the range's first offset, so that
+// base + inv_ptr[p0] is the buffer and only the range's patches are touched.  (For p0 > 0 that address lies before the buffer;
+// it is formed in integers and never dereferenced.)
+static double* range_base(const alfi_level* L, PatchStoreHeld target, int64_t p0) {
+  if (target != HELD_F32) return L->inv;
+  return reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(L->ctx->f32_work) -
+                                   sizeof(double) * (uintptr_t)L->lay.inv_ptr[(size_t)p0]);
+}
+
+// The factor kernels of one pass: the patches [p0, p1), inverses to inv + inv_ptr[p] (condensed factors and dense levels of small
+// patches: the whole level).
+static int launch_factor_range(alfi_level* L, PatchStoreHeld target, double* inv, int64_t p0, int64_t p1) {
+  if (target == HELD_COND) return launch_cond_factor(L);      // group inverses + Schur complements
+  if (L->lay.max_np > SMALL_PATCH_MAX) {
+    // macro-star sized patches: blocked Gauss-Jordan on the matrix cores (facet rule and polish inside).  A patch's elimination
+    // reads its own scratch only, so what is stored does not depend on the ranges.
+    ALFI_CHECK(launch_big_factor_range(L, inv, p0, p1));
   } else {
     // (an FP32 level with a canonical order eliminates in that order and turns the inverses back: the rest sees patch_dofs' order)
-    const bool ranked = L->f32_req && L->canon_rank;
-    ALFI_CHECK(launch_patch_gather_dense(L, ranked));
-    if (L->fc_ptr && L->fc_scale != 0.0) ALFI_CHECK(launch_patch_facet_correct(L, 0, L->npatch, L->inv_ptr, L->inv, 0));
-    ALFI_CHECK(launch_patch_invert(L));
-    if (ranked) ALFI_CHECK(launch_patch_unrank(L));
+    const bool ranked = target == HELD_F32 && L->canon_rank;
+    ALFI_CHECK(launch_patch_gather_dense(L, inv, ranked));
+    if (facet_rule_active(L)) ALFI_CHECK(launch_patch_facet_correct(L, 0, L->npatch, L->inv_ptr, inv, 0));
+    ALFI_CHECK(launch_patch_invert(L, inv));
+    if (ranked) ALFI_CHECK(launch_patch_unrank(L, inv));
   }
-  ALFI_CHECK(build_patch_il(L));                  // small-patch levels: the wave-contiguous copy the apply streams
-  prof.close();
-  int st = 0;
-  ALFI_HIP_CHECK(ctx, hipMemcpyAsync(&st, L->status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  // every stored inverse is probed (|| A_p X_p e - e ||); the ones that fail -- an unpivoted elimination met a zero or
-  // tiny pivot -- are re-inverted with partial pivoting, as the reference's LAPACK / UMFPACK factorisations would
-  ALFI_CHECK(patch_verify_and_repair(L, st));
-  if (L->f32_req) {                                // the probed (and repaired) FP64 inverses, rounded to nearest
-    ALFI_CHECK(launch_patch_f32_convert(L, L->inv));
-    L->f32 = true;
+  return build_patch_il(L, inv);                  // small-patch levels: the wave-contiguous copy the apply streams
+}
+
+int alfi_patches_factor(alfi_level* L) {
+  alfi_ctx* ctx = L->ctx;
+  if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_factor before alfi_patches_set");
+  ALFI_CHECK(decide_condensation(L));
+  const PatchStoreHeld target = L->cond ? HELD_COND : wants_f32(L) ? HELD_F32 : HELD_F64;
+  std::optional<ProfScope> prof;                   // the factor kernels of every pass (the first one: with the storage's allocation)
+  prof.emplace(ctx, ALFI_EV_PATCH_FACTOR);
+  ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->status, 0, sizeof(int), ctx->stream));
+  std::vector<int64_t> ranges;
+  ALFI_CHECK(prepare_factor_storage(L, target, &ranges));
+  if (target == HELD_COND && facet_rule_active(L))
+    return alfi_set_error(ctx, ALFI_E_STATE, "condensed patch factors on a Burman level (the facet rule couples macro interiors)");
+  // Every pass: the factor kernels, their status, then -- with the FP64 kernels on the FP64 inverses, whatever the level will
+  // store -- the probe of every inverse (|| A_p X_p e - e ||), the pivoted re-inversion of the ones that fail (an unpivoted
+  // elimination met a zero or tiny pivot; the reference's LAPACK / UMFPACK factorisations pivot) and the second probe; for an
+  // FP32 level the rounding of the probed (and repaired) inverses into its copy.
+  double* probe_vec = nullptr;                     // one per factorisation, made when the first pass has its inverses
+  PatchCheckAcc acc;
+  int rc = 0;
+  for (size_t r = 0; r + 1 < ranges.size() && rc == 0; ++r) {
+    const int64_t p0 = ranges[r], p1 = ranges[r + 1];
+    double* inv = range_base(L, target, p0);
+    if (!prof) prof.emplace(ctx, ALFI_EV_PATCH_FACTOR);
+    rc = launch_factor_range(L, target, inv, p0, p1);
+    prof.reset();
+    int st = 0;
+    if (rc == 0 && (hipMemcpyAsync(&st, L->status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                    hipStreamSynchronize(ctx->stream) != hipSuccess))
+      rc = alfi_set_error(ctx, ALFI_E_HIP, "reading the factorisation status failed");
+    if (rc == 0 && !probe_vec) rc = patch_probe_vector(L, &probe_vec);
+    if (rc == 0) rc = patch_verify_and_repair_range(L, inv, st, p0, p1, probe_vec, &acc);
+    if (rc == 0 && target == HELD_F32) rc = launch_patch_f32_convert_range(L, inv, p0, p1);
   }
+  (void)hipStreamSynchronize(ctx->stream);
+  (void)hipFree(probe_vec);
+  patch_check_finish(L, acc);
+  ALFI_CHECK(rc);
+  set_held(L, target);                             // what was factored is what the level holds, and may be applied, from here on
   L->factored = true;
   return 0;
 }
+
 
 int alfi_patches_check(alfi_level* L, double* worst_residual, int64_t* flagged, int64_t* repaired, double* worst_after) {
   if (!L->factored) return alfi_set_error(L->ctx, ALFI_E_STATE, "alfi_patches_check before alfi_patches_factor");
@@ -676,7 +659,7 @@ int alfi_patch_get_inverse(alfi_level* L, int64_t p, double* out) {
   if (p < 0 || p >= L->npatch) return alfi_set_error(ctx, ALFI_E_ARG, "patch index out of range");
   if (L->cond) return cond_get_inverse(L, p, out);
   const int64_t n = L->lay.patch_ptr[p + 1] - L->lay.patch_ptr[p];
-  if (L->f32) {                                    // the stored floats, widened
+  if (L->held == HELD_F32) {                       // the stored floats, widened
     std::vector<float> tmp32((size_t)(n * f32_ld((int)n)));
     ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     ALFI_HIP_CHECK(ctx, hipMemcpy(tmp32.data(), L->inv32 + L->f32_ptr[(size_t)p], tmp32.size() * sizeof(float), hipMemcpyDeviceToHost));

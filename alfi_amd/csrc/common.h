@@ -331,6 +331,20 @@ struct AssemblyDev {
   uint16_t* fna = nullptr;
 };
 
+// ---- the state of a level's patch factors --------------------------------------------------------------------------------------
+// What the next alfi_patches_factor is asked to store.  "Macro" belongs to the request (alfi_patches_set_macro_storage: patches
+// above 160 dofs and a facet correction are accepted) and lives and dies with it.
+enum PatchStoreRequest { STORE_REQ_F64 = 0, STORE_REQ_F32_STAR, STORE_REQ_F32_MACRO };
+// What the level holds.  HELD_NONE: `inv` is the 16-double placeholder (a kernel argument and part of the graph signature, so
+// never NULL once the patches are set) and nothing else; HELD_F64: `inv` is the lay.inv_doubles dense inverses; HELD_F32: inv32
+// (and the placeholder); HELD_COND: the condensed factors of `cd` (and the placeholder).  Whether the contents are those of the
+// current operator is `factored`.
+enum PatchStoreHeld { HELD_NONE = 0, HELD_F64, HELD_F32, HELD_COND };
+// Who decided about condensation for this patch set: nobody yet (the first FP64 factorisation will), dense for good (the
+// caller's alfi_patches_set_groups(NULL), a search without result, or something condensed factors do not support), the caller's
+// groups, the groups the library found itself.
+enum CondDecision { COND_UNDECIDED = 0, COND_DENSE, COND_BY_CALLER, COND_BY_LIBRARY };
+
 struct alfi_level {
   alfi_ctx* ctx = nullptr;
   AssemblyDev asmb;
@@ -413,19 +427,17 @@ struct alfi_level {
   int chk_cap = 0;
   double chk_worst = -1.0, chk_worst_after = -1.0;   // of the last factorisation: before / after the repair (-1: not run)
   int64_t chk_flagged = 0, chk_repaired = 0;
+  // what the level's patch factors are: the three enums above (api_internal.h has the questions the code asks of them)
+  PatchStoreRequest store_req = STORE_REQ_F64;
+  PatchStoreHeld held = HELD_NONE;
+  CondDecision cond_by = COND_UNDECIDED;
   // condensed patch factors (alfi_patches_set_groups)
-  bool cond = false;
-  bool inv_shrunk = false;               // the dense inverse storage was released in favour of the condensed factors
-  bool cond_auto = false;                // the groups are the library's own (alfi_patches_find_groups at the first factorisation)
-  bool cond_decided = false;             // this patch set has had its decision: groups of the caller, found ones, or dense
+  bool cond = false;                     // held == HELD_COND: written by set_held (api_internal.h) only, with `held`
   CondDev cd;
   std::vector<void*> cond_allocs;        // every device array cd points to
   CondPlan cplan;                        // host side of the plan cd was uploaded from (patch_plan.h): sptr, gptr, chptr, gcptr, limits
-  // single-precision storage of the dense inverses (alfi_patches_set_storage; layout: patch_plan.h, f32_inv_index)
-  bool f32_req = false;                  // what the next alfi_patches_factor stores
-  bool f32 = false;                      // what the level holds: inv32 is what the additive apply streams, inv is a placeholder
-  bool f32_macro = false;                // the FP32 request came through alfi_patches_set_macro_storage: patches above 160 dofs and
-                                         // a facet correction are accepted (cleared with the single-precision copy)
+  // single-precision storage of the dense inverses (alfi_patches_set_storage; layout: patch_plan.h, f32_inv_index): with
+  // held == HELD_F32, inv32 is what the additive apply streams and inv is the placeholder
   float* inv32 = nullptr;
   int64_t* inv32_ptr = nullptr;          // (npatch+1) offsets (floats) into inv32
   std::vector<int64_t> f32_ptr;          // the same on the host
@@ -559,22 +571,24 @@ int launch_bsr_spmv(alfi_ctx* ctx, const DevBSR& A, const double* x, double* y, 
 // host (nnzb, bs, bs) values -> d->vals in d's layout (staged through a bounded device buffer)
 int upload_bsr_values(alfi_ctx* ctx, DevBSR* d, const double* host_vals);
 int build_spmv_dedup(alfi_ctx* ctx, DevBSR* d);     // column de-duplication tables of the flat product (kernels_vec.hip)
+// The dense factor pipeline (alfi_patches_factor).  Every launcher takes `inv`, the base of the dense FP64 inverses it works on:
+// patch p at inv + inv_ptr[p].  That is lvl->inv for an FP64 level and the ctx's work buffer, biased by the range's first offset,
+// for an FP32 level (api_patches.hip: range_base).
 // A_p into the row-major scratch of the inversion; ranked (FP32 levels with a canonical order): row / column a of a patch at
 // position canon_rank[a]
-int launch_patch_gather_dense(alfi_level* lvl, bool ranked = false);
-int launch_patch_invert(alfi_level* lvl);
-// kernels_check.hip: probe || A_p X_p e - e || of every stored inverse, pivoted re-inversion of the patches that fail
-int patch_verify_and_repair(alfi_level* lvl, int unpivoted_status);
-// the same for the patches [p0, p1) of a level that is factored range by range (FP32 storage of big patches): probe_vec is the
-// level's +-1 vector (patch_probe_vector, made once per factorisation); the figures accumulate in *acc, which
-// patch_check_finish turns into what alfi_patches_check reports -- the figures of one probe of the whole level
+int launch_patch_gather_dense(alfi_level* lvl, double* inv, bool ranked);
+int launch_patch_invert(alfi_level* lvl, double* inv);
+// kernels_check.hip: probe || A_p X_p e - e || of the inverses of the patches [p0, p1) (condensed levels: the factors of the
+// whole level), pivoted re-inversion of the patches that fail, second probe.  unpivoted_status: the zero-pivot flag of the fast
+// inversion; probe_vec: the level's +-1 vector (patch_probe_vector, made once per factorisation); the figures accumulate in
+// *acc, which patch_check_finish turns into what alfi_patches_check reports -- the figures of one probe of the whole level
 struct PatchCheckAcc {
   double worst = -1.0, worst_after = -1.0;
   int64_t flagged = 0, repaired = 0;
 };
 int patch_probe_vector(alfi_level* lvl, double** probe_vec);
-int patch_verify_and_repair_range(alfi_level* lvl, int unpivoted_status, int64_t p0, int64_t p1, const double* probe_vec,
-                                  PatchCheckAcc* acc);
+int patch_verify_and_repair_range(alfi_level* lvl, double* inv, int unpivoted_status, int64_t p0, int64_t p1,
+                                  const double* probe_vec, PatchCheckAcc* acc);
 int patch_check_finish(alfi_level* lvl, const PatchCheckAcc& acc);
 int launch_patch_invert_arrays(alfi_ctx* ctx, int64_t npatch, int max_np, const int64_t* patch_ptr,
                                const int64_t* inv_ptr, double* inv, int* status);
@@ -583,7 +597,10 @@ int launch_patch_apply_arrays(alfi_ctx* ctx, int64_t npatch, const int64_t* patc
                               double* stage);
 int launch_patch_apply(alfi_level* lvl, const double* x, double* y);          // both stages, all patches
 int launch_patch_apply_range(alfi_level* lvl, int64_t p0, int64_t p1, const double* x);   // stage 1, patches [p0, p1)
-int launch_big_apply_range(alfi_level* lvl, int64_t p0, int64_t p1, const double* x);     // the same for levels with n_p > 160
+// its dense FP64 branch on the inverses at inv (lvl->inv; the factor pipeline's probe: the inverses it is working on)
+int launch_patch_apply_f64_range(alfi_level* lvl, const double* inv, int64_t p0, int64_t p1, const double* x);
+// the same for levels with n_p > 160
+int launch_big_apply_range(alfi_level* lvl, const double* inv, int64_t p0, int64_t p1, const double* x);
 int launch_big_factor_transfer(alfi_transfer* tr);                                            // dense nu K + gamma D blocks, m > 160
 int launch_big_apply_arrays(alfi_ctx* ctx, int64_t npatch, int max_np, const int64_t* patch_ptr,
                             const int32_t* patch_dofs, const int64_t* inv_ptr, const int64_t* stage_ptr, const double* inv,
@@ -597,18 +614,18 @@ int mf_solve_slot(alfi_level* lvl, const struct MfDev* m, const double* b, doubl
 void mf_free(struct MfDev* m);
 int64_t mf_bytes(const struct MfDev* m);
 int launch_coarse_factor(alfi_level* lvl, double* out);                                   // dense inverse of the whole level operator
-int launch_big_factor(alfi_level* lvl);
-int launch_big_factor_range(alfi_level* lvl, int64_t p0, int64_t p1);      // the patches [p0, p1) only
+int launch_big_factor_range(alfi_level* lvl, double* inv, int64_t p0, int64_t p1);   // gather + blocked MFMA inversion, patches [p0, p1)
 int launch_big_apply_f32_range(alfi_level* lvl, int64_t p0, int64_t p1, const double* x);   // FP32 levels with n_p > 160
 // condensed patches (kernels_bigpatch.hip): block factorisation / its apply for the patches [p0, p1)
 int launch_cond_factor(alfi_level* lvl);
 int launch_cond_apply_range(alfi_level* lvl, int64_t p0, int64_t p1, const double* x);
-int launch_cond_schur_one(alfi_level* lvl, int64_t p, const int64_t* d_zero, double* scr);   // repair path (kernels_check.hip)                                                    // gather + blocked MFMA inversion
-// FP32 levels: inv32 <- the FP64 inverses at src (row-piece layout, offsets lvl->inv_ptr), rounded to nearest, pad rows zero
-int launch_patch_f32_convert(alfi_level* lvl, const double* src);
+int launch_cond_schur_one(alfi_level* lvl, int64_t p, const int64_t* d_zero, double* scr);   // repair path (kernels_check.hip)
+// FP32 levels: inv32 <- the FP64 inverses at src (row-piece layout, offsets lvl->inv_ptr) of the patches [p0, p1), rounded to
+// nearest, pad rows zero
 int launch_patch_f32_convert_range(alfi_level* lvl, const double* src, int64_t p0, int64_t p1);
-int launch_patch_unrank(alfi_level* lvl);          // a ranked gather's inverses back into the order of patch_dofs
-int build_patch_il(alfi_level* lvl);   // small-patch levels: (re)build the interleaved copy of the inverses from lvl->inv
+int launch_patch_unrank(alfi_level* lvl, double* inv);   // a ranked gather's inverses back into the order of patch_dofs
+// small-patch levels (every n_p <= 32): (re)build the interleaved copy of the dense inverses at inv; other sizes: no copy
+int build_patch_il(alfi_level* lvl, const double* inv);
 int launch_patch_sum(alfi_level* lvl, const double* x, double* y);             // stage 2
 int launch_patch_sum_range(alfi_level* lvl, int64_t i0, int64_t i1, const double* x, double* y);   // stage 2, dofs [i0, i1)
 // one dependency wavefront of a multiplicative sweep: patches seq[0..count): y_p += inv(A_p) (x - A y)_p

@@ -785,7 +785,7 @@ struct alfi_host_plan {
   PatchLayout lay;
   CondPlan cond;
   SweepPlan sweep;
-  std::vector<int64_t> f32_ptr;
+  std::vector<int64_t> f32_ptr, ranges;
   int rc = 0;
   std::string err;
   struct Entry {
@@ -803,6 +803,23 @@ struct alfi_host_plan {
 #define ALFI_PLAN_TABLE(s, f) h->table(#f, h->s.f)
 #define ALFI_PLAN_SCALAR(s, f) h->scalar(#f, (int64_t)h->s.f)
 
+// alfi_host_plan_f32_layout and alfi_host_plan_macro_f32_layout: patches of up to max_np dofs
+static alfi_host_plan* plan_f32_layout(int64_t npatch, const int64_t* patch_ptr, int max_np, const char* what) {
+  alfi_host_plan* h = new alfi_host_plan();
+  for (int64_t p = 0; p < npatch; ++p)
+    if (patch_ptr[p + 1] - patch_ptr[p] <= 0 || patch_ptr[p + 1] - patch_ptr[p] > max_np) {
+      h->rc = plan_fail(&h->err, "patch %lld has %lld dofs; %s holds patches of 1..%d", (long long)p,
+                        (long long)(patch_ptr[p + 1] - patch_ptr[p]), what, max_np);
+      return h;
+    }
+  const int64_t total = plan_f32_offsets(npatch, patch_ptr, &h->f32_ptr);
+  h->table("f32_ptr", h->f32_ptr);
+  h->scalar("inv32_floats", total);
+  h->scalar("rows_per_load", F32_ROWS);
+  h->scalar("align_floats", F32_ALIGN);
+  return h;
+}
+
 extern "C" {
 
 alfi_host_plan* alfi_host_plan_patch_layout(int64_t n, int64_t npatch, const int64_t* patch_ptr, const int32_t* patch_dofs) {
@@ -818,34 +835,19 @@ alfi_host_plan* alfi_host_plan_patch_layout(int64_t n, int64_t npatch, const int
 // the single-precision storage of a level's dense inverses (patch_plan.h): the offsets of the patches (floats, npatch + 1) and
 // the scalars of the layout
 alfi_host_plan* alfi_host_plan_f32_layout(int64_t npatch, const int64_t* patch_ptr) {
-  alfi_host_plan* h = new alfi_host_plan();
-  for (int64_t p = 0; p < npatch; ++p)
-    if (patch_ptr[p + 1] - patch_ptr[p] <= 0 || patch_ptr[p + 1] - patch_ptr[p] > SMALL_PATCH_MAX) {
-      h->rc = plan_fail(&h->err, "patch %lld has %lld dofs; FP32 storage holds patches of 1..%d", (long long)p,
-                        (long long)(patch_ptr[p + 1] - patch_ptr[p]), SMALL_PATCH_MAX);
-      return h;
-    }
-  const int64_t total = plan_f32_offsets(npatch, patch_ptr, &h->f32_ptr);
-  h->table("f32_ptr", h->f32_ptr);
-  h->scalar("inv32_floats", total);
-  h->scalar("rows_per_load", F32_ROWS);
-  h->scalar("align_floats", F32_ALIGN);
-  return h;
+  return plan_f32_layout(npatch, patch_ptr, SMALL_PATCH_MAX, "FP32 storage");
 }
 // the same for the levels of alfi_patches_set_macro_storage: patches of up to PATCH_MAX dofs
 alfi_host_plan* alfi_host_plan_macro_f32_layout(int64_t npatch, const int64_t* patch_ptr) {
+  return plan_f32_layout(npatch, patch_ptr, PATCH_MAX, "FP32 macro-star storage");
+}
+// the ranges an FP32 level of big patches is factored in (patch_plan.h: plan_f32_ranges): inv_ptr as plan_patch_layout returns
+// it, the cap in doubles
+alfi_host_plan* alfi_host_plan_f32_ranges(int64_t npatch, const int64_t* inv_ptr, int64_t cap_doubles) {
   alfi_host_plan* h = new alfi_host_plan();
-  for (int64_t p = 0; p < npatch; ++p)
-    if (patch_ptr[p + 1] - patch_ptr[p] <= 0 || patch_ptr[p + 1] - patch_ptr[p] > PATCH_MAX) {
-      h->rc = plan_fail(&h->err, "patch %lld has %lld dofs; FP32 macro-star storage holds patches of 1..%d", (long long)p,
-                        (long long)(patch_ptr[p + 1] - patch_ptr[p]), PATCH_MAX);
-      return h;
-    }
-  const int64_t total = plan_f32_offsets(npatch, patch_ptr, &h->f32_ptr);
-  h->table("f32_ptr", h->f32_ptr);
-  h->scalar("inv32_floats", total);
-  h->scalar("rows_per_load", F32_ROWS);
-  h->scalar("align_floats", F32_ALIGN);
+  const int64_t work = plan_f32_ranges(npatch, inv_ptr, cap_doubles, &h->ranges);
+  h->table("ranges", h->ranges);
+  h->scalar("work_doubles", work);
   return h;
 }
 // all offsets of an n x n inverse at once: out[r * n + c] = f32_inv_index(r, c, n), r < f32_ld(n) (big patches: 16 M entries)

@@ -687,8 +687,8 @@ static int launch_big_apply(alfi_ctx* ctx, int64_t p0, int64_t p1, int max_np, c
   return 0;
 }
 
-int launch_big_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double* x) {
-  return launch_big_apply(L->ctx, p0, p1, L->lay.max_np, L->patch_ptr, L->patch_dofs, L->inv_ptr, L->stage_ptr, L->inv, x, L->stage);
+int launch_big_apply_range(alfi_level* L, const double* inv, int64_t p0, int64_t p1, const double* x) {
+  return launch_big_apply(L->ctx, p0, p1, L->lay.max_np, L->patch_ptr, L->patch_dofs, L->inv_ptr, L->stage_ptr, inv, x, L->stage);
 }
 
 // FP32 levels with a patch above 160 dofs (alfi_patches_set_macro_storage): the same split, the single-precision copy
@@ -1015,30 +1015,6 @@ __global__ __launch_bounds__(256) void cond_schur_kernel(int64_t p0, CondDev cd,
 // (sum_g s_g), ys (s).  The small matrices are streamed with COND_U loads in flight per lane (they are read once).
 constexpr int COND_U = 8;
 
-// acc += sum_k M[k * ld + lane] * bcast_k, k < m, for the lanes < rows; bcast_k = lane k's value of `v`
-template <bool NT>
-__device__ __forceinline__ double cond_gemv_shfl(const double* __restrict__ M, int ld, int rows, int m, double v, int lane,
-                                                 double acc) {
-  const bool act = lane < rows;
-  int k = 0;
-  for (; k + COND_U <= m; k += COND_U) {
-    double a[COND_U];
-#pragma unroll
-    for (int u = 0; u < COND_U; ++u) {
-      const double* q = M + (int64_t)(k + u) * ld + lane;
-      a[u] = act ? (NT ? __builtin_nontemporal_load(q) : *q) : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < COND_U; ++u) acc = __builtin_fma(a[u], __shfl(v, k + u, 64), acc);
-  }
-  for (; k < m; ++k) {
-    const double* q = M + (int64_t)k * ld + lane;
-    const double a = act ? (NT ? __builtin_nontemporal_load(q) : *q) : 0.0;
-    acc = __builtin_fma(a, __shfl(v, k, 64), acc);
-  }
-  return acc;
-}
-
 // The apply as THREE launches (rounds 1-2: one launch per patch, a wave per group with a lane per row -- dropped).  Measured on config 5's
 // finest level (1765 macro stars, 4.85 GB of factors; kernel trace, same box): the one-launch kernel takes 949 us; its
 // group phases -- a wave per group, a lane per row, 8-byte loads, 30-95 % of the lanes without a row for groups of 3, 9 or
@@ -1253,8 +1229,8 @@ __global__ __launch_bounds__(64 * COND_WAVES) void cond_back_kernel(int64_t p0, 
   for (int i = threadIdx.x; i < s; i += NT_) out[cd.slot[off + nI + i]] = ys[i];
 }
 
-// ---- the group products by CHUNKS of groups (the default since the end of round 3; ALFI_COND_SPLIT=2 keeps the per-patch
-// front / back kernels above).  With a workgroup per patch the front and back launches on config 5's finest level spend their
+// ---- the group products by CHUNKS of groups (launch_cond_apply_range chooses by launch size: these kernels for launches of
+// fewer than 1024 patches, the per-patch front / back kernels above for larger ones).  With a workgroup per patch the front and back launches on config 5's finest level spend their
 // second half on the ~1000 small stars of the level -- short chains of dependent phases, 3 workgroups per CU because the LDS
 // is sized for the largest star -- at a third of the bandwidth of the first half.  Here the unit of work is a run of
 // consecutive groups of one patch holding at most 256 row pairs of X / W and of B (8 macro-cell groups of a [P3]^3 star):
@@ -1694,18 +1670,11 @@ static int big_factor_core(alfi_ctx* ctx, const BigSource& src, int64_t pfirst, 
   return 0;
 }
 
-int launch_big_factor(alfi_level* L) {
+// the patches [p0, p1) of a level (all of them, or one range of an FP32 level), inverses to inv + inv_ptr[p]
+int launch_big_factor_range(alfi_level* L, double* inv, int64_t p0, int64_t p1) {
   BigSource src;
   src.L = L;
-  return big_factor_core(L->ctx, src, 0, L->npatch, L->lay.patch_ptr.data(), L->patch_ptr, L->inv_ptr, L->inv, L->status);
-}
-
-// the patches [p0, p1) of a level that is factored range by range (FP32 storage: L->inv is the ctx's work area, biased so that
-// L->inv + inv_ptr[p0] is its start)
-int launch_big_factor_range(alfi_level* L, int64_t p0, int64_t p1) {
-  BigSource src;
-  src.L = L;
-  return big_factor_core(L->ctx, src, p0, p1, L->lay.patch_ptr.data(), L->patch_ptr, L->inv_ptr, L->inv, L->status);
+  return big_factor_core(L->ctx, src, p0, p1, L->lay.patch_ptr.data(), L->patch_ptr, L->inv_ptr, inv, L->status);
 }
 
 // interior blocks of a transfer with 160 < m <= 4096 (macro-cell blocks of the 3-D Scott-Vogelius transfer, m = 390 for P3)

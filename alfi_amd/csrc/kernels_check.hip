@@ -284,18 +284,13 @@ __global__ __launch_bounds__(256) void patch_repair_kernel(const int32_t* __rest
 
 }  // namespace
 
-// probe the patches [p0, p1): e = +-1 by dof (probe_vec, or made here), the level's stage-1 apply, residual per patch; results
-// accumulate in L->chk (device)
-static int launch_check(alfi_level* L, double tol, int64_t p0, int64_t p1, const double* probe_vec = nullptr) {
+// probe the patches [p0, p1): e = +-1 by dof (probe_vec), the stage-1 apply of the condensed factors the level holds or of the
+// dense FP64 inverses at inv, residual per patch; results accumulate in L->chk (device)
+static int launch_check(alfi_level* L, const double* inv, double tol, int64_t p0, int64_t p1, const double* probe_vec) {
   alfi_ctx* ctx = L->ctx;
   if (p1 <= p0) return 0;
   const bool fc = L->fc_ptr && L->fc_scale != 0.0;
-  double* own = nullptr;
-  if (!probe_vec) {
-    ALFI_CHECK(patch_probe_vector(L, &own));
-    probe_vec = own;
-  }
-  int rc = launch_patch_apply_range(L, p0, p1, probe_vec);
+  int rc = L->cond ? launch_patch_apply_range(L, p0, p1, probe_vec) : launch_patch_apply_f64_range(L, inv, p0, p1, probe_vec);
   if (rc == 0) {
     const size_t lds = (size_t)L->lay.max_np * (sizeof(double) + sizeof(int32_t));
     unsigned long long* worst = reinterpret_cast<unsigned long long*>(L->chk);
@@ -312,7 +307,6 @@ static int launch_check(alfi_level* L, double tol, int64_t p0, int64_t p1, const
     if (hipGetLastError() != hipSuccess) rc = alfi_set_error(ctx, ALFI_E_HIP, "patch_check_kernel launch failed");
   }
   (void)hipStreamSynchronize(ctx->stream);
-  if (own) (void)hipFree(own);
   return rc;
 }
 
@@ -333,7 +327,7 @@ static int read_check(alfi_level* L, double* worst, int* nflag) {
 // setup, one patch at a time: the rare path) and inverted by the pivoted LU above, all in place: the level keeps its condensed
 // storage (round 2 fell back to dense inverses for the whole level, 6.8 x the memory exactly when a patch is ill-conditioned;
 // round 3 repaired the Schur complement only, so a bad pivot inside one macro-cell group still did).
-static int cond_repair(alfi_level* L, double tol, int nflag, double worst) {
+static int cond_repair(alfi_level* L, double tol, int nflag, double worst, const double* probe_vec) {
   alfi_ctx* ctx = L->ctx;
   const int smax = L->cplan.max_s;
   if (smax > 4096)
@@ -376,7 +370,7 @@ static int cond_repair(alfi_level* L, double tol, int nflag, double worst) {
   if (rc != 0) return rc;
   if (st != 0) return alfi_set_error(ctx, ALFI_E_SINGULAR, "a condensed patch operator is singular to working precision (pivoted inversion)");
   ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->chk, 0, 2 * sizeof(double), ctx->stream));
-  rc = launch_check(L, tol, 0, L->npatch);
+  rc = launch_check(L, nullptr, tol, 0, L->npatch, probe_vec);
   double worst2 = 0.0;
   int nflag2 = 0;
   if (rc == 0) rc = read_check(L, &worst2, &nflag2);
@@ -413,20 +407,13 @@ int patch_check_finish(alfi_level* L, const PatchCheckAcc& acc) {
   return 0;
 }
 
-// Called by alfi_patches_factor after the fast inversion.  unpivoted_status: the zero-pivot flag of that inversion (a
-// patch that met one holds non-finite entries and is caught by the probe).
-int patch_verify_and_repair(alfi_level* L, int unpivoted_status) {
-  PatchCheckAcc acc;
-  const int rc = patch_verify_and_repair_range(L, unpivoted_status, 0, L->npatch, nullptr, &acc);
-  patch_check_finish(L, acc);
-  return rc;
-}
-
-// The probe, the repair and the second probe for the patches [p0, p1) (dense inverses; condensed levels: the whole level only).
+// Called by alfi_patches_factor after the fast inversion of the patches [p0, p1): the probe, the repair and the second probe
+// (dense FP64 inverses at inv; condensed levels: the factors the level holds, the whole level only).  unpivoted_status: the
+// zero-pivot flag of that inversion (a patch that met one holds non-finite entries and is caught by the probe).
 // A level factored range by range sees in *acc what one pass over all its patches would have reported: the worst first residual,
 // the flagged and repaired counts, and the worst residual of the inverses it ends up with.
-int patch_verify_and_repair_range(alfi_level* L, int unpivoted_status, int64_t p0, int64_t p1, const double* probe_vec,
-                                  PatchCheckAcc* acc) {
+int patch_verify_and_repair_range(alfi_level* L, double* inv, int unpivoted_status, int64_t p0, int64_t p1,
+                                  const double* probe_vec, PatchCheckAcc* acc) {
   alfi_ctx* ctx = L->ctx;
   const bool enabled = alfi_env_patch_check();
   const double tol = alfi_env_patch_check_tol();
@@ -440,7 +427,7 @@ int patch_verify_and_repair_range(alfi_level* L, int unpivoted_status, int64_t p
     ALFI_HIP_CHECK(ctx, hipMalloc((void**)&L->chk_list, sizeof(int32_t) * (size_t)L->chk_cap));
   }
   ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->chk, 0, 2 * sizeof(double), ctx->stream));
-  ALFI_CHECK(launch_check(L, tol, p0, p1, probe_vec));
+  ALFI_CHECK(launch_check(L, inv, tol, p0, p1, probe_vec));
   double worst = 0.0;
   int nflag = 0;
   ALFI_CHECK(read_check(L, &worst, &nflag));
@@ -456,7 +443,7 @@ int patch_verify_and_repair_range(alfi_level* L, int unpivoted_status, int64_t p
   constexpr int REPAIR_MAX_NP = PATCH_MAX;     // (a 2000-dof patch takes ~0.5 s of one workgroup: a rare-path safety net)
   if (L->cond) {
     L->chk_repaired = 0;
-    const int rc = cond_repair(L, tol, nflag, worst);
+    const int rc = cond_repair(L, tol, nflag, worst, probe_vec);
     acc->repaired += L->chk_repaired;
     if (rc == 0) acc->worst_after = L->chk_worst_after;
     return rc;
@@ -487,11 +474,11 @@ int patch_verify_and_repair_range(alfi_level* L, int unpivoted_status, int64_t p
     dim3 grid((unsigned)nb), block(256);
     if (L->bs == 2)
       hipLaunchKernelGGL((patch_repair_kernel<2, false>), grid, block, lds, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals,
-                         L->A.flat, L->patch_ptr, L->patch_dofs, L->inv_ptr, L->inv, L->chk_list + b0, scratch, stride,
+                         L->A.flat, L->patch_ptr, L->patch_dofs, L->inv_ptr, inv, L->chk_list + b0, scratch, stride,
                          L->status, (const double*)nullptr, 0, fc);
     else
       hipLaunchKernelGGL((patch_repair_kernel<3, false>), grid, block, lds, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals,
-                         L->A.flat, L->patch_ptr, L->patch_dofs, L->inv_ptr, L->inv, L->chk_list + b0, scratch, stride,
+                         L->A.flat, L->patch_ptr, L->patch_dofs, L->inv_ptr, inv, L->chk_list + b0, scratch, stride,
                          L->status, (const double*)nullptr, 0, fc);
     if (hipGetLastError() != hipSuccess) rc = alfi_set_error(ctx, ALFI_E_HIP, "patch_repair_kernel launch failed");
   }
@@ -501,10 +488,10 @@ int patch_verify_and_repair_range(alfi_level* L, int unpivoted_status, int64_t p
   (void)hipFree(scratch);
   if (rc != 0) return rc;
   if (st != 0) return alfi_set_error(ctx, ALFI_E_SINGULAR, "a patch operator is singular to working precision (pivoted inversion)");
-  ALFI_CHECK(build_patch_il(L));      // small-patch levels: the repaired inverses into the interleaved copy the apply streams
+  ALFI_CHECK(build_patch_il(L, inv)); // small-patch levels: the repaired inverses into the interleaved copy the apply streams
   // probe again (every patch of the range, the untouched ones included)
   ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->chk, 0, 2 * sizeof(double), ctx->stream));
-  rc = launch_check(L, tol, p0, p1, probe_vec);
+  rc = launch_check(L, inv, tol, p0, p1, probe_vec);
   double worst2 = 0.0;
   int nflag2 = 0;
   if (rc == 0) rc = read_check(L, &worst2, &nflag2);

@@ -869,13 +869,13 @@ __global__ __launch_bounds__(256) void patch_sum_kernel(int64_t i0, int64_t n, c
 // ---------------------------------------------------------------------------------------------------------------------
 // launch wrappers
 // ---------------------------------------------------------------------------------------------------------------------
-int launch_patch_gather_dense(alfi_level* L, bool ranked) {
+int launch_patch_gather_dense(alfi_level* L, double* inv, bool ranked) {
   alfi_ctx* ctx = L->ctx;
   if (L->npatch == 0) return 0;
   dim3 grid((unsigned)L->npatch), block(256);
 #define ALFI_GATHER(BSV, RV)                                                                                              \
   hipLaunchKernelGGL((patch_gather_dense_kernel<BSV, RV>), grid, block, 0, ctx->stream, L->A.rowptr, L->A.colidx, L->A.vals, \
-                     L->patch_ptr, L->patch_dofs, L->canon_rank, L->inv_ptr, L->inv, L->A.flat)
+                     L->patch_ptr, L->patch_dofs, L->canon_rank, L->inv_ptr, inv, L->A.flat)
   if (L->bs == 2) {
     if (ranked) ALFI_GATHER(2, true); else ALFI_GATHER(2, false);
   } else if (L->bs == 3) {
@@ -935,8 +935,8 @@ int launch_patch_invert_arrays(alfi_ctx* ctx, int64_t npatch, int max_np, const 
   return 0;
 }
 
-int launch_patch_invert(alfi_level* L) {
-  return launch_patch_invert_arrays(L->ctx, L->npatch, L->lay.max_np, L->patch_ptr, L->inv_ptr, L->inv, L->status);
+int launch_patch_invert(alfi_level* L, double* inv) {
+  return launch_patch_invert_arrays(L->ctx, L->npatch, L->lay.max_np, L->patch_ptr, L->inv_ptr, inv, L->status);
 }
 
 // stage 1 of the patches [p0, p1) with W waves per patch, either storage
@@ -1039,17 +1039,14 @@ int launch_patch_mult_persistent(alfi_level* L, const double* x, double* y) {
   return 0;
 }
 
-// stage 1 for the patches [p0, p1) of the level
-int launch_patch_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double* x) {
+// stage 1 for the patches [p0, p1) of a level with dense FP64 inverses at inv: the level's own, or the ones the factor pipeline
+// is working on (its probe; such a level has no interleaved copy)
+int launch_patch_apply_f64_range(alfi_level* L, const double* inv, int64_t p0, int64_t p1, const double* x) {
   alfi_ctx* ctx = L->ctx;
   if (p1 <= p0) return 0;
   ProfScope prof(ctx, ALFI_EV_PATCH_APPLY);     // to the end of the function
-  if (L->cond) {                                // condensed factors (kernels_bigpatch.hip)
-    ALFI_CHECK(launch_cond_apply_range(L, p0, p1, x));
-    return 0;
-  }
-  if (L->lay.max_np > SMALL_PATCH_MAX) {         // macro stars, either storage (kernels_bigpatch.hip)
-    ALFI_CHECK(L->f32 ? launch_big_apply_f32_range(L, p0, p1, x) : launch_big_apply_range(L, p0, p1, x));
+  if (L->lay.max_np > SMALL_PATCH_MAX) {         // macro stars (kernels_bigpatch.hip)
+    ALFI_CHECK(launch_big_apply_range(L, inv, p0, p1, x));
     return 0;
   }
   // levels with FEW star patches of 3-D size (the lower levels of a hierarchy: 125 and 729 patches under config 3's 35 937)
@@ -1060,12 +1057,12 @@ int launch_patch_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double
   // from the patch size alone.
   // (ALFI_TEST_LARGE_PATHS: no level counts as small, so that test hierarchies take the kernels of the large levels)
   const int64_t few = alfi_test_large_paths() ? 0 : 1000, fewer = alfi_test_large_paths() ? 0 : 256;
-  if (!L->f32 && L->lay.max_np > 64 && L->npatch <= fewer) {     // kernels_bigpatch.hip
-    ALFI_CHECK(launch_big_apply_range(L, p0, p1, x));
+  if (L->lay.max_np > 64 && L->npatch <= fewer) {     // kernels_bigpatch.hip
+    ALFI_CHECK(launch_big_apply_range(L, inv, p0, p1, x));
     return 0;
   }
   // (the inverses are read once per apply: nontemporal loads keep x, the staging buffer and the index arrays in cache)
-  if (L->il_valid && !L->f32) {
+  if (L->il_valid) {
     // small patches, interleaved copy of the inverses: G lanes per patch, 64 / G patches per wave
     const int PW = 64 / L->il_G;
     const int64_t nwave = (p1 - 1) / PW - p0 / PW + 1;
@@ -1081,14 +1078,31 @@ int launch_patch_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double
     }
 #undef ALFI_IL
   } else {
-    // waves per patch: eight above 128 dofs (and on FP64 levels of few patches above 64), four above 64, one below
-    const int W = L->lay.max_np > 128 || (!L->f32 && L->lay.max_np > 64 && L->npatch <= few) ? 2 * APPLY_W
-                  : L->lay.max_np > 64 ? APPLY_W : 1;
-    if (L->f32)
-      launch_patch_apply_w(ctx, W, p0, p1, L->patch_ptr, L->patch_dofs, L->inv32_ptr, L->stage_ptr, L->inv32, x, L->stage);
-    else
-      launch_patch_apply_w(ctx, W, p0, p1, L->patch_ptr, L->patch_dofs, L->inv_ptr, L->stage_ptr, L->inv, x, L->stage);
+    // waves per patch: eight above 128 dofs (and on levels of few patches above 64), four above 64, one below
+    const int W = L->lay.max_np > 128 || (L->lay.max_np > 64 && L->npatch <= few) ? 2 * APPLY_W : L->lay.max_np > 64 ? APPLY_W : 1;
+    launch_patch_apply_w(ctx, W, p0, p1, L->patch_ptr, L->patch_dofs, L->inv_ptr, L->stage_ptr, inv, x, L->stage);
   }
+  ALFI_HIP_CHECK(ctx, hipGetLastError());
+  return 0;
+}
+
+// stage 1 for the patches [p0, p1) of the level, whatever it holds
+int launch_patch_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double* x) {
+  alfi_ctx* ctx = L->ctx;
+  if (p1 <= p0) return 0;
+  if (L->held != HELD_COND && L->held != HELD_F32) return launch_patch_apply_f64_range(L, L->inv, p0, p1, x);
+  ProfScope prof(ctx, ALFI_EV_PATCH_APPLY);     // to the end of the function
+  if (L->cond) {                                // condensed factors (kernels_bigpatch.hip)
+    ALFI_CHECK(launch_cond_apply_range(L, p0, p1, x));
+    return 0;
+  }
+  // single-precision storage: macro stars (kernels_bigpatch.hip), else waves per patch from the patch size alone
+  if (L->lay.max_np > SMALL_PATCH_MAX) {
+    ALFI_CHECK(launch_big_apply_f32_range(L, p0, p1, x));
+    return 0;
+  }
+  const int W = L->lay.max_np > 128 ? 2 * APPLY_W : L->lay.max_np > 64 ? APPLY_W : 1;
+  launch_patch_apply_w(ctx, W, p0, p1, L->patch_ptr, L->patch_dofs, L->inv32_ptr, L->stage_ptr, L->inv32, x, L->stage);
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   return 0;
 }
@@ -1107,7 +1121,7 @@ int launch_patch_sum_range(alfi_level* L, int64_t i0, int64_t i1, const double* 
 
 int launch_patch_sum(alfi_level* L, const double* x, double* y) { return launch_patch_sum_range(L, 0, L->n, x, y); }
 
-int launch_patch_unrank(alfi_level* L) {
+int launch_patch_unrank(alfi_level* L, double* inv) {
   alfi_ctx* ctx = L->ctx;
   if (L->npatch == 0) return 0;
   const int64_t ldmax = (L->lay.max_np + 1) & ~1;
@@ -1120,7 +1134,7 @@ int launch_patch_unrank(alfi_level* L) {
     const int64_t nb = std::min<int64_t>(batch, L->npatch - p0);
     for (int back = 0; back < 2; ++back)
       hipLaunchKernelGGL(patch_unrank_kernel, dim3((unsigned)nb), dim3(256), 0, ctx->stream, p0, L->patch_ptr, L->canon_rank,
-                         L->inv_ptr, L->inv, scratch, stride, back);
+                         L->inv_ptr, inv, scratch, stride, back);
     if (hipGetLastError() != hipSuccess) rc = alfi_set_error(ctx, ALFI_E_HIP, "patch_unrank_kernel launch failed");
   }
   (void)hipStreamSynchronize(ctx->stream);
@@ -1128,9 +1142,7 @@ int launch_patch_unrank(alfi_level* L) {
   return rc;
 }
 
-int launch_patch_f32_convert(alfi_level* L, const double* src) { return launch_patch_f32_convert_range(L, src, 0, L->npatch); }
-
-// the patches [p0, p1): src + inv_ptr[p] holds patch p's FP64 inverse
+// inv32 <- the patches [p0, p1), rounded to nearest: src + inv_ptr[p] holds patch p's FP64 inverse
 int launch_patch_f32_convert_range(alfi_level* L, const double* src, int64_t p0, int64_t p1) {
   alfi_ctx* ctx = L->ctx;
   if (p1 <= p0) return 0;
@@ -1140,12 +1152,12 @@ int launch_patch_f32_convert_range(alfi_level* L, const double* src, int64_t p0,
   return 0;
 }
 
-// Small-patch levels (every n_p <= 32, dense inverses): (re)build the interleaved copy the additive apply streams.  Called
-// at the end of every factorisation and after a pivoted repair has rewritten some inverses.
-int build_patch_il(alfi_level* L) {
+// Small-patch levels (every n_p <= 32, dense inverses at inv): (re)build the interleaved copy the additive apply streams.
+// Called at the end of every dense factorisation and after a pivoted repair has rewritten some inverses.
+int build_patch_il(alfi_level* L, const double* inv) {
   alfi_ctx* ctx = L->ctx;
   L->il_valid = false;
-  if (L->cond || L->npatch == 0 || L->lay.max_np > 32 || L->inv_shrunk) return 0;
+  if (L->npatch == 0 || L->lay.max_np > 32) return 0;
   const int need = (L->lay.max_np + 1) / 2;
   const int G = need <= 4 ? 4 : need <= 7 ? 7 : need <= 8 ? 8 : need <= 12 ? 12 : 16;
   const int PW = 64 / G, LW = PW * G, nc = L->lay.max_np;
@@ -1161,7 +1173,7 @@ int build_patch_il(alfi_level* L) {
   }
   const int64_t blocks = std::min<int64_t>((total + 255) / 256, 8192);
   hipLaunchKernelGGL(patch_il_build_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, L->npatch, G, nc, total,
-                     L->patch_ptr, L->inv_ptr, L->inv, L->inv_il);
+                     L->patch_ptr, L->inv_ptr, inv, L->inv_il);
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   L->il_G = G;
   L->il_nc = nc;

@@ -160,6 +160,22 @@ inline int64_t plan_f32_offsets(int64_t npatch, const int64_t* pptr, std::vector
   (*f32_ptr)[(size_t)npatch] = ip;
   return ip;
 }
+// The ranges of patches an FP32 level of big patches is factored in, through an FP64 work buffer of `cap` doubles
+// (alfi_ctx_set_f32_work_bytes).  Greedy: the longest run of consecutive patches whose FP64 row pieces (inv_ptr: the npatch + 1
+// offsets of PatchLayout) fit the cap; one patch above the cap is a range of its own.  ranges: the boundaries, 0 = r_0 < r_1 <
+// ... = npatch (no patches: 0 alone); returns the doubles of the largest range -- what the buffer must hold.
+inline int64_t plan_f32_ranges(int64_t npatch, const int64_t* inv_ptr, int64_t cap, std::vector<int64_t>* ranges) {
+  ranges->assign(1, 0);
+  int64_t work = 0;
+  for (int64_t p0 = 0; p0 < npatch;) {
+    int64_t p1 = p0 + 1;
+    while (p1 < npatch && inv_ptr[p1 + 1] - inv_ptr[p0] <= cap) ++p1;
+    work = std::max(work, inv_ptr[p1] - inv_ptr[p0]);
+    ranges->push_back(p1);
+    p0 = p1;
+  }
+  return work;
+}
 
 // ---- the condensed layout (alfi_patches_set_groups; the tables of CondDev, common.h) ---------------------------------------
 struct CondPlan {

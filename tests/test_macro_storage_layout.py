@@ -76,3 +76,66 @@ def test_a_patch_beyond_the_big_patch_kernels_is_refused():
     with pytest.raises(_hostlib.PlanError) as e:
         _hostlib.plan_macro_f32_layout(np.array([0, 40, 4137]))
     assert e.value.code == -2 and "4097" in str(e.value)
+
+
+def test_both_layout_entry_points_return_what_they_returned():
+    # one implementation behind the two: the same offsets and scalars as before (entry by entry from the per-patch export), each
+    # with its own limit and its own wording
+    sizes = np.array([33, 160, 1, 159, 64, 150])
+    pp = np.concatenate([[0], np.cumsum(sizes)])
+    L = _hostlib.lib()
+    floats = [L.alfi_host_f32_patch_floats(int(n)) for n in sizes]
+    for plan in (_hostlib.plan_f32_layout, _hostlib.plan_macro_f32_layout):
+        lay = plan(pp)
+        assert sorted(lay) == ["align_floats", "f32_ptr", "inv32_floats", "rows_per_load"]
+        assert np.array_equal(lay["f32_ptr"], np.concatenate([[0], np.cumsum(floats)])) and lay["inv32_floats"] == sum(floats)
+        assert lay["rows_per_load"] == 4 and lay["align_floats"] == 32
+    with pytest.raises(_hostlib.PlanError) as e:
+        _hostlib.plan_f32_layout(np.array([0, 40, 201]))
+    assert e.value.code == -2 and str(e.value) == "patch 1 has 161 dofs; FP32 storage holds patches of 1..160"
+    assert len(_hostlib.plan_f32_layout(np.array([0, 40, 200]))["f32_ptr"]) == 3
+    with pytest.raises(_hostlib.PlanError) as e:
+        _hostlib.plan_macro_f32_layout(np.array([0, 40, 4137]))
+    assert e.value.code == -2 and str(e.value) == "patch 1 has 4097 dofs; FP32 macro-star storage holds patches of 1..4096"
+    assert len(_hostlib.plan_macro_f32_layout(np.array([0, 40, 4136]))["f32_ptr"]) == 3
+
+
+def _greedy(ip, cap):
+    """the rule in six lines: the longest run of consecutive patches that fits the cap, one patch above it on its own"""
+    bounds, p0 = [0], 0
+    while p0 < len(ip) - 1:
+        p1 = p0 + 1
+        while p1 < len(ip) - 1 and ip[p1 + 1] - ip[p0] <= cap:
+            p1 += 1
+        bounds.append(p1)
+        p0 = p1
+    return bounds
+
+
+@pytest.mark.parametrize("npatch", [1, 2, 7, 40])
+def test_range_planner(npatch):
+    """plan_f32_ranges (csrc/patch_plan.h): the ranges an FP32 level of big patches is factored in"""
+    sizes = np.random.default_rng(100 + npatch).integers(161, 401, npatch)
+    pp = np.concatenate([[0], np.cumsum(sizes)])
+    ip = _hostlib.plan_patch_layout(int(pp[-1]), pp, np.arange(pp[-1], dtype=np.int32))["inv_ptr"]
+    doubles = np.diff(ip)
+    k = min(npatch // 2, npatch - 2) if npatch > 1 else 0            # a patch with a right neighbour (where there is one)
+    two = int(doubles[k] + doubles[k + 1]) if npatch > 1 else int(doubles[0])
+    caps = [1, int(doubles[k]), two, two - 1, int(ip[-1]) + 1000]
+    for cap in caps:
+        plan = _hostlib.plan_f32_ranges(ip, cap)
+        r = plan["ranges"]
+        assert list(r) == _greedy(ip, cap), cap
+        # a partition of [0, npatch) into non-empty ranges
+        assert r[0] == 0 and r[-1] == npatch and np.all(np.diff(r) > 0)
+        held = ip[r[1:]] - ip[r[:-1]]
+        # every range is a single patch or fits the cap
+        assert np.all((np.diff(r) == 1) | (held <= cap)), cap
+        # no range could take the next patch
+        assert all(ip[b + 1] - ip[a] > cap for a, b in zip(r[:-2], r[1:-1])), cap
+        # the work buffer is the largest range
+        assert plan["work_doubles"] == held.max(), cap
+    assert len(_hostlib.plan_f32_ranges(ip, 1)["ranges"]) == npatch + 1            # one patch per range
+    assert list(_hostlib.plan_f32_ranges(ip, caps[-1])["ranges"]) == [0, npatch]   # one range for the level
+    empty = _hostlib.plan_f32_ranges(np.zeros(1, dtype=np.int64), 8)
+    assert list(empty["ranges"]) == [0] and empty["work_doubles"] == 0
