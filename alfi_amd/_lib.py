@@ -163,6 +163,23 @@ SIGNATURES = {
     "alfi_saddle_factor_velocity": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
     "alfi_saddle_velocity_solve": (ctypes.c_int, [vp, vp, vp]),
     "alfi_saddle_velocity_info": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)]),
+    # block right-hand sides: (ncol, cols, nx) then (pointer, leading dimension) per operand
+    "alfi_ctx_set_block_kernels": (ctypes.c_int, [vp, ctypes.c_int]),
+    "alfi_patch_apply_block_info": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int)]),
+    "alfi_spmv_block_info": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int)]),
+    "alfi_patch_apply_block": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64]),
+    "alfi_spmv_block": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64]),
+    "alfi_residual_block": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64, vp,
+                                           ctypes.c_int64]),
+    "alfi_smooth_fgmres_block_info": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "alfi_smooth_fgmres_block": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64, vp,
+                                                ctypes.c_int64, ctypes.c_int]),
+    "alfi_mg_vcycle_block": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64]),
+    "alfi_mg_fcycle_block": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64]),
+    "alfi_saddle_mult_block": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64]),
+    "alfi_saddle_precond_block": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64]),
+    "alfi_saddle_solve_block": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64,
+                                               ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, vp, vp]),
 }
 
 COMM_ID_BYTES = 128      # ALFI_COMM_ID_BYTES

@@ -75,12 +75,31 @@ def adjoint_rhs(g_u, g_p, bc_dofs, n_p, vol=None):
     return np.concatenate([rhs_u, rhs_p])
 
 
+def as_functionals(J):
+    """(list of functionals, is_list): a list or tuple of functionals is a block of adjoint right-hand sides, anything else ONE
+    functional -- and then every return type is the single functional's."""
+    if isinstance(J, (list, tuple)):
+        if len(J) == 0:
+            raise ValueError("an empty list of functionals")
+        return list(J), True
+    return [J], False
+
+
+def adjoint_rhs_block(gradients, bc_dofs, n_p, vol=None):
+    """(n_u + n_p, K) matrix whose column i is ``adjoint_rhs`` of ``gradients[i] = (g_u, g_p)``: built column by column."""
+    return np.stack([adjoint_rhs(g_u, g_p, bc_dofs, n_p, vol) for g_u, g_p in gradients], axis=1)
+
+
 class AdjointSolver(object):
     """``solver.solver_adjoint``: ``solve(rtol=None, atol=None)`` writes ``solver.z_adj = (lam_u, lam_p)`` (host arrays) for the
-    functional given to ``setup_adjoint`` and returns an info dict."""
+    functional given to ``setup_adjoint`` and returns an info dict.  Given a LIST (or tuple) of K functionals it refreshes,
+    transposes and factors ONCE, solves the K systems with one ``Saddle.solve_block`` (the patch factors streamed once for up
+    to four of them), writes ``solver.z_adj = [(lam_u, lam_p), ...]`` and returns ``linear_iter``, ``residual_norm``,
+    ``rhs_norm`` and ``converged`` as lists with one entry per functional; the times stay single numbers."""
 
     def __init__(self, solver, J):
         self.solver, self.J = solver, J
+        self.functionals, self.is_list = as_functionals(J)
 
     def _operators(self, adv):
         """Transposed Jacobian blocks of z* on every level, factored.  Returns (refresh, transpose, factor) seconds."""
@@ -115,6 +134,8 @@ class AdjointSolver(object):
         _, adv = s._last_solve
         t0 = time.time()
         t_ref, t_tr, t_fac = self._operators(adv)
+        if self.is_list:
+            return self._solve_block(t0, (t_ref, t_tr, t_fac), rtol, atol)
         u, p = s.u, s.p
         g_u, g_p = self.J.gradient(s, u, p)
         rhs = adjoint_rhs(g_u, g_p, s.levels[-1].bc_dofs, s.n_p, s.vol if s.nullspace else None)
@@ -137,8 +158,34 @@ class AdjointSolver(object):
                 "factor_s": t_fac, "solve_s": t_solve}
 
 
+    def _solve_block(self, t0, times, rtol, atol):
+        """The K functionals of a list after ONE ``_operators`` pass: right-hand sides column by column, one block solve."""
+        s = self.solver
+        t_ref, t_tr, t_fac = times
+        rhs = adjoint_rhs_block([J.gradient(s, s.u, s.p) for J in self.functionals], s.levels[-1].bc_dofs, s.n_p,
+                                s.vol if s.nullspace else None)
+        rtol = s.rtol if rtol is None else float(rtol)
+        atol = s.atol if atol is None else float(atol)
+        t_s = time.time()
+        dB, dX = s.ctx.mat(rhs), s.ctx.mat(s.n_u + s.n_p, rhs.shape[1])
+        max_it = s.params["ksp_max_it"]
+        its, rn = s.saddle.solve_block(dB, dX, rtol, atol, max_it, 30)
+        lam = dX.get()
+        t_solve = time.time() - t_s
+        s.z_adj = []
+        for c in range(rhs.shape[1]):
+            lam_u, lam_p = lam[:s.n_u, c].copy(), lam[s.n_u:, c].copy()
+            if s.nullspace:              # zero integral per column, as the forward solve shifts p
+                lam_p -= (s.vol @ lam_p) / s.area
+            s.z_adj.append((lam_u, lam_p))
+        bnorm = [float(np.linalg.norm(rhs[:, c])) for c in range(rhs.shape[1])]
+        return {"linear_iter": its, "time": (time.time() - t0) / 60.0, "residual_norm": rn, "rhs_norm": bnorm,
+                "converged": [bool(i < max_it or r <= max(rtol * b, atol)) for i, r, b in zip(its, rn, bnorm)],
+                "refresh_s": t_ref, "transpose_s": t_tr, "factor_s": t_fac, "solve_s": t_solve}
+
+
 def setup_adjoint(solver, J):
-    """``solver.setup_adjoint(J)``: keep the functional and create ``solver.solver_adjoint``."""
+    """``solver.setup_adjoint(J)``: keep the functional -- or the list of functionals -- and create ``solver.solver_adjoint``."""
     if solver._partitioned:
         raise NotImplementedError("adjoint solves on partitioned levels: the mirror blocks of a rank's ghost columns belong to "
                                   "other ranks")
@@ -147,12 +194,21 @@ def setup_adjoint(solver, J):
     return solver.solver_adjoint
 
 
-def gradient(solver, dF_dm, dJ_dm=0.0):
+def gradient(solver, dF_dm, dJ_dm=0.0, index=None):
     """dJ/dm = dJ/dm|_z + z_adj . dF/dm for a parameter m the residual depends on, with the adjoint of the last
-    ``solver_adjoint.solve()``; ``dF_dm``: (dF_u/dm, dF_p/dm) or the concatenated vector, Dirichlet rows zeroed as F's."""
-    lam_u, lam_p = solver.z_adj
+    ``solver_adjoint.solve()``; ``dF_dm``: (dF_u/dm, dF_p/dm) or the concatenated vector, Dirichlet rows zeroed as F's.
+    ``index``: which functional of a list (``solver.z_adj`` is then a list of adjoints); None for a single functional."""
+    if isinstance(solver.z_adj, list):
+        if index is None:
+            raise ValueError("solver.z_adj holds %d adjoints: say which one (index=)" % len(solver.z_adj))
+        lam_u, lam_p = solver.z_adj[index]
+    else:
+        if index is not None:
+            raise ValueError("solver.z_adj holds one adjoint: no index")
+        lam_u, lam_p = solver.z_adj
     v = np.concatenate(dF_dm) if isinstance(dF_dm, tuple) else np.asarray(dF_dm)
     return float(dJ_dm) + float(lam_u @ v[:len(lam_u)] + lam_p @ v[len(lam_u):])
 
 
-__all__ = ["LinearFunctional", "LoadFunctional", "AdjointSolver", "adjoint_rhs", "setup_adjoint", "gradient"]
+__all__ = ["LinearFunctional", "LoadFunctional", "AdjointSolver", "adjoint_rhs", "adjoint_rhs_block", "as_functionals", "setup_adjoint",
+           "gradient"]

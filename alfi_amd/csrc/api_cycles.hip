@@ -3,6 +3,7 @@
 // (One file per concern since round 5: api_ctx / api_level / api_patches / api_smoother / api_cycles / api_saddle; the helpers they
 // share are declared in api_internal.h.)
 #include "api_internal.h"
+#include "block_cols.h"
 
 // ---- coarse solve ------------------------------------------------------------------------------------------------------------
 int alfi_coarse_set_inverse(alfi_level* L, const double* inv, int inv_is_device) {
@@ -671,6 +672,121 @@ static int run_cycle(alfi_mg* mg, int kind, const double* db, double* dx) {
 int alfi_mg_vcycle(alfi_mg* mg, const double* db, double* dx) { return run_cycle(mg, 0, db, dx); }
 
 int alfi_mg_fcycle(alfi_mg* mg, const double* db, double* dx) { return run_cycle(mg, 1, db, dx); }
+
+// ---- block cycles (alfi_mg_vcycle_block / _fcycle_block) ---------------------------------------------------------------------------
+// vcycle and fcycle above for the 1 .. BLOCK_NV columns of one chunk, eagerly (never a captured graph).  The smoother and the
+// residual are the block forms of api_block.hip; transfers, the coarse solve and the correction loop over the columns with the
+// single-vector code.  Below the level a cycle starts on, column i of the chunk lives in slot i of the levels' block vectors.
+static int64_t mg_block_ld(const alfi_level* L) { return (L->n + 1) & ~(int64_t)1; }
+
+static int mg_block_vectors(alfi_mg* mg, int ncol) {
+  alfi_ctx* ctx = mg->ctx;
+  for (alfi_level* L : mg->levels) {
+    const int need = block_slots_needed(L->blk_mg_slots, ncol);
+    if (need == L->blk_mg_slots) continue;         // (0 slots: not allocated yet; ncol >= 1, so need >= 1)
+    ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    dev_free(L->blk_mg_b);
+    dev_free(L->blk_mg_x);
+    dev_free(L->blk_mg_r);
+    L->blk_mg_b = L->blk_mg_x = L->blk_mg_r = nullptr;
+    L->blk_mg_slots = 0;
+    ALFI_CHECK(dev_alloc(ctx, &L->blk_mg_b, need * mg_block_ld(L)));
+    ALFI_CHECK(dev_alloc(ctx, &L->blk_mg_x, need * mg_block_ld(L)));
+    ALFI_CHECK(dev_alloc(ctx, &L->blk_mg_r, need * mg_block_ld(L)));
+    L->blk_mg_slots = need;
+  }
+  return 0;
+}
+
+static int mg_smooth_block(alfi_mg* mg, int l, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx,
+                           int nonzero_guess) {
+  alfi_level* L = mg->levels[l];
+  if (mg->smoother == ALFI_SMOOTHER_CHEBYSHEV) {
+    for (int i = 0; i < cols.n; ++i)
+      ALFI_CHECK(alfi_smooth_chebyshev(L, mg->k, mg->emin[l], mg->emax[l], B + cols.c[i] * ldb, X + cols.c[i] * ldx, nonzero_guess));
+    return 0;
+  }
+  return block_smooth_fgmres(L, mg->k, cols, B, ldb, X, ldx, nonzero_guess);
+}
+
+static int vcycle_block(alfi_mg* mg, int l, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx, bool x_zero) {
+  alfi_ctx* ctx = mg->ctx;
+  alfi_level* L = mg->levels[l];
+  const int nc = cols.n;
+  if (l == 0) {
+    for (int i = 0; i < nc; ++i) ALFI_CHECK(alfi_coarse_solve(L, B + cols.c[i] * ldb, X + cols.c[i] * ldx));
+    return 0;
+  }
+  alfi_level* C = mg->levels[l - 1];
+  alfi_transfer* T = mg->transfers[l - 1];
+  const BlockCols slots = block_chunk(nc, nullptr, 0);
+  const int64_t ldl = mg_block_ld(L), ldc = mg_block_ld(C);
+  ALFI_CHECK(mg_smooth_block(mg, l, cols, B, ldb, X, ldx, x_zero ? 0 : 1));                          // pre-smooth
+  ALFI_CHECK(block_spmv(L, cols, slots, X, ldx, L->blk_mg_r, ldl, B, ldb, 1));                      // r = b - A x
+  for (int i = 0; i < nc; ++i) ALFI_CHECK(alfi_restrict(T, L->blk_mg_r + i * ldl, C->blk_mg_b + i * ldc, mg->robust));
+  const int cycles = l == 1 ? 1 : mg->cycles;
+  for (int c = 0; c < cycles; ++c) ALFI_CHECK(vcycle_block(mg, l - 1, slots, C->blk_mg_b, ldc, C->blk_mg_x, ldc, c == 0));
+  for (int i = 0; i < nc; ++i) ALFI_CHECK(alfi_prolong(T, C->blk_mg_x + i * ldc, L->blk_mg_r + i * ldl));
+  ctx->cur_tag = L->id;
+  for (int i = 0; i < nc; ++i) {
+    ProfScope prof(ctx, ALFI_EV_BLAS1);
+    ALFI_CHECK(launch_axpy(ctx, X + cols.c[i] * ldx, L->blk_mg_r + i * ldl, 1.0, L->n_own));         // x += P x_{l-1}
+  }
+  return mg_smooth_block(mg, l, cols, B, ldb, X, ldx, 1);                                           // post-smooth
+}
+
+static int fcycle_block(alfi_mg* mg, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx) {
+  const int Lmax = (int)mg->levels.size() - 1, nc = cols.n;
+  if (Lmax == 0) return vcycle_block(mg, 0, cols, B, ldb, X, ldx, false);
+  const BlockCols slots = block_chunk(nc, nullptr, 0);
+  for (int i = 0; i < nc; ++i) {         // restrict the right-hand sides through all levels
+    const double* bf = B + cols.c[i] * ldb;
+    for (int l = Lmax; l >= 1; --l) {
+      double* bc = mg->levels[l - 1]->blk_mg_b + i * mg_block_ld(mg->levels[l - 1]);
+      ALFI_CHECK(alfi_restrict(mg->transfers[l - 1], bf, bc, mg->robust));
+      bf = bc;
+    }
+  }
+  for (int l = 0; l < Lmax; ++l) {
+    alfi_level* L = mg->levels[l];
+    const int64_t ldl = mg_block_ld(L);
+    ALFI_CHECK(vcycle_block(mg, l, slots, L->blk_mg_b, ldl, L->blk_mg_x, ldl, l == 0));
+    for (int i = 0; i < nc; ++i) {
+      double* xnext = l + 1 == Lmax ? X + cols.c[i] * ldx : mg->levels[l + 1]->blk_mg_x + i * mg_block_ld(mg->levels[l + 1]);
+      ALFI_CHECK(alfi_prolong(mg->transfers[l], L->blk_mg_x + i * ldl, xnext));
+    }
+  }
+  return vcycle_block(mg, Lmax, cols, B, ldb, X, ldx, false);
+}
+
+// one full cycle on the 1 .. BLOCK_NV columns `cols` of B and X, arguments unchecked (alfi_saddle_precond_block)
+int mg_fcycle_block_chunk(alfi_mg* mg, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx) {
+  ALFI_CHECK(mg_ready(mg));
+  ALFI_CHECK(mg_block_vectors(mg, cols.n));
+  return fcycle_block(mg, cols, B, ldb, X, ldx);
+}
+
+static int run_cycle_block(alfi_mg* mg, int kind, const char* what, int ncol, const int* cols, int nx, const double* B, int64_t ldb,
+                           double* X, int64_t ldx) {
+  if (!mg) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL multigrid");
+  ALFI_CHECK(mg_require_serial(mg, what));
+  const BlockOperand ops[2] = {{B, ldb, false}, {X, ldx, true}};
+  ALFI_CHECK(check_block_call(mg->levels.back(), what, ncol, cols, nx, ops, 2));
+  ALFI_CHECK(mg_ready(mg));
+  ALFI_CHECK(mg_block_vectors(mg, ncol));
+  for (int q = 0; q < block_chunks(ncol); ++q) {
+    const BlockCols c = block_chunk(ncol, cols, q);
+    ALFI_CHECK(kind ? fcycle_block(mg, c, B, ldb, X, ldx) : vcycle_block(mg, (int)mg->levels.size() - 1, c, B, ldb, X, ldx, false));
+  }
+  return 0;
+}
+
+int alfi_mg_vcycle_block(alfi_mg* mg, int ncol, const int* cols, int nx, const double* B, int64_t ldb, double* X, int64_t ldx) {
+  return run_cycle_block(mg, 0, "alfi_mg_vcycle_block", ncol, cols, nx, B, ldb, X, ldx);
+}
+int alfi_mg_fcycle_block(alfi_mg* mg, int ncol, const int* cols, int nx, const double* B, int64_t ldb, double* X, int64_t ldx) {
+  return run_cycle_block(mg, 1, "alfi_mg_fcycle_block", ncol, cols, nx, B, ldb, X, ldx);
+}
 
 // KSPCG [3P] with a zero initial guess and the unpreconditioned residual norm, preconditioned by one cycle of mg
 // (examples/graddiv/graddiv.py:85-95).  The step lengths are formed on the device from reduced scalars (kernels_cheb.hip);

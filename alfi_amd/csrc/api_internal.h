@@ -80,6 +80,29 @@ bool auto_cond_to_dense(alfi_level* L);
 // api_smoother.hip
 int ensure_fgmres_workspace(alfi_level* L, int k);
 int ensure_cheb_workspace(alfi_level* L);
+bool smoother_takes_fused_iteration(const alfi_level* L, int k, bool* flat_spmv = nullptr);   // alfi_smooth_fgmres on this level
+// api_block.hip (block right-hand sides)
+void free_block_smoother(alfi_level* L);   // the Krylov workspaces of alfi_smooth_fgmres_block
+// the block forms on one chunk of 1 .. 4 columns, arguments unchecked: entry i of ic names the column that is read (X, B), entry
+// i of oc the column its result goes to (block_patch_apply, block_spmv); the smoother works on the columns cols of B and X
+struct BlockCols;
+struct BlockOperand {      // a column-major operand of a block call
+  const double* p;
+  int64_t ld;
+  bool written;
+};
+// ALFI_E_ARG unless L is a serial level, (ncol, cols, nx) a column list, every operand non-NULL with an even leading dimension
+// >= L->n, and no written operand overlaps another one
+int check_block_call(alfi_level* L, const char* what, int ncol, const int* cols, int nx, const BlockOperand* ops, int nops);
+int check_block_operands(alfi_ctx* ctx, const char* what, int64_t n, int ncol, const int* cols, int nx, const BlockOperand* ops,
+                         int nops);
+// api_cycles.hip: one full cycle on the columns `cols` of B and X, unchecked
+int mg_fcycle_block_chunk(alfi_mg* mg, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx);
+int block_patch_apply(alfi_level* L, const BlockCols& ic, const BlockCols& oc, const double* X, int64_t ldx, double* Y, int64_t ldy);
+int block_spmv(alfi_level* L, const BlockCols& ic, const BlockCols& oc, const double* X, int64_t ldx, double* Y, int64_t ldy,
+               const double* B, int64_t ldb, int mode);
+int block_smooth_fgmres(alfi_level* L, int k, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx,
+                        int nonzero_guess);
 // api_saddle.hip
 int upload_csr(alfi_ctx* ctx, DevCSR* d, const alfi_csr_host* h);
 void free_csr(DevCSR* d);

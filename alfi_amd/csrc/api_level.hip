@@ -208,6 +208,9 @@ int alfi_level_destroy(alfi_level* L) {
   free_patch_factors(L);
   dev_free(L->canon_rank);
   dev_free(L->stage);
+  dev_free(L->blk_stage);
+  dev_free(L->blk_carry);
+  free_block_smoother(L);
   dev_free(L->dof_ptr);
   dev_free(L->dof_pos);
   dev_free(L->mult_seq);
@@ -229,6 +232,9 @@ int alfi_level_destroy(alfi_level* L) {
   dev_free(L->mg_b);
   dev_free(L->mg_x);
   dev_free(L->mg_r);
+  dev_free(L->blk_mg_b);
+  dev_free(L->blk_mg_x);
+  dev_free(L->blk_mg_r);
   delete L;
   return 0;
 }

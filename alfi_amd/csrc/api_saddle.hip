@@ -2,6 +2,7 @@
 // (One file per concern since round 5: api_ctx / api_level / api_patches / api_smoother / api_cycles / api_saddle; the helpers they
 // share are declared in api_internal.h.)
 #include "api_internal.h"
+#include "block_cols.h"
 
 // ---- outer saddle-point solve (alfi/solver.py:386-422) ----------------------------------------------------------------------------
 int upload_csr(alfi_ctx* ctx, DevCSR* d, const alfi_csr_host* h) {
@@ -233,6 +234,11 @@ int alfi_saddle_destroy(alfi_saddle* S) {
   dev_free(S->wb);
   dev_free(S->wc);
   dev_free(S->dotbuf);
+  dev_free(S->blk_V);
+  dev_free(S->blk_Z);
+  dev_free(S->blk_w);
+  dev_free(S->blk_hs);
+  dev_free(S->blk_tmp_u);
   mf_free(S->vmf);
   delete S;
   return 0;
@@ -523,5 +529,231 @@ int alfi_saddle_solve(alfi_saddle* S, const double* db, double* dx, double rtol,
   if (residual_norm) *residual_norm = tn;
   // a persistent multiplicative sweep inside a cycle may have run into its wait bound: the iterates above were then computed
   // from an incomplete smoother result -- report it instead of returning counts and norms of garbage
+  return check_dev_err(ctx);
+}
+
+// ---- block right-hand sides -----------------------------------------------------------------------------------------------------
+// alfi_saddle_mult / _precond / _solve for the columns of column-major operands (block_cols.h), columns of n_u + n_p entries.
+// Column c of every result is the single call on column c bit for bit: the velocity-block product and the full cycles are the
+// block forms of api_block.hip / api_cycles.hip (one launch for up to four columns where the finest level batches), everything
+// else -- the divergence and gradient products, the Schur solve, the mean removal, the BLAS-1 and Hessenberg launches of the
+// outer FGMRES, the exact velocity solve -- is the single call's launch, column after column.  Serial saddles only.
+static int saddle_block_check(alfi_saddle* S, const char* what, int ncol, const int* cols, int nx, const BlockOperand* ops, int nops) {
+  if (!S) return alfi_set_error(nullptr, ALFI_E_ARG, "%s: NULL saddle", what);
+  if (S->par || level_is_partitioned(S->fine))
+    return alfi_set_error(S->ctx, ALFI_E_ARG, "%s on a partitioned finest level (serial levels only)", what);
+  return check_block_operands(S->ctx, what, S->nu_dofs + S->np_dofs, ncol, cols, nx, ops, nops);
+}
+
+static int saddle_mult_chunk(alfi_saddle* S, const BlockCols& c, const double* X, int64_t ldx, double* Y, int64_t ldy) {
+  alfi_ctx* ctx = S->ctx;
+  const int64_t nu = S->nu_dofs;
+  ALFI_CHECK(block_spmv(S->fine, c, c, X, ldx, Y, ldy, nullptr, 0, 0));                    // y_u = A x_u
+  for (int i = 0; i < c.n; ++i) {
+    const double* x = X + c.c[i] * ldx;
+    double* y = Y + c.c[i] * ldy;
+    ALFI_CHECK(launch_csr_spmv(ctx, S->BT, x + nu, y, nullptr, 0.0, 2));                   // y_u += B^T x_p
+    ALFI_CHECK(launch_csr_spmv(ctx, S->B, x, y + nu, nullptr, 0.0, 0));                    // y_p = B x_u
+  }
+  return 0;
+}
+
+// nx: the columns the operands have (the velocity work columns are indexed like them)
+static int saddle_precond_chunk(alfi_saddle* S, const BlockCols& c, int nx, const double* X, int64_t ldx, double* Y, int64_t ldy) {
+  alfi_ctx* ctx = S->ctx;
+  const int64_t nu = S->nu_dofs, np = S->np_dofs, ldu = (nu + 1) & ~(int64_t)1;
+  if (S->vkind == ALFI_VELOCITY_DIRECT || c.n == 1) {
+    for (int i = 0; i < c.n; ++i) ALFI_CHECK(alfi_saddle_precond(S, X + c.c[i] * ldx, Y + c.c[i] * ldy));
+    return 0;
+  }
+  if (S->blk_tmp_cols < nx) {
+    ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    dev_free(S->blk_tmp_u);
+    S->blk_tmp_u = nullptr;
+    S->blk_tmp_cols = 0;
+    ALFI_CHECK(dev_alloc(ctx, &S->blk_tmp_u, nx * ldu));
+    S->blk_tmp_cols = nx;
+  }
+  ALFI_CHECK(mg_fcycle_block_chunk(S->mg, c, X, ldx, Y, ldy));                              // y_u = MG(b_u)
+  for (int i = 0; i < c.n; ++i) {
+    const double* x = X + c.c[i] * ldx;
+    double* y = Y + c.c[i] * ldy;
+    ALFI_CHECK(launch_csr_spmv(ctx, S->B, y, S->tmp_p, x + nu, 1.0, 1));                   // q = b_p - B y_u
+    ALFI_CHECK(saddle_schur(S, S->tmp_p, y + nu));                                         // y_p = -(nu+gamma) M^-1 q
+    ALFI_CHECK(launch_csr_spmv(ctx, S->BT, y + nu, S->blk_tmp_u + c.c[i] * ldu, x, 1.0, 1));   // t = b_u - B^T y_p
+  }
+  ALFI_CHECK(mg_fcycle_block_chunk(S->mg, c, S->blk_tmp_u, ldu, Y, ldy));                   // y_u = MG(t)
+  if (S->remove_nullspace)
+    for (int i = 0; i < c.n; ++i) ALFI_CHECK(launch_remove_mean(ctx, Y + c.c[i] * ldy + nu, np));
+  return 0;
+}
+
+int alfi_saddle_mult_block(alfi_saddle* S, int ncol, const int* cols, int nx, const double* X, int64_t ldx, double* Y, int64_t ldy) {
+  const BlockOperand ops[2] = {{X, ldx, false}, {Y, ldy, true}};
+  ALFI_CHECK(saddle_block_check(S, "alfi_saddle_mult_block", ncol, cols, nx, ops, 2));
+  for (int q = 0; q < block_chunks(ncol); ++q) ALFI_CHECK(saddle_mult_chunk(S, block_chunk(ncol, cols, q), X, ldx, Y, ldy));
+  return 0;
+}
+
+int alfi_saddle_precond_block(alfi_saddle* S, int ncol, const int* cols, int nx, const double* X, int64_t ldx, double* Y, int64_t ldy) {
+  const BlockOperand ops[2] = {{X, ldx, false}, {Y, ldy, true}};
+  ALFI_CHECK(saddle_block_check(S, "alfi_saddle_precond_block", ncol, cols, nx, ops, 2));
+  for (int q = 0; q < block_chunks(ncol); ++q) ALFI_CHECK(saddle_precond_chunk(S, block_chunk(ncol, cols, q), nx, X, ldx, Y, ldy));
+  return 0;
+}
+
+// alfi_saddle_solve on the 1 .. BLOCK_NV columns c of B and X in lockstep; slot s of the block workspace belongs to column
+// c.c[s].  The columns start together, so every active column is at the same inner iteration j and the same count `its`; a
+// column leaves the active list when its own test max(rtol |b_c|, atol) is met -- inside a cycle (finish and update at its own
+// j, as the single call's break) or at a restart's true residual.  its[s], rn[s]: the single call's two results per slot.
+static int saddle_solve_chunk(alfi_saddle* S, const BlockCols& c, const double* B, int64_t ldb, double* X, int64_t ldx, double rtol,
+                              double atol, int max_it, int* its_out, double* rn_out) {
+  alfi_ctx* ctx = S->ctx;
+  const int64_t n = S->nu_dofs + S->np_dofs, ldv = S->ldv;
+  const int K = S->blk_restart, nc = c.n;
+  HsLayout hl(K);
+  const int64_t vs = (int64_t)(K + 1) * ldv, zs = (int64_t)K * ldv;
+  const int G = red_blocks_for(n);
+  auto Vs = [&](int s) { return S->blk_V + s * vs; };
+  auto Zs = [&](int s) { return S->blk_Z + s * zs; };
+  auto ws = [&](int s) { return S->blk_w + s * ldv; };
+  auto hss = [&](int s) { return S->blk_hs + (int64_t)s * hl.total; };
+  auto bcol = [&](int s) { return B + c.c[s] * ldb; };
+  auto xcol = [&](int s) { return X + c.c[s] * ldx; };
+  auto list = [&](const bool* on) {           // the slots that are on, as a column list of the workspace operands
+    BlockCols b = block_chunk(nc, nullptr, 0);
+    int m = 0;
+    for (int s = 0; s < nc; ++s)
+      if (on[s]) b.c[m++] = s;
+    b.n = m;
+    for (int i = m; i < BLOCK_NV; ++i) b.c[i] = m ? b.c[0] : 0;
+    return b;
+  };
+  // out[s] = hs_s[off] for the slots that are on: the copies queued together, one synchronisation
+  auto read = [&](const bool* on, int off, double* out) -> int {
+    for (int s = 0; s < nc; ++s)
+      if (on[s]) ALFI_HIP_CHECK(ctx, hipMemcpyAsync(out + s, hss(s) + off, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+  };
+  auto norm_init = [&](int s) -> int {
+    ALFI_CHECK(launch_norm_partials(ctx, ws(s), n));
+    return launch_norm_init_finish(ctx, ctx->red_partial, G, hss(s), K);
+  };
+  bool active[BLOCK_NV] = {false, false, false, false}, all[BLOCK_NV] = {false, false, false, false};
+  double bnorm[BLOCK_NV] = {0, 0, 0, 0}, tol[BLOCK_NV] = {0, 0, 0, 0}, val[BLOCK_NV] = {0, 0, 0, 0};
+  int its[BLOCK_NV] = {0, 0, 0, 0};
+  for (int s = 0; s < nc; ++s) {
+    all[s] = true;
+    ALFI_HIP_CHECK(ctx, hipMemsetAsync(hss(s), 0, sizeof(double) * hl.total, ctx->stream));
+    ALFI_HIP_CHECK(ctx, hipMemsetAsync(xcol(s), 0, sizeof(double) * n, ctx->stream));
+    ALFI_CHECK(launch_copy(ctx, ws(s), bcol(s), n));                           // r = b (zero initial guess)
+    ALFI_CHECK(norm_init(s));
+  }
+  ALFI_CHECK(read(all, hl.beta, bnorm));
+  int nactive = 0;
+  for (int s = 0; s < nc; ++s) {
+    tol[s] = std::max(rtol * bnorm[s], atol);
+    active[s] = !(bnorm[s] <= tol[s]);
+    nactive += active[s] ? 1 : 0;
+  }
+  // w_s = b_s - K x_s and beta_s = |w_s| for the slots in `on`, column by column with the single call's launches (x is a
+  // column of the caller's operand, w one of the workspace: two column lists, which the block product does not take)
+  auto residual_of = [&](const bool* on) -> int {
+    for (int s = 0; s < nc; ++s) {
+      if (!on[s]) continue;
+      ALFI_CHECK(alfi_saddle_mult(S, xcol(s), ws(s)));
+      ALFI_CHECK(launch_xmy(ctx, ws(s), bcol(s), n));
+      ALFI_CHECK(norm_init(s));
+    }
+    return 0;
+  };
+  int it = 0;                                   // iterations of every still active column
+  while (nactive > 0 && it < max_it) {
+    for (int s = 0; s < nc; ++s)
+      if (active[s]) ALFI_CHECK(launch_scale_by_inv(ctx, Vs(s), ws(s), hss(s) + hl.beta, n));      // v_0 = r / |r|
+    int j = 0;
+    bool cycle[BLOCK_NV];                        // the columns that run this restart cycle to its end
+    for (int s = 0; s < nc; ++s) cycle[s] = active[s];
+    int ncycle = nactive;
+    for (; j < K && it < max_it && ncycle > 0; ++j) {
+      const BlockCols a = list(cycle);
+      ALFI_CHECK(saddle_precond_chunk(S, a, nc, S->blk_V + j * ldv, vs, S->blk_Z + j * ldv, zs));   // z_j = P^-1 v_j
+      ALFI_CHECK(saddle_mult_chunk(S, a, S->blk_Z + j * ldv, zs, S->blk_w, ldv));                   // w = K z_j
+      for (int s = 0; s < nc; ++s) {
+        if (!cycle[s]) continue;
+        double *hs = hss(s), *hdots = hs + hl.hd;
+        ALFI_CHECK(launch_multi_dot(ctx, Vs(s), ldv, j + 1, ws(s), hdots, n));
+        ALFI_CHECK(launch_multi_axpy_norm(ctx, Vs(s), ldv, j + 1, hdots, ws(s), n, ctx->red_partial2, 0));
+        ALFI_CHECK(launch_hessenberg_update(ctx, ctx->red_partial2, G, hdots, hs, j, K, nullptr));
+      }
+      ++it;
+      ALFI_CHECK(read(cycle, hl.grs + j + 1, val));                            // |rotated rhs| = residual norm estimates
+      for (int s = 0; s < nc; ++s) {
+        if (!cycle[s]) continue;
+        its[s] = it;
+        if (std::fabs(val[s]) <= tol[s]) {                                     // converged: finished at its own j, out of the list
+          ALFI_CHECK(launch_fgmres_finish(ctx, hss(s), j + 1, K));
+          ALFI_CHECK(launch_update_solution(ctx, xcol(s), Zs(s), ldv, j + 1, hss(s) + hl.y, n));
+          cycle[s] = active[s] = false;
+          --ncycle;
+          --nactive;
+        } else if (j + 1 < K) {
+          ALFI_CHECK(launch_scale_by_inv(ctx, Vs(s) + (int64_t)(j + 1) * ldv, ws(s), hss(s) + hl.tt, n));
+        }
+      }
+    }
+    for (int s = 0; s < nc; ++s) {
+      if (!cycle[s]) continue;
+      ALFI_CHECK(launch_fgmres_finish(ctx, hss(s), j, K));
+      ALFI_CHECK(launch_update_solution(ctx, xcol(s), Zs(s), ldv, j, hss(s) + hl.y, n));
+    }
+    if (nactive == 0 || it >= max_it) break;
+    ALFI_CHECK(residual_of(active));                                           // restart: true residuals
+    ALFI_CHECK(read(active, hl.beta, val));
+    for (int s = 0; s < nc; ++s)
+      if (active[s] && val[s] <= tol[s]) {
+        active[s] = false;
+        --nactive;
+      }
+  }
+  ALFI_CHECK(residual_of(all));                                                // final true residual norms
+  ALFI_CHECK(read(all, hl.beta, val));
+  for (int s = 0; s < nc; ++s) {
+    its_out[s] = its[s];
+    rn_out[s] = val[s];
+  }
+  return 0;
+}
+
+int alfi_saddle_solve_block(alfi_saddle* S, int ncol, const int* cols, int nx, const double* B, int64_t ldb, double* X, int64_t ldx,
+                            double rtol, double atol, int max_it, int restart, int* iterations, double* residual_norms) {
+  const BlockOperand ops[2] = {{B, ldb, false}, {X, ldx, true}};
+  ALFI_CHECK(saddle_block_check(S, "alfi_saddle_solve_block", ncol, cols, nx, ops, 2));
+  alfi_ctx* ctx = S->ctx;
+  if (!iterations || !residual_norms) return alfi_set_error(ctx, ALFI_E_ARG, "alfi_saddle_solve_block: NULL result arrays");
+  if (restart < 1 || restart > RED_MAXV - 2) return alfi_set_error(ctx, ALFI_E_ARG, "restart must be in 1..%d", RED_MAXV - 2);
+  const int64_t n = S->nu_dofs + S->np_dofs;
+  const int need = block_slots_needed(S->blk_slots, ncol);
+  if (restart != S->blk_restart || need != S->blk_slots) {
+    ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    dev_free(S->blk_V);
+    dev_free(S->blk_Z);
+    dev_free(S->blk_w);
+    dev_free(S->blk_hs);
+    S->blk_V = S->blk_Z = S->blk_w = S->blk_hs = nullptr;
+    S->blk_restart = S->blk_slots = 0;
+    S->ldv = (n + 1) & ~(int64_t)1;             // (what alfi_saddle_solve sets too: a function of n alone)
+    HsLayout hl0(restart);
+    ALFI_CHECK(dev_alloc(ctx, &S->blk_V, (int64_t)need * (restart + 1) * S->ldv));
+    ALFI_CHECK(dev_alloc(ctx, &S->blk_Z, (int64_t)need * restart * S->ldv));
+    ALFI_CHECK(dev_alloc(ctx, &S->blk_w, (int64_t)need * S->ldv));
+    ALFI_CHECK(dev_alloc(ctx, &S->blk_hs, (int64_t)need * hl0.total));
+    S->blk_restart = restart;
+    S->blk_slots = need;
+  }
+  for (int q = 0; q < block_chunks(ncol); ++q)
+    ALFI_CHECK(saddle_solve_chunk(S, block_chunk(ncol, cols, q), B, ldb, X, ldx, rtol, atol, max_it, iterations + q * BLOCK_NV,
+                                  residual_norms + q * BLOCK_NV));
   return check_dev_err(ctx);
 }

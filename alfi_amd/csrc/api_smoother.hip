@@ -85,6 +85,27 @@ static int smooth_fgmres_fused(alfi_level* L, int k, const double* db, double* d
   return 0;
 }
 
+// Does alfi_smooth_fgmres(L, k, ...) take the four-launch iteration above?  *flat_spmv: with the flat product and the dots as a
+// pass of their own.  (The block smoother, api_block.hip, asks too: such a level is smoothed column by column.)
+bool smoother_takes_fused_iteration(const alfi_level* L, int k, bool* flat_spmv) {
+  // unpartitioned levels with short operator rows: the four-launch iteration (on the small levels a smoother iteration is
+  // launch latency, on the large 2-D ones the folded vector passes save BLAS-1 traffic, which is comparable to the patch
+  // traffic there): patch_sum_scale_kernel writes z_j and v_j in one pass (the normalisation follows the linear patch
+  // solves), the product is the lanes-per-row kernel with the dots folded in.
+  // Short rows = the 2-D operators (<= 32 blocks).  With the 50 .. 125 blocks per row of the 3-D ones the flat segmented
+  // product of the general path below is the faster kernel (config 3 19.0 against 18.9 ms, config 2 5.10 against 5.43, same
+  // box; with the bimodal rows of [P1+FB]^3 the lanes-per-row product idles most lanes: config 6 188.8 ms fused, 175.0
+  // general) ... except on levels of <= 50 000 dofs, which are bound by the number of dependent launches whatever the rows
+  // look like (config 3 18.66 -> 18.12-18.23 ms).  Sending every level here was measured too: nothing (config 3 17.33 /
+  // 17.35 ms, config 4 163.1 / 163.3, config 5 27.24 / 27.10).
+  constexpr int64_t small_n = 50000;
+  const bool fusable = !alfi_test_large_paths() && !L->distributed && L->n_own == L->n && !L->mult && k + 1 <= 16 &&
+                       L->A_own.flat && !L->jacobi;   // (the fused iteration launches the patch kernels itself)
+  const bool short_rows = L->max_row_blocks <= 32 || L->n <= small_n;
+  if (flat_spmv) *flat_spmv = !short_rows;
+  return fusable && short_rows;
+}
+
 int alfi_smooth_fgmres(alfi_level* L, int k, const double* db, double* dx, int nonzero_guess) {
   alfi_ctx* ctx = L->ctx;
   if (k < 1) return alfi_set_error(ctx, ALFI_E_ARG, "k must be >= 1");
@@ -92,21 +113,8 @@ int alfi_smooth_fgmres(alfi_level* L, int k, const double* db, double* dx, int n
   ALFI_CHECK(ensure_fgmres_workspace(L, k));
   ctx->cur_tag = L->id;
   {
-    // unpartitioned levels with short operator rows: the four-launch iteration (on the small levels a smoother iteration is
-    // launch latency, on the large 2-D ones the folded vector passes save BLAS-1 traffic, which is comparable to the patch
-    // traffic there): patch_sum_scale_kernel writes z_j and v_j in one pass (the normalisation follows the linear patch
-    // solves), the product is the lanes-per-row kernel with the dots folded in.
-    // Short rows = the 2-D operators (<= 32 blocks).  With the 50 .. 125 blocks per row of the 3-D ones the flat segmented
-    // product of the general path below is the faster kernel (config 3 19.0 against 18.9 ms, config 2 5.10 against 5.43, same
-    // box; with the bimodal rows of [P1+FB]^3 the lanes-per-row product idles most lanes: config 6 188.8 ms fused, 175.0
-    // general) ... except on levels of <= 50 000 dofs, which are bound by the number of dependent launches whatever the rows
-    // look like (config 3 18.66 -> 18.12-18.23 ms).  Sending every level here was measured too: nothing (config 3 17.33 /
-    // 17.35 ms, config 4 163.1 / 163.3, config 5 27.24 / 27.10).
-    constexpr int64_t small_n = 50000;
-    const bool fusable = !alfi_test_large_paths() && !L->distributed && L->n_own == L->n && !L->mult && k + 1 <= 16 &&
-                         L->A_own.flat && !L->jacobi;   // (the fused iteration launches the patch kernels itself)
-    const bool short_rows = L->max_row_blocks <= 32 || L->n <= small_n;
-    if (fusable && short_rows) return smooth_fgmres_fused(L, k, db, dx, nonzero_guess, !short_rows);
+    bool flat_spmv = false;
+    if (smoother_takes_fused_iteration(L, k, &flat_spmv)) return smooth_fgmres_fused(L, k, db, dx, nonzero_guess, flat_spmv);
   }
   const int K = L->kmax;
   const int64_t n = L->n_own;    // vector kernels and reductions run on the owned prefix

@@ -1,0 +1,63 @@
+// Block right-hand sides (alfi_*_block, include/alfi_hip.h): the arithmetic of column lists, chunks and lazily grown workspaces.
+// Host only, no HIP: api_block.hip includes it, and so can a stand-alone program built with host sanitizers.
+//
+// A block operand is column-major: column c of X is X + c * ldx, ldx >= n and even (16-byte aligned columns), nx columns in all.
+// A call names the columns it works on -- cols[0 .. ncol), distinct entries of [0, nx); NULL = 0, 1, ..., ncol - 1 -- so that a
+// caller drops converged columns without moving data.  One launch takes at most BLOCK_NV columns: a longer list is cut into
+// chunks of BLOCK_NV, the last one shorter.
+#pragma once
+#include <cstdint>
+
+constexpr int BLOCK_NV = 4;      // right-hand sides per stream of the stored values (piece_dot, row_piece.h)
+
+// the columns of one launch: a kernel argument, passed by value
+struct BlockCols {
+  int n;
+  int c[BLOCK_NV];
+};
+
+// NULL when (n, ncol, cols, nx, ldx) describe a block operand, else what is wrong with them
+inline const char* block_operand_error(int64_t n, int ncol, const int* cols, int nx, int64_t ldx) {
+  if (ncol < 1) return "ncol < 1";
+  if (nx < ncol) return "more columns listed than the operand has";
+  if (ldx < n) return "leading dimension below the vector length";
+  if (ldx & 1) return "odd leading dimension";
+  if (!cols) return nullptr;
+  for (int i = 0; i < ncol; ++i) {
+    if (cols[i] < 0 || cols[i] >= nx) return "column index out of range";
+    for (int j = 0; j < i; ++j)
+      if (cols[j] == cols[i]) return "column listed twice";
+  }
+  return nullptr;
+}
+
+// do the column-major operands X (ldx) and Y (ldy), nx columns of n entries each, share a byte?
+inline bool block_operands_overlap(const double* X, int64_t ldx, const double* Y, int64_t ldy, int nx, int64_t n) {
+  if (nx < 1 || n < 1) return false;
+  const uintptr_t x0 = (uintptr_t)X, x1 = x0 + sizeof(double) * (size_t)((nx - 1) * ldx + n);
+  const uintptr_t y0 = (uintptr_t)Y, y1 = y0 + sizeof(double) * (size_t)((nx - 1) * ldy + n);
+  return x0 < y1 && y0 < x1;
+}
+
+// chunks of a list of ncol columns
+inline int block_chunks(int ncol) { return (ncol + BLOCK_NV - 1) / BLOCK_NV; }
+
+// chunk k of the list (cols NULL: the identity list): the columns [BLOCK_NV k, min(ncol, BLOCK_NV (k + 1)))
+inline BlockCols block_chunk(int ncol, const int* cols, int k) {
+  BlockCols b;
+  const int first = k * BLOCK_NV;
+  b.n = ncol - first < BLOCK_NV ? ncol - first : BLOCK_NV;
+  if (b.n < 0) b.n = 0;
+  for (int i = 0; i < BLOCK_NV; ++i) {
+    const int q = first + (i < b.n ? i : 0);          // unused slots repeat the chunk's first column: always a valid index
+    b.c[i] = b.n == 0 ? 0 : cols ? cols[q] : q;
+  }
+  return b;
+}
+
+// A per-level workspace that holds `have` column slots and is asked to serve a call of ncol columns: the slots it has to hold
+// afterwards.  Grow-only, never more than one chunk.
+inline int block_slots_needed(int have, int ncol) {
+  const int want = ncol < BLOCK_NV ? ncol : BLOCK_NV;
+  return want > have ? want : have;
+}

@@ -58,6 +58,8 @@ struct alfi_ctx {
   int32_t* dev_err = nullptr;       // sticky device-side error word (a bounded wait of a persistent kernel ran out); read by
                                     // every call that synchronises (alfi_ctx_sync, alfi_memcpy_d2h)
   bool use_graph = false;           // alfi_ctx_set_graph: replay whole cycles as hipGraphs (not while profiling / partitioned)
+  bool block_kernels = true;        // alfi_ctx_set_block_kernels: block calls take the batched kernels where a level has them
+                                    // (false: every block call loops the single-vector call over its columns)
   void* big_arena = nullptr;        // scratch of the large-block factorisation (kernels_bigpatch.hip), kept between calls
   size_t big_arena_bytes = 0;
   void* asm_scratch = nullptr;      // element blocks / element vectors of the operator refresh (kernels_assemble.hip), grow-only
@@ -410,6 +412,13 @@ struct alfi_level {
   int il_G = 0, il_nc = 0;        // lanes per patch (row pairs), columns stored per patch (= max_np)
   bool il_valid = false;
   double* stage = nullptr;        // (sum ld_p) staged patch results
+  // block right-hand sides (api_block.hip), allocated by the first block call that needs them and grown to at most BLOCK_NV
+  // slots: staging buffers of the batched apply (blk_stage_slots x lay.stage_len; `stage` itself stays where captured cycles
+  // expect it), carries of the batched product's fix-up (blk_carry_slots x chunks x bs)
+  double* blk_stage = nullptr;
+  int blk_stage_slots = 0;
+  double* blk_carry = nullptr;
+  int blk_carry_slots = 0;
   int32_t* dof_ptr = nullptr;     // (n+1) CSR dof -> positions in stage
   int32_t* dof_pos = nullptr;     // (sum_n)
   bool factored = false;
@@ -460,6 +469,11 @@ struct alfi_level {
   double* Z = nullptr;   // kmax x n
   double* w = nullptr;   // n
   double* hs = nullptr;  // small device arrays: Hessenberg etc.
+  // alfi_smooth_fgmres_block: one such workspace per column slot in one allocation each, so that the Krylov vectors of the
+  // slots are the columns of a block operand -- v_j of slot s at blk_V + s * (blk_kmax + 1) * ldv + j * ldv, z_j at
+  // blk_Z + s * blk_kmax * ldv + j * ldv, w at blk_w + s * ldv, hs at blk_hs + s * HsLayout(blk_kmax).total
+  int blk_kmax = 0, blk_ws_slots = 0;
+  double *blk_V = nullptr, *blk_Z = nullptr, *blk_w = nullptr, *blk_hs = nullptr;
   // point-Jacobi level preconditioner (alfi_level_set_jacobi): replaces the patch solves in alfi_patch_apply and the smoothers
   bool jacobi = false;
   double* jac_diag = nullptr;        // (n) scalar diagonal of the operator, extracted from the diagonal blocks
@@ -473,6 +487,9 @@ struct alfi_level {
   double cinv_residual = -1.0;    // || A X e - e ||_inf of the inverse built by alfi_coarse_factor (-1: supplied by the caller)
   // multigrid work vectors (owned by alfi_mg but stored per level)
   double *mg_b = nullptr, *mg_x = nullptr, *mg_r = nullptr;
+  // the same for block cycles (alfi_mg_vcycle_block): blk_mg_slots columns of leading dimension n rounded up to even each
+  double *blk_mg_b = nullptr, *blk_mg_x = nullptr, *blk_mg_r = nullptr;
+  int blk_mg_slots = 0;
 };
 
 struct alfi_transfer {
@@ -557,6 +574,12 @@ struct alfi_saddle {
   int64_t ldv = 0;            // stride of V, Z: n rounded up to even
   double *V = nullptr, *Z = nullptr, *w = nullptr, *hs = nullptr, *tmp_u = nullptr, *tmp_p = nullptr;
   double* dotbuf = nullptr;   // result of alfi_saddle_dot (serial levels)
+  // block right-hand sides (alfi_saddle_solve_block): one outer workspace per column slot, each array ONE allocation -- v_j of
+  // slot s at blk_V + s * (blk_restart + 1) * ldv + j * ldv, z_j at blk_Z + s * blk_restart * ldv + j * ldv, w at
+  // blk_w + s * ldv, hs at blk_hs + s * HsLayout(blk_restart).total --, and blk_tmp_cols velocity work columns (leading
+  // dimension nu_dofs rounded up to even) for t = b_u - B^T y_p of alfi_saddle_precond_block, indexed by operand column
+  int blk_restart = 0, blk_slots = 0, blk_tmp_cols = 0;
+  double *blk_V = nullptr, *blk_Z = nullptr, *blk_w = nullptr, *blk_hs = nullptr, *blk_tmp_u = nullptr;
   // fieldsplit_0 (alfi_saddle_set_velocity_solver): ALFI_VELOCITY_MG (the full cycle of mg) or ALFI_VELOCITY_DIRECT (multifrontal
   // factors of the finest operator, held here -- not in fine->mf, which is the coarse slot when the finest level is level 0)
   int vkind = 0;
@@ -571,6 +594,20 @@ int launch_bsr_spmv(alfi_ctx* ctx, const DevBSR& A, const double* x, double* y, 
 // host (nnzb, bs, bs) values -> d->vals in d's layout (staged through a bounded device buffer)
 int upload_bsr_values(alfi_ctx* ctx, DevBSR* d, const double* host_vals);
 int build_spmv_dedup(alfi_ctx* ctx, DevBSR* d);     // column de-duplication tables of the flat product (kernels_vec.hip)
+// Block right-hand sides (kernels_block.hip; the operand layout and BlockCols: block_cols.h), one launch for 1 .. 4 columns:
+// entry i of cols names the column of the operands that are read (X, B), entry i of ocols the column of Y its result goes to.
+// The product: for operators bsr_spmv_block_batched accepts; carry: cols.n x ceil(nnzb / SPMV_CHUNK) x bs doubles.
+struct BlockCols;
+bool bsr_spmv_block_batched(const DevBSR& A);
+int launch_bsr_spmv_block(alfi_ctx* ctx, const DevBSR& A, const BlockCols& cols, const BlockCols& ocols, const double* X,
+                          int64_t ldx, double* Y, int64_t ldy, const double* B, int64_t ldb, double alpha, int mode, double* carry);
+// The additive apply, both stages: for levels whose single apply is patch_apply_kernel with W = patch_apply_dense_waves(lvl,
+// held == HELD_F32) != 0 waves per patch (kernels_patch.hip) that patch_apply_block_waves_ok accepts; stage: cols.n x
+// lay.stage_len doubles.
+int patch_apply_dense_waves(const alfi_level* lvl, bool f32);
+bool patch_apply_block_waves_ok(int W);
+int launch_patch_apply_block(alfi_level* lvl, int W, const BlockCols& cols, const BlockCols& ocols, const double* X, int64_t ldx,
+                             double* Y, int64_t ldy, double* stage);
 // The dense factor pipeline (alfi_patches_factor).  Every launcher takes `inv`, the base of the dense FP64 inverses it works on:
 // patch p at inv + inv_ptr[p].  That is lvl->inv for an FP64 level and the ctx's work buffer, biased by the range's first offset,
 // for an FP32 level (api_patches.hip: range_base).

@@ -1039,6 +1039,20 @@ int launch_patch_mult_persistent(alfi_level* L, const double* x, double* y) {
   return 0;
 }
 
+// Waves per patch with which the level's dense inverses -- FP64 or, f32, the single-precision copy -- go through
+// patch_apply_kernel: eight above 128 dofs (FP64: and on levels of few patches above 64), four above 64, one below.  0: they go
+// another way (macro stars, the macro stars' kernel on levels of very few patches, the interleaved copy), as the two functions
+// below decide.  The block apply (kernels_block.hip) asks too: it batches exactly the levels that get an answer here, with
+// these waves.
+int patch_apply_dense_waves(const alfi_level* L, bool f32) {
+  const int max_np = L->lay.max_np;
+  if (max_np > SMALL_PATCH_MAX) return 0;
+  if (f32) return max_np > 128 ? 2 * APPLY_W : max_np > 64 ? APPLY_W : 1;
+  const int64_t few = alfi_test_large_paths() ? 0 : 1000, fewer = alfi_test_large_paths() ? 0 : 256;
+  if ((max_np > 64 && L->npatch <= fewer) || L->il_valid) return 0;
+  return max_np > 128 || (max_np > 64 && L->npatch <= few) ? 2 * APPLY_W : max_np > 64 ? APPLY_W : 1;
+}
+
 // stage 1 for the patches [p0, p1) of a level with dense FP64 inverses at inv: the level's own, or the ones the factor pipeline
 // is working on (its probe; such a level has no interleaved copy)
 int launch_patch_apply_f64_range(alfi_level* L, const double* inv, int64_t p0, int64_t p1, const double* x) {
@@ -1056,7 +1070,7 @@ int launch_patch_apply_f64_range(alfi_level* L, const double* inv, int64_t p0, i
   // against 8.6 us).  Config 3: 17.27 -> 17.1 ms per cycle, same box.  A level with single-precision storage takes its waves
   // from the patch size alone.
   // (ALFI_TEST_LARGE_PATHS: no level counts as small, so that test hierarchies take the kernels of the large levels)
-  const int64_t few = alfi_test_large_paths() ? 0 : 1000, fewer = alfi_test_large_paths() ? 0 : 256;
+  const int64_t fewer = alfi_test_large_paths() ? 0 : 256;
   if (L->lay.max_np > 64 && L->npatch <= fewer) {     // kernels_bigpatch.hip
     ALFI_CHECK(launch_big_apply_range(L, inv, p0, p1, x));
     return 0;
@@ -1078,9 +1092,8 @@ int launch_patch_apply_f64_range(alfi_level* L, const double* inv, int64_t p0, i
     }
 #undef ALFI_IL
   } else {
-    // waves per patch: eight above 128 dofs (and on levels of few patches above 64), four above 64, one below
-    const int W = L->lay.max_np > 128 || (L->lay.max_np > 64 && L->npatch <= few) ? 2 * APPLY_W : L->lay.max_np > 64 ? APPLY_W : 1;
-    launch_patch_apply_w(ctx, W, p0, p1, L->patch_ptr, L->patch_dofs, L->inv_ptr, L->stage_ptr, inv, x, L->stage);
+    launch_patch_apply_w(ctx, patch_apply_dense_waves(L, false), p0, p1, L->patch_ptr, L->patch_dofs, L->inv_ptr, L->stage_ptr, inv,
+                         x, L->stage);
   }
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   return 0;
@@ -1101,8 +1114,8 @@ int launch_patch_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double
     ALFI_CHECK(launch_big_apply_f32_range(L, p0, p1, x));
     return 0;
   }
-  const int W = L->lay.max_np > 128 ? 2 * APPLY_W : L->lay.max_np > 64 ? APPLY_W : 1;
-  launch_patch_apply_w(ctx, W, p0, p1, L->patch_ptr, L->patch_dofs, L->inv32_ptr, L->stage_ptr, L->inv32, x, L->stage);
+  launch_patch_apply_w(ctx, patch_apply_dense_waves(L, true), p0, p1, L->patch_ptr, L->patch_dofs, L->inv32_ptr, L->stage_ptr,
+                       L->inv32, x, L->stage);
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   return 0;
 }

@@ -13,6 +13,13 @@
 // tests/test_gpu_row_piece_bits.py): ascending columns cg, cg + C, ... inside a lane, then the column groups by
 // acc += __shfl_xor(acc, o) for o = G, 2 G, ..., 32.  U and the tail policy change which loads are in flight together, never
 // the order of the sums.
+//
+// TWO bodies implement this order and must be kept in step: piece_dot / piece_apply for one vector (what every single-vector
+// kernel is compiled from) and their NV forms for 2 .. 4 vectors per stream (block right-hand sides, kernels_block.hip), whose
+// per-vector products and sums are the one-vector ones.  One template for both was tried three ways -- NV = 1 forwarded to the NV
+// body, `if constexpr (NV == 1)` around its stores, a shared per-value helper: each compiled the single-vector kernels of
+// kernels_bigpatch.hip or kernels_patch.hip to other code (scripts/device_code_equal.py), so the one-vector bodies stay verbatim.
+// tests/test_gpu_block_rhs.py compares the two bit for bit at every piece width.
 #pragma once
 #include <type_traits>
 #include "patch_plan.h"
@@ -116,6 +123,86 @@ __device__ __forceinline__ void piece_apply(const S* __restrict__ T, int stride,
 #pragma unroll
     for (int k = 0; k < V; ++k)
       if (ST == PieceStore::ALL || V * l + k < lim) out[V * l + k] = acc[k];
+  }
+}
+
+// ---- block right-hand sides: the same for NV = 2 .. 4 vectors per stream of the stored values -----------------------------------
+// acc[c][k] = sum over the columns j of (double)base[j * stride + k] * xs[j * NV + c]: every stored value is loaded ONCE and
+// multiplied into NV accumulators; the products and sums of right-hand side c are exactly those of piece_dot above on that
+// vector, in the order stated at the top (column c of a block apply is the single apply bit for bit).  xs: the NV gathered
+// vectors interleaved entry by entry, so that the NV values of a column are consecutive in LDS.
+// (A template of its own, not piece_dot with NV = 1 forwarded to it: the forwarded form compiles the macro stars' kernels to
+// other register allocations -- scripts/device_code_equal.py --, and the single-vector kernels are to stay what they were.)
+template <typename S, int G, bool NT, int U, bool BATCH_TAIL, int NV>
+__device__ __forceinline__ void piece_dot(const S* __restrict__ base, int stride, int n, const double* __restrict__ xs, int cg,
+                                          double (&acc)[NV][RowPiece<S>::V]) {
+  typedef typename RowPiece<S>::vec vec;
+  constexpr int C = 64 / G, V = RowPiece<S>::V;
+  static_assert(NV >= 1 && NV <= 4, "one to four right-hand sides per stream of the stored values");
+  auto fma_all = [&](const vec& v, int j) {      // the NV accumulators take one loaded value each
+#pragma unroll
+    for (int c = 0; c < NV; ++c) {
+      const double xj = xs[j * NV + c];
+#pragma unroll
+      for (int k = 0; k < V; ++k) acc[c][k] = __builtin_fma((double)v[k], xj, acc[c][k]);
+    }
+  };
+#pragma unroll
+  for (int c = 0; c < NV; ++c)
+#pragma unroll
+    for (int k = 0; k < V; ++k) acc[c][k] = 0.0;
+  int j = cg;
+  for (; j + (U - 1) * C < n; j += U * C) {
+    vec v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = piece_load<S, NT>(base + (int64_t)(j + u * C) * stride);
+#pragma unroll
+    for (int u = 0; u < U; ++u) fma_all(v[u], j + u * C);
+  }
+  if constexpr (BATCH_TAIL) {
+    if (j < n) {
+      const vec zero = {};
+      vec v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[u] = j + u * C < n ? piece_load<S, NT>(base + (int64_t)(j + u * C) * stride) : zero;
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (j + u * C < n) fma_all(v[u], j + u * C);
+    }
+  } else {
+    for (; j < n; j += C) fma_all(piece_load<S, NT>(base + (int64_t)j * stride), j);
+  }
+  if (C > 1) {
+#pragma unroll
+    for (int o = G; o < 64; o <<= 1) {
+#pragma unroll
+      for (int c = 0; c < NV; ++c)
+#pragma unroll
+        for (int k = 0; k < V; ++k) acc[c][k] += __shfl_xor(acc[c][k], o);
+    }
+  }
+}
+
+// piece_apply for NV vectors: the sums of right-hand side c go to out + c * ostride
+template <typename S, int G, bool NT, int U, bool BATCH_TAIL, PieceStore ST, int NV>
+__device__ __forceinline__ void piece_apply(const S* __restrict__ T, int stride, int n, const double* __restrict__ xs, int lane,
+                                            double* __restrict__ out, int ostride, int lim) {
+  constexpr int V = RowPiece<S>::V;
+  const int cg = lane / G, l = lane % G;
+  double acc[NV][V];
+  piece_dot<S, G, NT, U, BATCH_TAIL, NV>(T + V * l, stride, n, xs, cg, acc);
+  if (cg != 0) return;
+#pragma unroll
+  for (int c = 0; c < NV; ++c) {
+    double* o = out + c * ostride;
+    if constexpr (ST == PieceStore::PAIR) {
+      static_assert(V == 2, "a row pair");
+      *reinterpret_cast<double2*>(o + 2 * l) = make_double2(acc[c][0], acc[c][1]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < V; ++k)
+        if (ST == PieceStore::ALL || V * l + k < lim) o[V * l + k] = acc[c][k];
+    }
   }
 }
 

@@ -98,6 +98,23 @@ class Context(object):
         v.set(a)
         return v
 
+    def mat(self, n_or_array, ncol=None, ld=None):
+        """A block operand (DeviceMat): ``mat(n, ncol)`` zeroed, or ``mat(array)`` from an (n, ncol) array, one column per
+        right-hand side; ``ld``: its leading dimension (default: n rounded up to even)."""
+        if isinstance(n_or_array, (int, np.integer)):
+            return DeviceMat(self, int(n_or_array), int(ncol), ld)
+        a = np.asarray(n_or_array, dtype=np.float64)
+        if a.ndim != 2:
+            raise ValueError("a block operand is an (n, ncol) array")
+        m = DeviceMat(self, a.shape[0], a.shape[1], ld)
+        m.set(a)
+        return m
+
+    def set_block_kernels(self, on=True):
+        """Block calls take the batched kernels where a level has them (alfi_ctx_set_block_kernels; default on).  Off: every
+        block call loops the single-vector call over its columns -- the same bits at the cost of ncol single calls."""
+        self.check(self.lib.alfi_ctx_set_block_kernels(self.h, 1 if on else 0))
+
     # profiling (PETSc-event style report, driver.py:77-92) ----------------------------------------------------------------
     def transfer_stats(self, reset=False):
         """(bytes host -> device, bytes device -> host) of every copy the library made since the last reset, process-wide
@@ -189,6 +206,53 @@ class DeviceVec(object):
         except Exception:
             pass
         self.ptr = None
+
+
+class DeviceMat(object):
+    """A block operand of the ``*_block`` calls: ncol right-hand sides as the columns of a column-major device matrix, column c
+    at ``ptr + 8 c ld`` (``ld`` >= n and even, so that every column is 16-byte aligned).  The entries between n and ld are never
+    read or written by the library."""
+
+    def __init__(self, ctx, n, ncol, ld=None):
+        self.ctx, self.n, self.ncol = ctx, int(n), int(ncol)
+        self.ld = (self.n + 1) & ~1 if ld is None else int(ld)
+        if self.ncol < 1 or self.ld < self.n or self.ld & 1:
+            raise ValueError("a block operand needs ncol >= 1 and an even leading dimension >= n (n %d, ncol %d, ld %d)"
+                             % (self.n, self.ncol, self.ld))
+        self._buf = DeviceVec(ctx, max(self.ld * self.ncol, 1))
+        self._buf.zero()
+        self.ptr = self._buf.ptr
+
+    def set(self, a):
+        a = np.asarray(a, dtype=np.float64)
+        assert a.shape == (self.n, self.ncol), (a.shape, self.n, self.ncol)
+        h = np.zeros((self.ncol, self.ld))
+        h[:, :self.n] = a.T
+        self._buf.set(h.ravel())
+
+    def get(self):
+        """The (n, ncol) array."""
+        return np.ascontiguousarray(self._buf.get().reshape(self.ncol, self.ld)[:, :self.n].T)
+
+    def col(self, c):
+        """Column c as a device vector (no copy)."""
+        assert 0 <= c < self.ncol
+        return view(self._buf, c * self.ld, self.n)
+
+    def zero(self):
+        self._buf.zero()
+
+
+def _block_args(n, cols, *mats):
+    """(ncol, cols pointer, nx, kept array) of a block call on the DeviceMats ``mats`` of n-vectors; cols None: every column."""
+    nx = mats[0].ncol
+    for m in mats:
+        if m.n != n or m.ncol != nx:
+            raise ValueError("block operands of %d columns of length %d expected, got %d of length %d" % (nx, n, m.ncol, m.n))
+    if cols is None:
+        return nx, None, nx, None
+    c = np.ascontiguousarray(cols, dtype=np.int32)
+    return len(c), _ptr(c), nx, c
 
 
 class IntVec(object):
@@ -601,6 +665,45 @@ class Level(object):
     def smooth(self, k, b, x, nonzero_guess=True):
         self.ctx.check(self.ctx.lib.alfi_smooth_fgmres(self.h, int(k), b.ptr, x.ptr, 1 if nonzero_guess else 0))
 
+    # block right-hand sides (DeviceMat operands; cols: the columns to work on, None = all) -- column c of every result is the
+    # single-vector call on column c bit for bit
+    def patch_apply_block(self, X, Y, cols=None):
+        ncol, cp, nx, keep = _block_args(self.n, cols, X, Y)
+        self.ctx.check(self.ctx.lib.alfi_patch_apply_block(self.h, ncol, cp, nx, X.ptr, X.ld, Y.ptr, Y.ld))
+
+    def spmv_block(self, X, Y, cols=None):
+        ncol, cp, nx, keep = _block_args(self.n, cols, X, Y)
+        self.ctx.check(self.ctx.lib.alfi_spmv_block(self.h, ncol, cp, nx, X.ptr, X.ld, Y.ptr, Y.ld))
+
+    def residual_block(self, B, X, R, cols=None):
+        ncol, cp, nx, keep = _block_args(self.n, cols, B, X, R)
+        self.ctx.check(self.ctx.lib.alfi_residual_block(self.h, ncol, cp, nx, B.ptr, B.ld, X.ptr, X.ld, R.ptr, R.ld))
+
+    def smooth_block(self, k, B, X, nonzero_guess=True, cols=None):
+        ncol, cp, nx, keep = _block_args(self.n, cols, B, X)
+        self.ctx.check(self.ctx.lib.alfi_smooth_fgmres_block(self.h, int(k), ncol, cp, nx, B.ptr, B.ld, X.ptr, X.ld,
+                                                             1 if nonzero_guess else 0))
+
+    def patch_apply_block_batched(self):
+        """Does a block apply of two or more columns on this level, as it stands, take the batched kernel
+        (alfi_patch_apply_block_info)?  False: it loops the single apply."""
+        b = ctypes.c_int()
+        self.ctx.check(self.ctx.lib.alfi_patch_apply_block_info(self.h, ctypes.byref(b)))
+        return bool(b.value)
+
+    def smooth_block_lockstep(self, k):
+        """Does ``smooth_block(k, ...)`` on two or more columns run the smoother's general path in lockstep (one block apply and
+        one block product per iteration; alfi_smooth_fgmres_block_info)?  False: whole smoother calls loop over the columns."""
+        b = ctypes.c_int()
+        self.ctx.check(self.ctx.lib.alfi_smooth_fgmres_block_info(self.h, int(k), ctypes.byref(b)))
+        return bool(b.value)
+
+    def spmv_block_batched(self):
+        """The same for the product and the residual (alfi_spmv_block_info)."""
+        b = ctypes.c_int()
+        self.ctx.check(self.ctx.lib.alfi_spmv_block_info(self.h, ctypes.byref(b)))
+        return bool(b.value)
+
     def set_jacobi(self, on=True):
         """pc_type jacobi (alfi_level_set_jacobi): the level's preconditioner application -- ``patch_apply`` and every smoother --
         becomes y = x / diag(A) (y = x on Dirichlet dofs); such a level needs no patches.  Serial levels only."""
@@ -882,6 +985,15 @@ class Multigrid(object):
     def fcycle(self, b, x):
         self.ctx.check(self.ctx.lib.alfi_mg_fcycle(self.h, b.ptr, x.ptr))
 
+    def vcycle_block(self, B, X, cols=None):
+        """``vcycle`` on the columns of the DeviceMats B and X (alfi_mg_vcycle_block; eager, never a captured graph)."""
+        ncol, cp, nx, keep = _block_args(self.levels[-1].n, cols, B, X)
+        self.ctx.check(self.ctx.lib.alfi_mg_vcycle_block(self.h, ncol, cp, nx, B.ptr, B.ld, X.ptr, X.ld))
+
+    def fcycle_block(self, B, X, cols=None):
+        ncol, cp, nx, keep = _block_args(self.levels[-1].n, cols, B, X)
+        self.ctx.check(self.ctx.lib.alfi_mg_fcycle_block(self.h, ncol, cp, nx, B.ptr, B.ld, X.ptr, X.ld))
+
     SMOOTHERS = {"fgmres": 0, "chebyshev": 1}      # ALFI_SMOOTHER_FGMRES / ALFI_SMOOTHER_CHEBYSHEV
     CYCLES = {"v": 1, "w": 2}
 
@@ -1088,6 +1200,26 @@ class Saddle(object):
         self.ctx.check(self.ctx.lib.alfi_saddle_solve(self.h, b.ptr, x.ptr, float(rtol), float(atol), int(max_it),
                                                       int(restart), ctypes.byref(its), ctypes.byref(rn)))
         return its.value, rn.value
+
+    # block right-hand sides (DeviceMats of n_u + n_p rows; cols: the columns to work on, None = all) -- column c of every
+    # result is the single call on column c bit for bit
+    def mult_block(self, X, Y, cols=None):
+        ncol, cp, nx, keep = _block_args(self.n, cols, X, Y)
+        self.ctx.check(self.ctx.lib.alfi_saddle_mult_block(self.h, ncol, cp, nx, X.ptr, X.ld, Y.ptr, Y.ld))
+
+    def precond_block(self, X, Y, cols=None):
+        ncol, cp, nx, keep = _block_args(self.n, cols, X, Y)
+        self.ctx.check(self.ctx.lib.alfi_saddle_precond_block(self.h, ncol, cp, nx, X.ptr, X.ld, Y.ptr, Y.ld))
+
+    def solve_block(self, B, X, rtol=1e-8, atol=1e-8, max_it=500, restart=30, cols=None):
+        """``solve`` on the listed columns in lockstep (alfi_saddle_solve_block): every column has its own tolerance
+        max(rtol |b_c|, atol), iteration count and restarts, and drops out when it has converged.  Returns (iterations,
+        true residual norms), one entry per listed column."""
+        ncol, cp, nx, keep = _block_args(self.n, cols, B, X)
+        its, rn = np.zeros(max(ncol, 1), dtype=np.int32), np.zeros(max(ncol, 1))
+        self.ctx.check(self.ctx.lib.alfi_saddle_solve_block(self.h, ncol, cp, nx, B.ptr, B.ld, X.ptr, X.ld, float(rtol), float(atol),
+                                                            int(max_it), int(restart), _ptr(its), _ptr(rn)))
+        return [int(i) for i in its[:ncol]], [float(r) for r in rn[:ncol]]
 
     def close(self):
         if self.h:

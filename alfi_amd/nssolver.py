@@ -606,7 +606,9 @@ class HipNavierStokesSolver(object):
         return setup_adjoint(self, J)
 
     def solve_adjoint(self, J, rtol=None, atol=None):
-        """``setup_adjoint(J)`` and one adjoint solve: returns (z_adj, info)."""
+        """``setup_adjoint(J)`` and one adjoint solve: returns (z_adj, info).  J a list or tuple of functionals: ONE refresh,
+        transpose and factorisation and one block solve; z_adj is then a list of (lam_u, lam_p), and ``linear_iter``,
+        ``residual_norm``, ``rhs_norm`` and ``converged`` of info are lists."""
         info = self.setup_adjoint(J).solve(rtol=rtol, atol=atol)
         return self.z_adj, info
 

@@ -282,6 +282,47 @@ def _as_device(ctx, v, n):
     return ctx.vec(arr), arr
 
 
+def _dense_array(M):
+    """The (n, ncol) array behind a dense operand of ``matApply``: a NumPy array, or anything with getDenseArray() (a
+    petsc4py dense Mat, one column per right-hand side)."""
+    return np.asarray(M.getDenseArray() if hasattr(M, "getDenseArray") else M)
+
+
+def check_mat_apply_args(X, Y, n):
+    """The operands of a ``matApply(pc, X, Y)`` (PETSc's PCMatApply, which KSPMatSolve calls): dense, one column of n
+    entries per right-hand side, as many columns in Y as in X, X and Y distinct.  Each is a hip.DeviceMat or a host array
+    (``_dense_array``).  ValueError before anything touches the device; returns the number of columns."""
+    shapes = []
+    for name, M in (("X", X), ("Y", Y)):
+        if isinstance(M, hip.DeviceMat):
+            shapes.append((M.n, M.ncol))
+            continue
+        a = _dense_array(M)
+        if a.ndim != 2 or a.dtype != np.float64:
+            raise ValueError("matApply: %s must be a dense float64 matrix with one column per right-hand side, got %s %s"
+                             % (name, a.dtype, a.shape))
+        shapes.append(a.shape)
+    if X is Y or (not isinstance(X, hip.DeviceMat) and not isinstance(Y, hip.DeviceMat)
+                  and np.shares_memory(_dense_array(X), _dense_array(Y))):
+        raise ValueError("matApply: X and Y must not alias")
+    for name, s in zip("XY", shapes):
+        if s[0] != n or s[1] < 1:
+            raise ValueError("matApply: %s is %d x %d, expected %d rows and at least one column" % (name, s[0], s[1], n))
+    if shapes[0][1] != shapes[1][1]:
+        raise ValueError("matApply: X has %d columns, Y has %d" % (shapes[0][1], shapes[1][1]))
+    if not isinstance(Y, hip.DeviceMat) and not _dense_array(Y).flags.writeable:
+        raise ValueError("matApply: Y is read-only")
+    return shapes[0][1]
+
+
+def _as_device_mat(ctx, M):
+    """(DeviceMat, writeback) for a checked operand of ``matApply``"""
+    if isinstance(M, hip.DeviceMat):
+        return M, None
+    a = _dense_array(M)
+    return ctx.mat(a), a
+
+
 class HipPatchPC(object):
     """PCPATCH on the GPU behind the PCPython protocol (solver.py:15-38 shows the protocol)."""
 
@@ -394,6 +435,16 @@ class HipPatchPC(object):
         if ywb is not None:
             ywb[:] = dy.get()
 
+    def matApply(self, pc, X, Y):
+        """PCMatApply: ``apply`` on every column of the dense X into the same column of Y (hip.Level.patch_apply_block: the
+        patch factors are streamed once for up to four columns where the level batches)."""
+        check_mat_apply_args(X, Y, self.n)
+        dX, _ = _as_device_mat(pc.ctx, X)
+        dY, ywb = _as_device_mat(pc.ctx, Y)
+        self.level.patch_apply_block(dX, dY)
+        if ywb is not None:
+            ywb[...] = dY.get()
+
     def applyTranspose(self, pc, x, y):
         raise NotImplementedError("Sorry!")
 
@@ -478,6 +529,20 @@ class HipMG(object):
             self.mg.vcycle(db, dx)
         if xwb is not None:
             xwb[:] = dx.get()
+
+    def matApply(self, B, X):
+        """``apply`` on every column of the dense B into the same column of X (PCMatApply's shape; hip.Multigrid.fcycle_block /
+        vcycle_block)."""
+        check_mat_apply_args(B, X, self.n)
+        dB, _ = _as_device_mat(self.ctx, B)
+        dX, xwb = _as_device_mat(self.ctx, X)
+        if self.full:
+            self.mg.fcycle_block(dB, dX)
+        else:
+            dX.zero()
+            self.mg.vcycle_block(dB, dX)
+        if xwb is not None:
+            xwb[...] = dX.get()
 
 
 class HipJacobiPC(object):
@@ -573,6 +638,13 @@ class DGMassInv(object):
 
     def apply(self, pc, x, y):
         y[...] = -(self.nu + self.gamma) * self.minv * np.asarray(x)
+
+    def matApply(self, pc, X, Y):
+        """PCMatApply: ``apply`` on every column of the dense host matrix X into the same column of Y."""
+        check_mat_apply_args(X, Y, len(self.minv))
+        if isinstance(X, hip.DeviceMat) or isinstance(Y, hip.DeviceMat):
+            raise ValueError("DGMassInv.matApply works on host matrices")
+        _dense_array(Y)[...] = -(self.nu + self.gamma) * self.minv[:, None] * _dense_array(X)
 
     def applyTranspose(self, pc, x, y):
         raise NotImplementedError("Sorry!")

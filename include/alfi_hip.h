@@ -597,6 +597,54 @@ int alfi_saddle_factor_velocity(alfi_saddle* s, const double* node_coords, int d
 int alfi_saddle_velocity_solve(alfi_saddle* s, const double* db, double* dx);
 int alfi_saddle_velocity_info(alfi_saddle* s, int64_t* bytes, double* probe_residual);
 
+/* ---- block right-hand sides: one stream of the stored values for up to four vectors -------------------------------------- */
+/* A block operand is a column-major device matrix: column c of X is X + c * ldx, nx columns in all, ldx >= the vector length and
+ * even.  Every call names the columns it works on: cols[0 .. ncol), distinct entries of [0, nx), or NULL for 0 .. ncol - 1 -- a
+ * caller drops converged columns without moving data.  Column c of every result equals the single-vector call on column c BIT
+ * FOR BIT.  Lists of more than four columns are taken four at a time.  Where a level has a batched kernel, a chunk of two to
+ * four columns is ONE launch that reads the stored values once: the additive apply of dense patch inverses of 33 .. 160 dofs
+ * in either storage precision (the levels whose single apply gives a workgroup to every patch) and the nnz-balanced flat
+ * product without column de-duplication.  Everything else runs the single-vector code column after column inside the library:
+ * the interleaved copy of small patches, macro stars, levels of few patches, condensed factors, multiplicative sweeps, point
+ * Jacobi, the de-duplicated and the lanes-per-row product, the four-launch smoother iteration, Chebyshev, transfers, coarse
+ * solves.  A chunk of one column always does.  alfi_patch_apply_block_info / alfi_spmv_block_info: does the level, as it stands,
+ * batch?  alfi_ctx_set_block_kernels(ctx, 0) makes every block call loop (default on): same bits, the cost of ncol single calls.
+ * Serial levels only.  ALFI_E_ARG before any device work, nothing touched: a partitioned level, ncol < 1 or > nx, an odd
+ * leading dimension or one below the vector length, a column index outside [0, nx) or listed twice, a NULL operand, an operand
+ * that is written overlapping another one. */
+int alfi_ctx_set_block_kernels(alfi_ctx* ctx, int on);
+int alfi_patch_apply_block_info(alfi_level* lvl, int* batched);
+int alfi_spmv_block_info(alfi_level* lvl, int* batched);
+/* Y[:, c] = alfi_patch_apply of X[:, c] */
+int alfi_patch_apply_block(alfi_level* lvl, int ncol, const int* cols, int nx, const double* X, int64_t ldx, double* Y, int64_t ldy);
+/* Y[:, c] = A X[:, c];  R[:, c] = B[:, c] - A X[:, c] */
+int alfi_spmv_block(alfi_level* lvl, int ncol, const int* cols, int nx, const double* X, int64_t ldx, double* Y, int64_t ldy);
+int alfi_residual_block(alfi_level* lvl, int ncol, const int* cols, int nx, const double* B, int64_t ldb, const double* X,
+                        int64_t ldx, double* R, int64_t ldr);
+/* alfi_smooth_fgmres on every column: its general path in lockstep, one Krylov workspace per column (allocated at first use,
+ * freed with the level), ONE block apply and ONE block product per iteration; a level on which the single call takes the
+ * four-launch iteration of small levels is smoothed column by column. */
+int alfi_smooth_fgmres_block_info(alfi_level* lvl, int k, int* lockstep);   /* which of the two, for this level and k */
+int alfi_smooth_fgmres_block(alfi_level* lvl, int k, int ncol, const int* cols, int nx, const double* B, int64_t ldb, double* X,
+                             int64_t ldx, int nonzero_guess);
+/* alfi_mg_vcycle / alfi_mg_fcycle on every column (columns of the finest level's length), run eagerly: block cycles are never
+ * captured as graphs.  Smoothers and residuals are the block forms above; transfers and the coarse solve go column by column. */
+int alfi_mg_vcycle_block(alfi_mg* mg, int ncol, const int* cols, int nx, const double* B, int64_t ldb, double* X, int64_t ldx);
+int alfi_mg_fcycle_block(alfi_mg* mg, int ncol, const int* cols, int nx, const double* B, int64_t ldb, double* X, int64_t ldx);
+/* alfi_saddle_mult / alfi_saddle_precond on every column (columns of n_u + n_p entries): the velocity-block product and the
+ * full cycles are the block forms above, the divergence / gradient products, the Schur solve and the mean removal run per column;
+ * with ALFI_VELOCITY_DIRECT the whole preconditioner runs per column.  ALFI_E_ARG on a partitioned finest level. */
+int alfi_saddle_mult_block(alfi_saddle* s, int ncol, const int* cols, int nx, const double* X, int64_t ldx, double* Y, int64_t ldy);
+int alfi_saddle_precond_block(alfi_saddle* s, int ncol, const int* cols, int nx, const double* X, int64_t ldx, double* Y, int64_t ldy);
+/* alfi_saddle_solve on every listed column in lockstep (four columns at a time): each column has its own Krylov workspace
+ * (allocated at first use, freed with the saddle), its own tolerance max(rtol |b_c|, atol), iteration count and restarts; a
+ * column that converges is finished at its own iteration and leaves the list, the call ends when the list is empty or max_it is
+ * reached.  ONE block preconditioner application and ONE block product per iteration for the columns still active; the
+ * per-iteration read-back fetches all active columns' values with one synchronisation.  iterations[i], residual_norms[i]
+ * (true residual) belong to the i-th listed column; a zero column takes 0 iterations, as in the single call. */
+int alfi_saddle_solve_block(alfi_saddle* s, int ncol, const int* cols, int nx, const double* B, int64_t ldb, double* X, int64_t ldx,
+                            double rtol, double atol, int max_it, int restart, int* iterations, double* residual_norms);
+
 #ifdef __cplusplus
 }
 #endif

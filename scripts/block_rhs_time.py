@@ -1,0 +1,114 @@
+"""Block right-hand sides against looping: time per block patch apply, per block product and per full cycle at 1, 2 and 4
+columns, the batched kernels on and off (Context.set_block_kernels: off = the single-vector call per column, which is what a
+caller paid before block calls existed), on one bench configuration with DENSE patch inverses, in ONE process.  The hierarchy is
+set up once; the two modes alternate, round after round.
+
+usage: timeout -k 10 900 python scripts/block_rhs_time.py cfg3 [--rounds 3] [--reps 20] [--cycles 3] [--dtype f32] [--out FILE]
+(one GPU step = one process: give each its own time limit)
+
+Per level with patches and per ncol: best ms per block apply (both stages) and per block product over the rounds, on / off and
+their ratio, and the stored bytes (alfi_patches_factor_bytes; operator values + column indices) per second of the batched call.
+ncol = 1 always takes the single-vector path, whatever the switch says.  The bytes argument: a batched apply of 4 columns moves
+8 n_p^2 + 4 * 20 n_p bytes per patch where 4 single applies move 4 (8 n_p^2 + 20 n_p): 0.26-0.27 of the time at n_p = 111-153
+while it stays bandwidth-bound."""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+NCOLS = (1, 2, 4)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("cfg")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--cycles", type=int, default=3)
+    ap.add_argument("--dtype", default=None, choices=[None, "f32"])
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    import bench
+    from alfi_amd import hip
+    if not torch.cuda.is_available():
+        raise SystemExit("block_rhs_time.py measures on the GPU; none is visible")
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+    t0 = time.time()
+    lv, tr, k = bench.build_problem(args.cfg, False)
+    say("%s: %s" % (args.cfg, bench.describe(args.cfg)))
+    say("hierarchy generated on the host in %.1f s; patches per level %s, largest patch %d dofs"
+        % (time.time() - t0, [len(L.patch_ptr) - 1 for L in lv[1:]], int(np.diff(lv[-1].patch_ptr).max())))
+    ctx = hip.Context(0)
+    ctx.set_condense_min_bytes(-1)                  # dense inverses on every level (condensed levels loop: nothing to compare)
+    mg = hip.Multigrid(ctx, lv, tr, k, patch_factor_dtype=args.dtype)
+    say("dense %s inverses; per level (dofs, patches, factor GB, apply batched, product batched): %s"
+        % (args.dtype or "f64", ["%d/%d/%.3f/%d/%d" % (d.n, len(L.patch_ptr) - 1, d.factor_bytes() / 1e9, d.patch_apply_block_batched(),
+                                                       d.spmv_block_batched()) for L, d in zip(lv[1:], mg.levels[1:])]))
+    rng = np.random.default_rng(0)
+
+    def timed(fn, reps):
+        ctx.sync()
+        t0 = time.time()
+        for _ in range(reps):
+            fn()
+        ctx.sync()
+        return 1e3 * (time.time() - t0) / reps
+
+    work = []      # (label, stored bytes or None, {ncol: callable})
+    for L, dl in zip(lv[1:], mg.levels[1:]):
+        X = {c: ctx.mat(rng.standard_normal((dl.n, c))) for c in NCOLS}
+        Y = {c: ctx.mat(dl.n, c) for c in NCOLS}
+        work.append(("level %d apply  " % dl.id, dl.factor_bytes(),
+                     {c: (lambda dl=dl, c=c, X=X, Y=Y: dl.patch_apply_block(X[c], Y[c])) for c in NCOLS}))
+        work.append(("level %d product" % dl.id, dl.nnzb * (8 * dl.bs * dl.bs + 4),
+                     {c: (lambda dl=dl, c=c, X=X, Y=Y: dl.spmv_block(X[c], Y[c])) for c in NCOLS}))
+    fine = lv[-1]
+    Bf = rng.standard_normal((fine.n, max(NCOLS)))
+    Bf[fine.bc_dofs] = 0.0
+    B = {c: ctx.mat(Bf[:, :c]) for c in NCOLS}
+    Xf = {c: ctx.mat(fine.n, c) for c in NCOLS}
+    work.append(("full cycle      ", None, {c: (lambda c=c: mg.fcycle_block(B[c], Xf[c])) for c in NCOLS}))
+    res = {(w[0], c, on): [] for w in work for c in NCOLS for on in (True, False)}
+    for on in (True, False):                        # warm-up: every shape, both modes (the lazy workspaces are allocated here)
+        ctx.set_block_kernels(on)
+        for label, _, fns in work:
+            for c in NCOLS:
+                fns[c]()
+    ctx.sync()
+    for _ in range(args.rounds):
+        for on in (True, False):
+            ctx.set_block_kernels(on)
+            for label, _, fns in work:
+                for c in NCOLS:
+                    res[(label, c, on)].append(timed(fns[c], args.cycles if label.startswith("full") else args.reps))
+    ctx.set_block_kernels(True)
+    say()
+    say("best ms per call over %d rounds (%d calls each, cycles %d), modes alternating; on = batched kernels, off = looped:"
+        % (args.rounds, args.reps, args.cycles))
+    say("  %-18s ncol       on      off   on/off   on/(ncol x single)   stored TB/s (on)" % "")
+    for label, nbytes, _ in work:
+        single = min(res[(label, 1, False)])
+        for c in NCOLS:
+            on, off = min(res[(label, c, True)]), min(res[(label, c, False)])
+            say("  %-18s %4d %8.4f %8.4f   %6.3f   %18.3f   %s"
+                % (label, c, on, off, on / off, on / (c * single), "%16.3f" % (nbytes / (on * 1e-3) / 1e12) if nbytes else ""))
+    say()
+    say("spread over the rounds (max - min, ms), finest level apply at 4 columns: on %.4f, off %.4f"
+        % tuple(max(res[(work[-3][0], 4, on)]) - min(res[(work[-3][0], 4, on)]) for on in (True, False)))
+    mg.close()
+    ctx.close()
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
