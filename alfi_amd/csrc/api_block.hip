@@ -4,7 +4,9 @@
 // Column c of every block result is the single-vector call's result on column c bit for bit.  A list of more than BLOCK_NV
 // columns is taken BLOCK_NV at a time.  Where a level has a batched kernel (kernels_block.hip: dense inverses through
 // patch_apply_kernel, the flat product) a chunk of two or more columns is ONE launch that streams the stored values once;
-// everything else -- and every chunk of one column -- is the single-vector code, column after column.
+// condensed factors of at least COND_PER_PATCH_MIN patches (kernels_block_cond.hip) take a chunk in pieces of as many columns
+// as fit the LDS budget (block_cond_width); everything else -- and every chunk or piece of one column -- is the single-vector
+// code, column after column.
 #include "api_internal.h"
 #include "block_cols.h"
 
@@ -15,12 +17,25 @@ int alfi_ctx_set_block_kernels(alfi_ctx* ctx, int on) {
 }
 
 // ---- which way a level goes ----------------------------------------------------------------------------------------------------
-// waves per patch of the batched apply, 0: the level's apply loops
+// waves per patch of the batched apply of dense inverses, 0: the level holds none, or its apply loops
 static int block_apply_waves(const alfi_level* L) {
   if (!L->ctx->block_kernels || !L->factored || L->jacobi || L->mult || level_is_partitioned(L)) return 0;
-  if (L->held != HELD_F64 && L->held != HELD_F32) return 0;            // condensed factors
+  if (L->held != HELD_F64 && L->held != HELD_F32) return 0;            // condensed factors: block_cond_apply_width
   const int W = patch_apply_dense_waves(L, L->held == HELD_F32);
   return patch_apply_block_waves_ok(W) ? W : 0;
+}
+// Condensed factors: the widest batch of the level (block_cond_width, block_cols.h), 0: its apply loops.  What batches is the
+// workgroup-per-patch form (kernels_block_cond.hip): a level of fewer than COND_PER_PATCH_MIN patches takes the chunked form
+// and loops; so does a level whose LDS does not fit two columns into the ctx's budget.
+static int block_cond_apply_width(const alfi_level* L) {
+  if (!L->ctx->block_kernels || !L->factored || L->jacobi || L->mult || level_is_partitioned(L)) return 0;
+  if (L->held != HELD_COND || L->npatch < COND_PER_PATCH_MIN) return 0;
+  if (L->lay.sum_n > INT32_MAX / BLOCK_NV) return 0;      // (piece_apply takes the stride between two columns' slots as an int)
+  return block_cond_width(L->cplan.lds_front, L->cplan.lds_back, L->ctx->block_lds_bytes);
+}
+// the widest batch of the level's apply: BLOCK_NV for dense inverses that batch, the condensed width, 0: it loops
+static int block_apply_width(const alfi_level* L) {
+  return block_apply_waves(L) != 0 ? BLOCK_NV : block_cond_apply_width(L);
 }
 static bool block_spmv_batched(const alfi_level* L) {
   return L->ctx->block_kernels && !level_is_partitioned(L) && bsr_spmv_block_batched(L->A_own);
@@ -28,7 +43,21 @@ static bool block_spmv_batched(const alfi_level* L) {
 
 int alfi_patch_apply_block_info(alfi_level* L, int* batched) {
   if (!L || !batched) return alfi_set_error(L ? L->ctx : nullptr, ALFI_E_ARG, "alfi_patch_apply_block_info: NULL argument");
-  *batched = block_apply_waves(L) != 0 ? 1 : 0;
+  *batched = block_apply_width(L) >= 2 ? 1 : 0;
+  return 0;
+}
+int alfi_patch_apply_block_width(alfi_level* L, int* width) {
+  if (!L || !width) return alfi_set_error(L ? L->ctx : nullptr, ALFI_E_ARG, "alfi_patch_apply_block_width: NULL argument");
+  *width = block_apply_width(L);
+  return 0;
+}
+// LDS a workgroup of the condensed block apply may ask for (default 64 KiB: no launch needs its limit raised, and as many
+// workgroups share a CU as in a plain launch), clamped to what the device gives one workgroup
+int alfi_ctx_set_block_lds_bytes(alfi_ctx* ctx, int64_t bytes) {
+  if (!ctx) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL context");
+  int limit = 0;
+  ALFI_HIP_CHECK(ctx, hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+  ctx->block_lds_bytes = (int)std::min<int64_t>(std::max<int64_t>(bytes, 0), limit);
   return 0;
 }
 // does alfi_smooth_fgmres_block(L, k, ...) on two or more columns run in lockstep (one block apply and one block product per
@@ -50,7 +79,7 @@ int alfi_spmv_block_info(alfi_level* L, int* batched) {
 // ---- lazily grown workspaces ---------------------------------------------------------------------------------------------------
 // *buf holds *slots column slots of `per` doubles (0 slots: not allocated yet) and is asked to serve ncol >= 1 columns
 // (block_slots_needed: grow-only).  `per` is fixed while the buffer lives: the staging length until the next alfi_patches_set,
-// which frees blk_stage; the chunk count of the level's operator, which is set at alfi_level_create for good.
+// which frees blk_stage and blk_ctmp; the chunk count of the level's operator, which is set at alfi_level_create for good.
 static int grow_slots(alfi_ctx* ctx, double** buf, int* slots, int ncol, int64_t per) {
   const int need = block_slots_needed(*slots, ncol);
   if (need == *slots) return 0;
@@ -101,7 +130,18 @@ int block_patch_apply(alfi_level* L, const BlockCols& ic, const BlockCols& oc, c
     ALFI_CHECK(grow_slots(ctx, &L->blk_stage, &L->blk_stage_slots, ic.n, L->lay.stage_len));
     return launch_patch_apply_block(L, W, ic, oc, X, ldx, Y, ldy, L->blk_stage);
   }
-  for (int i = 0; i < ic.n; ++i) ALFI_CHECK(level_patch_apply(L, X + ic.c[i] * ldx, Y + oc.c[i] * ldy));
+  // condensed factors: the chunk in pieces of the level's width, a piece of one column through the single apply
+  const int width = ic.n > 1 ? block_cond_apply_width(L) : 0;
+  for (int k = 0; k < block_pieces(ic.n, width); ++k) {
+    const BlockCols pi = block_piece(ic, width, k), po = block_piece(oc, width, k);
+    if (pi.n == 1) {
+      ALFI_CHECK(level_patch_apply(L, X + pi.c[0] * ldx, Y + po.c[0] * ldy));
+      continue;
+    }
+    ALFI_CHECK(grow_slots(ctx, &L->blk_stage, &L->blk_stage_slots, pi.n, L->lay.stage_len));
+    ALFI_CHECK(grow_slots(ctx, &L->blk_ctmp, &L->blk_ctmp_slots, pi.n, L->lay.sum_n));
+    ALFI_CHECK(launch_cond_apply_block(L, pi, po, X, ldx, Y, ldy, L->blk_stage, L->blk_ctmp));
+  }
   return 0;
 }
 

@@ -209,6 +209,7 @@ int alfi_level_destroy(alfi_level* L) {
   dev_free(L->canon_rank);
   dev_free(L->stage);
   dev_free(L->blk_stage);
+  dev_free(L->blk_ctmp);
   dev_free(L->blk_carry);
   free_block_smoother(L);
   dev_free(L->dof_ptr);

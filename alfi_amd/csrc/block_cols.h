@@ -61,3 +61,31 @@ inline int block_slots_needed(int have, int ncol) {
   const int want = ncol < BLOCK_NV ? ncol : BLOCK_NV;
   return want > have ? want : have;
 }
+
+// ---- levels whose batch is narrower than a chunk (condensed factors: the LDS of a workgroup holds NV copies of its operands) ----
+// The widest batch of the condensed apply whose one-vector kernels ask for lds_front / lds_back bytes of LDS: the largest NV of
+// 4, 3, 2 with NV * max(lds_front, lds_back) <= budget_bytes; 0: not even two columns fit, the level loops.
+inline int block_cond_width(int64_t lds_front, int64_t lds_back, int64_t budget_bytes) {
+  const int64_t per = lds_front > lds_back ? lds_front : lds_back;
+  if (per <= 0 || budget_bytes <= 0) return 0;
+  for (int nv = BLOCK_NV; nv >= 2; --nv)
+    if (nv * per <= budget_bytes) return nv;
+  return 0;
+}
+
+// A chunk of b.n columns on a level of batch width `width` is taken in pieces of at most `width` columns, the last one shorter
+// (a width below 2: a column at a time).  A piece of one column is the single-vector path.
+inline int block_piece_width(int width) { return width < 1 ? 1 : width > BLOCK_NV ? BLOCK_NV : width; }
+inline int block_pieces(int n, int width) {
+  const int w = block_piece_width(width);
+  return n < 1 ? 0 : (n + w - 1) / w;
+}
+// piece k of the chunk: its columns [w k, min(b.n, w (k + 1))); unused slots repeat the piece's first column
+inline BlockCols block_piece(const BlockCols& b, int width, int k) {
+  const int w = block_piece_width(width), first = k * w;
+  BlockCols q;
+  q.n = b.n - first < w ? b.n - first : w;
+  if (q.n < 0 || k < 0) q.n = 0;
+  for (int i = 0; i < BLOCK_NV; ++i) q.c[i] = q.n == 0 ? b.c[0] : b.c[first + (i < q.n ? i : 0)];
+  return q;
+}

@@ -59,6 +59,7 @@ struct alfi_ctx {
                                     // every call that synchronises (alfi_ctx_sync, alfi_memcpy_d2h)
   bool use_graph = false;           // alfi_ctx_set_graph: replay whole cycles as hipGraphs (not while profiling / partitioned)
   bool block_kernels = true;        // alfi_ctx_set_block_kernels: block calls take the batched kernels where a level has them
+  int block_lds_bytes = 64 * 1024;  // alfi_ctx_set_block_lds_bytes: LDS a workgroup of the condensed block apply may ask for
                                     // (false: every block call loops the single-vector call over its columns)
   void* big_arena = nullptr;        // scratch of the large-block factorisation (kernels_bigpatch.hip), kept between calls
   size_t big_arena_bytes = 0;
@@ -417,6 +418,10 @@ struct alfi_level {
   // expect it), carries of the batched product's fix-up (blk_carry_slots x chunks x bs)
   double* blk_stage = nullptr;
   int blk_stage_slots = 0;
+  // ... and, on condensed levels, the block twin of cd.tmp (blk_ctmp_slots x lay.sum_n: t and y_S of every column between the
+  // launches); freed and grown with blk_stage
+  double* blk_ctmp = nullptr;
+  int blk_ctmp_slots = 0;
   double* blk_carry = nullptr;
   int blk_carry_slots = 0;
   int32_t* dof_ptr = nullptr;     // (n+1) CSR dof -> positions in stage
@@ -608,6 +613,13 @@ int patch_apply_dense_waves(const alfi_level* lvl, bool f32);
 bool patch_apply_block_waves_ok(int W);
 int launch_patch_apply_block(alfi_level* lvl, int W, const BlockCols& cols, const BlockCols& ocols, const double* X, int64_t ldx,
                              double* Y, int64_t ldy, double* stage);
+// its second stage alone (the dof-wise sum of the staged columns, the partition-of-unity weight, the Dirichlet copy)
+int launch_patch_sum_block(alfi_level* lvl, const BlockCols& cols, const BlockCols& ocols, const double* X, int64_t ldx, double* Y,
+                           int64_t ldy, const double* stage);
+// Both stages on a serial level of condensed factors with at least COND_PER_PATCH_MIN patches (kernels_block_cond.hip), 2 .. 4
+// columns whose LDS the caller has checked (block_cond_width, block_cols.h); stage as above, ctmp: cols.n x lay.sum_n doubles.
+int launch_cond_apply_block(alfi_level* lvl, const BlockCols& cols, const BlockCols& ocols, const double* X, int64_t ldx, double* Y,
+                            int64_t ldy, double* stage, double* ctmp);
 // The dense factor pipeline (alfi_patches_factor).  Every launcher takes `inv`, the base of the dense FP64 inverses it works on:
 // patch p at inv + inv_ptr[p].  That is lvl->inv for an FP64 level and the ctx's work buffer, biased by the range's first offset,
 // for an FP32 level (api_patches.hip: range_base).

@@ -32,6 +32,22 @@ struct CondChunk {
 #endif
 constexpr int COND_SIGMA_ROWS = ALFI_COND_SIGMA_ROWS;
 
+// Launches of at least this many patches take the workgroup-per-patch form of the condensed apply (cond_front / cond_sigma /
+// cond_back), smaller ones the chunked form (launch_cond_apply_range, kernels_bigpatch.hip).  The block apply batches the
+// workgroup-per-patch form alone (kernels_block_cond.hip).
+constexpr int64_t COND_PER_PATCH_MIN = 1024;
+
+// Waves per patch of the workgroup-per-patch form: a lane owns one row pair per phase, so a workgroup wider than the patch's
+// row pairs (max_pairs: most row pairs of X / W or of B in one patch of the level) is idle lanes.
+ALFI_HD inline int cond_patch_waves(int max_pairs) {
+#ifdef ALFI_COND_WAVES_FORCE      // A/B builds only (scripts/build_variant.sh): every launch with this many waves per patch
+  (void)max_pairs;
+  return ALFI_COND_WAVES_FORCE;
+#else
+  return max_pairs <= 64 ? 1 : max_pairs <= 128 ? 2 : max_pairs <= 256 ? 4 : 8;
+#endif
+}
+
 // storage of one group's matrices in CondDev::mat: [X (m x m) | B (sc x m) | W (m x sc)], column-major each, the leading
 // dimensions rounded up to EVEN (a lane streams two rows of a column with one 16-byte load; the pad row is never stored)
 // (Measured and dropped, round 5: leading dimensions of > 8 rows rounded up to whole 128-byte lines and every group on a line

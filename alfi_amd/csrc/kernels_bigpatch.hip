@@ -15,6 +15,7 @@
 #include <vector>
 #include "common.h"
 #include "row_piece.h"
+#include "cond_apply.h"
 
 constexpr int BIG_NB = 64;          // pivot block / GEMM k-extent
 constexpr int BIG_MAX_NP = PATCH_MAX;
@@ -376,92 +377,6 @@ __global__ __launch_bounds__(256) void big_store_kernel(int64_t p0, const int64_
 // ---------------------------------------------------------------------------------------------------------------------
 // 3. additive apply, stage 1: one workgroup per patch, row pieces dealt to the four waves
 // ---------------------------------------------------------------------------------------------------------------------
-typedef double big_d2 __attribute__((ext_vector_type(2)));
-constexpr int BIG_U = 8;            // 16-byte loads in flight per lane (piece_dot, row_piece.h); the tail a column at a time
-
-// Rows [r0, r1) of y = T x for a wave, T in the row-piece layout (pieces of 128 rows, then the binary digits of the rest;
-// piece (row0, P rows): entry (r, c) at T[row0 * n + c * P + (r - row0)]).  The range is cut into aligned power-of-two
-// blocks of rows inside the stored pieces: a block of 2 G rows takes G lanes per column and 64 / G columns per load
-// instruction.  Used where whole pieces dealt round-robin leave waves idle (a Schur complement of 312 rows is
-// 2 x 128 + 32 + 16 + 8: two of eight waves would stream 82 % of it).
-// the next block of a range of rows [r, r1): the stored piece (row0, P rows) that holds row r and R, the rows of the block
-__device__ __forceinline__ void big_block(int ld, int r, int r1, int& row0, int& P, int& R) {
-  const int full = ld & ~127;
-  if (r < full) {
-    row0 = r & ~127;
-    P = 128;
-  } else {
-    row0 = full;
-    P = 64;
-    const int rem = ld - full;
-    for (; P >= 2; P >>= 1)
-      if (rem & P) {
-        if (r < row0 + P) break;
-        row0 += P;
-      }
-  }
-  const int o = r - row0;
-  R = P;                               // the largest aligned power-of-two block at o that ends inside the piece and the range
-  while (R > 2 && ((o & (R - 1)) != 0 || o + R > P || r + R > r1)) R >>= 1;
-}
-
-template <bool NT>
-__device__ __forceinline__ void big_rows(const double* __restrict__ T, int n, int ld, int r0, int r1,
-                                         const double* __restrict__ xs, int lane, double* __restrict__ ys) {
-  // ys: n doubles (LDS or global); rows >= n (the zero pad row) are not stored
-  int r = r0;
-  while (r < r1) {
-    int row0, P, R;
-    big_block(ld, r, r1, row0, P, R);
-    const int o = r - row0;
-    const double* Tp = T + (int64_t)row0 * n + o;
-    // (lim = n - r: the pad row of an odd n is not written)
-#define ALFI_BIG_BLOCK(RV) \
-  case RV: piece_apply<double, RV / 2, NT, BIG_U, false, PieceStore::GUARDED>(Tp, P, n, xs, lane, ys + r, n - r); break;
-    switch (R) {
-      ALFI_BIG_BLOCK(128) ALFI_BIG_BLOCK(64) ALFI_BIG_BLOCK(32) ALFI_BIG_BLOCK(16) ALFI_BIG_BLOCK(8) ALFI_BIG_BLOCK(4)
-      default: piece_apply<double, 1, NT, BIG_U, false, PieceStore::GUARDED>(Tp, P, n, xs, lane, ys + r, n - r); break;
-    }
-#undef ALFI_BIG_BLOCK
-    r += R;
-  }
-}
-
-// One block of big_rows in two halves, for a kernel that requests the block before its operand exists: the loads of a block of
-// R = 2 << lg <= 16 rows over n <= BIG_U * 64 / (R / 2) columns -- every column group of the lane, BIG_U 16-byte loads held in
-// registers -- and, later, the sums.  The sums are those of piece_apply<double, R / 2, ., BIG_U, false, GUARDED> to the bit: a
-// lane's columns ascending, then the column groups by shuffles (row_piece.h).  Tp: (first row of the block, column 0), P: the
-// rows of the stored piece.
-template <bool NT>
-__device__ __forceinline__ void big_block_prefetch(const double* __restrict__ Tp, int P, int n, int lg, int lane,
-                                                   big_d2 (&v)[BIG_U]) {
-  const int C = 64 >> lg, cg = lane >> lg, l = lane & ((1 << lg) - 1);
-#pragma unroll
-  for (int u = 0; u < BIG_U; ++u) {
-    const big_d2 z = {0.0, 0.0};
-    v[u] = cg + u * C < n ? piece_load<double, NT>(Tp + 2 * l + (int64_t)(cg + u * C) * P) : z;
-  }
-}
-__device__ __forceinline__ void big_block_finish(const big_d2 (&v)[BIG_U], int n, int lg, const double* __restrict__ xs, int lane,
-                                                 double* __restrict__ out, int lim) {
-  const int G = 1 << lg, C = 64 >> lg, cg = lane >> lg, l = lane & (G - 1);
-  double acc0 = 0.0, acc1 = 0.0;
-#pragma unroll
-  for (int u = 0; u < BIG_U; ++u)
-    if (cg + u * C < n) {
-      const double xj = xs[cg + u * C];
-      acc0 = __builtin_fma(v[u].x, xj, acc0);
-      acc1 = __builtin_fma(v[u].y, xj, acc1);
-    }
-  for (int o = G; o < 64; o <<= 1) {
-    acc0 += __shfl_xor(acc0, o);
-    acc1 += __shfl_xor(acc1, o);
-  }
-  if (cg != 0) return;
-  if (2 * l < lim) out[2 * l] = acc0;
-  if (2 * l + 1 < lim) out[2 * l + 1] = acc1;
-}
-
 // One workgroup of 4 waves per patch (``split`` workgroups on launches of few patches): x_p into LDS, the stored row pieces of
 // the inverse dealt round-robin to the 4 split waves, every wave streaming its pieces whole (piece_apply, row_piece.h) and
 // writing their rows of the staged result.  S is the storage scalar of the inverse; the arithmetic is FP64 for both.
@@ -1012,8 +927,8 @@ __global__ __launch_bounds__(256) void cond_schur_kernel(int64_t p0, CondDev cd,
 
 // additive apply, stage 1, condensed patches [p0, p1): one workgroup of COND_WAVES waves per patch.  Dynamic LDS (doubles):
 // xs (n: gathered x, condensed order; interior slices become t_g, the skeleton slice becomes x_S - sum B_g t_g), us
-// (sum_g s_g), ys (s).  The small matrices are streamed with COND_U loads in flight per lane (they are read once).
-constexpr int COND_U = 8;
+// (sum_g s_g), ys (s).  The small matrices are streamed with COND_U loads in flight per lane (they are read once).  The row-pair
+// product (cond_row2_dot) and the walk over inv(Sigma) (big_rows, big_block_prefetch / _finish): cond_apply.h.
 
 // The apply as THREE launches (rounds 1-2: one launch per patch, a wave per group with a lane per row -- dropped).  Measured on config 5's
 // finest level (1765 macro stars, 4.85 GB of factors; kernel trace, same box): the one-launch kernel takes 949 us; its
@@ -1025,37 +940,6 @@ constexpr int COND_U = 8;
 // y_g = t_g - W_g y_S[S_g] and the staging, a workgroup per patch, row pairs again.  t and y_S travel through cd.tmp
 // (sum_n doubles), the right-hand side through the patch's own staging slots (overwritten by the back kernel): 16 (n + s)
 // bytes of extra traffic per patch against megabytes of factors.
-
-// wave-wide maximum of a small non-negative int
-__device__ __forceinline__ int cond_wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-
-// TWO ROWS of a group product per lane (rows 2 i, 2 i + 1 of a column-major block with an even leading dimension: one
-// 16-byte load per column):   acc += sum_{k < kn} M[k * ld + (0, 1)] * v[k],   M -> the lane's rows, v -> LDS (the group's
-// operand).  kn differs between the lanes of a wave; the loop runs to the wave's maximum with the loads predicated.
-template <bool NT, int RU>
-__device__ __forceinline__ void cond_row2_dot(const double* __restrict__ M, int ld, int kn, const double* __restrict__ v,
-                                              double& acc0, double& acc1) {
-  const int kmax = cond_wave_max(kn);
-  for (int k = 0; k < kmax; k += RU) {
-    big_d2 a[RU];
-#pragma unroll
-    for (int u = 0; u < RU; ++u) {
-      const big_d2* q = reinterpret_cast<const big_d2*>(M + (int64_t)(k + u) * ld);
-      const big_d2 z = {0.0, 0.0};
-      a[u] = (k + u < kn) ? (NT ? __builtin_nontemporal_load(q) : *q) : z;
-    }
-#pragma unroll
-    for (int u = 0; u < RU; ++u) {
-      const double vk = (k + u < kn) ? v[k + u] : 0.0;
-      acc0 = __builtin_fma(a[u].x, vk, acc0);
-      acc1 = __builtin_fma(a[u].y, vk, acc1);
-    }
-  }
-}
 
 template <bool NT, int COND_WAVES, int RU>
 __global__ __launch_bounds__(64 * COND_WAVES) void cond_front_kernel(int64_t p0, int64_t p1, CondDev cd,
@@ -1755,7 +1639,7 @@ int launch_cond_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double*
   // config 5's size the big patches must not come last); range launches (overlapped exchanges) keep the natural order
   const int ordered = p0 == 0 && p1 == L->npatch && L->cd.order ? 1 : 0;
   const int64_t c0 = L->cplan.chptr[p0], c1 = L->cplan.chptr[p1];
-  if (p1 - p0 < 1024) {
+  if (p1 - p0 < COND_PER_PATCH_MIN) {
     const int64_t k0 = L->cplan.gcptr[p0], k1 = L->cplan.gcptr[p1];
     const size_t lds_f = (size_t)L->cplan.lds_gfront, lds_b = (size_t)L->cplan.lds_gback;
     const size_t lds_s = (size_t)(L->cplan.max_s + 2 + COND_SIGMA_ROWS) * sizeof(double);
@@ -1794,10 +1678,12 @@ int launch_cond_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double*
 #ifdef ALFI_COND_WAVES_FORCE      // A/B builds only (scripts/build_variant.sh): every launch with this many waves per patch
   ALFI_COND_LAUNCH3(ALFI_COND_WAVES_FORCE);
 #else
-  if (L->cplan.max_pairs <= 64) ALFI_COND_LAUNCH3(1);
-  else if (L->cplan.max_pairs <= 128) ALFI_COND_LAUNCH3(2);
-  else if (L->cplan.max_pairs <= 256) ALFI_COND_LAUNCH3(4);
-  else ALFI_COND_LAUNCH3(8);
+  switch (cond_patch_waves(L->cplan.max_pairs)) {       // (cond_layout.h; the block apply asks the same function)
+    case 1: ALFI_COND_LAUNCH3(1); break;
+    case 2: ALFI_COND_LAUNCH3(2); break;
+    case 4: ALFI_COND_LAUNCH3(4); break;
+    default: ALFI_COND_LAUNCH3(8); break;
+  }
 #endif
 #undef ALFI_COND_LAUNCH3
   ALFI_HIP_CHECK(ctx, hipGetLastError());

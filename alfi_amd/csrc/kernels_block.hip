@@ -297,6 +297,13 @@ int launch_patch_apply_block(alfi_level* L, int W, const BlockCols& cols, const 
     else ALFI_CHECK(launch_apply_block_w<double>(L, W, L->inv, L->inv_ptr, X, ldx, cols, stage));
     ALFI_HIP_CHECK(ctx, hipGetLastError());
   }
+  return launch_patch_sum_block(L, cols, ocols, X, ldx, Y, ldy, stage);
+}
+
+// stage 2 for the columns of cols: what the dense and the condensed (kernels_block_cond.hip) block apply share
+int launch_patch_sum_block(alfi_level* L, const BlockCols& cols, const BlockCols& ocols, const double* X, int64_t ldx, double* Y,
+                           int64_t ldy, const double* stage) {
+  alfi_ctx* ctx = L->ctx;
   if (L->n <= 0) return 0;
   ProfScope prof(ctx, ALFI_EV_PATCH_SCATTER);   // to the end of the function
   const dim3 grid((unsigned)((L->n + 255) / 256)), block(256);

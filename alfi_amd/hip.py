@@ -115,6 +115,12 @@ class Context(object):
         block call loops the single-vector call over its columns -- the same bits at the cost of ncol single calls."""
         self.check(self.lib.alfi_ctx_set_block_kernels(self.h, 1 if on else 0))
 
+    def set_block_lds_bytes(self, nbytes=64 * 1024):
+        """LDS a workgroup of the condensed block apply may ask for (alfi_ctx_set_block_lds_bytes; default 64 KiB, clamped to the
+        device's limit per workgroup): a condensed level batches the widest NV of 4, 3, 2 with NV x the LDS of its one-vector
+        kernels within it (``Level.patch_apply_block_width``).  The A/B and test switch of that width; never the bits."""
+        self.check(self.lib.alfi_ctx_set_block_lds_bytes(self.h, int(nbytes)))
+
     # profiling (PETSc-event style report, driver.py:77-92) ----------------------------------------------------------------
     def transfer_stats(self, reset=False):
         """(bytes host -> device, bytes device -> host) of every copy the library made since the last reset, process-wide
@@ -690,6 +696,13 @@ class Level(object):
         b = ctypes.c_int()
         self.ctx.check(self.ctx.lib.alfi_patch_apply_block_info(self.h, ctypes.byref(b)))
         return bool(b.value)
+
+    def patch_apply_block_width(self):
+        """The widest batch of a block apply on this level as it stands (alfi_patch_apply_block_width): 4 for dense inverses that
+        batch, 4 / 3 / 2 for condensed factors (what fits ``Context.set_block_lds_bytes``), 0: it loops the single apply."""
+        w = ctypes.c_int()
+        self.ctx.check(self.ctx.lib.alfi_patch_apply_block_width(self.h, ctypes.byref(w)))
+        return int(w.value)
 
     def smooth_block_lockstep(self, k):
         """Does ``smooth_block(k, ...)`` on two or more columns run the smoother's general path in lockstep (one block apply and

@@ -605,16 +605,25 @@ int alfi_saddle_velocity_info(alfi_saddle* s, int64_t* bytes, double* probe_resi
  * four columns is ONE launch that reads the stored values once: the additive apply of dense patch inverses of 33 .. 160 dofs
  * in either storage precision (the levels whose single apply gives a workgroup to every patch) and the nnz-balanced flat
  * product without column de-duplication.  Everything else runs the single-vector code column after column inside the library:
- * the interleaved copy of small patches, macro stars, levels of few patches, condensed factors, multiplicative sweeps, point
+ * the interleaved copy of small patches, dense macro stars, levels of few patches, multiplicative sweeps, point
  * Jacobi, the de-duplicated and the lanes-per-row product, the four-launch smoother iteration, Chebyshev, transfers, coarse
  * solves.  A chunk of one column always does.  alfi_patch_apply_block_info / alfi_spmv_block_info: does the level, as it stands,
  * batch?  alfi_ctx_set_block_kernels(ctx, 0) makes every block call loop (default on): same bits, the cost of ncol single calls.
+ * Condensed factors batch too where their single apply gives a workgroup to every patch (levels of at least 1024 patches), as
+ * wide as the LDS of a workgroup allows: the widest NV of 4, 3, 2 with NV x the LDS of the one-vector kernels within the budget
+ * of alfi_ctx_set_block_lds_bytes (default 64 KiB, clamped to the device's limit per workgroup); a chunk is taken in pieces of
+ * that width, a piece of one column through the single apply.  Condensed levels of fewer patches (the chunked form of the
+ * apply) and levels whose LDS does not fit two columns loop.  alfi_patch_apply_block_width: the widest batch of the level as it
+ * stands -- 4 for dense inverses that batch, 4 / 3 / 2 for condensed factors, 0: it loops; alfi_patch_apply_block_info reports 1
+ * exactly when the width is >= 2.
  * Serial levels only.  ALFI_E_ARG before any device work, nothing touched: a partitioned level, ncol < 1 or > nx, an odd
  * leading dimension or one below the vector length, a column index outside [0, nx) or listed twice, a NULL operand, an operand
  * that is written overlapping another one. */
 int alfi_ctx_set_block_kernels(alfi_ctx* ctx, int on);
 int alfi_patch_apply_block_info(alfi_level* lvl, int* batched);
 int alfi_spmv_block_info(alfi_level* lvl, int* batched);
+int alfi_patch_apply_block_width(alfi_level* lvl, int* width);
+int alfi_ctx_set_block_lds_bytes(alfi_ctx* ctx, int64_t bytes);
 /* Y[:, c] = alfi_patch_apply of X[:, c] */
 int alfi_patch_apply_block(alfi_level* lvl, int ncol, const int* cols, int nx, const double* X, int64_t ldx, double* Y, int64_t ldy);
 /* Y[:, c] = A X[:, c];  R[:, c] = B[:, c] - A X[:, c] */

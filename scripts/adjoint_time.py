@@ -6,7 +6,8 @@ After every forward ``solve(re)`` one adjoint solve with J = int w . u (LoadFunc
 Prints the refresh, transpose, factor and solve seconds of the adjoint, its Krylov iterations and those of the last Newton
 step of the forward solve (same operator state, same tolerances).
 --functionals K (default 1): K functionals J_i = int e_(i mod dim) (1 + i) . u as ONE list: one refresh, transpose and
-factorisation and one block solve for the K adjoints; the iterations and residual norms are printed per functional."""
+factorisation and one block solve for the K adjoints; the iterations and residual norms are printed per functional.
+--compare-block-kernels: that block solve twice more each with the batched kernels off and on (Context.set_block_kernels)."""
 import argparse
 import os
 import sys
@@ -41,6 +42,8 @@ def main():
     ap.add_argument("--sv", action="store_true", help="cfg5s (Scott-Vogelius) with Burman stabilisation instead of CONFIG")
     ap.add_argument("--burman-weight", type=float, default=5e-3)
     ap.add_argument("--functionals", type=int, default=1, help="K functionals given as one list (K = 1: the single path)")
+    ap.add_argument("--compare-block-kernels", action="store_true",
+                    help="with --functionals K > 1: the block solve again with the batched kernels off and on (same bits), solve seconds")
     ap.add_argument("--host", action="store_true", help="host assembly (the transpose still runs on the device values)")
     args = ap.parse_args()
     from alfi_amd.adjoint import LoadFunctional
@@ -86,6 +89,12 @@ def main():
                      args.functionals, a["linear_iter"], a["converged"], ["%.2e" % r for r in a["residual_norm"]],
                      ["%.2e" % b for b in a["rhs_norm"]], a["refresh_s"], a["transpose_s"], a["factor_s"], a["solve_s"],
                      60.0 * a["time"]), flush=True)
+            if args.compare_block_kernels:          # off = every block call loops the single-vector call: what a list cost before
+                for on in (False, True, False, True):
+                    s.ctx.set_block_kernels(on)
+                    r = s.solver_adjoint.solve()
+                    print("    batched kernels %-3s: solve %.3f s, Krylov its %s" % ("on" if on else "off", r["solve_s"], r["linear_iter"]),
+                          flush=True)
             continue
         print("Re %g: forward %d Newton steps, %d Krylov its (last step %s), converged %s, %.2f s per Newton step | "
               "adjoint %d Krylov its, converged %s, |r| %.2e of |b| %.2e; refresh %.3f s, transpose %.4f s, factor %.3f s, "

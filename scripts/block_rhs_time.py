@@ -1,10 +1,14 @@
 """Block right-hand sides against looping: time per block patch apply, per block product and per full cycle at 1, 2 and 4
 columns, the batched kernels on and off (Context.set_block_kernels: off = the single-vector call per column, which is what a
-caller paid before block calls existed), on one bench configuration with DENSE patch inverses, in ONE process.  The hierarchy is
-set up once; the two modes alternate, round after round.
+caller paid before block calls existed), on one bench configuration with DENSE patch inverses -- or, --condensed, with the
+default policy (config 4's two large levels and config 5's macro stars hold condensed factors) --, in ONE process.  The hierarchy
+is set up once; the two modes alternate, round after round.
 
 usage: timeout -k 10 900 python scripts/block_rhs_time.py cfg3 [--rounds 3] [--reps 20] [--cycles 3] [--dtype f32] [--out FILE]
+       timeout -k 10 900 python scripts/block_rhs_time.py cfg4 --condensed [--lds-bytes N] [--out FILE]
 (one GPU step = one process: give each its own time limit)
+--lds-bytes: Context.set_block_lds_bytes, the LDS a workgroup of the condensed block apply may ask for (default 64 KiB; the
+width of every level is printed).
 
 Per level with patches and per ncol: best ms per block apply (both stages) and per block product over the rounds, on / off and
 their ratio, and the stored bytes (alfi_patches_factor_bytes; operator values + column indices) per second of the batched call.
@@ -29,6 +33,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--cycles", type=int, default=3)
     ap.add_argument("--dtype", default=None, choices=[None, "f32"])
+    ap.add_argument("--condensed", action="store_true", help="the default condensation policy instead of dense inverses")
+    ap.add_argument("--lds-bytes", type=int, default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -47,11 +53,27 @@ def main():
     say("hierarchy generated on the host in %.1f s; patches per level %s, largest patch %d dofs"
         % (time.time() - t0, [len(L.patch_ptr) - 1 for L in lv[1:]], int(np.diff(lv[-1].patch_ptr).max())))
     ctx = hip.Context(0)
-    ctx.set_condense_min_bytes(-1)                  # dense inverses on every level (condensed levels loop: nothing to compare)
+    if not args.condensed:
+        ctx.set_condense_min_bytes(-1)              # dense inverses on every level
+    if args.lds_bytes is not None:
+        ctx.set_block_lds_bytes(args.lds_bytes)
     mg = hip.Multigrid(ctx, lv, tr, k, patch_factor_dtype=args.dtype)
-    say("dense %s inverses; per level (dofs, patches, factor GB, apply batched, product batched): %s"
-        % (args.dtype or "f64", ["%d/%d/%.3f/%d/%d" % (d.n, len(L.patch_ptr) - 1, d.factor_bytes() / 1e9, d.patch_apply_block_batched(),
-                                                       d.spmv_block_batched()) for L, d in zip(lv[1:], mg.levels[1:])]))
+    say("%s; per level (dofs, patches, factor GB, apply batched, product batched): %s"
+        % ("the default condensation policy" if args.condensed else "dense %s inverses" % (args.dtype or "f64"),
+           ["%d/%d/%.3f/%d/%d" % (d.n, len(L.patch_ptr) - 1, d.factor_bytes() / 1e9, d.patch_apply_block_batched(),
+                                  d.spmv_block_batched()) for L, d in zip(lv[1:], mg.levels[1:])]))
+    if args.condensed:
+        # per level: condensed() (0 dense, 1 the caller's groups, 2 the library's), the width of the block apply, the expectation
+        # from bytes at 4 columns -- (factor bytes + 4 vector bytes) / (4 (factor bytes + vector bytes)), vector bytes = 20 per
+        # patch entry (index, value, staged result) -- and the per-column scratch of a batched apply (one slot of blk_stage and
+        # one of blk_ctmp, 8 bytes per patch entry each)
+        for L, d in zip(lv[1:], mg.levels[1:]):
+            fb, vb = float(d.factor_bytes()), 20.0 * float(L.patch_ptr[-1])
+            say("  level %d: condensed %d, block width %d%s, expected 4-column ratio from bytes %.3f, scratch per column slot: stage "
+                "%.3f GB + ctmp %.3f GB" % (d.id, d.condensed(), d.patch_apply_block_width(),
+                                            "" if args.lds_bytes is None else " (LDS budget %d)" % args.lds_bytes,
+                                            (fb + 4 * vb) / (4 * (fb + vb)),
+                                            8e-9 * float(((np.diff(L.patch_ptr) + 1) & ~1).sum()), 8e-9 * float(L.patch_ptr[-1])))
     rng = np.random.default_rng(0)
 
     def timed(fn, reps):

@@ -5,7 +5,7 @@
 
 Every csrc/*.hip of REV (taken from git into a temporary directory) and of the working tree is compiled device-only with the
 flags of alfi_amd/build.py, the gfx950 code object is unbundled, and the SHA-256 of its .text, .rodata and .note sections
-are compared file by file.  Host-only changes and shifted line numbers leave those sections alone; only the __hip_cuid_*
+are compared file by file (a file REV does not have is listed as new and compared with nothing).  Host-only changes and shifted line numbers leave those sections alone; only the __hip_cuid_*
 symbol name (.dynsym / .dynstr) differs between two builds.  Exit status 0: equal for every file.
 """
 import argparse
@@ -77,17 +77,20 @@ def main():
     for (side, _, f), h in zip(jobs, hashes):
         res[side][f] = h
     files = sorted(set(res["rev"]) | set(res["tree"]))
-    differ = [f for f in files if res["rev"].get(f) != res["tree"].get(f)]
+    new = [f for f in files if f not in res["rev"]]               # files REV does not have: nothing to compare them with
+    differ = [f for f in files if f not in new and res["rev"].get(f) != res["tree"].get(f)]
     print("%-22s %-8s %-64s %-64s" % ("file", "section", "sha256 at " + rev[:7], "sha256 of this tree"))
     for f in files:
         for sec in SECTIONS:
             r, t = res["rev"].get(f, {}).get(sec, "-"), res["tree"].get(f, {}).get(sec, "-")
-            print("%-22s %-8s %-64s %-64s %s" % (f, sec, r, t, "equal" if r == t else "DIFFERS"))
+            print("%-22s %-8s %-64s %-64s %s" % (f, sec, r, t, "new" if f in new else "equal" if r == t else "DIFFERS"))
     print("device code (%s of gfx950) against %s: %s" % (", ".join(SECTIONS), rev[:7],
-                                                        "DIFFERS in " + ", ".join(differ) if differ else "identical in all %d files" % len(files)))
+                                                        "DIFFERS in " + ", ".join(differ) if differ else "identical in all %d files of that revision" % (len(files) - len(new))))
+    if new:
+        print("new in this tree: " + ", ".join(new))
     if a.json:
         with open(a.json, "w") as f:
-            json.dump({"rev": rev, "flags": FLAGS + ["--cuda-device-only"], "sections": SECTIONS, "equal": not differ,
+            json.dump({"rev": rev, "flags": FLAGS + ["--cuda-device-only"], "sections": SECTIONS, "equal": not differ, "new": new,
                        "hashes_rev": res["rev"], "hashes_tree": res["tree"]}, f, indent=1, sort_keys=True)
             f.write("\n")
     return 1 if differ else 0
