@@ -4,9 +4,10 @@
 // Column c of every block result is the single-vector call's result on column c bit for bit.  A list of more than BLOCK_NV
 // columns is taken BLOCK_NV at a time.  Where a level has a batched kernel (kernels_block.hip: dense inverses through
 // patch_apply_kernel, the flat product) a chunk of two or more columns is ONE launch that streams the stored values once;
-// condensed factors of at least COND_PER_PATCH_MIN patches (kernels_block_cond.hip) take a chunk in pieces of as many columns
-// as fit the LDS budget (block_cond_width); everything else -- and every chunk or piece of one column -- is the single-vector
-// code, column after column.
+// condensed factors of at least COND_PER_PATCH_MIN patches (kernels_block_cond.hip) and dense macro-star inverses of at least
+// BIG_BLOCK_MIN_PATCHES patches (kernels_block_big.hip) take a chunk in pieces of as many columns as fit the LDS budget
+// (block_cond_width, block_big_width); everything else -- and every chunk or piece of one column -- is the single-vector code,
+// column after column.
 #include "api_internal.h"
 #include "block_cols.h"
 
@@ -33,9 +34,24 @@ static int block_cond_apply_width(const alfi_level* L) {
   if (L->lay.sum_n > INT32_MAX / BLOCK_NV) return 0;      // (piece_apply takes the stride between two columns' slots as an int)
   return block_cond_width(L->cplan.lds_front, L->cplan.lds_back, L->ctx->block_lds_bytes);
 }
-// the widest batch of the level's apply: BLOCK_NV for dense inverses that batch, the condensed width, 0: it loops
+// Dense macro-star inverses (a patch above SMALL_PATCH_MAX dofs, FP64 or the single-precision copy: big_apply_kernel): the
+// widest batch of the level (block_big_width, block_cols.h), 0: its apply loops -- levels of fewer than BIG_BLOCK_MIN_PATCHES
+// patches, and levels whose x_p does not fit the ctx's budget twice.  (The few-patches detour of smaller stars through the same
+// single kernel, patch_apply_dense_waves, loops as before.)
+static int block_big_apply_width(const alfi_level* L) {
+  if (!L->ctx->block_kernels || !L->factored || L->jacobi || L->mult || level_is_partitioned(L)) return 0;
+  if (L->held != HELD_F64 && L->held != HELD_F32) return 0;
+  if (L->lay.max_np <= SMALL_PATCH_MAX || L->npatch < BIG_BLOCK_MIN_PATCHES) return 0;
+  if (L->lay.stage_len > INT32_MAX / BLOCK_NV) return 0;  // (piece_apply takes the stride between two columns' slots as an int)
+  return block_big_width(L->lay.max_np, L->ctx->block_lds_bytes);
+}
+// the width of the levels that take a chunk in pieces: condensed factors or dense macro stars (a level holds one of the two)
+static int block_piece_apply_width(const alfi_level* L) {
+  return L->held == HELD_COND ? block_cond_apply_width(L) : block_big_apply_width(L);
+}
+// the widest batch of the level's apply: BLOCK_NV for dense inverses that batch, the condensed or macro-star width, 0: it loops
 static int block_apply_width(const alfi_level* L) {
-  return block_apply_waves(L) != 0 ? BLOCK_NV : block_cond_apply_width(L);
+  return block_apply_waves(L) != 0 ? BLOCK_NV : block_piece_apply_width(L);
 }
 static bool block_spmv_batched(const alfi_level* L) {
   return L->ctx->block_kernels && !level_is_partitioned(L) && bsr_spmv_block_batched(L->A_own);
@@ -51,8 +67,8 @@ int alfi_patch_apply_block_width(alfi_level* L, int* width) {
   *width = block_apply_width(L);
   return 0;
 }
-// LDS a workgroup of the condensed block apply may ask for (default 64 KiB: no launch needs its limit raised, and as many
-// workgroups share a CU as in a plain launch), clamped to what the device gives one workgroup
+// LDS a workgroup of a block apply may ask for -- one budget for the condensed apply and the macro stars' (default 64 KiB: no
+// launch needs its limit raised), clamped to what the device gives one workgroup
 int alfi_ctx_set_block_lds_bytes(alfi_ctx* ctx, int64_t bytes) {
   if (!ctx) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL context");
   int limit = 0;
@@ -130,8 +146,8 @@ int block_patch_apply(alfi_level* L, const BlockCols& ic, const BlockCols& oc, c
     ALFI_CHECK(grow_slots(ctx, &L->blk_stage, &L->blk_stage_slots, ic.n, L->lay.stage_len));
     return launch_patch_apply_block(L, W, ic, oc, X, ldx, Y, ldy, L->blk_stage);
   }
-  // condensed factors: the chunk in pieces of the level's width, a piece of one column through the single apply
-  const int width = ic.n > 1 ? block_cond_apply_width(L) : 0;
+  // condensed factors, dense macro stars: the chunk in pieces of the level's width, a piece of one column through the single apply
+  const int width = ic.n > 1 ? block_piece_apply_width(L) : 0;
   for (int k = 0; k < block_pieces(ic.n, width); ++k) {
     const BlockCols pi = block_piece(ic, width, k), po = block_piece(oc, width, k);
     if (pi.n == 1) {
@@ -139,6 +155,10 @@ int block_patch_apply(alfi_level* L, const BlockCols& ic, const BlockCols& oc, c
       continue;
     }
     ALFI_CHECK(grow_slots(ctx, &L->blk_stage, &L->blk_stage_slots, pi.n, L->lay.stage_len));
+    if (L->held != HELD_COND) {
+      ALFI_CHECK(launch_big_apply_block(L, pi, po, X, ldx, Y, ldy, L->blk_stage));
+      continue;
+    }
     ALFI_CHECK(grow_slots(ctx, &L->blk_ctmp, &L->blk_ctmp_slots, pi.n, L->lay.sum_n));
     ALFI_CHECK(launch_cond_apply_block(L, pi, po, X, ldx, Y, ldy, L->blk_stage, L->blk_ctmp));
   }

@@ -73,6 +73,24 @@ inline int block_cond_width(int64_t lds_front, int64_t lds_back, int64_t budget_
   return 0;
 }
 
+// ---- dense macro-star inverses (patches above SMALL_PATCH_MAX dofs; kernels_block_big.hip) -------------------------------------
+// The block form of big_apply_kernel keeps x_p of its nv columns in dynamic LDS, interleaved entry by entry and sized by the
+// level's largest patch (rounded up to even), not by the largest patch there can be:
+inline int64_t block_big_lds(int max_np, int nv) { return (int64_t)nv * 8 * ((max_np + 1) & ~1); }
+// The widest batch of such a level: the largest nv of 4, 3, 2 with block_big_lds(max_np, nv) <= budget_bytes (the ctx's
+// block_lds_bytes, the same budget as the condensed apply's); 0: not even two columns fit, the level loops.  At the default
+// 64 KiB: max_np <= 2048 gives 4, <= 2730 gives 3, <= 4096 gives 2.
+inline int block_big_width(int max_np, int64_t budget_bytes) {
+  if (max_np <= 0 || budget_bytes <= 0) return 0;
+  for (int nv = BLOCK_NV; nv >= 2; --nv)
+    if (block_big_lds(max_np, nv) <= budget_bytes) return nv;
+  return 0;
+}
+// Macro-star levels of fewer patches than this loop the single apply.  The one reason: tests/test_gpu_block_rhs.py
+// (test_looped_applies_are_the_single_apply) pins that a level of 4 patches with one of 161 dofs reports "not batched", and
+// existing tests do not change; 8 is the smallest level the block kernel is tested on.  Nothing about speed was measured for it.
+constexpr int64_t BIG_BLOCK_MIN_PATCHES = 8;
+
 // A chunk of b.n columns on a level of batch width `width` is taken in pieces of at most `width` columns, the last one shorter
 // (a width below 2: a column at a time).  A piece of one column is the single-vector path.
 inline int block_piece_width(int width) { return width < 1 ? 1 : width > BLOCK_NV ? BLOCK_NV : width; }

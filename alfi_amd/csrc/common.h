@@ -59,8 +59,9 @@ struct alfi_ctx {
                                     // every call that synchronises (alfi_ctx_sync, alfi_memcpy_d2h)
   bool use_graph = false;           // alfi_ctx_set_graph: replay whole cycles as hipGraphs (not while profiling / partitioned)
   bool block_kernels = true;        // alfi_ctx_set_block_kernels: block calls take the batched kernels where a level has them
-  int block_lds_bytes = 64 * 1024;  // alfi_ctx_set_block_lds_bytes: LDS a workgroup of the condensed block apply may ask for
                                     // (false: every block call loops the single-vector call over its columns)
+  int block_lds_bytes = 64 * 1024;  // alfi_ctx_set_block_lds_bytes: LDS a workgroup of a block apply may ask for -- the one budget
+                                    // of the condensed apply (block_cond_width) and the macro stars' (block_big_width)
   void* big_arena = nullptr;        // scratch of the large-block factorisation (kernels_bigpatch.hip), kept between calls
   size_t big_arena_bytes = 0;
   void* asm_scratch = nullptr;      // element blocks / element vectors of the operator refresh (kernels_assemble.hip), grow-only
@@ -620,6 +621,10 @@ int launch_patch_sum_block(alfi_level* lvl, const BlockCols& cols, const BlockCo
 // columns whose LDS the caller has checked (block_cond_width, block_cols.h); stage as above, ctmp: cols.n x lay.sum_n doubles.
 int launch_cond_apply_block(alfi_level* lvl, const BlockCols& cols, const BlockCols& ocols, const double* X, int64_t ldx, double* Y,
                             int64_t ldy, double* stage, double* ctmp);
+// Both stages on a serial level of dense inverses (FP64 or FP32) with a patch above SMALL_PATCH_MAX dofs (kernels_block_big.hip),
+// 2 .. 4 columns whose LDS the caller has checked (block_big_width, block_cols.h); stage as above.
+int launch_big_apply_block(alfi_level* lvl, const BlockCols& cols, const BlockCols& ocols, const double* X, int64_t ldx, double* Y,
+                           int64_t ldy, double* stage);
 // The dense factor pipeline (alfi_patches_factor).  Every launcher takes `inv`, the base of the dense FP64 inverses it works on:
 // patch p at inv + inv_ptr[p].  That is lvl->inv for an FP64 level and the ctx's work buffer, biased by the range's first offset,
 // for an FP32 level (api_patches.hip: range_base).

@@ -581,14 +581,7 @@ int launch_big_mult_wave(alfi_level* L, const int32_t* seq, int64_t count, const
 // ---------------------------------------------------------------------------------------------------------------------
 // launch wrappers
 // ---------------------------------------------------------------------------------------------------------------------
-// workgroups per patch: enough of them to fill 256 CUs several times over, but no more waves than 128-row pieces
-static int big_split(int64_t npatch, int max_np) {
-  const int64_t want = (2048 + npatch - 1) / npatch;
-  const int pieces = (max_np + 127) / 128;
-  const int cap = (pieces + 3) / 4;
-  return (int)(want < 1 ? 1 : (want > cap ? cap : want));
-}
-
+// (workgroups per patch: big_split, patch_plan.h -- the block launcher of kernels_block_big.hip reads the same function)
 // the patches [p0, p1) of either storage (factors are read once per apply: nontemporal loads)
 template <typename S>
 static int launch_big_apply(alfi_ctx* ctx, int64_t p0, int64_t p1, int max_np, const int64_t* patch_ptr, const int32_t* patch_dofs,

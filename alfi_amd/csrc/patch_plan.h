@@ -177,6 +177,15 @@ inline int64_t plan_f32_ranges(int64_t npatch, const int64_t* inv_ptr, int64_t c
   return work;
 }
 
+// ---- the macro stars' apply (big_apply_kernel, kernels_bigpatch.hip; its block form, kernels_block_big.hip) ------------------
+// workgroups per patch: enough of them to fill 256 CUs several times over, but no more waves than 128-row pieces
+inline int big_split(int64_t npatch, int max_np) {
+  const int64_t want = (2048 + npatch - 1) / npatch;
+  const int pieces = (max_np + 127) / 128;
+  const int cap = (pieces + 3) / 4;
+  return (int)(want < 1 ? 1 : (want > cap ? cap : want));
+}
+
 // ---- the condensed layout (alfi_patches_set_groups; the tables of CondDev, common.h) ---------------------------------------
 struct CondPlan {
   // per patch entry, condensed order [groups | skeleton]

@@ -116,9 +116,12 @@ class Context(object):
         self.check(self.lib.alfi_ctx_set_block_kernels(self.h, 1 if on else 0))
 
     def set_block_lds_bytes(self, nbytes=64 * 1024):
-        """LDS a workgroup of the condensed block apply may ask for (alfi_ctx_set_block_lds_bytes; default 64 KiB, clamped to the
-        device's limit per workgroup): a condensed level batches the widest NV of 4, 3, 2 with NV x the LDS of its one-vector
-        kernels within it (``Level.patch_apply_block_width``).  The A/B and test switch of that width; never the bits."""
+        """LDS a workgroup of a block apply may ask for (alfi_ctx_set_block_lds_bytes; default 64 KiB, clamped to the device's
+        limit per workgroup).  One budget for both applies that batch by it: a condensed level batches the widest NV of 4, 3, 2
+        with NV x the LDS of its one-vector kernels within it, a level of dense macro-star inverses (a patch above 160 dofs) the
+        widest NV with NV x 8 x (its largest patch, rounded up to even) bytes within it -- 4 columns up to 2048 dofs at the
+        default, 3 up to 2730, 2 up to 4096 (``Level.patch_apply_block_width``).  The A/B and test switch of that width; never the
+        bits."""
         self.check(self.lib.alfi_ctx_set_block_lds_bytes(self.h, int(nbytes)))
 
     # profiling (PETSc-event style report, driver.py:77-92) ----------------------------------------------------------------
@@ -699,7 +702,8 @@ class Level(object):
 
     def patch_apply_block_width(self):
         """The widest batch of a block apply on this level as it stands (alfi_patch_apply_block_width): 4 for dense inverses that
-        batch, 4 / 3 / 2 for condensed factors (what fits ``Context.set_block_lds_bytes``), 0: it loops the single apply."""
+        batch, 4 / 3 / 2 for condensed factors and dense macro stars (what fits ``Context.set_block_lds_bytes``), 0: it loops the
+        single apply."""
         w = ctypes.c_int()
         self.ctx.check(self.ctx.lib.alfi_patch_apply_block_width(self.h, ctypes.byref(w)))
         return int(w.value)

@@ -605,7 +605,7 @@ int alfi_saddle_velocity_info(alfi_saddle* s, int64_t* bytes, double* probe_resi
  * four columns is ONE launch that reads the stored values once: the additive apply of dense patch inverses of 33 .. 160 dofs
  * in either storage precision (the levels whose single apply gives a workgroup to every patch) and the nnz-balanced flat
  * product without column de-duplication.  Everything else runs the single-vector code column after column inside the library:
- * the interleaved copy of small patches, dense macro stars, levels of few patches, multiplicative sweeps, point
+ * the interleaved copy of small patches, dense macro stars on levels of fewer than 8 patches, levels of few patches, multiplicative sweeps, point
  * Jacobi, the de-duplicated and the lanes-per-row product, the four-launch smoother iteration, Chebyshev, transfers, coarse
  * solves.  A chunk of one column always does.  alfi_patch_apply_block_info / alfi_spmv_block_info: does the level, as it stands,
  * batch?  alfi_ctx_set_block_kernels(ctx, 0) makes every block call loop (default on): same bits, the cost of ncol single calls.
@@ -613,9 +613,12 @@ int alfi_saddle_velocity_info(alfi_saddle* s, int64_t* bytes, double* probe_resi
  * wide as the LDS of a workgroup allows: the widest NV of 4, 3, 2 with NV x the LDS of the one-vector kernels within the budget
  * of alfi_ctx_set_block_lds_bytes (default 64 KiB, clamped to the device's limit per workgroup); a chunk is taken in pieces of
  * that width, a piece of one column through the single apply.  Condensed levels of fewer patches (the chunked form of the
- * apply) and levels whose LDS does not fit two columns loop.  alfi_patch_apply_block_width: the widest batch of the level as it
- * stands -- 4 for dense inverses that batch, 4 / 3 / 2 for condensed factors, 0: it loops; alfi_patch_apply_block_info reports 1
- * exactly when the width is >= 2.
+ * apply) and levels whose LDS does not fit two columns loop.  Dense macro-star inverses (a patch above 160 dofs, FP64 or FP32
+ * storage, serial additive levels of at least 8 patches) batch under the SAME budget: a workgroup keeps x_p of its NV columns in
+ * NV x 8 x (largest patch, rounded up to even) bytes of LDS, so at the default 64 KiB a level batches 4 columns up to 2048 dofs
+ * per patch, 3 up to 2730, 2 up to 4096.  alfi_patch_apply_block_width: the widest batch of the level as it
+ * stands -- 4 for dense inverses that batch, 4 / 3 / 2 for condensed factors and dense macro stars, 0: it loops;
+ * alfi_patch_apply_block_info reports 1 exactly when the width is >= 2.
  * Serial levels only.  ALFI_E_ARG before any device work, nothing touched: a partitioned level, ncol < 1 or > nx, an odd
  * leading dimension or one below the vector length, a column index outside [0, nx) or listed twice, a NULL operand, an operand
  * that is written overlapping another one. */

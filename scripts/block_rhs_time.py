@@ -6,9 +6,14 @@ is set up once; the two modes alternate, round after round.
 
 usage: timeout -k 10 900 python scripts/block_rhs_time.py cfg3 [--rounds 3] [--reps 20] [--cycles 3] [--dtype f32] [--out FILE]
        timeout -k 10 900 python scripts/block_rhs_time.py cfg4 --condensed [--lds-bytes N] [--out FILE]
+       timeout -k 10 900 python scripts/block_rhs_time.py cfg5 [--macro-dtype f32] [--lds-bytes N] [--ncols 1,2,3,4] [--out FILE]
 (one GPU step = one process: give each its own time limit)
---lds-bytes: Context.set_block_lds_bytes, the LDS a workgroup of the condensed block apply may ask for (default 64 KiB; the
-width of every level is printed).
+Without --condensed every level holds dense inverses: the library looks for no groups and the generator's group labels (the
+Scott-Vogelius macro stars of config 5) are dropped.
+--lds-bytes: Context.set_block_lds_bytes, the LDS a workgroup of the condensed or the macro stars' block apply may ask for
+(default 64 KiB; the width of every level is printed).
+--macro-dtype f32: every level is asked for the FP32 storage of dense macro-star inverses (Level.set_macro_patch_storage) and
+factored again; a level that refuses keeps FP64.
 
 Per level with patches and per ncol: best ms per block apply (both stages) and per block product over the rounds, on / off and
 their ratio, and the stored bytes (alfi_patches_factor_bytes; operator values + column indices) per second of the batched call.
@@ -23,9 +28,6 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
-NCOLS = (1, 2, 4)
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("cfg")
@@ -35,8 +37,11 @@ def main():
     ap.add_argument("--dtype", default=None, choices=[None, "f32"])
     ap.add_argument("--condensed", action="store_true", help="the default condensation policy instead of dense inverses")
     ap.add_argument("--lds-bytes", type=int, default=None)
+    ap.add_argument("--macro-dtype", default=None, choices=[None, "f32"])
+    ap.add_argument("--ncols", default="1,2,4", help="column counts to time; 1 is always among them (the single apply)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    NCOLS = tuple(sorted({1} | {int(c) for c in args.ncols.split(",")}))
     import torch
     import bench
     from alfi_amd import hip
@@ -54,12 +59,19 @@ def main():
         % (time.time() - t0, [len(L.patch_ptr) - 1 for L in lv[1:]], int(np.diff(lv[-1].patch_ptr).max())))
     ctx = hip.Context(0)
     if not args.condensed:
-        ctx.set_condense_min_bytes(-1)              # dense inverses on every level
+        ctx.set_condense_min_bytes(-1)              # dense inverses on every level: the library looks for no groups ...
+        for L in lv[1:]:
+            L.patch_groups = None                   # ... and the generator's are dropped
     if args.lds_bytes is not None:
         ctx.set_block_lds_bytes(args.lds_bytes)
     mg = hip.Multigrid(ctx, lv, tr, k, patch_factor_dtype=args.dtype)
+    if args.macro_dtype is not None:
+        for d in mg.levels[1:]:
+            hip.ask_macro_patch_storage(d, args.macro_dtype)
+            d.factor()
+        ctx.sync()
     say("%s; per level (dofs, patches, factor GB, apply batched, product batched): %s"
-        % ("the default condensation policy" if args.condensed else "dense %s inverses" % (args.dtype or "f64"),
+        % ("the default condensation policy" if args.condensed else "dense %s inverses" % (args.dtype or args.macro_dtype or "f64"),
            ["%d/%d/%.3f/%d/%d" % (d.n, len(L.patch_ptr) - 1, d.factor_bytes() / 1e9, d.patch_apply_block_batched(),
                                   d.spmv_block_batched()) for L, d in zip(lv[1:], mg.levels[1:])]))
     if args.condensed:
@@ -74,6 +86,13 @@ def main():
                                             "" if args.lds_bytes is None else " (LDS budget %d)" % args.lds_bytes,
                                             (fb + 4 * vb) / (4 * (fb + vb)),
                                             8e-9 * float(((np.diff(L.patch_ptr) + 1) & ~1).sum()), 8e-9 * float(L.patch_ptr[-1])))
+    else:
+        # dense levels: what each one holds, the width of its block apply and, for macro stars, the LDS of a workgroup at that width
+        for L, d in zip(lv[1:], mg.levels[1:]):
+            w, m = d.patch_apply_block_width(), int(np.diff(L.patch_ptr).max())
+            say("  level %d: storage %s, largest patch %d dofs, block width %d%s%s"
+                % (d.id, d.patch_storage_dtype(), m, w, "" if args.lds_bytes is None else " (LDS budget %d)" % args.lds_bytes,
+                   ", %d bytes of LDS per workgroup" % (w * 8 * ((m + 1) & ~1)) if m > 160 and w >= 2 else ""))
     rng = np.random.default_rng(0)
 
     def timed(fn, reps):
@@ -123,8 +142,15 @@ def main():
             say("  %-18s %4d %8.4f %8.4f   %6.3f   %18.3f   %s"
                 % (label, c, on, off, on / off, on / (c * single), "%16.3f" % (nbytes / (on * 1e-3) / 1e12) if nbytes else ""))
     say()
-    say("spread over the rounds (max - min, ms), finest level apply at 4 columns: on %.4f, off %.4f"
-        % tuple(max(res[(work[-3][0], 4, on)]) - min(res[(work[-3][0], 4, on)]) for on in (True, False)))
+    say("spread over the rounds (max - min, ms), finest level apply at %d columns: on %.4f, off %.4f"
+        % ((NCOLS[-1],) + tuple(max(res[(work[-3][0], NCOLS[-1], on)]) - min(res[(work[-3][0], NCOLS[-1], on)]) for on in (True, False))))
+    say("every round, ms per block apply (on/off) -- is batched faster than looped in EVERY round?")
+    for label, _, _ in work:
+        if "apply" in label:
+            for c in NCOLS[1:]:
+                pairs = list(zip(res[(label, c, True)], res[(label, c, False)]))
+                say("  %-18s %4d  %s  %s" % (label, c, " ".join("%.4f/%.4f" % t for t in pairs),
+                                             "faster in every round" if all(a < b for a, b in pairs) else "NOT faster in every round"))
     mg.close()
     ctx.close()
     if args.out:
