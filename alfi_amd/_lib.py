@@ -168,6 +168,7 @@ SIGNATURES = {
     "alfi_patch_apply_block_info": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int)]),
     "alfi_spmv_block_info": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int)]),
     "alfi_patch_apply_block_width": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int)]),
+    "alfi_spmv_block_width": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int)]),
     "alfi_ctx_set_block_lds_bytes": (ctypes.c_int, [vp, ctypes.c_int64]),
     "alfi_patch_apply_block": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64]),
     "alfi_spmv_block": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64]),

@@ -4,10 +4,10 @@
 // Column c of every block result is the single-vector call's result on column c bit for bit.  A list of more than BLOCK_NV
 // columns is taken BLOCK_NV at a time.  Where a level has a batched kernel (kernels_block.hip: dense inverses through
 // patch_apply_kernel, the flat product) a chunk of two or more columns is ONE launch that streams the stored values once;
-// condensed factors of at least COND_PER_PATCH_MIN patches (kernels_block_cond.hip) and dense macro-star inverses of at least
-// BIG_BLOCK_MIN_PATCHES patches (kernels_block_big.hip) take a chunk in pieces of as many columns as fit the LDS budget
-// (block_cond_width, block_big_width); everything else -- and every chunk or piece of one column -- is the single-vector code,
-// column after column.
+// condensed factors of at least COND_PER_PATCH_MIN patches (kernels_block_cond.hip), dense macro-star inverses of at least
+// BIG_BLOCK_MIN_PATCHES patches (kernels_block_big.hip) and the de-duplicated product (kernels_block.hip) take a chunk in pieces
+// of as many columns as fit the LDS budget (block_cond_width, block_big_width, block_dedup_width); everything else -- and every
+// chunk or piece of one column -- is the single-vector code, column after column.
 #include "api_internal.h"
 #include "block_cols.h"
 
@@ -53,8 +53,12 @@ static int block_piece_apply_width(const alfi_level* L) {
 static int block_apply_width(const alfi_level* L) {
   return block_apply_waves(L) != 0 ? BLOCK_NV : block_piece_apply_width(L);
 }
-static bool block_spmv_batched(const alfi_level* L) {
-  return L->ctx->block_kernels && !level_is_partitioned(L) && bsr_spmv_block_batched(L->A_own);
+// the widest batch of the level's product: BLOCK_NV on flat and whole-row operators, what fits the ctx's LDS budget on
+// de-duplicated ones (bsr_spmv_block_width, kernels_block.hip), 0: it loops
+static int block_spmv_width(const alfi_level* L) {
+  if (!L->ctx->block_kernels || level_is_partitioned(L)) return 0;
+  const int w = bsr_spmv_block_width(L->A_own, L->ctx->block_lds_bytes);
+  return w >= 2 ? w : 0;
 }
 
 int alfi_patch_apply_block_info(alfi_level* L, int* batched) {
@@ -67,8 +71,8 @@ int alfi_patch_apply_block_width(alfi_level* L, int* width) {
   *width = block_apply_width(L);
   return 0;
 }
-// LDS a workgroup of a block apply may ask for -- one budget for the condensed apply and the macro stars' (default 64 KiB: no
-// launch needs its limit raised), clamped to what the device gives one workgroup
+// LDS a workgroup of a block kernel may ask for -- one budget for the condensed apply, the macro stars' and the de-duplicated
+// product (default 64 KiB: no launch needs its limit raised), clamped to what the device gives one workgroup
 int alfi_ctx_set_block_lds_bytes(alfi_ctx* ctx, int64_t bytes) {
   if (!ctx) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL context");
   int limit = 0;
@@ -88,7 +92,12 @@ int alfi_smooth_fgmres_block_info(alfi_level* L, int k, int* lockstep) {
 }
 int alfi_spmv_block_info(alfi_level* L, int* batched) {
   if (!L || !batched) return alfi_set_error(L ? L->ctx : nullptr, ALFI_E_ARG, "alfi_spmv_block_info: NULL argument");
-  *batched = block_spmv_batched(L) ? 1 : 0;
+  *batched = block_spmv_width(L) >= 2 ? 1 : 0;
+  return 0;
+}
+int alfi_spmv_block_width(alfi_level* L, int* width) {
+  if (!L || !width) return alfi_set_error(L ? L->ctx : nullptr, ALFI_E_ARG, "alfi_spmv_block_width: NULL argument");
+  *width = block_spmv_width(L);
   return 0;
 }
 
@@ -170,17 +179,22 @@ int block_spmv(alfi_level* L, const BlockCols& ic, const BlockCols& oc, const do
                const double* B, int64_t ldb, int mode) {
   alfi_ctx* ctx = L->ctx;
   ctx->cur_tag = L->id;
-  if (ic.n > 1 && block_spmv_batched(L)) {
+  // the chunk in pieces of the product's width (BLOCK_NV: one piece), a piece of one column through the single product
+  const int width = ic.n > 1 ? block_spmv_width(L) : 0;
+  for (int k = 0; k < block_pieces(ic.n, width); ++k) {
+    const BlockCols pi = block_piece(ic, width, k), po = block_piece(oc, width, k);
+    if (pi.n == 1) {
+      ALFI_CHECK(level_spmv(L, X + pi.c[0] * ldx, Y + po.c[0] * ldy, mode ? B + pi.c[0] * ldb : nullptr, mode));
+      continue;
+    }
     const DevBSR& A = L->A_own;
     if (!A.aligned) {
       const int64_t nchunks = (A.nnzb + SPMV_CHUNK - 1) / SPMV_CHUNK;
-      ALFI_CHECK(grow_slots(ctx, &L->blk_carry, &L->blk_carry_slots, ic.n, nchunks * A.bs));
+      ALFI_CHECK(grow_slots(ctx, &L->blk_carry, &L->blk_carry_slots, pi.n, nchunks * A.bs));
     }
-    ProfScope prof(ctx, ALFI_EV_MATMULT);   // to the end of the branch
-    return launch_bsr_spmv_block(ctx, A, ic, oc, X, ldx, Y, ldy, B, ldb, 1.0, mode, L->blk_carry);
+    ProfScope prof(ctx, ALFI_EV_MATMULT);   // to the end of the piece
+    ALFI_CHECK(launch_bsr_spmv_block(ctx, A, pi, po, X, ldx, Y, ldy, B, ldb, 1.0, mode, L->blk_carry));
   }
-  for (int i = 0; i < ic.n; ++i)
-    ALFI_CHECK(level_spmv(L, X + ic.c[i] * ldx, Y + oc.c[i] * ldy, mode ? B + ic.c[i] * ldb : nullptr, mode));
   return 0;
 }
 

@@ -91,6 +91,20 @@ inline int block_big_width(int max_np, int64_t budget_bytes) {
 // existing tests do not change; 8 is the smallest level the block kernel is tested on.  Nothing about speed was measured for it.
 constexpr int64_t BIG_BLOCK_MIN_PATCHES = 8;
 
+// ---- the de-duplicated level product (operators whose single product is bsr_spmv_dedup_kernel; kernels_block.hip) -------------
+// The block form stages the distinct x entries of a workgroup's group of blocks for its nv columns in dynamic LDS, bs doubles per
+// entry and column, sized by the operator's fullest group (max_uniq distinct columns, at most the 1024 blocks of a group):
+inline int64_t block_dedup_lds(int max_uniq, int bs, int nv) { return (int64_t)nv * 8 * bs * max_uniq; }
+// The widest batch of such an operator: the largest nv of 4, 3, 2 with block_dedup_lds(max_uniq, bs, nv) <= budget_bytes (the
+// ctx's block_lds_bytes, the budget of the applies above); 0: not even two columns fit, the product loops.  At the default
+// 64 KiB: bs 2 always gives 4; bs 3 gives 4 up to 682 distinct columns, 3 up to 910, 2 up to 1024 (always).
+inline int block_dedup_width(int max_uniq, int bs, int64_t budget_bytes) {
+  if (max_uniq <= 0 || bs <= 0 || budget_bytes <= 0) return 0;
+  for (int nv = BLOCK_NV; nv >= 2; --nv)
+    if (block_dedup_lds(max_uniq, bs, nv) <= budget_bytes) return nv;
+  return 0;
+}
+
 // A chunk of b.n columns on a level of batch width `width` is taken in pieces of at most `width` columns, the last one shorter
 // (a width below 2: a column at a time).  A piece of one column is the single-vector path.
 inline int block_piece_width(int width) { return width < 1 ? 1 : width > BLOCK_NV ? BLOCK_NV : width; }

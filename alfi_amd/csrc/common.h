@@ -204,6 +204,7 @@ struct DevBSR {
   uint16_t* lidx = nullptr;
   int32_t* ucol = nullptr;
   int32_t* uptr = nullptr;
+  int max_uniq = 0;             // the largest number of distinct columns of a group: what the block product sizes its LDS by
 };
 constexpr int SPMV_WG = 4 * SPMV_CHUNK;      // blocks per workgroup of the flat product
 constexpr int SPMV_DEDUP_MAX = 1024;         // distinct columns per group the product stages in LDS (24 KiB at bs = 3)
@@ -602,9 +603,16 @@ int upload_bsr_values(alfi_ctx* ctx, DevBSR* d, const double* host_vals);
 int build_spmv_dedup(alfi_ctx* ctx, DevBSR* d);     // column de-duplication tables of the flat product (kernels_vec.hip)
 // Block right-hand sides (kernels_block.hip; the operand layout and BlockCols: block_cols.h), one launch for 1 .. 4 columns:
 // entry i of cols names the column of the operands that are read (X, B), entry i of ocols the column of Y its result goes to.
-// The product: for operators bsr_spmv_block_batched accepts; carry: cols.n x ceil(nnzb / SPMV_CHUNK) x bs doubles.
+// The product: for operators whose bsr_spmv_block_width under the ctx's LDS budget is >= cols.n (flat operators: BLOCK_NV,
+// de-duplicated ones: block_dedup_width, 0: the product loops); carry: cols.n x ceil(nnzb / SPMV_CHUNK) x bs doubles.
 struct BlockCols;
-bool bsr_spmv_block_batched(const DevBSR& A);
+int bsr_spmv_block_width(const DevBSR& A, int64_t budget_bytes);
+bool bsr_spmv_block_batched(const DevBSR& A, int64_t budget_bytes);      // width >= 2
+bool bsr_spmv_is_dedup(const DevBSR& A);       // is the single product with A bsr_spmv_dedup_kernel?
+// the main launch on such an operator, 2 .. its width columns (kernels_block_dedup.hip; launch_bsr_spmv_block runs the fix-up)
+int launch_bsr_spmv_dedup_block(alfi_ctx* ctx, const DevBSR& A, const BlockCols& cols, const BlockCols& ocols, const double* X,
+                                int64_t ldx, double* Y, int64_t ldy, const double* B, int64_t ldb, double alpha, int mode,
+                                double* carry);
 int launch_bsr_spmv_block(alfi_ctx* ctx, const DevBSR& A, const BlockCols& cols, const BlockCols& ocols, const double* X,
                           int64_t ldx, double* Y, int64_t ldy, const double* B, int64_t ldb, double alpha, int mode, double* carry);
 // The additive apply, both stages: for levels whose single apply is patch_apply_kernel with W = patch_apply_dense_waves(lvl,

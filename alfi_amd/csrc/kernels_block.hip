@@ -94,7 +94,8 @@ __global__ __launch_bounds__(256) void patch_sum_block_kernel(int64_t n, const i
 // flat BSR product (bsr_spmv_flat_kernel): one colflag load and one set of value loads per block serve the NV x gathers; the
 // NV partial sums p[c][] and carries go through the same segmented scan.  carry_out: (NV, nchunks, BS).
 // Left out on purpose: the single kernel's workgroup -> chunk remap over the XCDs (its xcd_map argument).  It changes which
-// workgroup takes which chunk, never a result; the large operators it was measured on de-duplicate their columns and loop.
+// workgroup takes which chunk, never a result; the large operators it was measured on de-duplicate their columns and take
+// bsr_spmv_dedup_block_kernel (kernels_block_dedup.hip), which keeps it.
 // ---------------------------------------------------------------------------------------------------------------------
 typedef double blk_d2 __attribute__((ext_vector_type(2)));
 template <int BS, bool NT, bool ALIGNED, int NV>
@@ -321,11 +322,15 @@ int launch_patch_sum_block(alfi_level* L, const BlockCols& cols, const BlockCols
   return 0;
 }
 
-// does the product with A go through bsr_spmv_flat_kernel (whole-row chunks, or equal chunks + fix-up without de-duplication)?
-bool bsr_spmv_block_batched(const DevBSR& A) {
-  if (!A.flat || A.nbrows == 0 || A.nnzb == 0 || (A.bs != 2 && A.bs != 3)) return false;
-  return A.aligned || !(A.dedup && !A.view && A.kbase == 0);
+// The widest batch of the product with A under an LDS budget (the ctx's block_lds_bytes): BLOCK_NV where the single product is
+// bsr_spmv_flat_kernel (whole-row chunks, or equal chunks + fix-up without de-duplication); where it is bsr_spmv_dedup_kernel,
+// as many columns as the staged x entries of the fullest group fit the budget (block_dedup_width, block_cols.h); 0: it loops.
+bool bsr_spmv_is_dedup(const DevBSR& A) { return !A.aligned && A.dedup && !A.view && A.kbase == 0; }
+int bsr_spmv_block_width(const DevBSR& A, int64_t budget_bytes) {
+  if (!A.flat || A.nbrows == 0 || A.nnzb == 0 || (A.bs != 2 && A.bs != 3)) return 0;
+  return bsr_spmv_is_dedup(A) ? block_dedup_width(A.max_uniq, A.bs, budget_bytes) : BLOCK_NV;
 }
+bool bsr_spmv_block_batched(const DevBSR& A, int64_t budget_bytes) { return bsr_spmv_block_width(A, budget_bytes) >= 2; }
 
 template <int BS, int NV>
 static int launch_spmv_block_nv(alfi_ctx* ctx, const DevBSR& A, const BlockCols& cols, const BlockCols& ocols, const double* X, int64_t ldx, double* Y,
@@ -339,10 +344,14 @@ static int launch_spmv_block_nv(alfi_ctx* ctx, const DevBSR& A, const BlockCols&
     return 0;
   }
   const int64_t nchunks = (A.nnzb + SPMV_CHUNK - 1) / SPMV_CHUNK;
-  hipLaunchKernelGGL((bsr_spmv_flat_block_kernel<BS, true, false, NV>), dim3((unsigned)((nchunks + 3) / 4)), dim3(256), 0,
-                     ctx->stream, A.kbase, A.nnzb, nchunks, (const int64_t*)nullptr, A.colidx, A.vals, A.chunk_row, X, ldx, Y, ldy,
-                     B, ldb, cols, ocols, alpha, mode, carry, A.carry_row);
-  ALFI_HIP_CHECK(ctx, hipGetLastError());
+  if (bsr_spmv_is_dedup(A)) {     // the staged gathers: kernels_block_dedup.hip
+    ALFI_CHECK(launch_bsr_spmv_dedup_block(ctx, A, cols, ocols, X, ldx, Y, ldy, B, ldb, alpha, mode, carry));
+  } else {
+    hipLaunchKernelGGL((bsr_spmv_flat_block_kernel<BS, true, false, NV>), dim3((unsigned)((nchunks + 3) / 4)), dim3(256), 0,
+                       ctx->stream, A.kbase, A.nnzb, nchunks, (const int64_t*)nullptr, A.colidx, A.vals, A.chunk_row, X, ldx, Y, ldy,
+                       B, ldb, cols, ocols, alpha, mode, carry, A.carry_row);
+    ALFI_HIP_CHECK(ctx, hipGetLastError());
+  }
   hipLaunchKernelGGL((bsr_spmv_fixup_block_kernel<BS, NV>), dim3((unsigned)((nchunks + 255) / 256)), dim3(256), 0, ctx->stream,
                      nchunks, carry, A.carry_row, Y, ldy, ocols, alpha, mode);
   ALFI_HIP_CHECK(ctx, hipGetLastError());
@@ -359,13 +368,18 @@ static int launch_spmv_block_bs(alfi_ctx* ctx, const DevBSR& A, const BlockCols&
   }
 }
 
-// Y[:, c] = A X[:, c] (mode 0) or B[:, c] - alpha A X[:, c] (mode 1) for the 1 .. BLOCK_NV columns of cols; A as
-// bsr_spmv_block_batched says; carry: cols.n x ceil(nnzb / SPMV_CHUNK) x bs doubles (read by the fix-up of unaligned chunks alone)
+// Y[:, c] = A X[:, c] (mode 0) or B[:, c] - alpha A X[:, c] (mode 1) for the columns of cols: 1 .. BLOCK_NV of them on a flat
+// operator, 2 .. bsr_spmv_block_width(A, the ctx's block_lds_bytes) on a de-duplicated one; carry: cols.n x ceil(nnzb /
+// SPMV_CHUNK) x bs doubles (read by the fix-up of unaligned chunks alone)
 int launch_bsr_spmv_block(alfi_ctx* ctx, const DevBSR& A, const BlockCols& cols, const BlockCols& ocols, const double* X,
                           int64_t ldx, double* Y, int64_t ldy, const double* B, int64_t ldb, double alpha, int mode, double* carry) {
   if (cols.n < 1 || cols.n > BLOCK_NV || ocols.n != cols.n)
     return alfi_set_error(ctx, ALFI_E_ARG, "a block launch takes 1 .. %d columns", BLOCK_NV);
-  if (!bsr_spmv_block_batched(A)) return alfi_set_error(ctx, ALFI_E_STATE, "block product on an operator without the flat layout");
+  const int width = bsr_spmv_block_width(A, ctx->block_lds_bytes);
+  if (width < 2) return alfi_set_error(ctx, ALFI_E_STATE, "block product on an operator whose product does not batch");
+  if (cols.n > width)
+    return alfi_set_error(ctx, ALFI_E_STATE, "block product: %d columns of %d distinct x entries do not fit the LDS budget", cols.n,
+                          A.max_uniq);
   if (mode == 0) B = X, ldb = ldx;      // never read; a valid address for the kernel's pointer arithmetic
   if (A.bs == 2) return launch_spmv_block_bs<2>(ctx, A, cols, ocols, X, ldx, Y, ldy, B, ldb, alpha, mode, carry);
   return launch_spmv_block_bs<3>(ctx, A, cols, ocols, X, ldx, Y, ldy, B, ldb, alpha, mode, carry);

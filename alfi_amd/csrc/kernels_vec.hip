@@ -410,6 +410,7 @@ __global__ __launch_bounds__(256) void spmv_dedup_compact_kernel(const int32_t* 
 
 int build_spmv_dedup(alfi_ctx* ctx, DevBSR* d) {
   d->dedup = false;
+  d->max_uniq = 0;
   if (!d->flat || d->aligned || d->nnzb < SPMV_WG) return 0;
   const int64_t nnzb = d->nnzb, ng = (nnzb + SPMV_WG - 1) / SPMV_WG;
   int32_t *tmp = nullptr, *nuniq = nullptr;
@@ -429,6 +430,7 @@ int build_spmv_dedup(alfi_ctx* ctx, DevBSR* d) {
   if (fits) {
     int64_t tot = 0;
     for (int64_t g = 0; g < ng; ++g) {
+      d->max_uniq = std::max(d->max_uniq, (int)uptr[g + 1]);
       tot += uptr[g + 1];
       fits = fits && tot <= INT32_MAX;
       uptr[g + 1] = (int32_t)tot;

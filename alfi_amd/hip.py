@@ -120,8 +120,10 @@ class Context(object):
         limit per workgroup).  One budget for both applies that batch by it: a condensed level batches the widest NV of 4, 3, 2
         with NV x the LDS of its one-vector kernels within it, a level of dense macro-star inverses (a patch above 160 dofs) the
         widest NV with NV x 8 x (its largest patch, rounded up to even) bytes within it -- 4 columns up to 2048 dofs at the
-        default, 3 up to 2730, 2 up to 4096 (``Level.patch_apply_block_width``).  The A/B and test switch of that width; never the
-        bits."""
+        default, 3 up to 2730, 2 up to 4096 (``Level.patch_apply_block_width``).  The de-duplicated level product batches by it
+        too: the widest NV with NV x 8 x bs x (the largest number of distinct columns in a group of 1024 blocks) bytes within it --
+        at the default bs 2 always 4, bs 3 4 columns up to 682 distinct columns, 3 up to 910, 2 up to 1024
+        (``Level.spmv_block_width``).  The A/B and test switch of those widths; never the bits."""
         self.check(self.lib.alfi_ctx_set_block_lds_bytes(self.h, int(nbytes)))
 
     # profiling (PETSc-event style report, driver.py:77-92) ----------------------------------------------------------------
@@ -720,6 +722,14 @@ class Level(object):
         b = ctypes.c_int()
         self.ctx.check(self.ctx.lib.alfi_spmv_block_info(self.h, ctypes.byref(b)))
         return bool(b.value)
+
+    def spmv_block_width(self):
+        """The widest batch of a block product or residual on this level as it stands (alfi_spmv_block_width): 4 for flat
+        operators, 4 / 3 / 2 for de-duplicated ones (what fits ``Context.set_block_lds_bytes``), 0: it loops the single product.
+        ``spmv_block_batched`` is True exactly when this is >= 2."""
+        w = ctypes.c_int()
+        self.ctx.check(self.ctx.lib.alfi_spmv_block_width(self.h, ctypes.byref(w)))
+        return int(w.value)
 
     def set_jacobi(self, on=True):
         """pc_type jacobi (alfi_level_set_jacobi): the level's preconditioner application -- ``patch_apply`` and every smoother --

@@ -604,9 +604,10 @@ int alfi_saddle_velocity_info(alfi_saddle* s, int64_t* bytes, double* probe_resi
  * FOR BIT.  Lists of more than four columns are taken four at a time.  Where a level has a batched kernel, a chunk of two to
  * four columns is ONE launch that reads the stored values once: the additive apply of dense patch inverses of 33 .. 160 dofs
  * in either storage precision (the levels whose single apply gives a workgroup to every patch) and the nnz-balanced flat
- * product without column de-duplication.  Everything else runs the single-vector code column after column inside the library:
+ * product (with column de-duplication: as wide as the budget below allows).  Everything else runs the single-vector code column
+ * after column inside the library:
  * the interleaved copy of small patches, dense macro stars on levels of fewer than 8 patches, levels of few patches, multiplicative sweeps, point
- * Jacobi, the de-duplicated and the lanes-per-row product, the four-launch smoother iteration, Chebyshev, transfers, coarse
+ * Jacobi, the lanes-per-row product, the four-launch smoother iteration, Chebyshev, transfers, coarse
  * solves.  A chunk of one column always does.  alfi_patch_apply_block_info / alfi_spmv_block_info: does the level, as it stands,
  * batch?  alfi_ctx_set_block_kernels(ctx, 0) makes every block call loop (default on): same bits, the cost of ncol single calls.
  * Condensed factors batch too where their single apply gives a workgroup to every patch (levels of at least 1024 patches), as
@@ -619,6 +620,12 @@ int alfi_saddle_velocity_info(alfi_saddle* s, int64_t* bytes, double* probe_resi
  * per patch, 3 up to 2730, 2 up to 4096.  alfi_patch_apply_block_width: the widest batch of the level as it
  * stands -- 4 for dense inverses that batch, 4 / 3 / 2 for condensed factors and dense macro stars, 0: it loops;
  * alfi_patch_apply_block_info reports 1 exactly when the width is >= 2.
+ * The product of a large operator (more than 2^21 blocks, or a block row longer than 256 blocks; at least 1024 blocks) stages the
+ * distinct x entries of every group of 1024 blocks in LDS; its block form keeps them for NV columns, NV x 8 x bs x (the largest
+ * number of distinct columns of a group) bytes, under the SAME budget: at the default 64 KiB bs 2 batches 4 columns, bs 3 batches
+ * 4 up to 682 distinct columns, 3 up to 910, 2 up to 1024.  alfi_spmv_block_width: the widest batch of the level's product as it
+ * stands -- 4 for flat operators, 4 / 3 / 2 for de-duplicated ones, 0: it loops; alfi_spmv_block_info reports 1 exactly when the
+ * width is >= 2.
  * Serial levels only.  ALFI_E_ARG before any device work, nothing touched: a partitioned level, ncol < 1 or > nx, an odd
  * leading dimension or one below the vector length, a column index outside [0, nx) or listed twice, a NULL operand, an operand
  * that is written overlapping another one. */
@@ -626,6 +633,7 @@ int alfi_ctx_set_block_kernels(alfi_ctx* ctx, int on);
 int alfi_patch_apply_block_info(alfi_level* lvl, int* batched);
 int alfi_spmv_block_info(alfi_level* lvl, int* batched);
 int alfi_patch_apply_block_width(alfi_level* lvl, int* width);
+int alfi_spmv_block_width(alfi_level* lvl, int* width);
 int alfi_ctx_set_block_lds_bytes(alfi_ctx* ctx, int64_t bytes);
 /* Y[:, c] = alfi_patch_apply of X[:, c] */
 int alfi_patch_apply_block(alfi_level* lvl, int ncol, const int* cols, int nx, const double* X, int64_t ldx, double* Y, int64_t ldy);

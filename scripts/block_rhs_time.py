@@ -10,8 +10,9 @@ usage: timeout -k 10 900 python scripts/block_rhs_time.py cfg3 [--rounds 3] [--r
 (one GPU step = one process: give each its own time limit)
 Without --condensed every level holds dense inverses: the library looks for no groups and the generator's group labels (the
 Scott-Vogelius macro stars of config 5) are dropped.
---lds-bytes: Context.set_block_lds_bytes, the LDS a workgroup of the condensed or the macro stars' block apply may ask for
-(default 64 KiB; the width of every level is printed).
+--lds-bytes: Context.set_block_lds_bytes, the LDS a workgroup of the condensed or the macro stars' block apply or of the
+de-duplicated block product may ask for (default 64 KiB; the width of every level's apply and product is printed, with the
+largest number of distinct columns in a group of 1024 blocks, which is what sets the product's).
 --macro-dtype f32: every level is asked for the FP32 storage of dense macro-star inverses (Level.set_macro_patch_storage) and
 factored again; a level that refuses keeps FP64.
 
@@ -93,6 +94,20 @@ def main():
             say("  level %d: storage %s, largest patch %d dofs, block width %d%s%s"
                 % (d.id, d.patch_storage_dtype(), m, w, "" if args.lds_bytes is None else " (LDS budget %d)" % args.lds_bytes,
                    ", %d bytes of LDS per workgroup" % (w * 8 * ((m + 1) & ~1)) if m > 160 and w >= 2 else ""))
+    # the product: distinct columns per group of 1024 blocks (what the de-duplicated product stages in LDS; counted here from the
+    # host operator), its block width, and the expectation from bytes at ncol columns -- (operator bytes + ncol x vector bytes) /
+    # (ncol x (operator bytes + vector bytes)); operator bytes = values, 2-byte local indices and the groups' column lists, vector
+    # bytes = one x gather per distinct column of a group and the result
+    for L, d in zip(lv[1:], mg.levels[1:]):
+        col, bs = np.asarray(L.A.colidx, dtype=np.int64), d.bs
+        pad = np.full(-len(col) % 1024, -1, dtype=np.int64)
+        grp = np.sort(np.concatenate([col, pad]).reshape(-1, 1024), axis=1)
+        uniq = 1 + (np.diff(grp, axis=1) != 0).sum(axis=1) - (grp[:, 0] < 0)          # (the pad value is not a column)
+        ob, vb = float(len(col) * (8 * bs * bs + 2) + 4 * uniq.sum()), float(8 * bs * uniq.sum() + 8 * d.n)
+        say("  level %d product: %d blocks of bs %d, distinct columns per group of 1024 blocks max %d mean %.1f, block width %d%s, "
+            "expected ratio from bytes %s" % (d.id, len(col), bs, uniq.max(), uniq.mean(), d.spmv_block_width(),
+                                              "" if args.lds_bytes is None else " (LDS budget %d)" % args.lds_bytes,
+                                              " ".join("%d: %.3f" % (c, (ob + c * vb) / (c * (ob + vb))) for c in NCOLS[1:])))
     rng = np.random.default_rng(0)
 
     def timed(fn, reps):
@@ -144,9 +159,11 @@ def main():
     say()
     say("spread over the rounds (max - min, ms), finest level apply at %d columns: on %.4f, off %.4f"
         % ((NCOLS[-1],) + tuple(max(res[(work[-3][0], NCOLS[-1], on)]) - min(res[(work[-3][0], NCOLS[-1], on)]) for on in (True, False))))
-    say("every round, ms per block apply (on/off) -- is batched faster than looped in EVERY round?")
+    say("spread over the rounds (max - min, ms), finest level product at %d columns: on %.4f, off %.4f"
+        % ((NCOLS[-1],) + tuple(max(res[(work[-2][0], NCOLS[-1], on)]) - min(res[(work[-2][0], NCOLS[-1], on)]) for on in (True, False))))
+    say("every round, ms per block apply / block product (on/off) -- is batched faster than looped in EVERY round?")
     for label, _, _ in work:
-        if "apply" in label:
+        if "apply" in label or "product" in label:
             for c in NCOLS[1:]:
                 pairs = list(zip(res[(label, c, True)], res[(label, c, False)]))
                 say("  %-18s %4d  %s  %s" % (label, c, " ".join("%.4f/%.4f" % t for t in pairs),
