@@ -175,6 +175,8 @@ SIGNATURES = {
     "alfi_residual_block": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64, vp,
                                            ctypes.c_int64]),
     "alfi_smooth_fgmres_block_info": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "alfi_smooth_fgmres_block_mode": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "alfi_ctx_set_block_fused": (ctypes.c_int, [vp, ctypes.c_int]),
     "alfi_smooth_fgmres_block": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64, vp,
                                                 ctypes.c_int64, ctypes.c_int]),
     "alfi_mg_vcycle_block": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64]),

@@ -7,13 +7,20 @@
 // condensed factors of at least COND_PER_PATCH_MIN patches (kernels_block_cond.hip), dense macro-star inverses of at least
 // BIG_BLOCK_MIN_PATCHES patches (kernels_block_big.hip) and the de-duplicated product (kernels_block.hip) take a chunk in pieces
 // of as many columns as fit the LDS budget (block_cond_width, block_big_width, block_dedup_width); everything else -- and every
-// chunk or piece of one column -- is the single-vector code, column after column.
+// chunk or piece of one column -- is the single-vector code, column after column.  The smoother goes one of three ways
+// (block_smooth_mode, block_cols.h): the general path in lockstep, the block form of the four-launch iteration
+// (kernels_block_fused.hip), or whole single smoother calls column after column.
 #include "api_internal.h"
 #include "block_cols.h"
 
 int alfi_ctx_set_block_kernels(alfi_ctx* ctx, int on) {
   if (!ctx) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL context");
   ctx->block_kernels = on != 0;
+  return 0;
+}
+int alfi_ctx_set_block_fused(alfi_ctx* ctx, int on) {
+  if (!ctx) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL context");
+  ctx->block_fused = on != 0;
   return 0;
 }
 
@@ -80,10 +87,26 @@ int alfi_ctx_set_block_lds_bytes(alfi_ctx* ctx, int64_t bytes) {
   ctx->block_lds_bytes = (int)std::min<int64_t>(std::max<int64_t>(bytes, 0), limit);
   return 0;
 }
-// does alfi_smooth_fgmres_block(L, k, ...) on two or more columns run in lockstep (one block apply and one block product per
-// iteration), or does it loop whole smoother calls?
-static bool block_smoother_lockstep(alfi_level* L, int k) {
-  return L->ctx->block_kernels && !level_is_partitioned(L) && !smoother_takes_fused_iteration(L, k);
+// Which way alfi_smooth_fgmres_block(L, k, ...) goes on a chunk of two or more columns (block_smooth_mode, block_cols.h): the
+// general path in lockstep (one block apply and one block product per iteration), the block form of the four-launch iteration,
+// or a loop over whole smoother calls.
+static bool level_applies_il(const alfi_level* L) { return L->il_valid && L->held == HELD_F64; }   // launch_patch_apply_range
+static int block_smoother_mode(alfi_level* L, int k) {
+  BlockSmoothFacts f;
+  f.block_kernels = L->ctx->block_kernels;
+  f.block_fused = L->ctx->block_fused;
+  f.partitioned = level_is_partitioned(L);
+  f.fused_iteration = smoother_takes_fused_iteration(L, k);
+  f.applies_il = L->factored && level_applies_il(L);
+  f.apply_waves = block_apply_waves(L);
+  f.piece_width = block_piece_apply_width(L);
+  return block_smooth_mode(f);
+}
+static bool block_smoother_lockstep(alfi_level* L, int k) { return block_smoother_mode(L, k) == BLOCK_SMOOTH_LOCKSTEP; }
+int alfi_smooth_fgmres_block_mode(alfi_level* L, int k, int* mode) {
+  if (!L || !mode || k < 1) return alfi_set_error(L ? L->ctx : nullptr, ALFI_E_ARG, "alfi_smooth_fgmres_block_mode: bad argument");
+  *mode = block_smoother_mode(L, k);
+  return 0;
 }
 int alfi_smooth_fgmres_block_info(alfi_level* L, int k, int* lockstep) {
   if (!L || !lockstep || k < 1) return alfi_set_error(L ? L->ctx : nullptr, ALFI_E_ARG, "alfi_smooth_fgmres_block_info: bad argument");
@@ -123,8 +146,9 @@ void free_block_smoother(alfi_level* L) {
   dev_free(L->blk_Z);
   dev_free(L->blk_w);
   dev_free(L->blk_hs);
-  L->blk_V = L->blk_Z = L->blk_w = L->blk_hs = nullptr;
-  L->blk_kmax = L->blk_ws_slots = 0;
+  dev_free(L->blk_part);
+  L->blk_V = L->blk_Z = L->blk_w = L->blk_hs = L->blk_part = nullptr;
+  L->blk_kmax = L->blk_ws_slots = L->blk_part_slots = 0;
 }
 
 // one Krylov workspace per slot, with the level's own kmax (the Hessenberg layout the kernels index with is HsLayout(kmax))
@@ -198,17 +222,80 @@ int block_spmv(alfi_level* L, const BlockCols& ic, const BlockCols& oc, const do
   return 0;
 }
 
+// alfi_smooth_fgmres on the columns of one chunk of 2 .. BLOCK_NV columns, on a level where the single call takes the four-launch
+// iteration (smooth_fgmres_fused, api_smoother.hip) and stage 1 of the apply has a batched form: the same launches per
+// iteration for all columns -- stage 1 (on condensed and macro-star levels: per piece of the level's width), sum + scale,
+// product with dots, projection with norm partials.  ProfScope classes as in the single path.
+static int block_smooth_fgmres_fused(alfi_level* L, int k, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx,
+                                     int nonzero_guess) {
+  alfi_ctx* ctx = L->ctx;
+  const int nc = cols.n;
+  ALFI_CHECK(ensure_block_smoother(L, nc));
+  ALFI_CHECK(grow_slots(ctx, &L->blk_part, &L->blk_part_slots, nc, block_partial_per_slot(RED_BLOCKS, RED_MAXV)));
+  ALFI_CHECK(grow_slots(ctx, &L->blk_stage, &L->blk_stage_slots, nc, L->lay.stage_len));
+  if (L->held == HELD_COND) ALFI_CHECK(grow_slots(ctx, &L->blk_ctmp, &L->blk_ctmp_slots, nc, L->lay.sum_n));
+  const int64_t ldv = L->ldv;
+  const BlockCols slots = block_chunk(nc, nullptr, 0);
+  // r0 = b - A x, or x = 0 and r0 = b in the launch of the norm partials
+  if (nonzero_guess) ALFI_CHECK(block_spmv(L, cols, slots, X, ldx, L->blk_w, ldv, B, ldb, 1));
+  {
+    ProfScope prof(ctx, ALFI_EV_BLAS1);
+    ALFI_CHECK(launch_first_norm_block(L, cols, nonzero_guess ? nullptr : B, ldb, X, ldx));
+  }
+  const int G = red_blocks_for(L->n);
+  const bool il = level_applies_il(L);
+  const int W = il ? 0 : block_apply_waves(L), width = il || W != 0 ? BLOCK_NV : block_piece_apply_width(L);
+  const double* stage[BLOCK_NV];
+  for (int s = 0; s < BLOCK_NV; ++s) stage[s] = L->blk_stage + (s < nc ? s : 0) * L->lay.stage_len;
+  for (int j = 0; j < k; ++j) {
+    // stage 1: slot s's staged patch solves of w_s
+    if (il) {
+      ALFI_CHECK(launch_patch_apply_il_block(L, nc, L->blk_w, ldv, L->blk_stage));
+    } else if (W != 0) {
+      ALFI_CHECK(launch_patch_apply_block(L, W, slots, slots, L->blk_w, ldv, nullptr, 0, L->blk_stage));
+    } else {
+      for (int q = 0; q < block_pieces(nc, width); ++q) {
+        const BlockCols pi = block_piece(slots, width, q);
+        double* st = L->blk_stage + pi.c[0] * L->lay.stage_len;
+        if (pi.n == 1) {      // (at most one piece of a chunk has one column: the single apply into the level's own buffer)
+          ALFI_CHECK(launch_patch_apply_range(L, 0, L->npatch, L->blk_w + pi.c[0] * ldv));
+          stage[pi.c[0]] = L->stage;
+        } else if (L->held != HELD_COND) {
+          ALFI_CHECK(launch_big_apply_block(L, pi, pi, L->blk_w, ldv, nullptr, 0, st));
+        } else {
+          ALFI_CHECK(launch_cond_apply_block(L, pi, pi, L->blk_w, ldv, nullptr, 0, st, L->blk_ctmp));
+        }
+      }
+    }
+    {
+      ProfScope prof(ctx, ALFI_EV_PATCH_SCATTER);
+      ALFI_CHECK(launch_patch_sum_scale_block(L, nc, stage, j == 0 ? 0 : 1, G, j));      // z_j, v_j, H column j-1
+    }
+    int nb = 0;
+    {
+      ProfScope prof(ctx, ALFI_EV_MATMULT);
+      ALFI_CHECK(launch_bsr_spmv_dot_block(L, nc, j, &nb));                               // w = A z_j, V^T w partials
+    }
+    ProfScope prof(ctx, ALFI_EV_BLAS1);
+    ALFI_CHECK(launch_multi_axpy_norm_block(L, nc, j, nb));                               // h, w -= V h, |w|^2 partials
+  }
+  ProfScope prof(ctx, ALFI_EV_BLAS1);   // to the end of the function
+  return launch_fgmres_finish_update_block(L, cols, k, G, X, ldx);                        // H column k-1, y, x += Z y
+}
+
 // alfi_smooth_fgmres on the columns of one chunk: the general path of api_smoother.hip in lockstep -- slot s of the block
 // workspace belongs to column cols.c[s]; per iteration ONE block apply and ONE block product for all slots, the BLAS-1 and
 // Hessenberg launches slot by slot (each slot's chain of launches, which hands its reduction partials from one launch to the
 // next through the ctx's two partial buffers, is finished before the next slot's begins).  Levels on which the single call
-// takes the four-launch iteration are smoothed column by column.
+// takes the four-launch iteration take its block form above, or are smoothed column by column (block_smooth_mode).
 int block_smooth_fgmres(alfi_level* L, int k, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx,
                         int nonzero_guess) {
   alfi_ctx* ctx = L->ctx;
   ALFI_CHECK(ensure_fgmres_workspace(L, k));
   ctx->cur_tag = L->id;
-  if (cols.n == 1 || !block_smoother_lockstep(L, k)) {
+  const int mode = cols.n == 1 ? BLOCK_SMOOTH_LOOP : block_smoother_mode(L, k);
+  if (mode == BLOCK_SMOOTH_FUSED) return block_smooth_fgmres_fused(L, k, cols, B, ldb, X, ldx, nonzero_guess);
+  if (mode == BLOCK_SMOOTH_LOOP) {
     for (int i = 0; i < cols.n; ++i) ALFI_CHECK(alfi_smooth_fgmres(L, k, B + cols.c[i] * ldb, X + cols.c[i] * ldx, nonzero_guess));
     return 0;
   }

@@ -86,7 +86,8 @@ static int smooth_fgmres_fused(alfi_level* L, int k, const double* db, double* d
 }
 
 // Does alfi_smooth_fgmres(L, k, ...) take the four-launch iteration above?  *flat_spmv: with the flat product and the dots as a
-// pass of their own.  (The block smoother, api_block.hip, asks too: such a level is smoothed column by column.)
+// pass of their own.  (The block smoother, api_block.hip, asks too: such a level takes the block form of that iteration,
+// kernels_block_fused.hip, or is smoothed column by column.)
 bool smoother_takes_fused_iteration(const alfi_level* L, int k, bool* flat_spmv) {
   // unpartitioned levels with short operator rows: the four-launch iteration (on the small levels a smoother iteration is
   // launch latency, on the large 2-D ones the folded vector passes save BLAS-1 traffic, which is comparable to the patch

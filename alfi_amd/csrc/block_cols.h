@@ -121,3 +121,35 @@ inline BlockCols block_piece(const BlockCols& b, int width, int k) {
   for (int i = 0; i < BLOCK_NV; ++i) q.c[i] = q.n == 0 ? b.c[0] : b.c[first + (i < q.n ? i : 0)];
   return q;
 }
+
+// ---- the FGMRES(k) smoother on a chunk of 2 .. BLOCK_NV columns (alfi_smooth_fgmres_block; api_block.hip) ----------------------
+// Three ways.  LOOP: whole single smoother calls, column after column.  LOCKSTEP: the general path of the single call with one
+// block apply and one block product per iteration.  FUSED: the block form of the four-launch iteration (kernels_block_fused.hip)
+// -- as many launches per iteration as one column takes.
+enum BlockSmoothMode { BLOCK_SMOOTH_LOOP = 0, BLOCK_SMOOTH_LOCKSTEP = 1, BLOCK_SMOOTH_FUSED = 2 };
+// what the rule reads of a level, its ctx and k
+struct BlockSmoothFacts {
+  bool block_kernels;      // alfi_ctx_set_block_kernels
+  bool block_fused;        // alfi_ctx_set_block_fused
+  bool partitioned;        // the level is partitioned
+  bool fused_iteration;    // the single call takes the four-launch iteration (smoother_takes_fused_iteration)
+  bool applies_il;         // stage 1 of the level's apply streams the interleaved copy of small-patch inverses
+  int apply_waves;         // waves per patch of the batched apply of dense inverses, 0: none (block_apply_waves)
+  int piece_width;         // the widest batch of condensed factors or dense macro stars, 0: their apply loops
+};
+// Where the single call takes the general path the chunk goes in lockstep.  Where it takes the four-launch iteration the chunk
+// takes its block form if stage 1 of the level's apply has a batched form -- the interleaved copy, dense inverses through
+// patch_apply_block_kernel, or condensed factors / macro stars in pieces of at least two columns -- and loops otherwise
+// (condensed levels in the chunked form, macro-star levels of fewer than BIG_BLOCK_MIN_PATCHES patches, the few-patches detour).
+inline int block_smooth_mode(const BlockSmoothFacts& f) {
+  if (!f.block_kernels || f.partitioned) return BLOCK_SMOOTH_LOOP;
+  if (!f.fused_iteration) return BLOCK_SMOOTH_LOCKSTEP;
+  if (!f.block_fused) return BLOCK_SMOOTH_LOOP;
+  return f.applies_il || f.apply_waves != 0 || f.piece_width >= 2 ? BLOCK_SMOOTH_FUSED : BLOCK_SMOOTH_LOOP;
+}
+// The reduction partials of the block fused iteration: per column slot two sets (the dot partials are still being read while the
+// norm partials are written) of red_blocks rows of red_maxv doubles each -- the ctx's red_partial and red_partial2, once per slot.
+inline int64_t block_partial_set(int red_blocks, int red_maxv) { return (int64_t)red_blocks * red_maxv; }
+inline int64_t block_partial_per_slot(int red_blocks, int red_maxv) { return 2 * block_partial_set(red_blocks, red_maxv); }
+// Dot vectors of an instantiation of the product with dots: j + 1 rounded up to 4, 8 or 16 (a guard skips the rest), 0: too many
+inline int block_dot_vectors(int nvec) { return nvec < 1 || nvec > 16 ? 0 : nvec <= 4 ? 4 : nvec <= 8 ? 8 : 16; }

@@ -60,6 +60,8 @@ struct alfi_ctx {
   bool use_graph = false;           // alfi_ctx_set_graph: replay whole cycles as hipGraphs (not while profiling / partitioned)
   bool block_kernels = true;        // alfi_ctx_set_block_kernels: block calls take the batched kernels where a level has them
                                     // (false: every block call loops the single-vector call over its columns)
+  bool block_fused = true;          // alfi_ctx_set_block_fused: the block smoother takes the block form of the four-launch
+                                    // iteration where a level has it (false: such levels loop whole smoother calls)
   int block_lds_bytes = 64 * 1024;  // alfi_ctx_set_block_lds_bytes: LDS a workgroup of a block apply may ask for -- the one budget
                                     // of the condensed apply (block_cond_width) and the macro stars' (block_big_width)
   void* big_arena = nullptr;        // scratch of the large-block factorisation (kernels_bigpatch.hip), kept between calls
@@ -481,6 +483,10 @@ struct alfi_level {
   // blk_Z + s * blk_kmax * ldv + j * ldv, w at blk_w + s * ldv, hs at blk_hs + s * HsLayout(blk_kmax).total
   int blk_kmax = 0, blk_ws_slots = 0;
   double *blk_V = nullptr, *blk_Z = nullptr, *blk_w = nullptr, *blk_hs = nullptr;
+  // reduction partials of the block fused iteration (kernels_block_fused.hip): blk_part_slots x block_partial_per_slot doubles,
+  // per slot what red_partial and red_partial2 are to one column; grown lazily, freed with the workspace above
+  double* blk_part = nullptr;
+  int blk_part_slots = 0;
   // point-Jacobi level preconditioner (alfi_level_set_jacobi): replaces the patch solves in alfi_patch_apply and the smoothers
   bool jacobi = false;
   double* jac_diag = nullptr;        // (n) scalar diagonal of the operator, extracted from the diagonal blocks
@@ -617,7 +623,8 @@ int launch_bsr_spmv_block(alfi_ctx* ctx, const DevBSR& A, const BlockCols& cols,
                           int64_t ldx, double* Y, int64_t ldy, const double* B, int64_t ldb, double alpha, int mode, double* carry);
 // The additive apply, both stages: for levels whose single apply is patch_apply_kernel with W = patch_apply_dense_waves(lvl,
 // held == HELD_F32) != 0 waves per patch (kernels_patch.hip) that patch_apply_block_waves_ok accepts; stage: cols.n x
-// lay.stage_len doubles.
+// lay.stage_len doubles.  This launcher and the two of the condensed and the macro-star levels below run stage 1 alone when
+// Y == nullptr (the block fused iteration sums the staged columns itself, kernels_block_fused.hip).
 int patch_apply_dense_waves(const alfi_level* lvl, bool f32);
 bool patch_apply_block_waves_ok(int W);
 int launch_patch_apply_block(alfi_level* lvl, int W, const BlockCols& cols, const BlockCols& ocols, const double* X, int64_t ldx,
@@ -633,6 +640,21 @@ int launch_cond_apply_block(alfi_level* lvl, const BlockCols& cols, const BlockC
 // 2 .. 4 columns whose LDS the caller has checked (block_big_width, block_cols.h); stage as above.
 int launch_big_apply_block(alfi_level* lvl, const BlockCols& cols, const BlockCols& ocols, const double* X, int64_t ldx, double* Y,
                            int64_t ldy, double* stage);
+// The block form of the four-launch smoother iteration (kernels_block_fused.hip) on the first nc = 2 .. 4 slots of the level's
+// block workspace (blk_V, blk_Z, blk_w, blk_hs, blk_part; slot s belongs to column cols.c[s] of B and X).  Stage 1 from the
+// interleaved copy for the columns X + s * ldx into stage + s * lay.stage_len:
+int launch_patch_apply_il_block(alfi_level* lvl, int nc, const double* X, int64_t ldx, double* stage);
+// w_s = b_c and x_c = 0 (B != nullptr), then the |w_s|^2 partials, red_blocks_for(n) per slot, into the first partial set
+int launch_first_norm_block(alfi_level* lvl, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx);
+// z_j, v_j and column j - 1 of the Hessenberg per slot; stage[s]: slot s's staged patch results (BLOCK_NV entries), normset:
+// which partial set holds the nblocks norm partials
+int launch_patch_sum_scale_block(alfi_level* lvl, int nc, const double* const* stage, int normset, int nblocks, int j);
+// w_s = A z_{s,j} with the partials of the j + 1 dots against slot s's basis into the first set (*nblocks of them per vector)
+int launch_bsr_spmv_dot_block(alfi_level* lvl, int nc, int j, int* nblocks);
+// h_s from those partials, w_s -= V_s h_s, the |w_s|^2 partials into the second set
+int launch_multi_axpy_norm_block(alfi_level* lvl, int nc, int j, int hblocks);
+// column k - 1 of the Hessenberg and y per slot (norm partials: the second set), then x_c += Z_s y_s: two launches
+int launch_fgmres_finish_update_block(alfi_level* lvl, const BlockCols& cols, int k, int nblocks, double* X, int64_t ldx);
 // The dense factor pipeline (alfi_patches_factor).  Every launcher takes `inv`, the base of the dense FP64 inverses it works on:
 // patch p at inv + inv_ptr[p].  That is lvl->inv for an FP64 level and the ctx's work buffer, biased by the range's first offset,
 // for an FP32 level (api_patches.hip: range_base).

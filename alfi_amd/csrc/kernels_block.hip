@@ -298,6 +298,7 @@ int launch_patch_apply_block(alfi_level* L, int W, const BlockCols& cols, const 
     else ALFI_CHECK(launch_apply_block_w<double>(L, W, L->inv, L->inv_ptr, X, ldx, cols, stage));
     ALFI_HIP_CHECK(ctx, hipGetLastError());
   }
+  if (!Y) return 0;     // stage 1 alone: the caller sums the staged columns itself (kernels_block_fused.hip)
   return launch_patch_sum_block(L, cols, ocols, X, ldx, Y, ldy, stage);
 }
 

@@ -98,5 +98,6 @@ int launch_big_apply_block(alfi_level* L, const BlockCols& cols, const BlockCols
     if (L->held == HELD_F32) ALFI_CHECK(launch_big_block_s<float>(L, L->inv32, L->inv32_ptr, cols, X, ldx, stage));
     else ALFI_CHECK(launch_big_block_s<double>(L, L->inv, L->inv_ptr, cols, X, ldx, stage));
   }
+  if (!Y) return 0;     // stage 1 alone: the caller sums the staged columns itself (kernels_block_fused.hip)
   return launch_patch_sum_block(L, cols, ocols, X, ldx, Y, ldy, stage);
 }

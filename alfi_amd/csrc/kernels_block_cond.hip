@@ -296,5 +296,6 @@ int launch_cond_apply_block(alfi_level* L, const BlockCols& cols, const BlockCol
       default: ALFI_CHECK((launch_cond_block_w<8>(L, cols, X, ldx, stage, ctmp))); break;
     }
   }
+  if (!Y) return 0;     // stage 1 alone: the caller sums the staged columns itself (kernels_block_fused.hip)
   return launch_patch_sum_block(L, cols, ocols, X, ldx, Y, ldy, stage);
 }

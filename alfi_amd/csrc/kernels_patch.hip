@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "row_piece.h"
+#include "load_pair.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 1. gather A_p = A[dofs_p, dofs_p] from the BSR operator into row-major dense storage (ld_p columns per row)
@@ -225,14 +226,7 @@ __global__ __launch_bounds__(256) void invert_small_kernel(int64_t nmat, const i
 // ---------------------------------------------------------------------------------------------------------------------
 // 3. additive apply, stage 1: one wave per patch.  stage[patch_ptr[p] + r] = sum_c inv_p[r][c] * x[dofs_p[c]]
 // ---------------------------------------------------------------------------------------------------------------------
-// (one row piece: piece_apply, row_piece.h; load_pair serves the interleaved copy of section 3a)
-typedef double alfi_d2 __attribute__((ext_vector_type(2)));
-template <bool NT>
-__device__ __forceinline__ double2 load_pair(const double* p) {   // one aligned 16-byte load
-  const alfi_d2* q = reinterpret_cast<const alfi_d2*>(p);
-  const alfi_d2 v = NT ? __builtin_nontemporal_load(q) : *q;
-  return make_double2(v.x, v.y);
-}
+// (one row piece: piece_apply, row_piece.h; load_pair, load_pair.h, serves the interleaved copy of section 3a)
 
 #ifndef ALFI_APPLY_U
 #define ALFI_APPLY_U 8                    // tuning builds: -DALFI_APPLY_U=16

@@ -4,6 +4,7 @@
 #include <cstring>
 #include "common.h"
 #include "hs_layout.h"
+#include "reduce.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // BSR SpMV: LPR lanes cooperate on one block row (each lane takes whole bs x bs blocks), shuffle-reduce the bs sums.
@@ -647,58 +648,11 @@ int launch_copy_dofs(alfi_ctx* ctx, double* y, const double* x, const int32_t* i
   return 0;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// reductions: two-stage (RED_BLOCKS partials, then one block sums them in a fixed order) -> deterministic
-// ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-template <int NV>
-__device__ __forceinline__ void block_store_partials(double (&acc)[NV], double* __restrict__ partial) {
-  __shared__ double red[4][NV];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    const double s = wave_sum(acc[v]);
-    if (lane == 0) red[wave][v] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < NV)
-    partial[(int64_t)blockIdx.x * RED_MAXV + threadIdx.x] =
-        red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-}
-
-// every thread of the block gets out[v] = sum_{b < nblocks <= RED_BLOCKS} partial[b][v], summed in one fixed order: all
-// blocks of a launch (and the kernels that follow) see the identical value, and no separate reduction launch is needed
-template <int NV>
-__device__ __forceinline__ void block_reduce_partials(const double* __restrict__ partial, int nblocks, double (&out)[NV]) {
-  __shared__ double red2[4][NV];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) s += partial[(int64_t)b * RED_MAXV + v];
-    s = wave_sum(s);
-    if (lane == 0) red2[wave][v] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int v = 0; v < NV; ++v) out[v] = (red2[0][v] + red2[1][v]) + (red2[2][v] + red2[3][v]);
-}
+// (wave_sum, block_store_partials, block_reduce_partials, ld2 / st2, vec2_ok: reduce.h)
 
 // partial[b][v] = sum over the block's slice of V_v[i] * w[i]   (gridDim.x blocks: RED_BLOCKS, or fewer on small levels)
 // VEC: every vector starts on a 16-byte boundary (even stride): a lane reads entry PAIRS, one 16-byte load per vector and
 // iteration -- the scalar form (8 bytes per lane and load) ran at 1.7-2 TB/s on a 1.2 M-dof level with ~1 workgroup per CU
-typedef double vec_d2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ vec_d2 ld2(const double* p, int64_t i2) { return reinterpret_cast<const vec_d2*>(p)[i2]; }
-__device__ __forceinline__ void st2(double* p, int64_t i2, vec_d2 v) { reinterpret_cast<vec_d2*>(p)[i2] = v; }
-__host__ inline bool vec2_ok(const void* a, const void* b, int64_t stride) {
-  return (stride & 1) == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
-}
-
 template <int NV, bool VEC>
 __global__ __launch_bounds__(256) void multi_dot_kernel(const double* __restrict__ V, int64_t stride,
                                                          const double* __restrict__ w, double* __restrict__ partial,

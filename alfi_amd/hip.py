@@ -115,6 +115,12 @@ class Context(object):
         block call loops the single-vector call over its columns -- the same bits at the cost of ncol single calls."""
         self.check(self.lib.alfi_ctx_set_block_kernels(self.h, 1 if on else 0))
 
+    def set_block_fused(self, on=True):
+        """The block smoother takes the block form of the four-launch iteration on the levels that have it
+        (alfi_ctx_set_block_fused; default on; ``Level.smooth_block_mode`` says which).  Off: those levels loop whole smoother
+        calls over the columns while every other block kernel stays on -- the same bits; the A/B switch of that form."""
+        self.check(self.lib.alfi_ctx_set_block_fused(self.h, 1 if on else 0))
+
     def set_block_lds_bytes(self, nbytes=64 * 1024):
         """LDS a workgroup of a block apply may ask for (alfi_ctx_set_block_lds_bytes; default 64 KiB, clamped to the device's
         limit per workgroup).  One budget for both applies that batch by it: a condensed level batches the widest NV of 4, 3, 2
@@ -712,10 +718,19 @@ class Level(object):
 
     def smooth_block_lockstep(self, k):
         """Does ``smooth_block(k, ...)`` on two or more columns run the smoother's general path in lockstep (one block apply and
-        one block product per iteration; alfi_smooth_fgmres_block_info)?  False: whole smoother calls loop over the columns."""
+        one block product per iteration; alfi_smooth_fgmres_block_info)?  False: the level takes the block form of the four-launch
+        iteration or whole smoother calls loop over the columns -- ``smooth_block_mode(k)`` says which."""
         b = ctypes.c_int()
         self.ctx.check(self.ctx.lib.alfi_smooth_fgmres_block_info(self.h, int(k), ctypes.byref(b)))
         return bool(b.value)
+
+    def smooth_block_mode(self, k):
+        """Which way ``smooth_block(k, ...)`` goes on two or more columns (alfi_smooth_fgmres_block_mode): 1 the general path in
+        lockstep, 2 the block form of the four-launch iteration (the launches per iteration of one column), 0 whole smoother
+        calls loop over the columns.  ``smooth_block_lockstep(k)`` is ``smooth_block_mode(k) == 1``."""
+        m = ctypes.c_int()
+        self.ctx.check(self.ctx.lib.alfi_smooth_fgmres_block_mode(self.h, int(k), ctypes.byref(m)))
+        return int(m.value)
 
     def spmv_block_batched(self):
         """The same for the product and the residual (alfi_spmv_block_info)."""

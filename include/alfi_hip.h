@@ -607,7 +607,7 @@ int alfi_saddle_velocity_info(alfi_saddle* s, int64_t* bytes, double* probe_resi
  * product (with column de-duplication: as wide as the budget below allows).  Everything else runs the single-vector code column
  * after column inside the library:
  * the interleaved copy of small patches, dense macro stars on levels of fewer than 8 patches, levels of few patches, multiplicative sweeps, point
- * Jacobi, the lanes-per-row product, the four-launch smoother iteration, Chebyshev, transfers, coarse
+ * Jacobi, the lanes-per-row product outside the block smoother, Chebyshev, transfers, coarse
  * solves.  A chunk of one column always does.  alfi_patch_apply_block_info / alfi_spmv_block_info: does the level, as it stands,
  * batch?  alfi_ctx_set_block_kernels(ctx, 0) makes every block call loop (default on): same bits, the cost of ncol single calls.
  * Condensed factors batch too where their single apply gives a workgroup to every patch (levels of at least 1024 patches), as
@@ -641,10 +641,22 @@ int alfi_patch_apply_block(alfi_level* lvl, int ncol, const int* cols, int nx, c
 int alfi_spmv_block(alfi_level* lvl, int ncol, const int* cols, int nx, const double* X, int64_t ldx, double* Y, int64_t ldy);
 int alfi_residual_block(alfi_level* lvl, int ncol, const int* cols, int nx, const double* B, int64_t ldb, const double* X,
                         int64_t ldx, double* R, int64_t ldr);
-/* alfi_smooth_fgmres on every column: its general path in lockstep, one Krylov workspace per column (allocated at first use,
- * freed with the level), ONE block apply and ONE block product per iteration; a level on which the single call takes the
- * four-launch iteration of small levels is smoothed column by column. */
-int alfi_smooth_fgmres_block_info(alfi_level* lvl, int k, int* lockstep);   /* which of the two, for this level and k */
+/* alfi_smooth_fgmres on every column, one Krylov workspace per column (allocated at first use, freed with the level).  A chunk
+ * of two to four columns goes one of three ways (alfi_smooth_fgmres_block_mode):
+ *   1  the general path of the single call in lockstep: ONE block apply and ONE block product per iteration;
+ *   2  where the single call takes the four-launch iteration of small levels and 2-D operators: its block form -- the same
+ *      launches per iteration as one column, the interleaved small-patch inverses (or the dense / condensed / macro-star factors
+ *      that batch, see above) and the operator read once for all columns;
+ *   0  whole single smoother calls column after column: levels of the four-launch iteration whose apply has no batched form
+ *      (condensed levels in the chunked form, macro stars on fewer than 8 patches, levels of few patches), partitioned levels,
+ *      and everything with alfi_ctx_set_block_kernels(ctx, 0).
+ * alfi_ctx_set_block_fused(ctx, 0) (default on) sends the levels of way 2 to way 0 and leaves every other block kernel on: the
+ * A/B switch of the block fused iteration, never the bits.
+ * alfi_smooth_fgmres_block_info keeps its meaning: *lockstep = 1 exactly for way 1, "the general path in lockstep"; it is 0 on
+ * every level of the four-launch iteration, whichever of ways 0 and 2 that level takes.  The query for that is _block_mode. */
+int alfi_smooth_fgmres_block_info(alfi_level* lvl, int k, int* lockstep);
+int alfi_smooth_fgmres_block_mode(alfi_level* lvl, int k, int* mode);
+int alfi_ctx_set_block_fused(alfi_ctx* ctx, int on);
 int alfi_smooth_fgmres_block(alfi_level* lvl, int k, int ncol, const int* cols, int nx, const double* B, int64_t ldb, double* X,
                              int64_t ldx, int nonzero_guess);
 /* alfi_mg_vcycle / alfi_mg_fcycle on every column (columns of the finest level's length), run eagerly: block cycles are never

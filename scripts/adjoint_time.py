@@ -7,7 +7,9 @@ Prints the refresh, transpose, factor and solve seconds of the adjoint, its Kryl
 step of the forward solve (same operator state, same tolerances).
 --functionals K (default 1): K functionals J_i = int e_(i mod dim) (1 + i) . u as ONE list: one refresh, transpose and
 factorisation and one block solve for the K adjoints; the iterations and residual norms are printed per functional.
---compare-block-kernels: that block solve twice more each with the batched kernels off and on (Context.set_block_kernels)."""
+--compare-block-kernels: that block solve twice more each with the batched kernels off and on (Context.set_block_kernels).
+--compare-block-fused: that block solve three times each with the block form of the four-launch smoother iteration off and on
+(Context.set_block_fused), alternating; a 2-D config (cfg1, cfg2) is where every level takes that form."""
 import argparse
 import os
 import sys
@@ -44,6 +46,9 @@ def main():
     ap.add_argument("--functionals", type=int, default=1, help="K functionals given as one list (K = 1: the single path)")
     ap.add_argument("--compare-block-kernels", action="store_true",
                     help="with --functionals K > 1: the block solve again with the batched kernels off and on (same bits), solve seconds")
+    ap.add_argument("--compare-block-fused", action="store_true",
+                    help="with --functionals K > 1: the block solve again, three rounds, with the block fused smoother iteration off "
+                         "and on (Context.set_block_fused; same bits), solve seconds")
     ap.add_argument("--host", action="store_true", help="host assembly (the transpose still runs on the device values)")
     args = ap.parse_args()
     from alfi_amd.adjoint import LoadFunctional
@@ -95,6 +100,15 @@ def main():
                     r = s.solver_adjoint.solve()
                     print("    batched kernels %-3s: solve %.3f s, Krylov its %s" % ("on" if on else "off", r["solve_s"], r["linear_iter"]),
                           flush=True)
+            if args.compare_block_fused:            # off = the levels of the four-launch iteration loop whole smoother calls
+                k = s.hmg.mg.k
+                print("    smoother modes of the levels (Level.smooth_block_mode(%d)): %s"
+                      % (k, [dl.smooth_block_mode(k) for dl in s.hmg.mg.levels[1:]]), flush=True)
+                for on in (False, True) * 3:
+                    s.ctx.set_block_fused(on)
+                    r = s.solver_adjoint.solve()
+                    print("    block fused iteration %-3s: solve %.3f s, Krylov its %s" % ("on" if on else "off", r["solve_s"],
+                                                                                         r["linear_iter"]), flush=True)
             continue
         print("Re %g: forward %d Newton steps, %d Krylov its (last step %s), converged %s, %.2f s per Newton step | "
               "adjoint %d Krylov its, converged %s, |r| %.2e of |b| %.2e; refresh %.3f s, transpose %.4f s, factor %.3f s, "

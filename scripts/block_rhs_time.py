@@ -7,6 +7,7 @@ is set up once; the two modes alternate, round after round.
 usage: timeout -k 10 900 python scripts/block_rhs_time.py cfg3 [--rounds 3] [--reps 20] [--cycles 3] [--dtype f32] [--out FILE]
        timeout -k 10 900 python scripts/block_rhs_time.py cfg4 --condensed [--lds-bytes N] [--out FILE]
        timeout -k 10 900 python scripts/block_rhs_time.py cfg5 [--macro-dtype f32] [--lds-bytes N] [--ncols 1,2,3,4] [--out FILE]
+       timeout -k 10 900 python scripts/block_rhs_time.py cfg2 --fused [--ncols 1,2,3,4] [--out FILE]
 (one GPU step = one process: give each its own time limit)
 Without --condensed every level holds dense inverses: the library looks for no groups and the generator's group labels (the
 Scott-Vogelius macro stars of config 5) are dropped.
@@ -15,6 +16,11 @@ de-duplicated block product may ask for (default 64 KiB; the width of every leve
 largest number of distinct columns in a group of 1024 blocks, which is what sets the product's).
 --macro-dtype f32: every level is asked for the FP32 storage of dense macro-star inverses (Level.set_macro_patch_storage) and
 factored again; a level that refuses keeps FP64.
+
+--fused: the A/B of the block form of the four-launch smoother iteration instead (Context.set_block_fused; every other block
+kernel stays on in both modes, so "off" is what these levels did before that form existed): per level ``smooth_block(k)`` with a
+zero guess, and the full cycle, at every ncol, on and off alternating round after round; per level its mode
+(Level.smooth_block_mode) and which stage 1 it has (interleaved copy, dense stars, pieces).
 
 Per level with patches and per ncol: best ms per block apply (both stages) and per block product over the rounds, on / off and
 their ratio, and the stored bytes (alfi_patches_factor_bytes; operator values + column indices) per second of the batched call.
@@ -40,6 +46,7 @@ def main():
     ap.add_argument("--lds-bytes", type=int, default=None)
     ap.add_argument("--macro-dtype", default=None, choices=[None, "f32"])
     ap.add_argument("--ncols", default="1,2,4", help="column counts to time; 1 is always among them (the single apply)")
+    ap.add_argument("--fused", action="store_true", help="A/B of Context.set_block_fused: smoother per level and full cycle")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     NCOLS = tuple(sorted({1} | {int(c) for c in args.ncols.split(",")}))
@@ -118,6 +125,14 @@ def main():
         ctx.sync()
         return 1e3 * (time.time() - t0) / reps
 
+    if args.fused:
+        fused_ab(args, say, ctx, lv, mg, k, NCOLS, rng, timed)
+        mg.close()
+        ctx.close()
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     work = []      # (label, stored bytes or None, {ncol: callable})
     for L, dl in zip(lv[1:], mg.levels[1:]):
         X = {c: ctx.mat(rng.standard_normal((dl.n, c))) for c in NCOLS}
@@ -173,6 +188,61 @@ def main():
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
+
+
+def fused_ab(args, say, ctx, lv, mg, k, NCOLS, rng, timed):
+    """Context.set_block_fused on / off alternating: smooth_block(k) per level and the full cycle at every ncol"""
+    say()
+    say("block fused iteration, k = %d; per level (dofs, patches, largest patch, mode on, class of stage 1):" % k)
+    for L, d in zip(lv[1:], mg.levels[1:]):
+        m = int(np.diff(L.patch_ptr).max())
+        cls = ("interleaved copy" if m <= 32 and d.condensed() == 0 and d.patch_storage_dtype() == "f64" else
+               "dense stars" if d.patch_apply_block_batched() and d.condensed() == 0 and m <= 160 else
+               "pieces of %d" % d.patch_apply_block_width() if d.patch_apply_block_width() >= 2 else "none")
+        say("  level %d: %d dofs, %d patches, %d dofs, mode %d, %s" % (d.id, d.n, len(L.patch_ptr) - 1, m, d.smooth_block_mode(k), cls))
+    work = []
+    for L, dl in zip(lv[1:], mg.levels[1:]):
+        Bm = {c: ctx.mat(rng.standard_normal((dl.n, c))) for c in NCOLS}
+        Xm = {c: ctx.mat(dl.n, c) for c in NCOLS}
+        work.append(("level %d smoother " % dl.id, dl.smooth_block_mode(k),
+                     {c: (lambda dl=dl, c=c, Bm=Bm, Xm=Xm: dl.smooth_block(k, Bm[c], Xm[c], nonzero_guess=False)) for c in NCOLS}))
+    fine = lv[-1]
+    Bf = rng.standard_normal((fine.n, max(NCOLS)))
+    Bf[fine.bc_dofs] = 0.0
+    B = {c: ctx.mat(Bf[:, :c]) for c in NCOLS}
+    Xf = {c: ctx.mat(fine.n, c) for c in NCOLS}
+    work.append(("full cycle       ", None, {c: (lambda c=c: mg.fcycle_block(B[c], Xf[c])) for c in NCOLS}))
+    res = {(w[0], c, on): [] for w in work for c in NCOLS for on in (True, False)}
+    for on in (True, False):                        # warm-up: every shape, both modes (the lazy workspaces are allocated here)
+        ctx.set_block_fused(on)
+        for label, _, fns in work:
+            for c in NCOLS:
+                fns[c]()
+    ctx.sync()
+    for _ in range(args.rounds):
+        for on in (True, False):
+            ctx.set_block_fused(on)
+            for label, _, fns in work:
+                for c in NCOLS:
+                    res[(label, c, on)].append(timed(fns[c], args.cycles if label.startswith("full") else args.reps))
+    ctx.set_block_fused(True)
+    say()
+    say("best ms per call over %d rounds (%d calls each, cycles %d), modes alternating; on = block fused iteration, off = these "
+        "levels loop whole smoother calls (every other block kernel on):" % (args.rounds, args.reps, args.cycles))
+    say("  %-18s ncol       on      off   on/off   on/(ncol x single)" % "")
+    for label, mode, _ in work:
+        single = min(res[(label, 1, False)])
+        for c in NCOLS:
+            on, off = min(res[(label, c, True)]), min(res[(label, c, False)])
+            say("  %-18s %4d %8.4f %8.4f   %6.3f   %18.3f%s" % (label, c, on, off, on / off, on / (c * single),
+                                                              "" if mode is None or mode == 2 else "   (mode %d: not the fused form)" % mode))
+    say()
+    say("every round, ms per call (on/off) -- is the block fused form faster than looping in EVERY round?")
+    for label, _, _ in work:
+        for c in NCOLS[1:]:
+            pairs = list(zip(res[(label, c, True)], res[(label, c, False)]))
+            say("  %-18s %4d  %s  %s" % (label, c, " ".join("%.4f/%.4f" % t for t in pairs),
+                                         "faster in every round" if all(a < b for a, b in pairs) else "NOT faster in every round"))
 
 
 if __name__ == "__main__":
