@@ -10,6 +10,13 @@
 // chunk or piece of one column -- is the single-vector code, column after column.  The smoother goes one of three ways
 // (block_smooth_mode, block_cols.h): the general path in lockstep, the block form of the four-launch iteration
 // (kernels_block_fused.hip), or whole single smoother calls column after column.
+//
+// Single call = one-column chunk.  The host drivers exist once, written for a chunk: the smoother's general path
+// (smooth_fgmres_general, api_smoother.hip), the V- and the full cycle (api_cycles.hip) and the outer FGMRES (saddle_solve_chunk,
+// api_saddle.hip).  The single entry points call them with one column on the level's or saddle's own workspace, the block entry
+// points chunk after chunk on the block workspace -- two instances of one type (KrylovWs, krylov_ws.h), because captured cycles
+// hold the addresses of the single one.  This file owns those workspaces and the slot buffers (SlotBuf): one ensure and one
+// release per type, and the functions that say what is released when.
 #include "api_internal.h"
 #include "block_cols.h"
 
@@ -124,49 +131,69 @@ int alfi_spmv_block_width(alfi_level* L, int* width) {
   return 0;
 }
 
-// ---- lazily grown workspaces ---------------------------------------------------------------------------------------------------
-// *buf holds *slots column slots of `per` doubles (0 slots: not allocated yet) and is asked to serve ncol >= 1 columns
-// (block_slots_needed: grow-only).  `per` is fixed while the buffer lives: the staging length until the next alfi_patches_set,
-// which frees blk_stage and blk_ctmp; the chunk count of the level's operator, which is set at alfi_level_create for good.
-static int grow_slots(alfi_ctx* ctx, double** buf, int* slots, int ncol, int64_t per) {
-  const int need = block_slots_needed(*slots, ncol);
-  if (need == *slots) return 0;
+// ---- the workspaces of the host drivers (krylov_ws.h) -----------------------------------------------------------------------
+int krylov_ws_ensure(alfi_ctx* ctx, KrylovWs* ws, int slots, int K, int64_t n) {
+  if (ws->K == K && ws->slots == slots) return 0;      // (n is fixed while the level or saddle lives)
   ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  dev_free(*buf);
-  *buf = nullptr;
-  *slots = 0;
-  ALFI_CHECK(dev_alloc(ctx, buf, need * per));
-  ALFI_HIP_CHECK(ctx, hipMemsetAsync(*buf, 0, sizeof(double) * (size_t)std::max<int64_t>(need * per, 1), ctx->stream));
-  *slots = need;
+  krylov_ws_release(ws);
+  ws->ldv = krylov_ldv(n);
+  const KrylovWsDoubles d = krylov_ws_doubles(slots, K, ws->ldv);
+  ALFI_CHECK(dev_alloc(ctx, &ws->V, d.V));
+  ALFI_CHECK(dev_alloc(ctx, &ws->Z, d.Z));
+  ALFI_CHECK(dev_alloc(ctx, &ws->w, d.w));
+  ALFI_CHECK(dev_alloc(ctx, &ws->hs, d.hs));
+  ALFI_HIP_CHECK(ctx, hipMemsetAsync(ws->hs, 0, sizeof(double) * (size_t)d.hs, ctx->stream));
+  ws->K = K;
+  ws->slots = slots;
   return 0;
 }
-
-void free_block_smoother(alfi_level* L) {
-  dev_free(L->blk_V);
-  dev_free(L->blk_Z);
-  dev_free(L->blk_w);
-  dev_free(L->blk_hs);
-  dev_free(L->blk_part);
-  L->blk_V = L->blk_Z = L->blk_w = L->blk_hs = L->blk_part = nullptr;
-  L->blk_kmax = L->blk_ws_slots = L->blk_part_slots = 0;
+void krylov_ws_release(KrylovWs* ws) {
+  dev_free(ws->V);
+  dev_free(ws->Z);
+  dev_free(ws->w);
+  dev_free(ws->hs);
+  *ws = KrylovWs();
 }
 
-// one Krylov workspace per slot, with the level's own kmax (the Hessenberg layout the kernels index with is HsLayout(kmax))
+int slot_buf_resize(alfi_ctx* ctx, SlotBuf* buf, int slots, int64_t per) {
+  ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  slot_buf_release(buf);
+  ALFI_CHECK(dev_alloc(ctx, &buf->p, slots * per));
+  ALFI_HIP_CHECK(ctx, hipMemsetAsync(buf->p, 0, sizeof(double) * (size_t)std::max<int64_t>(slots * per, 1), ctx->stream));
+  buf->slots = slots;
+  buf->per = per;
+  return 0;
+}
+int slot_buf_ensure(alfi_ctx* ctx, SlotBuf* buf, int ncol, int64_t per) {
+  const int need = slot_buf_needed(*buf, ncol);
+  return need == buf->slots ? 0 : slot_buf_resize(ctx, buf, need, per);      // (0 slots: not allocated yet; ncol >= 1)
+}
+void slot_buf_release(SlotBuf* buf) {
+  dev_free(buf->p);
+  *buf = SlotBuf();
+}
+
+// the staging length and sum_n are the old patch set's: the next block apply allocates the two again
+void block_release_patch_buffers(alfi_level* L) {
+  slot_buf_release(&L->blk_stage);
+  slot_buf_release(&L->blk_ctmp);
+}
+void release_workspaces(alfi_level* L) {
+  block_release_patch_buffers(L);
+  for (SlotBuf* b : {&L->blk_carry, &L->blk_part, &L->blk_mg_b, &L->blk_mg_x, &L->blk_mg_r}) slot_buf_release(b);
+  krylov_ws_release(&L->ws);
+  krylov_ws_release(&L->blk_ws);
+}
+void release_workspaces(alfi_saddle* S) {
+  slot_buf_release(&S->blk_tmp_u);
+  krylov_ws_release(&S->ws);
+  krylov_ws_release(&S->blk_ws);
+}
+
+// the level's block Krylov workspace for a chunk of ncol columns: grow-only in slots, with the single workspace's K (the
+// Hessenberg layout the kernels index with is HsLayout of it)
 static int ensure_block_smoother(alfi_level* L, int ncol) {
-  alfi_ctx* ctx = L->ctx;
-  const int need = block_slots_needed(L->blk_ws_slots, ncol), K = L->kmax;
-  if (L->blk_kmax == K && need == L->blk_ws_slots) return 0;     // (0 slots: not allocated yet)
-  ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  free_block_smoother(L);
-  HsLayout hl(K);
-  ALFI_CHECK(dev_alloc(ctx, &L->blk_V, (int64_t)need * (K + 1) * L->ldv));
-  ALFI_CHECK(dev_alloc(ctx, &L->blk_Z, (int64_t)need * K * L->ldv));
-  ALFI_CHECK(dev_alloc(ctx, &L->blk_w, (int64_t)need * L->ldv));
-  ALFI_CHECK(dev_alloc(ctx, &L->blk_hs, (int64_t)need * hl.total));
-  ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->blk_hs, 0, sizeof(double) * (size_t)need * hl.total, ctx->stream));
-  L->blk_kmax = K;
-  L->blk_ws_slots = need;
-  return 0;
+  return krylov_ws_ensure(L->ctx, &L->blk_ws, block_slots_needed(L->blk_ws.slots, ncol), L->ws.K, L->n);
 }
 
 // ---- the block forms on one chunk (1 .. BLOCK_NV columns), unchecked --------------------------------------------------------------
@@ -176,8 +203,8 @@ int block_patch_apply(alfi_level* L, const BlockCols& ic, const BlockCols& oc, c
   ctx->cur_tag = L->id;
   const int W = ic.n > 1 ? block_apply_waves(L) : 0;
   if (W != 0) {
-    ALFI_CHECK(grow_slots(ctx, &L->blk_stage, &L->blk_stage_slots, ic.n, L->lay.stage_len));
-    return launch_patch_apply_block(L, W, ic, oc, X, ldx, Y, ldy, L->blk_stage);
+    ALFI_CHECK(slot_buf_ensure(ctx, &L->blk_stage, ic.n, L->lay.stage_len));
+    return launch_patch_apply_block(L, W, ic, oc, X, ldx, Y, ldy, L->blk_stage.p);
   }
   // condensed factors, dense macro stars: the chunk in pieces of the level's width, a piece of one column through the single apply
   const int width = ic.n > 1 ? block_piece_apply_width(L) : 0;
@@ -187,13 +214,13 @@ int block_patch_apply(alfi_level* L, const BlockCols& ic, const BlockCols& oc, c
       ALFI_CHECK(level_patch_apply(L, X + pi.c[0] * ldx, Y + po.c[0] * ldy));
       continue;
     }
-    ALFI_CHECK(grow_slots(ctx, &L->blk_stage, &L->blk_stage_slots, pi.n, L->lay.stage_len));
+    ALFI_CHECK(slot_buf_ensure(ctx, &L->blk_stage, pi.n, L->lay.stage_len));
     if (L->held != HELD_COND) {
-      ALFI_CHECK(launch_big_apply_block(L, pi, po, X, ldx, Y, ldy, L->blk_stage));
+      ALFI_CHECK(launch_big_apply_block(L, pi, po, X, ldx, Y, ldy, L->blk_stage.p));
       continue;
     }
-    ALFI_CHECK(grow_slots(ctx, &L->blk_ctmp, &L->blk_ctmp_slots, pi.n, L->lay.sum_n));
-    ALFI_CHECK(launch_cond_apply_block(L, pi, po, X, ldx, Y, ldy, L->blk_stage, L->blk_ctmp));
+    ALFI_CHECK(slot_buf_ensure(ctx, &L->blk_ctmp, pi.n, L->lay.sum_n));
+    ALFI_CHECK(launch_cond_apply_block(L, pi, po, X, ldx, Y, ldy, L->blk_stage.p, L->blk_ctmp.p));
   }
   return 0;
 }
@@ -214,10 +241,10 @@ int block_spmv(alfi_level* L, const BlockCols& ic, const BlockCols& oc, const do
     const DevBSR& A = L->A_own;
     if (!A.aligned) {
       const int64_t nchunks = (A.nnzb + SPMV_CHUNK - 1) / SPMV_CHUNK;
-      ALFI_CHECK(grow_slots(ctx, &L->blk_carry, &L->blk_carry_slots, pi.n, nchunks * A.bs));
+      ALFI_CHECK(slot_buf_ensure(ctx, &L->blk_carry, pi.n, nchunks * A.bs));
     }
     ProfScope prof(ctx, ALFI_EV_MATMULT);   // to the end of the piece
-    ALFI_CHECK(launch_bsr_spmv_block(ctx, A, pi, po, X, ldx, Y, ldy, B, ldb, 1.0, mode, L->blk_carry));
+    ALFI_CHECK(launch_bsr_spmv_block(ctx, A, pi, po, X, ldx, Y, ldy, B, ldb, 1.0, mode, L->blk_carry.p));
   }
   return 0;
 }
@@ -231,13 +258,13 @@ static int block_smooth_fgmres_fused(alfi_level* L, int k, const BlockCols& cols
   alfi_ctx* ctx = L->ctx;
   const int nc = cols.n;
   ALFI_CHECK(ensure_block_smoother(L, nc));
-  ALFI_CHECK(grow_slots(ctx, &L->blk_part, &L->blk_part_slots, nc, block_partial_per_slot(RED_BLOCKS, RED_MAXV)));
-  ALFI_CHECK(grow_slots(ctx, &L->blk_stage, &L->blk_stage_slots, nc, L->lay.stage_len));
-  if (L->held == HELD_COND) ALFI_CHECK(grow_slots(ctx, &L->blk_ctmp, &L->blk_ctmp_slots, nc, L->lay.sum_n));
-  const int64_t ldv = L->ldv;
+  ALFI_CHECK(slot_buf_ensure(ctx, &L->blk_part, nc, block_partial_per_slot(RED_BLOCKS, RED_MAXV)));
+  ALFI_CHECK(slot_buf_ensure(ctx, &L->blk_stage, nc, L->lay.stage_len));
+  if (L->held == HELD_COND) ALFI_CHECK(slot_buf_ensure(ctx, &L->blk_ctmp, nc, L->lay.sum_n));
+  const int64_t ldv = L->blk_ws.ldv;
   const BlockCols slots = block_chunk(nc, nullptr, 0);
   // r0 = b - A x, or x = 0 and r0 = b in the launch of the norm partials
-  if (nonzero_guess) ALFI_CHECK(block_spmv(L, cols, slots, X, ldx, L->blk_w, ldv, B, ldb, 1));
+  if (nonzero_guess) ALFI_CHECK(block_spmv(L, cols, slots, X, ldx, L->blk_ws.w, ldv, B, ldb, 1));
   {
     ProfScope prof(ctx, ALFI_EV_BLAS1);
     ALFI_CHECK(launch_first_norm_block(L, cols, nonzero_guess ? nullptr : B, ldb, X, ldx));
@@ -246,24 +273,24 @@ static int block_smooth_fgmres_fused(alfi_level* L, int k, const BlockCols& cols
   const bool il = level_applies_il(L);
   const int W = il ? 0 : block_apply_waves(L), width = il || W != 0 ? BLOCK_NV : block_piece_apply_width(L);
   const double* stage[BLOCK_NV];
-  for (int s = 0; s < BLOCK_NV; ++s) stage[s] = L->blk_stage + (s < nc ? s : 0) * L->lay.stage_len;
+  for (int s = 0; s < BLOCK_NV; ++s) stage[s] = L->blk_stage.slot(s < nc ? s : 0);
   for (int j = 0; j < k; ++j) {
     // stage 1: slot s's staged patch solves of w_s
     if (il) {
-      ALFI_CHECK(launch_patch_apply_il_block(L, nc, L->blk_w, ldv, L->blk_stage));
+      ALFI_CHECK(launch_patch_apply_il_block(L, nc, L->blk_ws.w, ldv, L->blk_stage.p));
     } else if (W != 0) {
-      ALFI_CHECK(launch_patch_apply_block(L, W, slots, slots, L->blk_w, ldv, nullptr, 0, L->blk_stage));
+      ALFI_CHECK(launch_patch_apply_block(L, W, slots, slots, L->blk_ws.w, ldv, nullptr, 0, L->blk_stage.p));
     } else {
       for (int q = 0; q < block_pieces(nc, width); ++q) {
         const BlockCols pi = block_piece(slots, width, q);
-        double* st = L->blk_stage + pi.c[0] * L->lay.stage_len;
+        double* st = L->blk_stage.slot(pi.c[0]);
         if (pi.n == 1) {      // (at most one piece of a chunk has one column: the single apply into the level's own buffer)
-          ALFI_CHECK(launch_patch_apply_range(L, 0, L->npatch, L->blk_w + pi.c[0] * ldv));
+          ALFI_CHECK(launch_patch_apply_range(L, 0, L->npatch, L->blk_ws.wv(pi.c[0])));
           stage[pi.c[0]] = L->stage;
         } else if (L->held != HELD_COND) {
-          ALFI_CHECK(launch_big_apply_block(L, pi, pi, L->blk_w, ldv, nullptr, 0, st));
+          ALFI_CHECK(launch_big_apply_block(L, pi, pi, L->blk_ws.w, ldv, nullptr, 0, st));
         } else {
-          ALFI_CHECK(launch_cond_apply_block(L, pi, pi, L->blk_w, ldv, nullptr, 0, st, L->blk_ctmp));
+          ALFI_CHECK(launch_cond_apply_block(L, pi, pi, L->blk_ws.w, ldv, nullptr, 0, st, L->blk_ctmp.p));
         }
       }
     }
@@ -283,16 +310,12 @@ static int block_smooth_fgmres_fused(alfi_level* L, int k, const BlockCols& cols
   return launch_fgmres_finish_update_block(L, cols, k, G, X, ldx);                        // H column k-1, y, x += Z y
 }
 
-// alfi_smooth_fgmres on the columns of one chunk: the general path of api_smoother.hip in lockstep -- slot s of the block
-// workspace belongs to column cols.c[s]; per iteration ONE block apply and ONE block product for all slots, the BLAS-1 and
-// Hessenberg launches slot by slot (each slot's chain of launches, which hands its reduction partials from one launch to the
-// next through the ctx's two partial buffers, is finished before the next slot's begins).  Levels on which the single call
-// takes the four-launch iteration take its block form above, or are smoothed column by column (block_smooth_mode).
+// alfi_smooth_fgmres on the columns of one chunk, one of the three ways of block_smooth_mode; a chunk of one column is the
+// single call.  LOCKSTEP is the single call's general path (smooth_fgmres_general, api_smoother.hip) on the block workspace.
 int block_smooth_fgmres(alfi_level* L, int k, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx,
                         int nonzero_guess) {
-  alfi_ctx* ctx = L->ctx;
   ALFI_CHECK(ensure_fgmres_workspace(L, k));
-  ctx->cur_tag = L->id;
+  L->ctx->cur_tag = L->id;
   const int mode = cols.n == 1 ? BLOCK_SMOOTH_LOOP : block_smoother_mode(L, k);
   if (mode == BLOCK_SMOOTH_FUSED) return block_smooth_fgmres_fused(L, k, cols, B, ldb, X, ldx, nonzero_guess);
   if (mode == BLOCK_SMOOTH_LOOP) {
@@ -300,52 +323,7 @@ int block_smooth_fgmres(alfi_level* L, int k, const BlockCols& cols, const doubl
     return 0;
   }
   ALFI_CHECK(ensure_block_smoother(L, cols.n));
-  const int K = L->kmax, nc = cols.n;
-  const int64_t n = L->n, ldv = L->ldv, vs = (int64_t)(K + 1) * ldv, zs = (int64_t)K * ldv;
-  HsLayout hl(K);
-  const BlockCols slots = block_chunk(nc, nullptr, 0);
-  auto Vs = [&](int s) { return L->blk_V + s * vs; };
-  auto Zs = [&](int s) { return L->blk_Z + s * zs; };
-  auto ws = [&](int s) { return L->blk_w + s * ldv; };
-  auto hss = [&](int s) { return L->blk_hs + (int64_t)s * hl.total; };
-  // r0 = b - A x, beta = |r0|, v0 = r0 / beta
-  if (nonzero_guess) {
-    ALFI_CHECK(block_spmv(L, cols, slots, X, ldx, L->blk_w, ldv, B, ldb, 1));
-  } else {
-    for (int s = 0; s < nc; ++s) {
-      ALFI_HIP_CHECK(ctx, hipMemsetAsync(X + cols.c[s] * ldx, 0, sizeof(double) * n, ctx->stream));
-      ProfScope prof(ctx, ALFI_EV_BLAS1);
-      ALFI_CHECK(launch_copy(ctx, ws(s), B + cols.c[s] * ldb, n));
-    }
-  }
-  const int G = red_blocks_for(n);
-  const bool fused = G <= 256 && k + 1 <= 16;      // the consumer of a reduced value sums the partials itself (api_smoother.hip)
-  for (int s = 0; s < nc; ++s) {
-    ProfScope prof(ctx, ALFI_EV_BLAS1);
-    ALFI_CHECK(launch_norm_partials(ctx, ws(s), n));
-    ALFI_CHECK(launch_norm_init_finish(ctx, ctx->red_partial, G, hss(s), K));
-    ALFI_CHECK(launch_scale_by_inv(ctx, Vs(s), ws(s), hss(s) + hl.beta, n));
-  }
-  for (int j = 0; j < k; ++j) {
-    ALFI_CHECK(block_patch_apply(L, slots, slots, L->blk_V + j * ldv, vs, L->blk_Z + j * ldv, zs));   // z_j = M^-1 v_j
-    ALFI_CHECK(block_spmv(L, slots, slots, L->blk_Z + j * ldv, zs, L->blk_w, ldv, nullptr, 0, 0));    // w = A z_j
-    for (int s = 0; s < nc; ++s) {
-      double *hs = hss(s), *hdots = hs + hl.hd, *w = ws(s);
-      ProfScope prof(ctx, ALFI_EV_BLAS1);   // to the end of the loop body
-      ALFI_CHECK(launch_multi_dot(ctx, Vs(s), ldv, j + 1, w, fused ? nullptr : hdots, n));
-      ALFI_CHECK(launch_multi_axpy_norm(ctx, Vs(s), ldv, j + 1, hdots, w, n, ctx->red_partial2, fused ? G : 0));
-      if (j + 1 < k)
-        ALFI_CHECK(launch_hessenberg_scale(ctx, ctx->red_partial2, G, hdots, hs, j, K, Vs(s) + (int64_t)(j + 1) * ldv, w, n, nullptr));
-      else
-        ALFI_CHECK(launch_hessenberg_update(ctx, ctx->red_partial2, G, hdots, hs, j, K, nullptr));
-    }
-  }
-  for (int s = 0; s < nc; ++s) {
-    ProfScope prof(ctx, ALFI_EV_BLAS1);
-    ALFI_CHECK(launch_fgmres_finish(ctx, hss(s), k, K));
-    ALFI_CHECK(launch_update_solution(ctx, X + cols.c[s] * ldx, Zs(s), ldv, k, hss(s) + hl.y, n));
-  }
-  return 0;
+  return smooth_fgmres_general(L, L->blk_ws, k, cols, B, ldb, X, ldx, nonzero_guess);
 }
 
 // ---- the entry points ------------------------------------------------------------------------------------------------------------

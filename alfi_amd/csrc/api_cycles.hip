@@ -477,12 +477,30 @@ int alfi_mg_set_cycles(alfi_mg* mg, int cycles) {
   return 0;
 }
 
+// ---- the cycles, for the 1 .. BLOCK_NV columns `cols` of B and X -------------------------------------------------------------------
+// The single calls (alfi_mg_vcycle / _fcycle) are the one-column case.  The smoother and the residual are the block forms of
+// api_block.hip, which are the single-vector code on one column; transfers, the coarse solve and the correction loop over the
+// columns with the single-vector code.  Below the level a cycle starts on, column i of the chunk lives in column i of the levels'
+// work vectors (b, x, r of leading dimension ld): own_work -- the level's mg_b / mg_x / mg_r, one column, whose addresses a
+// captured single cycle holds -- or block_work, the slots of blk_mg_b / _x / _r (mg_block_vectors).
+struct MgWork {
+  double *b, *x, *r;
+  int64_t ld;
+};
+typedef MgWork (*MgWorkOf)(const alfi_level*);
+static MgWork own_work(const alfi_level* L) { return {L->mg_b, L->mg_x, L->mg_r, 0}; }
+static MgWork block_work(const alfi_level* L) { return {L->blk_mg_b.p, L->blk_mg_x.p, L->blk_mg_r.p, L->blk_mg_b.per}; }
+
 // the level smoother of the hierarchy (alfi_mg_set_smoother)
-static int mg_smooth(alfi_mg* mg, int l, const double* b, double* x, int nonzero_guess) {
+static int mg_smooth(alfi_mg* mg, int l, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx,
+                     int nonzero_guess) {
   alfi_level* L = mg->levels[l];
-  if (mg->smoother == ALFI_SMOOTHER_CHEBYSHEV)
-    return alfi_smooth_chebyshev(L, mg->k, mg->emin[l], mg->emax[l], b, x, nonzero_guess);
-  return alfi_smooth_fgmres(L, mg->k, b, x, nonzero_guess);
+  if (mg->smoother == ALFI_SMOOTHER_CHEBYSHEV) {
+    for (int i = 0; i < cols.n; ++i)
+      ALFI_CHECK(alfi_smooth_chebyshev(L, mg->k, mg->emin[l], mg->emax[l], B + cols.c[i] * ldb, X + cols.c[i] * ldx, nonzero_guess));
+    return 0;
+  }
+  return block_smooth_fgmres(L, mg->k, cols, B, ldb, X, ldx, nonzero_guess);
 }
 
 // PCMGMCycle_Private [3P]: x_l <- M(b_l, x_l), the V-cycle for cycles = 1 and the W-cycle for cycles = 2: level 1 visits the
@@ -490,50 +508,57 @@ static int mg_smooth(alfi_mg* mg, int l, const double* b, double* x, int nonzero
 // continuing from the coarse iterate of the one before.  x_zero: the incoming x is known to be zero (every level below the one the
 // cycle starts on): the pre-smoother then runs with a zero initial guess -- r0 = b, no residual SpMV -- as PCMG does by
 // switching KSPSetInitialGuessNonzero off for the down-smoother of those levels; the result is the same bit for bit.
-static int vcycle(alfi_mg* mg, int l, const double* b, double* x, bool x_zero) {
+static int vcycle(alfi_mg* mg, MgWorkOf work, int l, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx,
+                  bool x_zero) {
   alfi_ctx* ctx = mg->ctx;
   alfi_level* L = mg->levels[l];
-  // partitioned hierarchies: a rank's lowest level is either the coarse grid it owns or ghost copies of a level another
-  // rank owns and solves (then there is nothing to do here); every level above is owned in part by every rank
-  if (l == 0) return L->n_own > 0 ? alfi_coarse_solve(L, b, x) : 0;
-  alfi_level* C = mg->levels[l - 1];
+  const int nc = cols.n;
+  if (l == 0) {
+    // partitioned hierarchies: a rank's lowest level is either the coarse grid it owns or ghost copies of a level another
+    // rank owns and solves (then there is nothing to do here); every level above is owned in part by every rank
+    for (int i = 0; i < nc && L->n_own > 0; ++i) ALFI_CHECK(alfi_coarse_solve(L, B + cols.c[i] * ldb, X + cols.c[i] * ldx));
+    return 0;
+  }
   alfi_transfer* T = mg->transfers[l - 1];
-  ALFI_CHECK(mg_smooth(mg, l, b, x, x_zero ? 0 : 1));                // pre-smooth
-  ALFI_CHECK(alfi_residual(L, b, x, L->mg_r));                       // r = b - A x
-  ALFI_CHECK(alfi_restrict(T, L->mg_r, C->mg_b, mg->robust));        // b_{l-1} = R r
+  const BlockCols slots = block_chunk(nc, nullptr, 0);
+  const MgWork wl = work(L), wc = work(mg->levels[l - 1]);
+  ALFI_CHECK(mg_smooth(mg, l, cols, B, ldb, X, ldx, x_zero ? 0 : 1));                                // pre-smooth
+  ALFI_CHECK(block_spmv(L, cols, slots, X, ldx, wl.r, wl.ld, B, ldb, 1));                           // r = b - A x
+  for (int i = 0; i < nc; ++i) ALFI_CHECK(alfi_restrict(T, wl.r + i * wl.ld, wc.b + i * wc.ld, mg->robust));   // b_{l-1} = R r
   // x_{l-1} = 0: the coarse solve overwrites it, a smoother with a zero initial guess zeroes it itself
   const int cycles = l == 1 ? 1 : mg->cycles;
-  for (int c = 0; c < cycles; ++c) ALFI_CHECK(vcycle(mg, l - 1, C->mg_b, C->mg_x, c == 0));
-  ALFI_CHECK(alfi_prolong(T, C->mg_x, L->mg_r));                     // x += P x_{l-1}
+  for (int c = 0; c < cycles; ++c) ALFI_CHECK(vcycle(mg, work, l - 1, slots, wc.b, wc.ld, wc.x, wc.ld, c == 0));
+  for (int i = 0; i < nc; ++i) ALFI_CHECK(alfi_prolong(T, wc.x + i * wc.ld, wl.r + i * wl.ld));
   ctx->cur_tag = L->id;
-  {
+  for (int i = 0; i < nc; ++i) {
     ProfScope prof(ctx, ALFI_EV_BLAS1);
-    ALFI_CHECK(launch_axpy(ctx, x, L->mg_r, 1.0, L->n_own));
+    ALFI_CHECK(launch_axpy(ctx, X + cols.c[i] * ldx, wl.r + i * wl.ld, 1.0, L->n_own));              // x += P x_{l-1}
   }
-  ALFI_CHECK(mg_smooth(mg, l, b, x, 1));                             // post-smooth
-  return 0;
+  return mg_smooth(mg, l, cols, B, ldb, X, ldx, 1);                                                 // post-smooth
 }
 
 // PCMGFCycle_Private [3P]
-static int fcycle(alfi_mg* mg, const double* db, double* dx) {
-  const int Lmax = (int)mg->levels.size() - 1;
-  if (Lmax == 0) return mg->levels[0]->n_own > 0 ? alfi_coarse_solve(mg->levels[0], db, dx) : 0;
-  // restrict the right-hand side through all levels
-  const double* bf = db;
-  for (int l = Lmax; l >= 1; --l) {
-    ALFI_CHECK(alfi_restrict(mg->transfers[l - 1], bf, mg->levels[l - 1]->mg_b, mg->robust));
-    bf = mg->levels[l - 1]->mg_b;
+static int fcycle(alfi_mg* mg, MgWorkOf work, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx) {
+  const int Lmax = (int)mg->levels.size() - 1, nc = cols.n;
+  if (Lmax == 0) return vcycle(mg, work, 0, cols, B, ldb, X, ldx, false);
+  const BlockCols slots = block_chunk(nc, nullptr, 0);
+  for (int i = 0; i < nc; ++i) {         // restrict the right-hand sides through all levels
+    const double* bf = B + cols.c[i] * ldb;
+    for (int l = Lmax; l >= 1; --l) {
+      const MgWork wc = work(mg->levels[l - 1]);
+      ALFI_CHECK(alfi_restrict(mg->transfers[l - 1], bf, wc.b + i * wc.ld, mg->robust));
+      bf = wc.b + i * wc.ld;
+    }
   }
   for (int l = 0; l < Lmax; ++l) {
-    alfi_level* L = mg->levels[l];
-    // note: inside vcycle(l) the coarser levels' mg_b / mg_x are overwritten; level l's own b must survive, and it
-    // does: vcycle(l) only writes mg_b of levels < l.  But the restricted rhs of levels < l is then gone -- it is
-    // not needed any more at that point (levels are visited in increasing order).
-    ALFI_CHECK(vcycle(mg, l, L->mg_b, L->mg_x, l == 0));    // l >= 1: x_l is the prolonged coarser solution
-    double* xnext = (l + 1 == Lmax) ? dx : mg->levels[l + 1]->mg_x;
-    ALFI_CHECK(alfi_prolong(mg->transfers[l], L->mg_x, xnext));
+    // inside vcycle(l) the coarser levels' b and x are overwritten; level l's own b survives: vcycle(l) only writes b of
+    // levels < l.  The restricted right-hand sides of levels < l are gone then, and no longer needed (increasing order).
+    const MgWork wl = work(mg->levels[l]), wn = work(mg->levels[l + 1]);
+    ALFI_CHECK(vcycle(mg, work, l, slots, wl.b, wl.ld, wl.x, wl.ld, l == 0));    // l >= 1: x_l is the prolonged coarser solution
+    for (int i = 0; i < nc; ++i)
+      ALFI_CHECK(alfi_prolong(mg->transfers[l], wl.x + i * wl.ld, l + 1 == Lmax ? X + cols.c[i] * ldx : wn.x + i * wn.ld));
   }
-  return vcycle(mg, Lmax, db, dx, false);
+  return vcycle(mg, work, Lmax, cols, B, ldb, X, ldx, false);
 }
 
 // ---- whole cycles as hipGraphs (alfi_ctx_set_graph) -----------------------------------------------------------------------
@@ -575,10 +600,10 @@ static void cycle_signature(alfi_mg* mg, std::vector<uint64_t>* sig) {
     push(L->patch_dofs);
     push(L->cinv);
     push(L->mf);
-    push(L->V);
+    push(L->ws.V);
     push(L->mult_seq);
     sig->push_back((uint64_t)L->npatch);
-    sig->push_back((uint64_t)L->kmax);
+    sig->push_back((uint64_t)L->ws.K);
     sig->push_back((uint64_t)(L->mult ? 1 + (L->mult_symmetrise ? 1 : 0) + 4 * L->sweep.wave_ptr.size() : 0));
   }
   for (alfi_transfer* T : mg->transfers) {
@@ -612,7 +637,10 @@ static int mg_ready(alfi_mg* mg) {
 static int run_cycle(alfi_mg* mg, int kind, const double* db, double* dx) {
   alfi_ctx* ctx = mg->ctx;
   ALFI_CHECK(mg_ready(mg));
-  auto eager = [&]() { return kind ? fcycle(mg, db, dx) : vcycle(mg, (int)mg->levels.size() - 1, db, dx, false); };
+  const BlockCols one = block_chunk(1, nullptr, 0);      // the vector pair as a one-column operand
+  auto eager = [&]() {
+    return kind ? fcycle(mg, own_work, one, db, 0, dx, 0) : vcycle(mg, own_work, (int)mg->levels.size() - 1, one, db, 0, dx, 0, false);
+  };
   bool ok = ctx->use_graph && ctx->prof == 0;
   for (alfi_level* L : mg->levels) ok = ok && !L->has_halo;
   if (!ok) return eager();
@@ -674,96 +702,18 @@ int alfi_mg_vcycle(alfi_mg* mg, const double* db, double* dx) { return run_cycle
 int alfi_mg_fcycle(alfi_mg* mg, const double* db, double* dx) { return run_cycle(mg, 1, db, dx); }
 
 // ---- block cycles (alfi_mg_vcycle_block / _fcycle_block) ---------------------------------------------------------------------------
-// vcycle and fcycle above for the 1 .. BLOCK_NV columns of one chunk, eagerly (never a captured graph).  The smoother and the
-// residual are the block forms of api_block.hip; transfers, the coarse solve and the correction loop over the columns with the
-// single-vector code.  Below the level a cycle starts on, column i of the chunk lives in slot i of the levels' block vectors.
-static int64_t mg_block_ld(const alfi_level* L) { return (L->n + 1) & ~(int64_t)1; }
-
+// The cycles above on the block work vectors, chunk after chunk, eagerly (never a captured graph).
 static int mg_block_vectors(alfi_mg* mg, int ncol) {
-  alfi_ctx* ctx = mg->ctx;
-  for (alfi_level* L : mg->levels) {
-    const int need = block_slots_needed(L->blk_mg_slots, ncol);
-    if (need == L->blk_mg_slots) continue;         // (0 slots: not allocated yet; ncol >= 1, so need >= 1)
-    ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    dev_free(L->blk_mg_b);
-    dev_free(L->blk_mg_x);
-    dev_free(L->blk_mg_r);
-    L->blk_mg_b = L->blk_mg_x = L->blk_mg_r = nullptr;
-    L->blk_mg_slots = 0;
-    ALFI_CHECK(dev_alloc(ctx, &L->blk_mg_b, need * mg_block_ld(L)));
-    ALFI_CHECK(dev_alloc(ctx, &L->blk_mg_x, need * mg_block_ld(L)));
-    ALFI_CHECK(dev_alloc(ctx, &L->blk_mg_r, need * mg_block_ld(L)));
-    L->blk_mg_slots = need;
-  }
+  for (alfi_level* L : mg->levels)
+    for (SlotBuf* v : {&L->blk_mg_b, &L->blk_mg_x, &L->blk_mg_r}) ALFI_CHECK(slot_buf_ensure(mg->ctx, v, ncol, krylov_ldv(L->n)));
   return 0;
-}
-
-static int mg_smooth_block(alfi_mg* mg, int l, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx,
-                           int nonzero_guess) {
-  alfi_level* L = mg->levels[l];
-  if (mg->smoother == ALFI_SMOOTHER_CHEBYSHEV) {
-    for (int i = 0; i < cols.n; ++i)
-      ALFI_CHECK(alfi_smooth_chebyshev(L, mg->k, mg->emin[l], mg->emax[l], B + cols.c[i] * ldb, X + cols.c[i] * ldx, nonzero_guess));
-    return 0;
-  }
-  return block_smooth_fgmres(L, mg->k, cols, B, ldb, X, ldx, nonzero_guess);
-}
-
-static int vcycle_block(alfi_mg* mg, int l, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx, bool x_zero) {
-  alfi_ctx* ctx = mg->ctx;
-  alfi_level* L = mg->levels[l];
-  const int nc = cols.n;
-  if (l == 0) {
-    for (int i = 0; i < nc; ++i) ALFI_CHECK(alfi_coarse_solve(L, B + cols.c[i] * ldb, X + cols.c[i] * ldx));
-    return 0;
-  }
-  alfi_level* C = mg->levels[l - 1];
-  alfi_transfer* T = mg->transfers[l - 1];
-  const BlockCols slots = block_chunk(nc, nullptr, 0);
-  const int64_t ldl = mg_block_ld(L), ldc = mg_block_ld(C);
-  ALFI_CHECK(mg_smooth_block(mg, l, cols, B, ldb, X, ldx, x_zero ? 0 : 1));                          // pre-smooth
-  ALFI_CHECK(block_spmv(L, cols, slots, X, ldx, L->blk_mg_r, ldl, B, ldb, 1));                      // r = b - A x
-  for (int i = 0; i < nc; ++i) ALFI_CHECK(alfi_restrict(T, L->blk_mg_r + i * ldl, C->blk_mg_b + i * ldc, mg->robust));
-  const int cycles = l == 1 ? 1 : mg->cycles;
-  for (int c = 0; c < cycles; ++c) ALFI_CHECK(vcycle_block(mg, l - 1, slots, C->blk_mg_b, ldc, C->blk_mg_x, ldc, c == 0));
-  for (int i = 0; i < nc; ++i) ALFI_CHECK(alfi_prolong(T, C->blk_mg_x + i * ldc, L->blk_mg_r + i * ldl));
-  ctx->cur_tag = L->id;
-  for (int i = 0; i < nc; ++i) {
-    ProfScope prof(ctx, ALFI_EV_BLAS1);
-    ALFI_CHECK(launch_axpy(ctx, X + cols.c[i] * ldx, L->blk_mg_r + i * ldl, 1.0, L->n_own));         // x += P x_{l-1}
-  }
-  return mg_smooth_block(mg, l, cols, B, ldb, X, ldx, 1);                                           // post-smooth
-}
-
-static int fcycle_block(alfi_mg* mg, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx) {
-  const int Lmax = (int)mg->levels.size() - 1, nc = cols.n;
-  if (Lmax == 0) return vcycle_block(mg, 0, cols, B, ldb, X, ldx, false);
-  const BlockCols slots = block_chunk(nc, nullptr, 0);
-  for (int i = 0; i < nc; ++i) {         // restrict the right-hand sides through all levels
-    const double* bf = B + cols.c[i] * ldb;
-    for (int l = Lmax; l >= 1; --l) {
-      double* bc = mg->levels[l - 1]->blk_mg_b + i * mg_block_ld(mg->levels[l - 1]);
-      ALFI_CHECK(alfi_restrict(mg->transfers[l - 1], bf, bc, mg->robust));
-      bf = bc;
-    }
-  }
-  for (int l = 0; l < Lmax; ++l) {
-    alfi_level* L = mg->levels[l];
-    const int64_t ldl = mg_block_ld(L);
-    ALFI_CHECK(vcycle_block(mg, l, slots, L->blk_mg_b, ldl, L->blk_mg_x, ldl, l == 0));
-    for (int i = 0; i < nc; ++i) {
-      double* xnext = l + 1 == Lmax ? X + cols.c[i] * ldx : mg->levels[l + 1]->blk_mg_x + i * mg_block_ld(mg->levels[l + 1]);
-      ALFI_CHECK(alfi_prolong(mg->transfers[l], L->blk_mg_x + i * ldl, xnext));
-    }
-  }
-  return vcycle_block(mg, Lmax, cols, B, ldb, X, ldx, false);
 }
 
 // one full cycle on the 1 .. BLOCK_NV columns `cols` of B and X, arguments unchecked (alfi_saddle_precond_block)
 int mg_fcycle_block_chunk(alfi_mg* mg, const BlockCols& cols, const double* B, int64_t ldb, double* X, int64_t ldx) {
   ALFI_CHECK(mg_ready(mg));
   ALFI_CHECK(mg_block_vectors(mg, cols.n));
-  return fcycle_block(mg, cols, B, ldb, X, ldx);
+  return fcycle(mg, block_work, cols, B, ldb, X, ldx);
 }
 
 static int run_cycle_block(alfi_mg* mg, int kind, const char* what, int ncol, const int* cols, int nx, const double* B, int64_t ldb,
@@ -776,7 +726,8 @@ static int run_cycle_block(alfi_mg* mg, int kind, const char* what, int ncol, co
   ALFI_CHECK(mg_block_vectors(mg, ncol));
   for (int q = 0; q < block_chunks(ncol); ++q) {
     const BlockCols c = block_chunk(ncol, cols, q);
-    ALFI_CHECK(kind ? fcycle_block(mg, c, B, ldb, X, ldx) : vcycle_block(mg, (int)mg->levels.size() - 1, c, B, ldb, X, ldx, false));
+    ALFI_CHECK(kind ? fcycle(mg, block_work, c, B, ldb, X, ldx)
+                    : vcycle(mg, block_work, (int)mg->levels.size() - 1, c, B, ldb, X, ldx, false));
   }
   return 0;
 }

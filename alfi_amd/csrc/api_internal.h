@@ -81,8 +81,23 @@ bool auto_cond_to_dense(alfi_level* L);
 int ensure_fgmres_workspace(alfi_level* L, int k);
 int ensure_cheb_workspace(alfi_level* L);
 bool smoother_takes_fused_iteration(const alfi_level* L, int k, bool* flat_spmv = nullptr);   // alfi_smooth_fgmres on this level
-// api_block.hip (block right-hand sides)
-void free_block_smoother(alfi_level* L);   // the Krylov workspaces of alfi_smooth_fgmres_block
+// The general path of the FGMRES(k) smoother on the 1 .. BLOCK_NV columns `cols` of B and X, slot s of ws for column cols.c[s]:
+// alfi_smooth_fgmres with one column on L->ws, the lockstep mode of alfi_smooth_fgmres_block on L->blk_ws.  Unchecked.
+int smooth_fgmres_general(alfi_level* L, const KrylovWs& ws, int k, const BlockCols& cols, const double* B, int64_t ldb, double* X,
+                          int64_t ldx, int nonzero_guess);
+// api_block.hip: the two workspace types of krylov_ws.h on the device.  Whoever changes a workspace synchronises the stream,
+// frees, allocates and zeroes (hs; a slot buffer whole) here and nowhere else.
+// ws becomes `slots` workspaces of FGMRES(K) for vectors of n entries (ldv = krylov_ldv(n)); nothing happens if it is that already
+int krylov_ws_ensure(alfi_ctx* ctx, KrylovWs* ws, int slots, int K, int64_t n);
+void krylov_ws_release(KrylovWs* ws);
+// buf serves a chunk of ncol columns of `per` doubles each (grow-only: slot_buf_needed) / holds exactly `slots` of them
+int slot_buf_ensure(alfi_ctx* ctx, SlotBuf* buf, int ncol, int64_t per);
+int slot_buf_resize(alfi_ctx* ctx, SlotBuf* buf, int slots, int64_t per);
+void slot_buf_release(SlotBuf* buf);
+// Lifetime of every workspace of the two types.  Callers have synchronised the stream.
+void block_release_patch_buffers(alfi_level* L);   // what a new patch set invalidates: the buffers sized by the old one
+void release_workspaces(alfi_level* L);            // all of a level's (alfi_level_destroy)
+void release_workspaces(alfi_saddle* S);           // all of a saddle's (alfi_saddle_destroy)
 // the block forms on one chunk of 1 .. 4 columns, arguments unchecked: entry i of ic names the column that is read (X, B), entry
 // i of oc the column its result goes to (block_patch_apply, block_spmv); the smoother works on the columns cols of B and X
 struct BlockCols;

@@ -52,7 +52,7 @@ int alfi_level_set_partition(alfi_level* L, int64_t nb_owned, int distributed, i
   for (int64_t i = 0; i < nsend; ++i)
     if (send_nodes[i] < 0 || send_nodes[i] >= nb_owned)
       return alfi_set_error(ctx, ALFI_E_ARG, "send node %d is not an owned node", send_nodes[i]);
-  if (L->patch_ptr || L->V) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_level_set_partition must precede patches");
+  if (L->patch_ptr || L->ws.V) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_level_set_partition must precede patches");
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   dev_free(L->halo_send_nodes);
@@ -208,10 +208,7 @@ int alfi_level_destroy(alfi_level* L) {
   free_patch_factors(L);
   dev_free(L->canon_rank);
   dev_free(L->stage);
-  dev_free(L->blk_stage);
-  dev_free(L->blk_ctmp);
-  dev_free(L->blk_carry);
-  free_block_smoother(L);
+  release_workspaces(L);      // Krylov workspaces, block buffers
   dev_free(L->dof_ptr);
   dev_free(L->dof_pos);
   dev_free(L->mult_seq);
@@ -220,10 +217,6 @@ int alfi_level_destroy(alfi_level* L) {
   dev_free(L->tr_mirror);
   dev_free(L->chk);
   dev_free(L->chk_list);
-  dev_free(L->V);
-  dev_free(L->Z);
-  dev_free(L->w);
-  dev_free(L->hs);
   dev_free(L->jac_diag);
   dev_free(L->cheb_r);
   dev_free(L->cheb_z);
@@ -233,9 +226,6 @@ int alfi_level_destroy(alfi_level* L) {
   dev_free(L->mg_b);
   dev_free(L->mg_x);
   dev_free(L->mg_r);
-  dev_free(L->blk_mg_b);
-  dev_free(L->blk_mg_x);
-  dev_free(L->blk_mg_r);
   delete L;
   return 0;
 }

@@ -66,12 +66,7 @@ int alfi_patches_set(alfi_level* L, int64_t npatch, const int64_t* pptr, const i
   dev_free(L->canon_rank);
   L->canon_rank = nullptr;
   dev_free(L->stage);
-  dev_free(L->blk_stage);          // sized by the old patch set: the next block apply allocates it again
-  L->blk_stage = nullptr;
-  L->blk_stage_slots = 0;
-  dev_free(L->blk_ctmp);           // (slots of the old set's sum_n)
-  L->blk_ctmp = nullptr;
-  L->blk_ctmp_slots = 0;
+  block_release_patch_buffers(L);
   dev_free(L->dof_ptr);
   dev_free(L->dof_pos);
   L->patch_ptr = nullptr; L->patch_dofs = nullptr; L->inv_ptr = nullptr; L->stage_ptr = nullptr;

@@ -224,21 +224,13 @@ int alfi_saddle_destroy(alfi_saddle* S) {
   free_csr(&S->BT);
   if (S->has_Minv) free_csr(&S->Minv);
   dev_free(S->minv);
-  dev_free(S->V);
-  dev_free(S->Z);
-  dev_free(S->w);
-  dev_free(S->hs);
+  release_workspaces(S);      // Krylov workspaces, block buffers
   dev_free(S->tmp_u);
   dev_free(S->tmp_p);
   dev_free(S->wa);
   dev_free(S->wb);
   dev_free(S->wc);
   dev_free(S->dotbuf);
-  dev_free(S->blk_V);
-  dev_free(S->blk_Z);
-  dev_free(S->blk_w);
-  dev_free(S->blk_hs);
-  dev_free(S->blk_tmp_u);
   mf_free(S->vmf);
   delete S;
   return 0;
@@ -421,117 +413,6 @@ int alfi_saddle_precond(alfi_saddle* S, const double* dx, double* dy) {
   return 0;
 }
 
-int alfi_saddle_solve(alfi_saddle* S, const double* db, double* dx, double rtol, double atol, int max_it, int restart,
-                      int* iterations, double* residual_norm) {
-  alfi_ctx* ctx = S->ctx;
-  alfi_level* F = S->fine;
-  const bool par = S->par;
-  const int64_t n = S->nu_dofs + S->np_dofs;
-  if (restart < 1 || restart > RED_MAXV - 2) return alfi_set_error(ctx, ALFI_E_ARG, "restart must be in 1..%d", RED_MAXV - 2);
-  if (restart != S->restart) {
-    ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    dev_free(S->V);
-    dev_free(S->Z);
-    dev_free(S->w);
-    dev_free(S->hs);
-    S->V = S->Z = S->w = S->hs = nullptr;
-    S->restart = 0;
-    S->ldv = (n + 1) & ~(int64_t)1;           // every basis vector on a 16-byte boundary
-    ALFI_CHECK(dev_alloc(ctx, &S->V, (int64_t)(restart + 1) * S->ldv));
-    ALFI_CHECK(dev_alloc(ctx, &S->Z, (int64_t)restart * S->ldv));
-    ALFI_CHECK(dev_alloc(ctx, &S->w, S->ldv));
-    HsLayout hl0(restart);
-    ALFI_CHECK(dev_alloc(ctx, &S->hs, hl0.total));
-    S->restart = restart;
-  }
-  const int K = restart;
-  const int64_t ldv = S->ldv;
-  HsLayout hl(K);
-  double *V = S->V, *Z = S->Z, *w = S->w, *hs = S->hs;
-  // partitioned: dots and norms are reduced into the ctx's reduction buffer and all-reduced there (as in the level smoother);
-  // the values every rank reads back are identical, so all ranks take the same branches
-  double* hdots = par ? ctx->dred : hs + hl.hd;
-  double* nrm2 = par ? ctx->dred + RED_MAXV : nullptr;
-  const int G = red_blocks_for(n);
-  ALFI_HIP_CHECK(ctx, hipMemsetAsync(hs, 0, sizeof(double) * hl.total, ctx->stream));
-  ALFI_HIP_CHECK(ctx, hipMemsetAsync(dx, 0, sizeof(double) * n, ctx->stream));
-  auto read = [&](const double* p, double* out) -> int {
-    ALFI_HIP_CHECK(ctx, hipMemcpyAsync(out, p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-  };
-  // beta = |w| into hs (and the rotated right-hand side)
-  auto norm_init = [&]() -> int {
-    ALFI_CHECK(launch_norm_partials(ctx, w, n));
-    if (par) {
-      ctx->cur_tag = F->id;
-      ALFI_CHECK(launch_reduce_partials(ctx, ctx->red_partial, G, 1, nrm2));
-      ALFI_CHECK(comm_allreduce(F, RED_MAXV, 1));
-      return launch_norm_init_finish(ctx, nrm2, 1, hs, K);
-    }
-    return launch_norm_init_finish(ctx, ctx->red_partial, G, hs, K);
-  };
-  int its = 0;
-  double bnorm = 0.0, rnorm = 0.0;
-  // r = b (zero initial guess)
-  ALFI_CHECK(launch_copy(ctx, w, db, n));
-  ALFI_CHECK(norm_init());
-  ALFI_CHECK(read(hs + hl.beta, &bnorm));
-  rnorm = bnorm;
-  const double tol = std::max(rtol * bnorm, atol);
-  bool converged = rnorm <= tol;
-  while (!converged && its < max_it) {
-    ALFI_CHECK(launch_scale_by_inv(ctx, V, w, hs + hl.beta, n));            // v_0 = r / |r|
-    int j = 0;
-    for (; j < K && its < max_it; ++j) {
-      double* zj = Z + (int64_t)j * ldv;
-      ALFI_CHECK(alfi_saddle_precond(S, V + (int64_t)j * ldv, zj));          // z_j = P^-1 v_j
-      ALFI_CHECK(alfi_saddle_mult(S, zj, w));                               // w = K z_j
-      ALFI_CHECK(launch_multi_dot(ctx, V, ldv, j + 1, w, hdots, n));
-      if (par) {
-        ctx->cur_tag = F->id;
-        ALFI_CHECK(comm_allreduce(F, 0, j + 1));
-      }
-      ALFI_CHECK(launch_multi_axpy_norm(ctx, V, ldv, j + 1, hdots, w, n, ctx->red_partial2, 0));
-      if (par) {                                                            // |w - V h| by its own all-reduce (VecNorm)
-        ALFI_CHECK(launch_reduce_partials(ctx, ctx->red_partial2, G, 1, nrm2));
-        ALFI_CHECK(comm_allreduce(F, RED_MAXV, 1));
-      }
-      ALFI_CHECK(launch_hessenberg_update(ctx, par ? nrm2 : ctx->red_partial2, par ? 1 : G, hdots, hs, j, K, nullptr));
-      ++its;
-      double g = 0.0;
-      ALFI_CHECK(read(hs + hl.grs + j + 1, &g));                            // |rotated rhs| = residual norm estimate
-      rnorm = std::fabs(g);
-      if (rnorm <= tol) {
-        converged = true;
-        ++j;
-        break;
-      }
-      if (j + 1 < K) ALFI_CHECK(launch_scale_by_inv(ctx, V + (int64_t)(j + 1) * ldv, w, hs + hl.tt, n));
-    }
-    ALFI_CHECK(launch_fgmres_finish(ctx, hs, j, K));
-    ALFI_CHECK(launch_update_solution(ctx, dx, Z, ldv, j, hs + hl.y, n));
-    if (converged || its >= max_it) break;
-    // restart: true residual
-    ALFI_CHECK(alfi_saddle_mult(S, dx, w));
-    ALFI_CHECK(launch_xmy(ctx, w, db, n));                                   // w = b - K x
-    ALFI_CHECK(norm_init());
-    ALFI_CHECK(read(hs + hl.beta, &rnorm));
-    converged = rnorm <= tol;
-  }
-  // final true residual norm
-  ALFI_CHECK(alfi_saddle_mult(S, dx, w));
-  ALFI_CHECK(launch_xmy(ctx, w, db, n));
-  ALFI_CHECK(norm_init());
-  double tn = 0.0;
-  ALFI_CHECK(read(hs + hl.beta, &tn));
-  if (iterations) *iterations = its;
-  if (residual_norm) *residual_norm = tn;
-  // a persistent multiplicative sweep inside a cycle may have run into its wait bound: the iterates above were then computed
-  // from an incomplete smoother result -- report it instead of returning counts and norms of garbage (ADVICE r4)
-  return check_dev_err(ctx);
-}
-
 // ---- block right-hand sides -----------------------------------------------------------------------------------------------------
 // alfi_saddle_mult / _precond / _solve for the columns of column-major operands (block_cols.h), columns of n_u + n_p entries.
 // Column c of every result is the single call on column c bit for bit: the velocity-block product and the full cycles are the
@@ -548,6 +429,7 @@ static int saddle_block_check(alfi_saddle* S, const char* what, int ncol, const 
 static int saddle_mult_chunk(alfi_saddle* S, const BlockCols& c, const double* X, int64_t ldx, double* Y, int64_t ldy) {
   alfi_ctx* ctx = S->ctx;
   const int64_t nu = S->nu_dofs;
+  if (c.n == 1) return alfi_saddle_mult(S, X + c.c[0] * ldx, Y + c.c[0] * ldy);            // (on a partitioned level too)
   ALFI_CHECK(block_spmv(S->fine, c, c, X, ldx, Y, ldy, nullptr, 0, 0));                    // y_u = A x_u
   for (int i = 0; i < c.n; ++i) {
     const double* x = X + c.c[i] * ldx;
@@ -561,28 +443,21 @@ static int saddle_mult_chunk(alfi_saddle* S, const BlockCols& c, const double* X
 // nx: the columns the operands have (the velocity work columns are indexed like them)
 static int saddle_precond_chunk(alfi_saddle* S, const BlockCols& c, int nx, const double* X, int64_t ldx, double* Y, int64_t ldy) {
   alfi_ctx* ctx = S->ctx;
-  const int64_t nu = S->nu_dofs, np = S->np_dofs, ldu = (nu + 1) & ~(int64_t)1;
+  const int64_t nu = S->nu_dofs, np = S->np_dofs, ldu = krylov_ldv(nu);
   if (S->vkind == ALFI_VELOCITY_DIRECT || c.n == 1) {
     for (int i = 0; i < c.n; ++i) ALFI_CHECK(alfi_saddle_precond(S, X + c.c[i] * ldx, Y + c.c[i] * ldy));
     return 0;
   }
-  if (S->blk_tmp_cols < nx) {
-    ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    dev_free(S->blk_tmp_u);
-    S->blk_tmp_u = nullptr;
-    S->blk_tmp_cols = 0;
-    ALFI_CHECK(dev_alloc(ctx, &S->blk_tmp_u, nx * ldu));
-    S->blk_tmp_cols = nx;
-  }
+  if (S->blk_tmp_u.slots < nx) ALFI_CHECK(slot_buf_resize(ctx, &S->blk_tmp_u, nx, ldu));      // (by operand columns, not by chunk)
   ALFI_CHECK(mg_fcycle_block_chunk(S->mg, c, X, ldx, Y, ldy));                              // y_u = MG(b_u)
   for (int i = 0; i < c.n; ++i) {
     const double* x = X + c.c[i] * ldx;
     double* y = Y + c.c[i] * ldy;
     ALFI_CHECK(launch_csr_spmv(ctx, S->B, y, S->tmp_p, x + nu, 1.0, 1));                   // q = b_p - B y_u
     ALFI_CHECK(saddle_schur(S, S->tmp_p, y + nu));                                         // y_p = -(nu+gamma) M^-1 q
-    ALFI_CHECK(launch_csr_spmv(ctx, S->BT, y + nu, S->blk_tmp_u + c.c[i] * ldu, x, 1.0, 1));   // t = b_u - B^T y_p
+    ALFI_CHECK(launch_csr_spmv(ctx, S->BT, y + nu, S->blk_tmp_u.slot(c.c[i]), x, 1.0, 1));   // t = b_u - B^T y_p
   }
-  ALFI_CHECK(mg_fcycle_block_chunk(S->mg, c, S->blk_tmp_u, ldu, Y, ldy));                   // y_u = MG(t)
+  ALFI_CHECK(mg_fcycle_block_chunk(S->mg, c, S->blk_tmp_u.p, ldu, Y, ldy));                   // y_u = MG(t)
   if (S->remove_nullspace)
     for (int i = 0; i < c.n; ++i) ALFI_CHECK(launch_remove_mean(ctx, Y + c.c[i] * ldy + nu, np));
   return 0;
@@ -602,24 +477,32 @@ int alfi_saddle_precond_block(alfi_saddle* S, int ncol, const int* cols, int nx,
   return 0;
 }
 
-// alfi_saddle_solve on the 1 .. BLOCK_NV columns c of B and X in lockstep; slot s of the block workspace belongs to column
-// c.c[s].  The columns start together, so every active column is at the same inner iteration j and the same count `its`; a
-// column leaves the active list when its own test max(rtol |b_c|, atol) is met -- inside a cycle (finish and update at its own
-// j, as the single call's break) or at a restart's true residual.  its[s], rn[s]: the single call's two results per slot.
-static int saddle_solve_chunk(alfi_saddle* S, const BlockCols& c, const double* B, int64_t ldb, double* X, int64_t ldx, double rtol,
-                              double atol, int max_it, int* its_out, double* rn_out) {
+// Restarted FGMRES (zero initial guess) on the 1 .. BLOCK_NV columns c of B and X in lockstep; slot s of ws belongs to column
+// c.c[s].  alfi_saddle_solve is the one-column case on the saddle's own workspace.  The columns start together, so every active
+// column is at the same inner iteration j and the same count `its`; a column leaves the active list when its own test
+// max(rtol |b_c|, atol) is met -- inside a cycle (finish and update at its own j) or at a restart's true residual.  its_out[s],
+// rn_out[s]: iterations and final true residual norm per slot.  A partitioned saddle comes with one column only
+// (saddle_block_check): dots and norms are reduced into the ctx's reduction buffer and all-reduced there, as in the level
+// smoother; the values every rank reads back are identical, so all ranks take the same branches.
+static int saddle_solve_chunk(alfi_saddle* S, const KrylovWs& ws, const BlockCols& c, const double* B, int64_t ldb, double* X,
+                              int64_t ldx, double rtol, double atol, int max_it, int* its_out, double* rn_out) {
   alfi_ctx* ctx = S->ctx;
-  const int64_t n = S->nu_dofs + S->np_dofs, ldv = S->ldv;
-  const int K = S->blk_restart, nc = c.n;
+  alfi_level* F = S->fine;
+  const bool par = S->par;
+  const int64_t n = S->nu_dofs + S->np_dofs, ldv = ws.ldv;
+  const int K = ws.K, nc = c.n;
   HsLayout hl(K);
-  const int64_t vs = (int64_t)(K + 1) * ldv, zs = (int64_t)K * ldv;
   const int G = red_blocks_for(n);
-  auto Vs = [&](int s) { return S->blk_V + s * vs; };
-  auto Zs = [&](int s) { return S->blk_Z + s * zs; };
-  auto ws = [&](int s) { return S->blk_w + s * ldv; };
-  auto hss = [&](int s) { return S->blk_hs + (int64_t)s * hl.total; };
+  double* nrm2 = par ? ctx->dred + RED_MAXV : nullptr;
+  const double* normpart = par ? nrm2 : ctx->red_partial2;      // |w - V h|^2: all-reduced, or nblk partials
+  const int nblk = par ? 1 : G;
+  auto hdots_of = [&](int s) { return par ? ctx->dred : ws.h(s) + hl.hd; };
   auto bcol = [&](int s) { return B + c.c[s] * ldb; };
   auto xcol = [&](int s) { return X + c.c[s] * ldx; };
+  auto allreduce = [&](int64_t offset, int64_t count) -> int {
+    ctx->cur_tag = F->id;
+    return comm_allreduce(F, offset, count);
+  };
   auto list = [&](const bool* on) {           // the slots that are on, as a column list of the workspace operands
     BlockCols b = block_chunk(nc, nullptr, 0);
     int m = 0;
@@ -632,22 +515,28 @@ static int saddle_solve_chunk(alfi_saddle* S, const BlockCols& c, const double* 
   // out[s] = hs_s[off] for the slots that are on: the copies queued together, one synchronisation
   auto read = [&](const bool* on, int off, double* out) -> int {
     for (int s = 0; s < nc; ++s)
-      if (on[s]) ALFI_HIP_CHECK(ctx, hipMemcpyAsync(out + s, hss(s) + off, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+      if (on[s]) ALFI_HIP_CHECK(ctx, hipMemcpyAsync(out + s, ws.h(s) + off, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
   };
+  // beta = |w| into hs (and the rotated right-hand side)
   auto norm_init = [&](int s) -> int {
-    ALFI_CHECK(launch_norm_partials(ctx, ws(s), n));
-    return launch_norm_init_finish(ctx, ctx->red_partial, G, hss(s), K);
+    ALFI_CHECK(launch_norm_partials(ctx, ws.wv(s), n));
+    if (par) {
+      ALFI_CHECK(launch_reduce_partials(ctx, ctx->red_partial, G, 1, nrm2));
+      ALFI_CHECK(allreduce(RED_MAXV, 1));
+      return launch_norm_init_finish(ctx, nrm2, 1, ws.h(s), K);
+    }
+    return launch_norm_init_finish(ctx, ctx->red_partial, G, ws.h(s), K);
   };
   bool active[BLOCK_NV] = {false, false, false, false}, all[BLOCK_NV] = {false, false, false, false};
   double bnorm[BLOCK_NV] = {0, 0, 0, 0}, tol[BLOCK_NV] = {0, 0, 0, 0}, val[BLOCK_NV] = {0, 0, 0, 0};
   int its[BLOCK_NV] = {0, 0, 0, 0};
   for (int s = 0; s < nc; ++s) {
     all[s] = true;
-    ALFI_HIP_CHECK(ctx, hipMemsetAsync(hss(s), 0, sizeof(double) * hl.total, ctx->stream));
+    ALFI_HIP_CHECK(ctx, hipMemsetAsync(ws.h(s), 0, sizeof(double) * hl.total, ctx->stream));
     ALFI_HIP_CHECK(ctx, hipMemsetAsync(xcol(s), 0, sizeof(double) * n, ctx->stream));
-    ALFI_CHECK(launch_copy(ctx, ws(s), bcol(s), n));                           // r = b (zero initial guess)
+    ALFI_CHECK(launch_copy(ctx, ws.wv(s), bcol(s), n));                           // r = b (zero initial guess)
     ALFI_CHECK(norm_init(s));
   }
   ALFI_CHECK(read(all, hl.beta, bnorm));
@@ -657,13 +546,13 @@ static int saddle_solve_chunk(alfi_saddle* S, const BlockCols& c, const double* 
     active[s] = !(bnorm[s] <= tol[s]);
     nactive += active[s] ? 1 : 0;
   }
-  // w_s = b_s - K x_s and beta_s = |w_s| for the slots in `on`, column by column with the single call's launches (x is a
-  // column of the caller's operand, w one of the workspace: two column lists, which the block product does not take)
+  // w_s = b_s - K x_s and beta_s = |w_s| for the slots in `on`, column by column (x is a column of the caller's operand, w one
+  // of the workspace: two column lists, which the block product does not take)
   auto residual_of = [&](const bool* on) -> int {
     for (int s = 0; s < nc; ++s) {
       if (!on[s]) continue;
-      ALFI_CHECK(alfi_saddle_mult(S, xcol(s), ws(s)));
-      ALFI_CHECK(launch_xmy(ctx, ws(s), bcol(s), n));
+      ALFI_CHECK(alfi_saddle_mult(S, xcol(s), ws.wv(s)));
+      ALFI_CHECK(launch_xmy(ctx, ws.wv(s), bcol(s), n));
       ALFI_CHECK(norm_init(s));
     }
     return 0;
@@ -671,21 +560,26 @@ static int saddle_solve_chunk(alfi_saddle* S, const BlockCols& c, const double* 
   int it = 0;                                   // iterations of every still active column
   while (nactive > 0 && it < max_it) {
     for (int s = 0; s < nc; ++s)
-      if (active[s]) ALFI_CHECK(launch_scale_by_inv(ctx, Vs(s), ws(s), hss(s) + hl.beta, n));      // v_0 = r / |r|
+      if (active[s]) ALFI_CHECK(launch_scale_by_inv(ctx, ws.v(s, 0), ws.wv(s), ws.h(s) + hl.beta, n));      // v_0 = r / |r|
     int j = 0;
     bool cycle[BLOCK_NV];                        // the columns that run this restart cycle to its end
     for (int s = 0; s < nc; ++s) cycle[s] = active[s];
     int ncycle = nactive;
     for (; j < K && it < max_it && ncycle > 0; ++j) {
       const BlockCols a = list(cycle);
-      ALFI_CHECK(saddle_precond_chunk(S, a, nc, S->blk_V + j * ldv, vs, S->blk_Z + j * ldv, zs));   // z_j = P^-1 v_j
-      ALFI_CHECK(saddle_mult_chunk(S, a, S->blk_Z + j * ldv, zs, S->blk_w, ldv));                   // w = K z_j
+      ALFI_CHECK(saddle_precond_chunk(S, a, nc, ws.v(0, j), ws.vs(), ws.z(0, j), ws.zs()));          // z_j = P^-1 v_j
+      ALFI_CHECK(saddle_mult_chunk(S, a, ws.z(0, j), ws.zs(), ws.w, ldv));                           // w = K z_j
       for (int s = 0; s < nc; ++s) {
         if (!cycle[s]) continue;
-        double *hs = hss(s), *hdots = hs + hl.hd;
-        ALFI_CHECK(launch_multi_dot(ctx, Vs(s), ldv, j + 1, ws(s), hdots, n));
-        ALFI_CHECK(launch_multi_axpy_norm(ctx, Vs(s), ldv, j + 1, hdots, ws(s), n, ctx->red_partial2, 0));
-        ALFI_CHECK(launch_hessenberg_update(ctx, ctx->red_partial2, G, hdots, hs, j, K, nullptr));
+        double *hs = ws.h(s), *hdots = hdots_of(s);
+        ALFI_CHECK(launch_multi_dot(ctx, ws.v(s, 0), ldv, j + 1, ws.wv(s), hdots, n));
+        if (par) ALFI_CHECK(allreduce(0, j + 1));
+        ALFI_CHECK(launch_multi_axpy_norm(ctx, ws.v(s, 0), ldv, j + 1, hdots, ws.wv(s), n, ctx->red_partial2, 0));
+        if (par) {                                                              // |w - V h| by its own all-reduce (VecNorm)
+          ALFI_CHECK(launch_reduce_partials(ctx, ctx->red_partial2, G, 1, nrm2));
+          ALFI_CHECK(allreduce(RED_MAXV, 1));
+        }
+        ALFI_CHECK(launch_hessenberg_update(ctx, normpart, nblk, hdots, hs, j, K, nullptr));
       }
       ++it;
       ALFI_CHECK(read(cycle, hl.grs + j + 1, val));                            // |rotated rhs| = residual norm estimates
@@ -693,20 +587,20 @@ static int saddle_solve_chunk(alfi_saddle* S, const BlockCols& c, const double* 
         if (!cycle[s]) continue;
         its[s] = it;
         if (std::fabs(val[s]) <= tol[s]) {                                     // converged: finished at its own j, out of the list
-          ALFI_CHECK(launch_fgmres_finish(ctx, hss(s), j + 1, K));
-          ALFI_CHECK(launch_update_solution(ctx, xcol(s), Zs(s), ldv, j + 1, hss(s) + hl.y, n));
+          ALFI_CHECK(launch_fgmres_finish(ctx, ws.h(s), j + 1, K));
+          ALFI_CHECK(launch_update_solution(ctx, xcol(s), ws.z(s, 0), ldv, j + 1, ws.h(s) + hl.y, n));
           cycle[s] = active[s] = false;
           --ncycle;
           --nactive;
         } else if (j + 1 < K) {
-          ALFI_CHECK(launch_scale_by_inv(ctx, Vs(s) + (int64_t)(j + 1) * ldv, ws(s), hss(s) + hl.tt, n));
+          ALFI_CHECK(launch_scale_by_inv(ctx, ws.v(s, j + 1), ws.wv(s), ws.h(s) + hl.tt, n));
         }
       }
     }
     for (int s = 0; s < nc; ++s) {
       if (!cycle[s]) continue;
-      ALFI_CHECK(launch_fgmres_finish(ctx, hss(s), j, K));
-      ALFI_CHECK(launch_update_solution(ctx, xcol(s), Zs(s), ldv, j, hss(s) + hl.y, n));
+      ALFI_CHECK(launch_fgmres_finish(ctx, ws.h(s), j, K));
+      ALFI_CHECK(launch_update_solution(ctx, xcol(s), ws.z(s, 0), ldv, j, ws.h(s) + hl.y, n));
     }
     if (nactive == 0 || it >= max_it) break;
     ALFI_CHECK(residual_of(active));                                           // restart: true residuals
@@ -726,34 +620,36 @@ static int saddle_solve_chunk(alfi_saddle* S, const BlockCols& c, const double* 
   return 0;
 }
 
+static int check_restart(alfi_ctx* ctx, int restart) {
+  if (restart < 1 || restart > RED_MAXV - 2) return alfi_set_error(ctx, ALFI_E_ARG, "restart must be in 1..%d", RED_MAXV - 2);
+  return 0;
+}
+
+int alfi_saddle_solve(alfi_saddle* S, const double* db, double* dx, double rtol, double atol, int max_it, int restart,
+                      int* iterations, double* residual_norm) {
+  alfi_ctx* ctx = S->ctx;
+  ALFI_CHECK(check_restart(ctx, restart));
+  ALFI_CHECK(krylov_ws_ensure(ctx, &S->ws, 1, restart, S->nu_dofs + S->np_dofs));
+  int its = 0;
+  double rn = 0.0;
+  ALFI_CHECK(saddle_solve_chunk(S, S->ws, block_chunk(1, nullptr, 0), db, 0, dx, 0, rtol, atol, max_it, &its, &rn));
+  if (iterations) *iterations = its;
+  if (residual_norm) *residual_norm = rn;
+  // a persistent multiplicative sweep inside a cycle may have run into its wait bound: the iterates above were then computed
+  // from an incomplete smoother result -- report it instead of returning counts and norms of garbage (ADVICE r4)
+  return check_dev_err(ctx);
+}
+
 int alfi_saddle_solve_block(alfi_saddle* S, int ncol, const int* cols, int nx, const double* B, int64_t ldb, double* X, int64_t ldx,
                             double rtol, double atol, int max_it, int restart, int* iterations, double* residual_norms) {
   const BlockOperand ops[2] = {{B, ldb, false}, {X, ldx, true}};
   ALFI_CHECK(saddle_block_check(S, "alfi_saddle_solve_block", ncol, cols, nx, ops, 2));
   alfi_ctx* ctx = S->ctx;
   if (!iterations || !residual_norms) return alfi_set_error(ctx, ALFI_E_ARG, "alfi_saddle_solve_block: NULL result arrays");
-  if (restart < 1 || restart > RED_MAXV - 2) return alfi_set_error(ctx, ALFI_E_ARG, "restart must be in 1..%d", RED_MAXV - 2);
-  const int64_t n = S->nu_dofs + S->np_dofs;
-  const int need = block_slots_needed(S->blk_slots, ncol);
-  if (restart != S->blk_restart || need != S->blk_slots) {
-    ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    dev_free(S->blk_V);
-    dev_free(S->blk_Z);
-    dev_free(S->blk_w);
-    dev_free(S->blk_hs);
-    S->blk_V = S->blk_Z = S->blk_w = S->blk_hs = nullptr;
-    S->blk_restart = S->blk_slots = 0;
-    S->ldv = (n + 1) & ~(int64_t)1;             // (what alfi_saddle_solve sets too: a function of n alone)
-    HsLayout hl0(restart);
-    ALFI_CHECK(dev_alloc(ctx, &S->blk_V, (int64_t)need * (restart + 1) * S->ldv));
-    ALFI_CHECK(dev_alloc(ctx, &S->blk_Z, (int64_t)need * restart * S->ldv));
-    ALFI_CHECK(dev_alloc(ctx, &S->blk_w, (int64_t)need * S->ldv));
-    ALFI_CHECK(dev_alloc(ctx, &S->blk_hs, (int64_t)need * hl0.total));
-    S->blk_restart = restart;
-    S->blk_slots = need;
-  }
+  ALFI_CHECK(check_restart(ctx, restart));
+  ALFI_CHECK(krylov_ws_ensure(ctx, &S->blk_ws, block_slots_needed(S->blk_ws.slots, ncol), restart, S->nu_dofs + S->np_dofs));
   for (int q = 0; q < block_chunks(ncol); ++q)
-    ALFI_CHECK(saddle_solve_chunk(S, block_chunk(ncol, cols, q), B, ldb, X, ldx, rtol, atol, max_it, iterations + q * BLOCK_NV,
-                                  residual_norms + q * BLOCK_NV));
+    ALFI_CHECK(saddle_solve_chunk(S, S->blk_ws, block_chunk(ncol, cols, q), B, ldb, X, ldx, rtol, atol, max_it,
+                                  iterations + q * BLOCK_NV, residual_norms + q * BLOCK_NV));
   return check_dev_err(ctx);
 }

@@ -2,31 +2,15 @@
 // Chebyshev(k) (KSPCHEBYSHEV, examples/graddiv/graddiv.py:109-110), and the Arnoldi steps its interval is estimated from.
 // (One file per concern since round 5: api_ctx / api_level / api_patches / api_smoother / api_cycles / api_saddle; the helpers they
 // share are declared in api_internal.h.)
+#include <optional>
 #include "api_internal.h"
 
 // ---- FGMRES(k) smoother ----------------------------------------------------------------------------------------------------
+// the single call's workspace: grow-only in K (a captured cycle holds its addresses; HsLayout is built from the K it holds)
 int ensure_fgmres_workspace(alfi_level* L, int k) {
-  alfi_ctx* ctx = L->ctx;
-  if (k <= L->kmax) return 0;
-  if (k > RED_MAXV - 1) return alfi_set_error(ctx, ALFI_E_ARG, "k = %d exceeds the supported maximum %d", k, RED_MAXV - 1);
-  ALFI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  dev_free(L->V);
-  dev_free(L->Z);
-  dev_free(L->w);
-  dev_free(L->hs);
-  L->V = L->Z = L->w = L->hs = nullptr;
-  L->kmax = 0;
-  // stride of the Krylov bases: the local length rounded up to even, so that every basis vector starts on a 16-byte
-  // boundary (the BLAS-1 kernels read entry pairs; n = 3 x nodes is odd on half of the 3-D levels)
-  L->ldv = (L->n + 1) & ~(int64_t)1;
-  ALFI_CHECK(dev_alloc(ctx, &L->V, (int64_t)(k + 1) * L->ldv));
-  ALFI_CHECK(dev_alloc(ctx, &L->Z, (int64_t)k * L->ldv));
-  ALFI_CHECK(dev_alloc(ctx, &L->w, L->ldv));
-  HsLayout hl(k);
-  ALFI_CHECK(dev_alloc(ctx, &L->hs, hl.total));
-  ALFI_HIP_CHECK(ctx, hipMemsetAsync(L->hs, 0, sizeof(double) * hl.total, ctx->stream));
-  L->kmax = k;
-  return 0;
+  if (k <= L->ws.K) return 0;
+  if (k > RED_MAXV - 1) return alfi_set_error(L->ctx, ALFI_E_ARG, "k = %d exceeds the supported maximum %d", k, RED_MAXV - 1);
+  return krylov_ws_ensure(L->ctx, &L->ws, 1, k, L->n);
 }
 
 // FGMRES(k) on a small, unpartitioned level with the additive smoother: four launches per iteration (see the kernels in
@@ -34,10 +18,10 @@ int ensure_fgmres_workspace(alfi_level* L, int k) {
 // explicit norms -- with the normalisation of the new Krylov vector moved behind the patch solves (they are linear).
 static int smooth_fgmres_fused(alfi_level* L, int k, const double* db, double* dx, int nonzero_guess, bool flat_spmv) {
   alfi_ctx* ctx = L->ctx;
-  const int K = L->kmax;
-  const int64_t n = L->n, ldv = L->ldv;
+  const int K = L->ws.K;
+  const int64_t n = L->n, ldv = L->ws.ldv;
   HsLayout hl(K);
-  double *V = L->V, *Z = L->Z, *w = L->w, *hs = L->hs;
+  double *V = L->ws.V, *Z = L->ws.Z, *w = L->ws.w, *hs = L->ws.hs;
   double* hdots = hs + hl.hd;
   if (nonzero_guess) {
     ALFI_CHECK(alfi_residual(L, db, dx, w));
@@ -113,29 +97,62 @@ int alfi_smooth_fgmres(alfi_level* L, int k, const double* db, double* dx, int n
   if (!level_pc_ready(L)) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_smooth_fgmres before alfi_patches_factor");
   ALFI_CHECK(ensure_fgmres_workspace(L, k));
   ctx->cur_tag = L->id;
-  {
-    bool flat_spmv = false;
-    if (smoother_takes_fused_iteration(L, k, &flat_spmv)) return smooth_fgmres_fused(L, k, db, dx, nonzero_guess, flat_spmv);
-  }
-  const int K = L->kmax;
+  bool flat_spmv = false;
+  if (smoother_takes_fused_iteration(L, k, &flat_spmv)) return smooth_fgmres_fused(L, k, db, dx, nonzero_guess, flat_spmv);
+  return smooth_fgmres_general(L, L->ws, k, block_chunk(1, nullptr, 0), db, 0, dx, 0, nonzero_guess);
+}
+
+namespace {
+// A BLAS-1 profiling event that can end and begin again.  It exists for the profile's event counts alone: the one-column call
+// has always recorded three events per iteration (dots | projection | Hessenberg column, split where a partitioned level
+// all-reduces), a chunk of two or more columns one event per slot and iteration -- and both counts stay what they were.
+class Blas1Event {
+ public:
+  explicit Blas1Event(alfi_ctx* ctx) : ctx_(ctx) { open(); }
+  void open() { ev_.emplace(ctx_, ALFI_EV_BLAS1); }
+  void close() { ev_.reset(); }
+
+ private:
+  alfi_ctx* ctx_;
+  std::optional<ProfScope> ev_;
+};
+}   // namespace
+
+// The general path: right-preconditioned FGMRES(k), classical Gram-Schmidt, explicit norms, for the 1 .. BLOCK_NV columns
+// `cols` of B and X with slot s of ws for column cols.c[s].  Per iteration ONE (block) apply and ONE (block) product for all
+// slots; the BLAS-1 and Hessenberg launches slot by slot: a slot's chain hands its reduction partials from one launch to the
+// next through the ctx's two partial buffers and is finished before the next slot's begins.  A partitioned level comes with
+// one column only (check_block_call): its dots and norms are reduced into the ctx's buffer and all-reduced there.
+int smooth_fgmres_general(alfi_level* L, const KrylovWs& ws, int k, const BlockCols& cols, const double* B, int64_t ldb, double* X,
+                          int64_t ldx, int nonzero_guess) {
+  alfi_ctx* ctx = L->ctx;
+  const int K = ws.K, nc = cols.n;
+  const bool one = nc == 1;
   const int64_t n = L->n_own;    // vector kernels and reductions run on the owned prefix
-  const int64_t ldv = L->ldv;    // stride of the Krylov bases (local length incl. ghost slots, rounded up to even)
+  const int64_t ldv = ws.ldv;    // stride of the Krylov bases (local length incl. ghost slots, rounded up to even)
   const bool par = L->distributed;
   HsLayout hl(K);
-  double* V = L->V;
-  double* Z = L->Z;
-  double* w = L->w;
-  double* hs = L->hs;
-  // partitioned level: dots / norms are reduced into the caller's buffer and all-reduced there
-  double* hdots = par ? ctx->dred : hs + hl.hd;
+  const BlockCols slots = block_chunk(nc, nullptr, 0);
+  auto hdots_of = [&](int s) { return par ? ctx->dred : ws.h(s) + hl.hd; };
   double* nrm2 = par ? ctx->dred + RED_MAXV : nullptr;
+  // One column: the BLAS-1 event ends here and the next one begins, and in between a partitioned level all-reduces `count`
+  // doubles at `offset` of the ctx's buffer.  Two or more columns: one event per slot and step, nothing to do.
+  auto event_ends = [&](Blas1Event& ev, bool reduce, int64_t offset, int64_t count) -> int {
+    if (!one) return 0;
+    ev.close();
+    if (reduce) ALFI_CHECK(comm_allreduce(L, offset, count));
+    ev.open();
+    return 0;
+  };
   // r0 = b - A x (MatMult), beta = |r0|, v0 = r0 / beta
   if (nonzero_guess) {
-    ALFI_CHECK(alfi_residual(L, db, dx, w));
+    ALFI_CHECK(block_spmv(L, cols, slots, X, ldx, ws.w, ldv, B, ldb, 1));
   } else {
-    ALFI_HIP_CHECK(ctx, hipMemsetAsync(dx, 0, sizeof(double) * L->n, ctx->stream));
-    ProfScope prof(ctx, ALFI_EV_BLAS1);
-    ALFI_CHECK(launch_copy(ctx, w, db, n));
+    for (int s = 0; s < nc; ++s) {
+      ALFI_HIP_CHECK(ctx, hipMemsetAsync(X + cols.c[s] * ldx, 0, sizeof(double) * L->n, ctx->stream));
+      ProfScope prof(ctx, ALFI_EV_BLAS1);
+      ALFI_CHECK(launch_copy(ctx, ws.wv(s), B + cols.c[s] * ldb, n));
+    }
   }
   // reductions: red_blocks_for(n) partials per vector.  Up to 256 of them (levels of <= 1 M dofs, where a smoother
   // iteration is a chain of launches of a few microseconds each) the kernel that needs a reduced value sums the partials
@@ -144,52 +161,54 @@ int alfi_smooth_fgmres(alfi_level* L, int k, const double* db, double* dx, int n
   // (G = n / 4096 partials per vector; a limit of 512 would include config 3's finest level, 319 partials: measured 18.31
   // against 18.13 ms per cycle, the re-summation in every consumer block costs more than the launch)
   const bool fused = !par && G <= 256 && k + 1 <= 16;
-  {
-    ProfScope prof(ctx, ALFI_EV_BLAS1);
-    ALFI_CHECK(launch_norm_partials(ctx, w, n));
+  const double* part1 = par ? nrm2 : ctx->red_partial;      // where the consumer of a norm finds it: all-reduced, or nblk partials
+  const double* part2 = par ? nrm2 : ctx->red_partial2;
+  const int nblk = par ? 1 : G;
+  for (int s = 0; s < nc; ++s) {
+    Blas1Event ev(ctx);
+    ALFI_CHECK(launch_norm_partials(ctx, ws.wv(s), n));
     if (par) ALFI_CHECK(launch_reduce_partials(ctx, ctx->red_partial, G, 1, nrm2));
-  }
-  if (par) ALFI_CHECK(comm_allreduce(L, RED_MAXV, 1));
-  {
-    ProfScope prof(ctx, ALFI_EV_BLAS1);
-    ALFI_CHECK(launch_norm_init_finish(ctx, par ? nrm2 : ctx->red_partial, par ? 1 : G, hs, K));
-    ALFI_CHECK(launch_scale_by_inv(ctx, V, w, hs + hl.beta, n));
+    ALFI_CHECK(event_ends(ev, par, RED_MAXV, 1));
+    ALFI_CHECK(launch_norm_init_finish(ctx, part1, nblk, ws.h(s), K));
+    ALFI_CHECK(launch_scale_by_inv(ctx, ws.v(s, 0), ws.wv(s), ws.h(s) + hl.beta, n));
   }
   for (int j = 0; j < k; ++j) {
-    bool zghosts = false;
-    ALFI_CHECK(level_patch_apply(L, V + (int64_t)j * ldv, Z + (int64_t)j * ldv, &zghosts));   // z_j = M^-1 v_j
-    ALFI_CHECK(level_spmv(L, Z + (int64_t)j * ldv, w, nullptr, 0, zghosts));                 // w = A z_j
+    if (one) {      // straight to the level: a sum exchange after the patch solves spares the product its forward exchange
+      bool zghosts = false;
+      ALFI_CHECK(level_patch_apply(L, ws.v(0, j), ws.z(0, j), &zghosts));                            // z_j = M^-1 v_j
+      ALFI_CHECK(level_spmv(L, ws.z(0, j), ws.w, nullptr, 0, zghosts));                              // w = A z_j
+    } else {
+      ALFI_CHECK(block_patch_apply(L, slots, slots, ws.v(0, j), ws.vs(), ws.z(0, j), ws.zs()));
+      ALFI_CHECK(block_spmv(L, slots, slots, ws.z(0, j), ws.zs(), ws.w, ldv, nullptr, 0, 0));
+    }
     // partitioned: |w|^2 rides along in the same all-reduce; |w - V h|^2 = |w|^2 - |h|^2 then needs no second one
     const bool pyth = par && !ctx->exact_norm;
-    const double* ww = pyth ? hdots + (j + 1) : nullptr;
-    {
-      ProfScope prof(ctx, ALFI_EV_BLAS1);
+    for (int s = 0; s < nc; ++s) {
+      double *V = ws.v(s, 0), *w = ws.wv(s), *hs = ws.h(s), *hdots = hdots_of(s);
+      const double* ww = pyth ? hdots + (j + 1) : nullptr;
+      Blas1Event ev(ctx);   // to the end of the loop body
       // h = V^T w (classical GS); fused: the partials stay in red_partial and the projection kernel sums them
       ALFI_CHECK(launch_multi_dot(ctx, V, ldv, j + 1, w, fused ? nullptr : hdots, n));
       if (pyth) {
         ALFI_CHECK(launch_norm_partials(ctx, w, n));
         ALFI_CHECK(launch_reduce_partials(ctx, ctx->red_partial, G, 1, hdots + (j + 1)));
       }
-    }
-    if (par) ALFI_CHECK(comm_allreduce(L, 0, pyth ? j + 2 : j + 1));
-    {
-      ProfScope prof(ctx, ALFI_EV_BLAS1);
+      ALFI_CHECK(event_ends(ev, par, 0, pyth ? j + 2 : j + 1));
       // w -= V h, |w|^2 partials (into the second partial buffer: the dot partials are still being read)
       ALFI_CHECK(launch_multi_axpy_norm(ctx, V, ldv, j + 1, hdots, w, n, ctx->red_partial2, fused ? G : 0));
       if (par && !pyth) ALFI_CHECK(launch_reduce_partials(ctx, ctx->red_partial2, G, 1, nrm2));
+      ALFI_CHECK(event_ends(ev, par && !pyth, RED_MAXV, 1));
+      if (j + 1 < k)   // Hessenberg column + v_{j+1} = w / |w| in one launch
+        ALFI_CHECK(launch_hessenberg_scale(ctx, part2, nblk, hdots, hs, j, K, ws.v(s, j + 1), w, n, ww));
+      else
+        ALFI_CHECK(launch_hessenberg_update(ctx, part2, nblk, hdots, hs, j, K, ww));
     }
-    if (par && !pyth) ALFI_CHECK(comm_allreduce(L, RED_MAXV, 1));
-    ProfScope prof(ctx, ALFI_EV_BLAS1);   // to the end of the loop body
-    const double* part = par ? nrm2 : ctx->red_partial2;
-    const int nblk = par ? 1 : G;
-    if (j + 1 < k)   // Hessenberg column + v_{j+1} = w / |w| in one launch
-      ALFI_CHECK(launch_hessenberg_scale(ctx, part, nblk, hdots, hs, j, K, V + (int64_t)(j + 1) * ldv, w, n, ww));
-    else
-      ALFI_CHECK(launch_hessenberg_update(ctx, part, nblk, hdots, hs, j, K, ww));
   }
-  ProfScope prof(ctx, ALFI_EV_BLAS1);   // to the end of the function
-  ALFI_CHECK(launch_fgmres_finish(ctx, hs, k, K));
-  ALFI_CHECK(launch_update_solution(ctx, dx, Z, ldv, k, hs + hl.y, n));
+  for (int s = 0; s < nc; ++s) {
+    ProfScope prof(ctx, ALFI_EV_BLAS1);
+    ALFI_CHECK(launch_fgmres_finish(ctx, ws.h(s), k, K));
+    ALFI_CHECK(launch_update_solution(ctx, X + cols.c[s] * ldx, ws.z(s, 0), ldv, k, ws.h(s) + hl.y, n));
+  }
   return 0;
 }
 
@@ -259,7 +278,7 @@ int alfi_level_arnoldi(alfi_level* L, int m, const double* dv0, double* H_host, 
   if (!level_pc_ready(L)) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_level_arnoldi before alfi_patches_factor");
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   ctx->cur_tag = L->id;
-  const int64_t n = L->n, ld = (n + 1) & ~(int64_t)1;     // 16-byte aligned basis vectors
+  const int64_t n = L->n, ld = krylov_ldv(n);             // 16-byte aligned basis vectors
   const int G = red_blocks_for(n);
   const int ldh = m + 2;                                  // device Hessenberg: column j at Hd + j * ldh, slot m + 1 = |v0|
   double *V = nullptr, *z = nullptr, *w = nullptr, *Hd = nullptr;

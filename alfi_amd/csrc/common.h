@@ -9,6 +9,7 @@
 #include <vector>
 #include "alfi_hip.h"
 #include "env.h"   // every environment switch of the library
+#include "krylov_ws.h"   // the two workspace types of the host drivers
 #include "patch_plan.h"   // host planners of the patch tables; with cond_layout.h, the layout they share with the kernels
 
 // Every host <-> device copy the library makes is counted (alfi_transfer_stats): that a Newton step moves nothing but scalars
@@ -418,16 +419,11 @@ struct alfi_level {
   bool il_valid = false;
   double* stage = nullptr;        // (sum ld_p) staged patch results
   // block right-hand sides (api_block.hip), allocated by the first block call that needs them and grown to at most BLOCK_NV
-  // slots: staging buffers of the batched apply (blk_stage_slots x lay.stage_len; `stage` itself stays where captured cycles
-  // expect it), carries of the batched product's fix-up (blk_carry_slots x chunks x bs)
-  double* blk_stage = nullptr;
-  int blk_stage_slots = 0;
-  // ... and, on condensed levels, the block twin of cd.tmp (blk_ctmp_slots x lay.sum_n: t and y_S of every column between the
-  // launches); freed and grown with blk_stage
-  double* blk_ctmp = nullptr;
-  int blk_ctmp_slots = 0;
-  double* blk_carry = nullptr;
-  int blk_carry_slots = 0;
+  // slots (krylov_ws.h): staging buffers of the batched apply (lay.stage_len per slot; `stage` itself stays where captured
+  // cycles expect it), on condensed levels the block twin of cd.tmp (lay.sum_n per slot: t and y_S of every column between the
+  // launches) -- a new patch set releases these two (block_release_patch_buffers) --, and the carries of the batched product's
+  // fix-up (chunks x bs per slot)
+  SlotBuf blk_stage, blk_ctmp, blk_carry;
   int32_t* dof_ptr = nullptr;     // (n+1) CSR dof -> positions in stage
   int32_t* dof_pos = nullptr;     // (sum_n)
   bool factored = false;
@@ -471,22 +467,12 @@ struct alfi_level {
   int32_t *mult_items = nullptr, *mult_pred0 = nullptr, *mult_pred = nullptr, *mult_succ_ptr = nullptr, *mult_succ = nullptr;
   int32_t* mult_ctl = nullptr;          // [0] ticket counter (zeroed before every launch)
   int32_t* mult_rowtab = nullptr;       // (npatch, 64, 3) first block, block count, node of every patch node (zero-padded)
-  // FGMRES workspace
-  int kmax = 0;
-  int64_t ldv = 0;       // stride of V and Z: n rounded up to even (16-byte aligned basis vectors)
-  double* V = nullptr;   // (kmax+1) x ldv
-  double* Z = nullptr;   // kmax x n
-  double* w = nullptr;   // n
-  double* hs = nullptr;  // small device arrays: Hessenberg etc.
-  // alfi_smooth_fgmres_block: one such workspace per column slot in one allocation each, so that the Krylov vectors of the
-  // slots are the columns of a block operand -- v_j of slot s at blk_V + s * (blk_kmax + 1) * ldv + j * ldv, z_j at
-  // blk_Z + s * blk_kmax * ldv + j * ldv, w at blk_w + s * ldv, hs at blk_hs + s * HsLayout(blk_kmax).total
-  int blk_kmax = 0, blk_ws_slots = 0;
-  double *blk_V = nullptr, *blk_Z = nullptr, *blk_w = nullptr, *blk_hs = nullptr;
-  // reduction partials of the block fused iteration (kernels_block_fused.hip): blk_part_slots x block_partial_per_slot doubles,
-  // per slot what red_partial and red_partial2 are to one column; grown lazily, freed with the workspace above
-  double* blk_part = nullptr;
-  int blk_part_slots = 0;
+  // FGMRES workspaces (layout: KrylovWs, krylov_ws.h).  ws: the single call's, one slot; K grows only, and captured cycles hold
+  // its addresses, so no block call touches it.  blk_ws: one slot per column of a chunk (alfi_smooth_fgmres_block), with ws's K.
+  KrylovWs ws, blk_ws;
+  // reduction partials of the block fused iteration (kernels_block_fused.hip): block_partial_per_slot doubles per slot, what
+  // red_partial and red_partial2 are to one column
+  SlotBuf blk_part;
   // point-Jacobi level preconditioner (alfi_level_set_jacobi): replaces the patch solves in alfi_patch_apply and the smoothers
   bool jacobi = false;
   double* jac_diag = nullptr;        // (n) scalar diagonal of the operator, extracted from the diagonal blocks
@@ -500,9 +486,8 @@ struct alfi_level {
   double cinv_residual = -1.0;    // || A X e - e ||_inf of the inverse built by alfi_coarse_factor (-1: supplied by the caller)
   // multigrid work vectors (owned by alfi_mg but stored per level)
   double *mg_b = nullptr, *mg_x = nullptr, *mg_r = nullptr;
-  // the same for block cycles (alfi_mg_vcycle_block): blk_mg_slots columns of leading dimension n rounded up to even each
-  double *blk_mg_b = nullptr, *blk_mg_x = nullptr, *blk_mg_r = nullptr;
-  int blk_mg_slots = 0;
+  // the same for block cycles (alfi_mg_vcycle_block): one column of krylov_ldv(n) doubles per slot, grown together
+  SlotBuf blk_mg_b, blk_mg_x, blk_mg_r;
 };
 
 struct alfi_transfer {
@@ -582,17 +567,14 @@ struct alfi_saddle {
   int64_t n_loc = 0;          // local velocity dofs incl. ghost slots (the length of a level vector)
   double np_global = 0.0;     // pressure dofs of all ranks (mean removal)
   double *wa = nullptr, *wb = nullptr, *wc = nullptr;   // level vectors (n_loc)
-  // outer FGMRES workspace
-  int restart = 0;
-  int64_t ldv = 0;            // stride of V, Z: n rounded up to even
-  double *V = nullptr, *Z = nullptr, *w = nullptr, *hs = nullptr, *tmp_u = nullptr, *tmp_p = nullptr;
+  // outer FGMRES workspaces (KrylovWs, krylov_ws.h; K = restart, vectors of n_u + n_p entries): the single call's and the one of
+  // alfi_saddle_solve_block (a slot per column); both are allocated again whenever restart changes
+  KrylovWs ws, blk_ws;
+  double *tmp_u = nullptr, *tmp_p = nullptr;
   double* dotbuf = nullptr;   // result of alfi_saddle_dot (serial levels)
-  // block right-hand sides (alfi_saddle_solve_block): one outer workspace per column slot, each array ONE allocation -- v_j of
-  // slot s at blk_V + s * (blk_restart + 1) * ldv + j * ldv, z_j at blk_Z + s * blk_restart * ldv + j * ldv, w at
-  // blk_w + s * ldv, hs at blk_hs + s * HsLayout(blk_restart).total --, and blk_tmp_cols velocity work columns (leading
-  // dimension nu_dofs rounded up to even) for t = b_u - B^T y_p of alfi_saddle_precond_block, indexed by operand column
-  int blk_restart = 0, blk_slots = 0, blk_tmp_cols = 0;
-  double *blk_V = nullptr, *blk_Z = nullptr, *blk_w = nullptr, *blk_hs = nullptr, *blk_tmp_u = nullptr;
+  // alfi_saddle_precond_block: velocity work columns (krylov_ldv(nu_dofs) doubles each) for t = b_u - B^T y_p, indexed by
+  // operand column -- as many as the widest operand seen so far has, not a chunk's slots
+  SlotBuf blk_tmp_u;
   // fieldsplit_0 (alfi_saddle_set_velocity_solver): ALFI_VELOCITY_MG (the full cycle of mg) or ALFI_VELOCITY_DIRECT (multifrontal
   // factors of the finest operator, held here -- not in fine->mf, which is the coarse slot when the finest level is level 0)
   int vkind = 0;
@@ -641,7 +623,7 @@ int launch_cond_apply_block(alfi_level* lvl, const BlockCols& cols, const BlockC
 int launch_big_apply_block(alfi_level* lvl, const BlockCols& cols, const BlockCols& ocols, const double* X, int64_t ldx, double* Y,
                            int64_t ldy, double* stage);
 // The block form of the four-launch smoother iteration (kernels_block_fused.hip) on the first nc = 2 .. 4 slots of the level's
-// block workspace (blk_V, blk_Z, blk_w, blk_hs, blk_part; slot s belongs to column cols.c[s] of B and X).  Stage 1 from the
+// block workspace (blk_ws, blk_part; slot s belongs to column cols.c[s] of B and X).  Stage 1 from the
 // interleaved copy for the columns X + s * ldx into stage + s * lay.stage_len:
 int launch_patch_apply_il_block(alfi_level* lvl, int nc, const double* X, int64_t ldx, double* stage);
 // w_s = b_c and x_c = 0 (B != nullptr), then the |w_s|^2 partials, red_blocks_for(n) per slot, into the first partial set

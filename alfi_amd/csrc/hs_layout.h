@@ -1,9 +1,14 @@
 // Layout of the small per-level device array holding the FGMRES Hessenberg data (K = max iterations).
 #pragma once
+#ifdef __HIPCC__
+#define HS_LAYOUT_HD __host__ __device__
+#else               // a host compiler (krylov_ws.h in a stand-alone program): plain functions
+#define HS_LAYOUT_HD
+#endif
 struct HsLayout {
   int K;
   int beta, tt, cs, sn, grs, y, hd, total;
-  __host__ __device__ explicit HsLayout(int K_) : K(K_) {
+  HS_LAYOUT_HD explicit HsLayout(int K_) : K(K_) {
     beta = 0;                 // |r0|
     tt = 1;                   // current |w|
     cs = 8 + K * (K + 1);     // Givens cosines (K)
@@ -13,8 +18,9 @@ struct HsLayout {
     hd = y + K;               // CGS dot products of the current column (K+1)
     total = hd + K + 1;
   }
-  __host__ __device__ int H(int j) const { return 8 + j * (K + 1); }  // column j of the Hessenberg (K+1 entries)
+  HS_LAYOUT_HD int H(int j) const { return 8 + j * (K + 1); }  // column j of the Hessenberg (K+1 entries)
 };
+#undef HS_LAYOUT_HD
 
 #ifdef __HIPCC__
 // ---- one-thread pieces of the FGMRES smoother, used by the kernels of kernels_vec.hip -------------------------------

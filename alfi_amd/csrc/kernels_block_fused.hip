@@ -8,7 +8,7 @@
 // plain + where it has that.  What is loaded once for the columns: the interleaved small-patch inverses, the operator values,
 // colflag, rowptr, dof_ptr / dof_pos and the Dirichlet mask.
 //
-// Slot s of the level's block workspace (common.h: blk_V, blk_Z, blk_w, blk_hs, blk_part) belongs to column cols.c[s] of the
+// Slot s of the level's block workspace (common.h: blk_ws, blk_part) belongs to column cols.c[s] of the
 // caller's operands; only the first and the last kernel touch those.
 #include "common.h"
 #include "hs_layout.h"
@@ -395,7 +395,7 @@ __global__ __launch_bounds__(256) void multi_axpy_add_block_kernel(const double*
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// launch wrappers.  ws: the level's block workspace of nc slots (the caller has grown it); slot strides as in common.h
+// launch wrappers.  ws: the level's block workspace of nc slots (the caller has grown it); slot strides: KrylovWs, krylov_ws.h
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
 struct Slots {
@@ -405,24 +405,25 @@ struct Slots {
 };
 Slots slots_of(const alfi_level* L, int nc) {
   Slots S;
+  const KrylovWs& ws = L->blk_ws;
   S.nc = nc;
-  S.K = L->kmax;
+  S.K = ws.K;
   S.n = L->n;
-  S.ldv = L->ldv;
-  S.vs = (int64_t)(S.K + 1) * S.ldv;
-  S.zs = (int64_t)S.K * S.ldv;
-  S.hstride = HsLayout(S.K).total;
-  S.pstride = block_partial_per_slot(RED_BLOCKS, RED_MAXV);
-  S.V = L->blk_V;
-  S.Z = L->blk_Z;
-  S.w = L->blk_w;
-  S.hs = L->blk_hs;
-  S.part1 = L->blk_part;
-  S.part2 = L->blk_part + block_partial_set(RED_BLOCKS, RED_MAXV);
+  S.ldv = ws.ldv;
+  S.vs = ws.vs();
+  S.zs = ws.zs();
+  S.hstride = ws.hstride();
+  S.pstride = L->blk_part.per;
+  S.V = ws.V;
+  S.Z = ws.Z;
+  S.w = ws.w;
+  S.hs = ws.hs;
+  S.part1 = L->blk_part.p;
+  S.part2 = L->blk_part.p + block_partial_set(RED_BLOCKS, RED_MAXV);
   return S;
 }
 int check_slots(alfi_level* L, int nc) {
-  if (nc < 2 || nc > BLOCK_NV || nc > L->blk_ws_slots || nc > L->blk_part_slots || L->blk_kmax != L->kmax)
+  if (nc < 2 || nc > BLOCK_NV || nc > L->blk_ws.slots || nc > L->blk_part.slots || L->blk_ws.K != L->ws.K)
     return alfi_set_error(L->ctx, ALFI_E_STATE, "block fused iteration on %d columns without its workspace", nc);
   return 0;
 }
