@@ -48,6 +48,21 @@ ALFI_HD inline int cond_patch_waves(int max_pairs) {
 #endif
 }
 
+// The early-load form of cond_front_kernel (kernels_bigpatch.hip): a lane requests its tables and ALL columns of its row pair
+// of X or of B at kernel entry, ahead of the barriers they do not depend on.  A level takes it when a group's matrix fits one
+// batch of COND_AHEAD_M 16-byte loads per lane and every phase of every patch is one pass (a lane owns at most one row pair of
+// X / W and one of B).  Macro stars (groups of 45, thousands of pairs) keep the loops.
+#ifndef ALFI_COND_AHEAD           // A/B builds only (scripts/build_variant.sh): 0 compiles the dispatch without the early-load form
+#define ALFI_COND_AHEAD 1
+#endif
+constexpr int COND_AHEAD_M = 16;
+ALFI_HD inline bool cond_ahead(int max_m, int max_pairs) {
+  return ALFI_COND_AHEAD != 0 && max_m <= COND_AHEAD_M && max_pairs <= 64 * cond_patch_waves(max_pairs);
+}
+// Waves per patch of the early-load front kernel: the X pairs and the B pairs of a patch go to DIFFERENT waves (a wave holds one
+// matrix batch in registers, not two), whole waves each.
+ALFI_HD inline int cond_ahead_front_waves(int xpairs, int bpairs) { return (xpairs + 63) / 64 + (bpairs + 63) / 64; }
+
 // storage of one group's matrices in CondDev::mat: [X (m x m) | B (sc x m) | W (m x sc)], column-major each, the leading
 // dimensions rounded up to EVEN (a lane streams two rows of a column with one 16-byte load; the pad row is never stored)
 // (Measured and dropped, round 5: leading dimensions of > 8 rows rounded up to whole 128-byte lines and every group on a line

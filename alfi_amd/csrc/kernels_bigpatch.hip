@@ -934,8 +934,155 @@ __global__ __launch_bounds__(256) void cond_schur_kernel(int64_t p0, CondDev cd,
 // (sum_n doubles), the right-hand side through the patch's own staging slots (overwritten by the back kernel): 16 (n + s)
 // bytes of extra traffic per patch against megabytes of factors.
 
-template <bool NT, int COND_WAVES, int RU>
-__global__ __launch_bounds__(64 * COND_WAVES) void cond_front_kernel(int64_t p0, int64_t p1, CondDev cd,
+// ---- the early-load form of the front kernel (AHEAD; cond_ahead, cond_layout.h: groups of <= COND_AHEAD_M entries, every phase
+// one pass) ----
+// With 15 columns of 16 bytes per lane and phase, a workgroup's life in cond_front_kernel's loop form is a chain of dependent
+// memory round trips -- scalars, dofs, x, barrier, the pair's group, the group's arrays, two batches of X, barrier, the same for
+// B, barrier, s_uptr (13) -- and none of the table or matrix loads depends on data.  Here a lane requests, at kernel entry and
+// in three rounds (tables behind the scalars; x and the group's arrays; the matrix), every table entry it will need and ALL
+// columns of its row pair, and only then waits for x and the first barrier: loads return in order, so the wait for x does not
+// wait for the matrix.  The trip count is the compile-time COND_AHEAD_M with the loads predicated by k < kn: no wave maximum, no
+// dynamic loop; the padded columns contribute fma(0, 0, acc), which leaves acc (never -0: it starts at +0) as it is -- the sums
+// are those of cond_row2_dot to the bit.  Every early load has the predicate and the address of the load it replaces (a lane
+// without a pair reads no group array: the loop form reads those of the patch's first group and uses none of them).
+// Config 4 (profiles/cond_ahead_cfg4.txt): front 1289 -> 1156 us per launch on the finest level, 119.8 -> 117.3 ms per cycle.
+// Measured and dropped there: the same for cond_back_kernel.  With 16 columns of W ahead (126 VGPRs, 4 waves per SIMD against
+// 5) the launch took 834 against 807 us; with 8 ahead (92 VGPRs, 5 waves) the cycle was 0.3 ms of 113 below the front-only
+// form in a job whose first runs were 4.7 ms above its later ones: not told from the noise.
+// A columns of a row pair requested ...
+template <bool NT, int A>
+__device__ __forceinline__ void cond_row2_request(const double* __restrict__ M, int ld, int kn, big_d2 (&a)[A]) {
+#pragma unroll
+  for (int u = 0; u < A; ++u) {
+    const big_d2* q = reinterpret_cast<const big_d2*>(M + (int64_t)u * ld);
+    const big_d2 z = {0.0, 0.0};
+    a[u] = (u < kn) ? (NT ? __builtin_nontemporal_load(q) : *q) : z;
+  }
+}
+// ... and their part of the product (k ascending, as cond_row2_dot)
+template <int A>
+__device__ __forceinline__ void cond_row2_sum(const big_d2 (&a)[A], int kn, const double* __restrict__ v, double& acc0,
+                                              double& acc1) {
+#pragma unroll
+  for (int u = 0; u < A; ++u) {
+    const double vk = (u < kn) ? v[u] : 0.0;
+    acc0 = __builtin_fma(a[u].x, vk, acc0);
+    acc1 = __builtin_fma(a[u].y, vk, acc1);
+  }
+}
+
+// The requests of one round are issued together and waited for together: cond_arrived(v) after a round is where the kernel
+// waits for v.  (No instruction: an empty asm statement that takes v in a register.  Without it the compiler moves the address
+// arithmetic that uses a predicated load's result into the load's branch and waits there, one round trip per table entry.)
+template <typename T>
+__device__ __forceinline__ void cond_arrived(T& v) {
+  asm volatile("" : "+v"(v));
+}
+
+// front: blockDim.x = 64 x (waves of X pairs + waves of B pairs) of the level's widest patch (CondPlan::front_waves).  The X
+// pairs of a patch take its first ceil(nxp / 64) waves, the B pairs the waves after them: a wave holds ONE batch of
+// COND_AHEAD_M columns (64 VGPRs), the branch between the two is wave-uniform.
+template <bool NT>
+__device__ __forceinline__ void cond_front_ahead(int64_t p, const CondDev& cd, const int64_t* __restrict__ patch_ptr,
+                                                 const int64_t* __restrict__ stage_ptr, const double* __restrict__ x,
+                                                 double* __restrict__ stage, double* __restrict__ smem) {
+  const int NT_ = (int)blockDim.x, tid = (int)threadIdx.x;
+  const int64_t off = patch_ptr[p];
+  const int n = (int)(patch_ptr[p + 1] - off);
+  const int nI = cd.p_nI[p];
+  const int s = n - nI;
+  const int64_t uo0 = cd.uptr[p];
+  const int64_t xp0 = cd.xp_ptr[p], bp0 = cd.bp_ptr[p];
+  const int nxp = (int)(cd.xp_ptr[p + 1] - xp0), nbp = (int)(cd.bp_ptr[p + 1] - bp0);
+  const int64_t srow0 = cd.sptr[p];
+  double* rhs = stage + stage_ptr[p] + nI;
+  double* xs = smem;                // n
+  double* ts = xs + n;              // nI
+  double* us = ts + nI;             // u buffer, in the order the right-hand side sums it (u_dst)
+  double* tmp = cd.tmp + off;
+  const int xw = (nxp + 63) >> 6;                     // waves of X pairs
+  const bool isx = (tid >> 6) < xw;                   // wave-uniform
+  const int q = isx ? tid : tid - 64 * xw;
+  const bool act = isx ? q < nxp : q < nbp;
+  const bool bact = act && !isx;
+  // round 1: tables that depend on the scalars alone
+  int32_t d[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) d[u] = (tid + u * NT_ < n) ? cd.dofs[off + tid + u * NT_] : 0;
+  const int32_t* pgrp = isx ? cd.xp_grp + xp0 : cd.bp_grp + bp0;     // (one load either way)
+  int32_t g = act ? pgrp[q] : 0;
+  const int32_t qb = cd.s_uptr[srow0];
+  const int32_t su0 = tid < s ? cd.s_uptr[srow0 + tid] : 0, su1 = tid < s ? cd.s_uptr[srow0 + tid + 1] : 0;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) cond_arrived(d[u]);
+  cond_arrived(g);
+  // round 2: x and the arrays of the lane's group
+  double v[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) v[u] = (tid + u * NT_ < n) ? x[d[u]] : 0.0;
+  int32_t m = act ? cd.g_m[g] : 0, o = act ? cd.g_off[g] : 0;
+  const int32_t* g_pr = isx ? cd.g_xp : cd.g_bp;
+  int32_t pr = act ? g_pr[g] : 0;                                    // first pair of the group
+  int64_t mat = act ? cd.g_mat[g] : 0;
+  int32_t sc = bact ? cd.g_sc[g] : 0, uoff = bact ? cd.g_uoff[g] : 0;
+  cond_arrived(m);
+  cond_arrived(o);
+  cond_arrived(pr);
+  cond_arrived(mat);
+  cond_arrived(sc);
+  cond_arrived(uoff);
+  // round 3: the whole row pair (r: its first row -- i in X, j in B)
+  const int r = 2 * (q - pr);
+  const int ld = isx ? cond_ldim(m) : cond_ldim(sc);
+  const double* M = cd.mat + mat + (isx ? 0 : (int64_t)cond_ldim(m) * m) + r;
+  const int64_t ue = uo0 + uoff + r;
+  big_d2 a[COND_AHEAD_M];
+  cond_row2_request<NT, COND_AHEAD_M>(M, ld, m, a);
+  const int32_t d0 = bact ? cd.u_dst[ue] : 0, d1 = (bact && r + 1 < sc) ? cd.u_dst[ue + 1] : 0;
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    if (tid + u * NT_ < n) xs[tid + u * NT_] = v[u];
+  for (int i = tid + 4 * NT_; i < n; i += NT_) xs[i] = x[cd.dofs[off + i]];
+  __syncthreads();
+  if (isx) {                                          // t = X x
+    double t0 = 0.0, t1 = 0.0;
+    cond_row2_sum<COND_AHEAD_M>(a, m, xs + o, t0, t1);
+    if (act) {
+      ts[o + r] = t0;
+      tmp[o + r] = t0;
+      if (r + 1 < m) {
+        ts[o + r + 1] = t1;
+        tmp[o + r + 1] = t1;
+      }
+    }
+  }
+  __syncthreads();
+  if (!isx) {                                         // u = B t
+    double u0 = 0.0, u1 = 0.0;
+    cond_row2_sum<COND_AHEAD_M>(a, m, ts + o, u0, u1);
+    if (act) {
+      us[d0] = u0;
+      if (r + 1 < sc) us[d1] = u1;
+    }
+  }
+  __syncthreads();
+  // right-hand side of the Schur system: the contributions to a row are adjacent in us, summed in ascending order
+  if (tid < s) {
+    double acc = xs[nI + tid];
+    for (int32_t k = su0 - qb; k < su1 - qb; ++k) acc -= us[k];
+    rhs[tid] = acc;
+  }
+  for (int i = tid + NT_; i < s; i += NT_) {
+    double acc = xs[nI + i];
+    const int32_t qe = cd.s_uptr[srow0 + i + 1] - qb;
+    for (int32_t k = cd.s_uptr[srow0 + i] - qb; k < qe; ++k) acc -= us[k];
+    rhs[i] = acc;
+  }
+}
+
+// AHEAD: the early-load form above (its workgroup is up to 2 COND_WAVES waves: X and B pairs in different waves)
+template <bool NT, int COND_WAVES, int RU, bool AHEAD = false>
+__global__ __launch_bounds__(64 * COND_WAVES * (AHEAD ? 2 : 1)) void cond_front_kernel(int64_t p0, int64_t p1, CondDev cd,
                                                                      const int64_t* __restrict__ patch_ptr,
                                                                      const int64_t* __restrict__ stage_ptr,
                                                                      const double* __restrict__ x, double* __restrict__ stage,
@@ -944,6 +1091,10 @@ __global__ __launch_bounds__(64 * COND_WAVES) void cond_front_kernel(int64_t p0,
   constexpr int NT_ = 64 * COND_WAVES;
   if (p0 + blockIdx.x >= p1) return;
   const int64_t p = ordered ? cd.order[blockIdx.x] : p0 + blockIdx.x;
+  if constexpr (AHEAD) {
+    cond_front_ahead<NT>(p, cd, patch_ptr, stage_ptr, x, stage, cond_dsmem);
+    return;
+  }
   const int64_t off = patch_ptr[p];
   const int n = (int)(patch_ptr[p + 1] - off);
   const int nI = cd.p_nI[p];
@@ -1610,9 +1761,11 @@ int launch_cond_schur_one(alfi_level* L, int64_t p, const int64_t* d_zero, doubl
 //     chunks of <= 8 consecutive groups per workgroup, one descriptor per workgroup, a lane's row pair decoded in the kernel, the
 //     Schur right-hand side formed by the sigma workgroups (cond_gfront / cond_gsigma / cond_gback): front + back 48 -> 39 us
 //     against a workgroup per patch there;
-//   * larger launches (the finest levels): a workgroup of 8 waves per patch (cond_front / cond_sigma / cond_back).  The chunked
-//     form on config 5's finest level, same box: 25.1 against 24.6 ms per cycle (round 4, with the decoded descriptors; round
-//     3 with a descriptor per lane: 338 against 326 us).
+//   * larger launches (the finest levels): a workgroup per patch, its waves from cond_patch_waves (cond_front / cond_sigma /
+//     cond_back).  The chunked form on config 5's finest level, same box: 25.1 against 24.6 ms per cycle (round 4, with the
+//     decoded descriptors; round 3 with a descriptor per lane: 338 against 326 us).  Levels of small groups (cond_ahead,
+//     cond_layout.h: config 4's vertex stars) take the front kernel's early-load form: tables and the whole row pair requested
+//     at kernel entry, X and B pairs in different waves.
 // The sigma launch takes chunks of <= 64 rows (COND_SIGMA_ROWS; 256 in round 3: config 5 24.8 -> 24.1 ms per cycle, the apply
 // from 0.70 to 0.73 of the HBM roofline, profiles/r04_ab_cond_cfg5.txt).
 // Measured and dropped (rounds 2-3, profiles/r03_cond_apply_ab_cfg5.txt): the whole apply as ONE launch per patch (941 against
@@ -1649,13 +1802,13 @@ int launch_cond_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double*
   }
   const size_t lds_f = (size_t)L->cplan.lds_front, lds_s = (size_t)(L->cplan.max_s + 2) * sizeof(double);
   const size_t lds_b = (size_t)L->cplan.lds_back;
-#define ALFI_COND_LAUNCH3(WV)                                                                                             \
+#define ALFI_COND_LAUNCH3(WV, AH, FW)                                                                                     \
   do {                                                                                                                    \
     if (lds_f > 64 * 1024)                                                                                                \
-      ALFI_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&cond_front_kernel<false, WV, 8>),            \
+      ALFI_HIP_CHECK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&cond_front_kernel<false, WV, 8, AH>),        \
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));                   \
-    hipLaunchKernelGGL((cond_front_kernel<false, WV, 8>), dim3(grid.x), dim3(64 * WV), lds_f, ctx->stream, p0, p1, L->cd, \
-                       L->patch_ptr, L->stage_ptr, x, L->stage, ordered);                                                 \
+    hipLaunchKernelGGL((cond_front_kernel<false, WV, 8, AH>), dim3(grid.x), dim3(64 * (FW)), lds_f, ctx->stream, p0, p1,  \
+                       L->cd, L->patch_ptr, L->stage_ptr, x, L->stage, ordered);                                          \
     if (c1 > c0)                                                                                                          \
       hipLaunchKernelGGL((cond_sigma_kernel<true>), dim3((unsigned)(c1 - c0)), dim3(256), lds_s, ctx->stream, c0, L->cd,  \
                          L->patch_ptr, L->stage_ptr, L->stage);                                                           \
@@ -1668,16 +1821,31 @@ int launch_cond_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double*
   // Waves per patch: a lane owns one row pair per phase, so a workgroup wider than the patch's row pairs is idle lanes.  Macro
   // stars (config 5: > 1000 pairs of X / W) keep 8 waves; condensed vertex stars ([P2+FB]^3: 48 pairs of X / W, 84 of B) take
   // 2 (128 lanes: one pass per phase), tiny patch sets 1.
+  // Levels of small groups whose phases are one pass (cond_ahead, cond_layout.h: the vertex stars, not the macro stars) take
+  // the early-load form of the front kernel; its workgroup has the X and the B pairs in different waves (3 for a star).
+#if ALFI_COND_AHEAD
+#define ALFI_COND_LAUNCH3_W(WV)                                  \
+  do {                                                           \
+    if (ahead)                                                   \
+      ALFI_COND_LAUNCH3(WV, true, L->cplan.front_waves);         \
+    else                                                         \
+      ALFI_COND_LAUNCH3(WV, false, WV);                          \
+  } while (0)
+  const bool ahead = cond_ahead(L->cplan.max_m, L->cplan.max_pairs);
+#else
+#define ALFI_COND_LAUNCH3_W(WV) ALFI_COND_LAUNCH3(WV, false, WV)
+#endif
 #ifdef ALFI_COND_WAVES_FORCE      // A/B builds only (scripts/build_variant.sh): every launch with this many waves per patch
-  ALFI_COND_LAUNCH3(ALFI_COND_WAVES_FORCE);
+  ALFI_COND_LAUNCH3_W(ALFI_COND_WAVES_FORCE);
 #else
   switch (cond_patch_waves(L->cplan.max_pairs)) {       // (cond_layout.h; the block apply asks the same function)
-    case 1: ALFI_COND_LAUNCH3(1); break;
-    case 2: ALFI_COND_LAUNCH3(2); break;
-    case 4: ALFI_COND_LAUNCH3(4); break;
-    default: ALFI_COND_LAUNCH3(8); break;
+    case 1: ALFI_COND_LAUNCH3_W(1); break;
+    case 2: ALFI_COND_LAUNCH3_W(2); break;
+    case 4: ALFI_COND_LAUNCH3_W(4); break;
+    default: ALFI_COND_LAUNCH3_W(8); break;
   }
 #endif
+#undef ALFI_COND_LAUNCH3_W
 #undef ALFI_COND_LAUNCH3
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   return 0;
