@@ -109,6 +109,7 @@ int alfi_level_set_partition(alfi_level* L, int64_t nb_owned, int distributed, i
   L->A_own.nbrows = nb_owned;
   L->A_own.nnzb = nnz_own;
   if (L->A.aligned) L->A_own.nchunks = nchunks_own;
+  L->A_own.cut = L->A.flat && !L->A.aligned && nnz_own < L->A.nnzb;
   return 0;
 }
 

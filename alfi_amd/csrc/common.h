@@ -193,6 +193,8 @@ struct DevBSR {
   int flat = 0;
   int64_t kbase = 0;            // first block of a block-row-range view (flat layout; 0 for the upload itself)
   bool view = false;            // a row-range view: rows outside the range are not touched
+  bool cut = false;             // equal chunks of the upload cut to the owned rows (kbase 0, fewer blocks than the upload): block
+                                // nnzb exists and starts the first ghost row (bsr_spmv_flat_kernel / _dedup_kernel: CUT)
   int64_t nchunks = 0;
   int32_t* chunk_row = nullptr;
   double* carry = nullptr;      // (nchunks, bs): partial sums of block rows that continue into the next chunk

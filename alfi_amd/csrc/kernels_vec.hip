@@ -62,7 +62,13 @@ typedef double spmv_d2 __attribute__((ext_vector_type(2)));
 // ALIGNED (small matrices, where a cycle is bound by the number of dependent launches rather than by bandwidth): the chunks
 // hold whole block rows -- chunk c = blocks [chunk_start[c], chunk_start[c + 1]), at most SPMV_CHUNK of them -- so no row
 // continues into the next chunk and the fix-up launch disappears.
-template <int BS, bool NT, bool ALIGNED>
+// CUT (equal chunks only; DevBSR::cut): the range ends in front of a block row of the upload -- the owned rows of a partitioned
+// level.  The lane of the first block past the range reads that block's row-start flag (and nothing else of it), so that the last
+// row of the range is closed by the lane of its last block, as in the product of the whole upload: the owned rows of a
+// partitioned level are the rows of the unpartitioned product BIT FOR BIT.  Without it the sum would travel on to lane 63 through
+// the idle lanes and be rounded in another order.  The row of the chunk's last lane is then the one past the range: the closing
+// store is left out.  CUT = false is the kernel as it was.
+template <int BS, bool NT, bool ALIGNED, bool CUT = false>
 __global__ __launch_bounds__(256) void bsr_spmv_flat_kernel(int64_t kbase, int64_t nnzb, int64_t nchunks,
                                                              const int64_t* __restrict__ chunk_start,
                                                              const int32_t* __restrict__ colflag,
@@ -107,7 +113,8 @@ __global__ __launch_bounds__(256) void bsr_spmv_flat_kernel(int64_t kbase, int64
     if (ALIGNED && base + u * 64 >= kend_all) break;     // wave-uniform: the chunk is shorter than SPMV_CHUNK
     const int64_t k = base + u * 64 + lane;
     const bool valid = k < kend_all;
-    const int32_t cf = valid ? (NT ? __builtin_nontemporal_load(colflag + k) : colflag[k]) : 0;
+    const bool flagged = valid || (CUT && k == kend_all);
+    const int32_t cf = flagged ? (NT ? __builtin_nontemporal_load(colflag + k) : colflag[k]) : 0;
     const bool head = cf < 0;
     const int64_t col = cf & 0x7fffffff;
     double p[BS];
@@ -174,7 +181,7 @@ __global__ __launch_bounds__(256) void bsr_spmv_flat_kernel(int64_t kbase, int64
   if (lane == 0) {
     const bool closed = kend >= kend_all || colflag[kend] < 0;
     if (closed) {
-      store_row(Rlast, carry);
+      if (!CUT || kend <= kend_all) store_row(Rlast, carry);
       carry_row[chunk] = -1;
     } else {
 #pragma unroll
@@ -210,7 +217,8 @@ __global__ __launch_bounds__(256) void bsr_spmv_fixup_kernel(int64_t nchunks, co
 // waves then take x from LDS through a 2-byte local index (bit 15 = first block of a block row; 2 + ~1 bytes of index
 // stream per block instead of 4).  Everything else (lane-major value planes, segmented scan, carries, fix-up) as above.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int BS>
+// CUT: as in bsr_spmv_flat_kernel.
+template <int BS, bool CUT = false>
 __global__ __launch_bounds__(256) void bsr_spmv_dedup_kernel(int64_t nnzb, int64_t nchunks,
                                                               const uint16_t* __restrict__ lidx,
                                                               const int32_t* __restrict__ ucol,
@@ -268,7 +276,8 @@ __global__ __launch_bounds__(256) void bsr_spmv_dedup_kernel(int64_t nnzb, int64
   for (int u = 0; u < SPMV_U; ++u) {
     const int64_t k = base + u * 64 + lane;
     const bool valid = k < nnzb;
-    const uint16_t li = valid ? __builtin_nontemporal_load(lidx + k) : (uint16_t)0;
+    const bool flagged = valid || (CUT && k == nnzb);
+    const uint16_t li = flagged ? __builtin_nontemporal_load(lidx + k) : (uint16_t)0;
     const bool head = (li & 0x8000u) != 0;
     const int lc = li & 0x7fff;
     double p[BS];
@@ -323,7 +332,7 @@ __global__ __launch_bounds__(256) void bsr_spmv_dedup_kernel(int64_t nnzb, int64
   if (lane == 0) {
     const bool closed = kend >= nnzb || colflag[kend] < 0;
     if (closed) {
-      store_row(Rlast, carry);
+      if (!CUT || kend <= nnzb) store_row(Rlast, carry);
       carry_row[chunk] = -1;
     } else {
 #pragma unroll
@@ -523,10 +532,18 @@ static int launch_bsr_spmv_bs(alfi_ctx* ctx, const DevBSR& A, const double* x, d
       return 0;
     }
     const int64_t nchunks = (A.nnzb + SPMV_CHUNK - 1) / SPMV_CHUNK;   // A may be a block-row-range view of the upload
-    if (A.dedup && !A.view && A.kbase == 0)
+    const bool dedup = A.dedup && !A.view && A.kbase == 0;
+    const dim3 grid((unsigned)((nchunks + 3) / 4)), block(256);
+    if (dedup && A.cut)       // the owned rows of a partitioned level: blocks of the upload follow the range
+      hipLaunchKernelGGL((bsr_spmv_dedup_kernel<BS, true>), grid, block, 0, ctx->stream, A.nnzb, nchunks, A.lidx, A.ucol, A.uptr,
+                         A.colidx, A.vals, A.chunk_row, x, y, b, alpha, mode, A.carry, A.carry_row, xcd);
+    else if (dedup)
       hipLaunchKernelGGL((bsr_spmv_dedup_kernel<BS>), dim3((unsigned)((nchunks + 3) / 4)), dim3(256), 0, ctx->stream,
                          A.nnzb, nchunks, A.lidx, A.ucol, A.uptr, A.colidx, A.vals, A.chunk_row, x, y, b, alpha, mode,
                          A.carry, A.carry_row, xcd);
+    else if (A.cut)
+      hipLaunchKernelGGL((bsr_spmv_flat_kernel<BS, true, false, true>), grid, block, 0, ctx->stream, A.kbase, A.nnzb, nchunks,
+                         (const int64_t*)nullptr, A.colidx, A.vals, A.chunk_row, x, y, b, alpha, mode, A.carry, A.carry_row, xcd);
     else
       hipLaunchKernelGGL((bsr_spmv_flat_kernel<BS, true, false>), dim3((unsigned)((nchunks + 3) / 4)), dim3(256), 0,
                          ctx->stream, A.kbase, A.nnzb, nchunks, (const int64_t*)nullptr, A.colidx, A.vals, A.chunk_row, x,
