@@ -94,6 +94,42 @@ __device__ __forceinline__ void big_block_finish(const big_d2 (&v)[BIG_U], int n
   if (2 * l + 1 < lim) out[2 * l + 1] = acc1;
 }
 
+// The same two halves for a kernel that holds SEVERAL small blocks of a wave's rows in one array of BIG_U loads
+// (cond_tail_kernel, kernels_bigpatch.hip: blocks of 8, 4 and 2 rows over <= 64 columns are 4 + 2 + 1 loads).  A block whose
+// columns fit U <= BIG_U loads per lane, n <= U * 64 / (R / 2): the loads into v[0 .. U), the sums those of big_block_finish
+// (the loads it would skip are not there).  u0: the request is for the loads u0 .. u0 + U - 1 of big_block_prefetch (a block
+// requested in several calls).
+template <bool NT, int U>
+__device__ __forceinline__ void big_part_prefetch(const double* __restrict__ Tp, int P, int n, int lg, int lane, int u0,
+                                                  big_d2* v) {
+  const int C = 64 >> lg, cg = lane >> lg, l = lane & ((1 << lg) - 1);
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const big_d2 z = {0.0, 0.0};
+    v[u] = cg + (u0 + u) * C < n ? piece_load<double, NT>(Tp + 2 * l + (int64_t)(cg + (u0 + u) * C) * P) : z;
+  }
+}
+template <int U>
+__device__ __forceinline__ void big_part_finish(const big_d2* v, int n, int lg, const double* __restrict__ xs, int lane,
+                                                 double* __restrict__ out, int lim) {
+  const int G = 1 << lg, C = 64 >> lg, cg = lane >> lg, l = lane & (G - 1);
+  double acc0 = 0.0, acc1 = 0.0;
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (cg + u * C < n) {
+      const double xj = xs[cg + u * C];
+      acc0 = __builtin_fma(v[u].x, xj, acc0);
+      acc1 = __builtin_fma(v[u].y, xj, acc1);
+    }
+  for (int o = G; o < 64; o <<= 1) {
+    acc0 += __shfl_xor(acc0, o);
+    acc1 += __shfl_xor(acc1, o);
+  }
+  if (cg != 0) return;
+  if (2 * l < lim) out[2 * l] = acc0;
+  if (2 * l + 1 < lim) out[2 * l + 1] = acc1;
+}
+
 // The small matrices of a group are streamed with COND_U loads in flight per lane (they are read once).
 constexpr int COND_U = 8;
 

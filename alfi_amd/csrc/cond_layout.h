@@ -63,6 +63,23 @@ ALFI_HD inline bool cond_ahead(int max_m, int max_pairs) {
 // matrix batch in registers, not two), whole waves each.
 ALFI_HD inline int cond_ahead_front_waves(int xpairs, int bpairs) { return (xpairs + 63) / 64 + (bpairs + 63) / 64; }
 
+// The tail launch of the workgroup-per-patch form (cond_tail_kernel, kernels_bigpatch.hip): y_S = inv(Sigma) rhs and the back
+// substitution of a patch in ONE workgroup of 256 threads, y_S through LDS.  A row pair of W belongs to four adjacent lanes, a
+// quarter of COND_TAIL_QUARTER columns each, all requested at kernel entry with the wave's block of inv(Sigma).  A level takes
+// it when every patch has a lane quartet per row pair of X / W (max_xpairs), every group's W fits the four quarters (max_sc:
+// most coupled skeleton entries of one group) and every skeleton is one chunk of the sigma launch (max_s).  Macro stars
+// (hundreds of pairs, skeletons of hundreds of rows) keep cond_sigma + cond_back.
+#ifndef ALFI_COND_TAIL            // A/B builds only (scripts/build_variant.sh): 0 compiles the dispatch without the tail launch
+#define ALFI_COND_TAIL 1
+#endif
+constexpr int COND_TAIL_THREADS = 256;
+constexpr int COND_TAIL_QUARTER = 8;      // (= COND_U, cond_apply.h: one batch of 16-byte loads per lane)
+constexpr int COND_TAIL_S = 64;           // 16 rows of inv(Sigma) per wave, held whole in one batch of loads
+ALFI_HD inline bool cond_tail(int max_xpairs, int max_sc, int max_s) {
+  return ALFI_COND_TAIL != 0 && 4 * max_xpairs <= COND_TAIL_THREADS && max_sc <= 4 * COND_TAIL_QUARTER &&
+         max_s <= COND_SIGMA_ROWS && max_s <= COND_TAIL_S;
+}
+
 // storage of one group's matrices in CondDev::mat: [X (m x m) | B (sc x m) | W (m x sc)], column-major each, the leading
 // dimensions rounded up to EVEN (a lane streams two rows of a column with one 16-byte load; the pad row is never stored)
 // (Measured and dropped, round 5: leading dimensions of > 8 rows rounded up to whole 128-byte lines and every group on a line

@@ -629,7 +629,8 @@ int launch_big_apply_arrays(alfi_ctx* ctx, int64_t npatch, int max_np, const int
 // ---------------------------------------------------------------------------------------------------------------------
 // 4. Condensed patch factors (CondDev, common.h): setup = fill (operator entries into the group matrices and the Schur
 //    scratch), group step (X_g = inv(A_gg), W_g = X_g A[g, S_g]), Schur step (Sigma -= B_g W_g), blocked inversion of
-//    Sigma by the kernels above; apply = three launches (cond_front / cond_sigma / cond_back below).
+//    Sigma by the kernels above; apply = three launches (cond_front / cond_sigma / cond_back below), two on vertex-star
+//    levels (cond_front / cond_tail).
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int COND_GMAX = 64;     // a group / its coupled skeleton set holds at most 64 entries (a lane per row)
 
@@ -1257,6 +1258,148 @@ __global__ __launch_bounds__(64 * COND_WAVES) void cond_back_kernel(int64_t p0, 
   for (int i = threadIdx.x; i < s; i += NT_) out[cd.slot[off + nI + i]] = ys[i];
 }
 
+// ---- the tail launch (cond_tail, cond_layout.h: vertex stars -- every patch <= 64 row pairs of X / W, groups coupled to <= 32
+// skeleton entries, a skeleton of <= 64: one sigma chunk per patch) ----
+// cond_sigma_kernel and cond_back_kernel as ONE launch of 256 threads per patch: y_S stays in LDS (the skeleton part of cd.tmp
+// is neither written nor read), and nothing the back phase streams waits behind the Schur solve.  At kernel entry a wave
+// requests ALL of its 16 rows of inv(Sigma) (cond_sigma_kernel: the first block, the rest by big_rows after its barrier), and a
+// QUARTET of adjacent lanes owns a row pair of W: lane r of the four requests columns 8 r .. 8 r + 7, one batch of COND_U
+// predicated loads, so all of W (<= 32 columns) is in flight from the start; the quartet's tables, t_g and the staging slots are
+// requested in the same three rounds (cond_arrived, as the front kernel's).  90 VGPRs, 5 waves per SIMD, no scratch.
+// The sums are the parent's: inv(Sigma) in the blocks and with the wave shares of cond_sigma_kernel (big_block_finish /
+// big_part_finish); a row pair's W sum is ONE chain, k ascending, that travels through the quartet (cond_row2_relay).  The
+// zero-padded columns up to 32 add fma(0, 0, acc), as cond_row2_dot's do up to the wave maximum.
+// Config 4 (profiles/cond_tail_cfg4.txt): sigma + back 1690 -> 1619 us per apply on the finest level, 233 -> 193 us on level 2;
+// 112.5 -> 107.8 ms per cycle.
+// a quartet's chain: every lane continues the sum it is handed with its own columns, lane r's result is what lane r + 1 starts
+// from (the other lanes' results of a round are discarded), the last round's is the row pair's sum
+__device__ __forceinline__ void cond_row2_relay(const big_d2 (&a)[COND_U], int k0, int kn, const double* __restrict__ v,
+                                                double& acc0, double& acc1) {
+  double vk[COND_U];
+#pragma unroll
+  for (int u = 0; u < COND_U; ++u) vk[u] = (k0 + u < kn) ? v[k0 + u] : 0.0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    double s0 = acc0, s1 = acc1;
+#pragma unroll
+    for (int u = 0; u < COND_U; ++u) {
+      s0 = __builtin_fma(a[u].x, vk[u], s0);
+      s1 = __builtin_fma(a[u].y, vk[u], s1);
+    }
+    acc0 = __shfl(s0, r, 4);
+    acc1 = __shfl(s1, r, 4);
+  }
+}
+
+// NTS / NTM: nontemporal loads of inv(Sigma) / of W (cond_sigma_kernel<true>, cond_back_kernel<false>: the launches it replaces)
+template <bool NTS, bool NTM>
+__global__ __launch_bounds__(COND_TAIL_THREADS) void cond_tail_kernel(int64_t p0, int64_t p1, CondDev cd,
+                                                                     const int64_t* __restrict__ patch_ptr,
+                                                                     const int64_t* __restrict__ stage_ptr,
+                                                                     double* __restrict__ stage, int ordered) {
+  extern __shared__ double cond_dsmem[];
+  constexpr int NT_ = COND_TAIL_THREADS;
+  static_assert(COND_TAIL_QUARTER == COND_U, "a quarter of a row pair is one batch of loads");
+  static_assert(COND_TAIL_S == 4 * 16 && BIG_U == 8, "a wave holds its 16 rows of <= 64 columns in one batch of loads");
+  if (p0 + blockIdx.x >= p1) return;
+  const int tid = (int)threadIdx.x;
+  const int64_t p = ordered ? cd.order[blockIdx.x] : p0 + blockIdx.x;
+  const int64_t off = patch_ptr[p];
+  const int n = (int)(patch_ptr[p + 1] - off);
+  const int nI = cd.p_nI[p];
+  const int s = n - nI;
+  const int uo = (int)(cd.uptr[p + 1] - cd.uptr[p]);
+  const int32_t* si = cd.sidx + (uo > 0 ? cd.g_sidx[cd.gptr[p]] : 0);      // the positions S_g of all groups (adjacent in sidx)
+  const int64_t xp0 = cd.xp_ptr[p];
+  const int nxp = (int)(cd.xp_ptr[p + 1] - xp0);
+  double* out = stage + stage_ptr[p];
+  double* rs = cond_dsmem;          // s: the Schur right-hand side (the front kernel left it in the staging slots)
+  double* ys = rs + s;              // s
+  double* yg = ys + s;              // uo: y_S[S_g], group after group (the layout of the u buffer)
+  const double* tmp = cd.tmp + off;
+  // the wave's rows of inv(Sigma), [a, a + nr): the shares of cond_sigma_kernel's only chunk of the patch (s <= 64: 16 rows per
+  // wave).  They are ONE block of 16 rows or, in the last, partial 16 of ld, its binary digits: stored pieces of 8, 4 and 2
+  // rows -- over <= 64 columns 4 + 2 + 1 loads per lane, so the whole share is requested at entry either way.  (The blocks are
+  // those of big_block for these ranges, written out: its loops would stand between the requests.  cond_sigma_kernel walks the
+  // blocks behind the first with big_rows after its barrier: the same blocks, the same sums.)
+  const int ld = (s + 1) & ~1;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;     // (scalar: the branches below are uniform)
+  const int a = 16 * wave, nr = max(0, min(ld - a, 16));
+  const double* T = cd.sinv + cd.sinv_ptr[p];
+  // a whole 16: inside the piece of 64 (ld = 64), of 32 (rows below 32 when ld has one) or the piece of 16 itself
+  const int P16 = ld == 64 ? 64 : ((ld & 32) && a < 32) ? 32 : 16, row16 = P16 == 16 ? a : 0;
+  const int r8 = a, r4 = r8 + (nr & 8), r2 = r4 + (nr & 4);                       // first rows of the partial 16's pieces
+  // the quartet's row pair
+  const int q = tid >> 2, k0 = COND_U * (tid & 3);
+  const bool act = q < nxp, last = act && (tid & 3) == 3;    // (the quartet's last lane stores)
+  // round 1: what depends on the scalars alone -- the pair's group, the right-hand side, the skeleton's slots (s <= 64: a
+  // lane has at most one entry), the positions S_g, the rows of inv(Sigma)
+  int32_t g = act ? cd.xp_grp[xp0 + q] : 0;
+  double rv = tid < s ? out[nI + tid] : 0.0;
+  int32_t ssl = tid < s ? cd.slot[off + nI + tid] : 0;
+  int32_t sq[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) sq[u] = (tid + u * NT_ < uo) ? si[tid + u * NT_] : 0;
+  big_d2 sv[BIG_U];
+  // ONE sequence of eight requests for both cases (a branch between them makes the second one wait for round 1: its loads
+  // reuse the registers of the first's): the loads 0-3 | 4-5 | 6 | 7 of big_block_prefetch for the block of 16, or the pieces
+  // of 8 | 4 | 2 rows | nothing (a piece the wave does not have: no columns, no loads)
+  const bool full = nr == 16;
+  const double* T16 = T + (int64_t)row16 * s + (a - row16);
+  big_part_prefetch<NTS, 4>(full ? T16 : T + (int64_t)r8 * s, full ? P16 : 8, (full || (nr & 8)) ? s : 0, full ? 3 : 2, lane,
+                            0, sv);
+  big_part_prefetch<NTS, 2>(full ? T16 : T + (int64_t)r4 * s, full ? P16 : 4, (full || (nr & 4)) ? s : 0, full ? 3 : 1, lane,
+                            full ? 4 : 0, sv + 4);
+  big_part_prefetch<NTS, 1>(full ? T16 : T + (int64_t)r2 * s, full ? P16 : 2, (full || (nr & 2)) ? s : 0, full ? 3 : 0, lane,
+                            full ? 6 : 0, sv + 6);
+  big_part_prefetch<NTS, 1>(T16, P16, full ? s : 0, 3, lane, 7, sv + 7);
+  cond_arrived(g);
+  // round 2: the arrays of the pair's group
+  int32_t m = act ? cd.g_m[g] : 0, sc = act ? cd.g_sc[g] : 0, o = act ? cd.g_off[g] : 0;
+  int32_t pr = act ? cd.g_xp[g] : 0, uoff = act ? cd.g_uoff[g] : 0;
+  int64_t mat = act ? cd.g_mat[g] : 0;
+  cond_arrived(m);
+  cond_arrived(sc);
+  cond_arrived(o);
+  cond_arrived(pr);
+  cond_arrived(uoff);
+  cond_arrived(mat);
+  // round 3: the lane's quarter of W, t_g and the slots of the pair
+  const int i = 2 * (q - pr);
+  const int ldm = cond_ldim(m);
+  big_d2 wa[COND_U];
+  cond_row2_request<NTM, COND_U>(cd.mat + mat + (int64_t)ldm * m + (int64_t)cond_ldim(sc) * m + i + (int64_t)k0 * ldm, ldm,
+                                sc - k0, wa);
+  const double tg0 = last ? tmp[o + i] : 0.0, tg1 = (last && i + 1 < m) ? tmp[o + i + 1] : 0.0;
+  int32_t sl0 = last ? cd.slot[off + o + i] : 0, sl1 = (last && i + 1 < m) ? cd.slot[off + o + i + 1] : 0;
+  if (tid < s) rs[tid] = rv;
+  __syncthreads();
+  if (full) {
+    big_block_finish(sv, s, 3, rs, lane, ys + a, s - a);
+  } else {
+    if (nr & 8) big_part_finish<4>(sv, s, 2, rs, lane, ys + r8, s - r8);
+    if (nr & 4) big_part_finish<2>(sv + 4, s, 1, rs, lane, ys + r4, s - r4);
+    if (nr & 2) big_part_finish<1>(sv + 6, s, 0, rs, lane, ys + r2, s - r2);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    if (tid + u * NT_ < uo) yg[tid + u * NT_] = ys[sq[u]];
+  for (int j = tid + 4 * NT_; j < uo; j += NT_) yg[j] = ys[si[j]];
+  __syncthreads();
+  // y_g = t_g - W_g y_S[S_g]
+  double y0 = 0.0, y1 = 0.0;
+  cond_row2_relay(wa, k0, sc, yg + uoff, y0, y1);
+  cond_arrived(sl0);                // (the slots are waited for HERE, not where they were requested)
+  cond_arrived(sl1);
+  cond_arrived(ssl);
+  if (last) {
+    out[sl0] = tg0 - y0;
+    if (i + 1 < m) out[sl1] = tg1 - y1;
+  }
+  if (tid < s) out[ssl] = ys[tid];
+}
+
 // ---- the group products by CHUNKS of groups (launch_cond_apply_range chooses by launch size: these kernels for launches of
 // fewer than 1024 patches, the per-patch front / back kernels above for larger ones).  With a workgroup per patch the front and back launches on config 5's finest level spend their
 // second half on the ~1000 small stars of the level -- short chains of dependent phases, 3 workgroups per CU because the LDS
@@ -1756,7 +1899,7 @@ int launch_cond_schur_one(alfi_level* L, int64_t p, const int64_t* d_zero, doubl
   return 0;
 }
 
-// One condensed apply = three launches (front / sigma / back).  Two forms of the group products:
+// One condensed apply = three launches (front / sigma / back; front / tail on vertex-star levels).  Two forms of the group products:
 //   * launches of fewer than 1024 patches (the lower levels: config 5's level 1 has 303 stars; ranges of an overlapped exchange):
 //     chunks of <= 8 consecutive groups per workgroup, one descriptor per workgroup, a lane's row pair decoded in the kernel, the
 //     Schur right-hand side formed by the sigma workgroups (cond_gfront / cond_gsigma / cond_gback): front + back 48 -> 39 us
@@ -1766,6 +1909,9 @@ int launch_cond_schur_one(alfi_level* L, int64_t p, const int64_t* d_zero, doubl
 //     decoded descriptors; round 3 with a descriptor per lane: 338 against 326 us).  Levels of small groups (cond_ahead,
 //     cond_layout.h: config 4's vertex stars) take the front kernel's early-load form: tables and the whole row pair requested
 //     at kernel entry, X and B pairs in different waves.
+//     Levels whose patches fit it (cond_tail, cond_layout.h: again the vertex stars) take cond_tail_kernel in place of the
+//     sigma and the back launch: y_S through LDS, all of inv(Sigma) and W requested at entry, 256 threads per patch.  Config 4
+//     (profiles/cond_tail_cfg4.txt): 112.5 -> 107.8 ms per cycle.
 // The sigma launch takes chunks of <= 64 rows (COND_SIGMA_ROWS; 256 in round 3: config 5 24.8 -> 24.1 ms per cycle, the apply
 // from 0.70 to 0.73 of the HBM roofline, profiles/r04_ab_cond_cfg5.txt).
 // Measured and dropped (rounds 2-3, profiles/r03_cond_apply_ab_cfg5.txt): the whole apply as ONE launch per patch (941 against
@@ -1802,6 +1948,9 @@ int launch_cond_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double*
   }
   const size_t lds_f = (size_t)L->cplan.lds_front, lds_s = (size_t)(L->cplan.max_s + 2) * sizeof(double);
   const size_t lds_b = (size_t)L->cplan.lds_back;
+  // Levels whose patches fit the tail launch (cond_tail, cond_layout.h: the vertex stars) take front + tail: two launches
+  const bool tail = cond_tail(L->cplan.max_xpairs, L->cplan.max_sc, L->cplan.max_s);
+  const size_t lds_t = (size_t)(2 * L->cplan.max_s + L->cplan.umax + 2) * sizeof(double);      // rhs, y_S, y_S[S_g]
 #define ALFI_COND_LAUNCH3(WV, AH, FW)                                                                                     \
   do {                                                                                                                    \
     if (lds_f > 64 * 1024)                                                                                                \
@@ -1809,6 +1958,11 @@ int launch_cond_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double*
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f));                   \
     hipLaunchKernelGGL((cond_front_kernel<false, WV, 8, AH>), dim3(grid.x), dim3(64 * (FW)), lds_f, ctx->stream, p0, p1,  \
                        L->cd, L->patch_ptr, L->stage_ptr, x, L->stage, ordered);                                          \
+    if (tail) {                                                                                                           \
+      hipLaunchKernelGGL((cond_tail_kernel<true, false>), dim3(grid.x), dim3(COND_TAIL_THREADS), lds_t, ctx->stream, p0,  \
+                         p1, L->cd, L->patch_ptr, L->stage_ptr, L->stage, ordered);                                       \
+      break;                                                                                                              \
+    }                                                                                                                     \
     if (c1 > c0)                                                                                                          \
       hipLaunchKernelGGL((cond_sigma_kernel<true>), dim3((unsigned)(c1 - c0)), dim3(256), lds_s, ctx->stream, c0, L->cd,  \
                          L->patch_ptr, L->stage_ptr, L->stage);                                                           \

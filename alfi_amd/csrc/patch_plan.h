@@ -208,6 +208,8 @@ struct CondPlan {
   int max_m = 0;       // largest group: <= 16 -> four groups per wave in the factorisation (cond_group16_kernel)
   int max_pairs = 0;   // most row pairs of X / W or of B in one patch: waves per patch of cond_front / cond_back
   int front_waves = 1; // most waves the early-load front kernel needs for one patch (cond_ahead_front_waves, cond_layout.h)
+  int max_xpairs = 0;  // most row pairs of X / W in one patch, and
+  int max_sc = 0;      // most coupled skeleton entries of one group: the tail launch (cond_tail, cond_layout.h)
   int umax = 0;
 
   // what later calls read on the host stays (sptr, gptr, chptr, gcptr and the scalars); the tables that live on the device go
@@ -218,6 +220,7 @@ struct CondPlan {
     keep.lds_bytes = lds_bytes; keep.lds_front = lds_front; keep.lds_back = lds_back;
     keep.lds_gfront = lds_gfront; keep.lds_gback = lds_gback;
     keep.max_s = max_s; keep.max_m = max_m; keep.max_pairs = max_pairs; keep.front_waves = front_waves; keep.umax = umax;
+    keep.max_xpairs = max_xpairs; keep.max_sc = max_sc;
     *this = std::move(keep);
   }
 };
@@ -348,7 +351,7 @@ inline int plan_condensed(int bs, int64_t nb, int64_t npatch, const int64_t* pp,
   std::vector<int32_t> ch_patch, ch_row, xp_grp, bp_grp, g_xp(g_m.size()), g_bp(g_m.size()), u_dst;
   std::vector<int64_t> chptr((size_t)npatch + 1, 0), uptr((size_t)npatch + 1, 0), xp_ptr((size_t)npatch + 1, 0),
       bp_ptr((size_t)npatch + 1, 0);
-  int lds_front = 0, lds_back = 0, max_pairs = 0, front_waves = 1;
+  int lds_front = 0, lds_back = 0, max_pairs = 0, max_xpairs = 0, front_waves = 1;
   for (int64_t p = 0; p < npatch; ++p) {
     const int s = (int)(sptr[p + 1] - sptr[p]), ld = (s + 1) & ~1;
     for (int r = 0; r < ld; r += sigma_rows) {
@@ -375,6 +378,7 @@ inline int plan_condensed(int bs, int64_t nb, int64_t npatch, const int64_t* pp,
     u_dst.resize((size_t)uptr[p + 1]);
     for (int32_t q = qb; q < qe; ++q) u_dst[uptr[p] + s_uidx[q]] = q - qb;
     max_pairs = std::max(max_pairs, std::max(xp, bp));
+    max_xpairs = std::max(max_xpairs, xp);
     front_waves = std::max(front_waves, cond_ahead_front_waves(xp, bp));
     lds_front = std::max(lds_front, (int)((pp[p + 1] - pp[p] + p_nI[p] + uo + 2) * (int64_t)sizeof(double)));
     lds_back = std::max(lds_back, (int)((s + uo + 2) * (int64_t)sizeof(double)));
@@ -431,6 +435,8 @@ inline int plan_condensed(int bs, int64_t nb, int64_t npatch, const int64_t* pp,
   o.max_m = g_m.empty() ? 0 : *std::max_element(g_m.begin(), g_m.end());
   o.max_pairs = max_pairs;
   o.front_waves = front_waves;
+  o.max_xpairs = max_xpairs;
+  o.max_sc = g_sc.empty() ? 0 : *std::max_element(g_sc.begin(), g_sc.end());
   o.umax = umax;
   o.dofs = std::move(c_dofs); o.slot = std::move(c_slot);
   o.gptr = std::move(gptr); o.g_mat = std::move(g_mat); o.g_sidx = std::move(g_sidx);
