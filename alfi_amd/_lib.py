@@ -87,6 +87,7 @@ SIGNATURES = {
     "alfi_level_assemble_burman": (ctypes.c_int, [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, ctypes.c_double,
                                                   ctypes.c_int]),
     "alfi_level_transpose": (ctypes.c_int, [vp]),
+    "alfi_level_set_assembly_transposed": (ctypes.c_int, [vp, ctypes.c_int]),
     "alfi_level_get_values": (ctypes.c_int, [vp, vp]),
     "alfi_level_size": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64)]),
     "alfi_spmv": (ctypes.c_int, [vp, vp, vp]),

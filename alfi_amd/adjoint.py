@@ -17,7 +17,16 @@ Burman acts on the velocity only), so J_F^T = [[A^T, B^T], [B, 0]]: only A chang
 3. solves with the saddle-point FGMRES of the forward solves (the Schoeberl transfers depend on (nu, gamma) only).
 
 The next ``solve(re)`` refreshes and refactors in its first Newton step, so an adjoint solve leaves no trace in the forward
-iteration.  Partitioned levels are refused: the mirror blocks of a rank's ghost columns live on other ranks.
+iteration.
+
+Partitioned levels (``DistNavierStokesSolver`` with the device-side refresh): the in-place transpose is not available there --
+the mirror blocks of a rank's ghost columns are other ranks' -- and not needed.  Every block of the operator is a sum over its
+contributor list, and block (i, j) of A^T is the sum of the transposed MIRROR element blocks over the same list, so steps 1
+and 2 become ONE refresh with ``hip.Level.set_assembly_transposed`` on (alfi_level_set_assembly_transposed): every rank forms
+its own rows of A^T, no halo and no collective beyond those of the forward refresh, bitwise what refresh + transpose would
+give.  Every rank forms the right-hand side from the gathered state, takes its entries (owned velocity dofs | owned pressure
+rows), solves with ``DistSaddle``; ``z_adj`` is gathered onto every rank.  Still refused there: host assembly
+(ALFI_DEVICE_ASSEMBLY=0 or a fallback to it).
 """
 import time
 
@@ -104,6 +113,8 @@ class AdjointSolver(object):
     def _operators(self, adv):
         """Transposed Jacobian blocks of z* on every level, factored.  Returns (refresh, transpose, factor) seconds."""
         s = self.solver
+        if s._partitioned:
+            return self._operators_partitioned(adv)
         mgl = s.hmg.mg.levels
         saved = dict(s.timings)
         t0 = time.time()
@@ -127,6 +138,73 @@ class AdjointSolver(object):
         s.timings.update(saved)            # the forward solve's accounting stays the forward solve's
         return t1 - t0, t2 - t1, t3 - t2
 
+    def _operators_partitioned(self, adv):
+        """Partitioned levels: every rank refreshes ITS rows of the transposed operators on the device -- the transposed
+        refresh about z*, through the state exchange or (``device_state=False``) the uploaded states --, then the factors."""
+        s = self.solver
+        saved = dict(s.timings)
+        t0 = time.time()
+        levels = [dl for dl, _, _ in s._device_levels()]
+        try:
+            with s._on_stream():
+                for dl in levels:
+                    dl.set_assembly_transposed(True)
+            if s._device_state_resident():
+                if not (s._device_newer or s._device_current):
+                    s._push_state()
+                    s._device_current = True
+                s._refresh_device(None, adv)
+            else:                           # the replicated host state, uploaded into every level's state vector
+                s._refresh_device(s.u.copy(), adv)
+        finally:
+            with s._on_stream():
+                for dl in levels:
+                    dl.set_assembly_transposed(False)
+        t1 = time.time()
+        s._factor_levels()
+        t2 = time.time()
+        s.timings.clear()
+        s.timings.update(saved)
+        return t1 - t0, 0.0, t2 - t1
+
+    def _solve_partitioned(self, t0, times, rtol, atol):
+        """Right-hand sides from the gathered state on every rank (``u`` / ``p`` gather collectively), the rank's entries
+        solved with DistSaddle (a list: its columns one after the other), the adjoints gathered onto every rank."""
+        s = self.solver
+        sad = s.saddle
+        t_ref, t_tr, t_fac = times
+        u, p = s.u, s.p
+        rhs = adjoint_rhs_block([J.gradient(s, u, p) for J in self.functionals], s.levels[-1].bc_dofs, s.n_p,
+                                s.vol if s.nullspace else None)
+        rtol = s.rtol if rtol is None else float(rtol)
+        atol = s.atol if atol is None else float(atol)
+        max_it = s.params["ksp_max_it"]
+        loc = np.ascontiguousarray(np.concatenate([rhs[:s.n_u][s._own_dofs], rhs[s.n_u:][np.asarray(sad.cells)]]))
+        t_s = time.time()
+        # (alfi_saddle_solve_block takes serial saddles only: the columns of a list are solved one after the other with the ONE
+        # set of factors -- block right-hand sides on partitioned levels are looped)
+        cols = [sad.solve(np.ascontiguousarray(loc[:, c]), rtol, atol, max_it, 30) for c in range(loc.shape[1])]
+        x = np.stack([c[0] for c in cols], axis=1)
+        its, rn = [c[1] for c in cols], [c[2] for c in cols]
+        lam = np.zeros((s.n_u + s.n_p, rhs.shape[1]))
+        for dofs, cells, xu, xp in s.dmg.comm.all_gather_object((s._own_dofs, sad.cells, x[:sad.n_own], x[sad.n_own:sad.n])):
+            lam[dofs] = xu
+            lam[s.n_u + np.asarray(cells, dtype=np.int64)] = xp
+        t_solve = time.time() - t_s
+        z = []
+        for c in range(rhs.shape[1]):
+            lam_u, lam_p = lam[:s.n_u, c].copy(), lam[s.n_u:, c].copy()
+            if s.nullspace:              # zero integral, as the forward solve shifts p
+                lam_p -= (s.vol @ lam_p) / s.area
+            z.append((lam_u, lam_p))
+        bnorm = [float(np.linalg.norm(rhs[:, c])) for c in range(rhs.shape[1])]
+        conv = [bool(i < max_it or r <= max(rtol * b, atol)) for i, r, b in zip(its, rn, bnorm)]
+        if not self.is_list:
+            z, its, rn, bnorm, conv = z[0], its[0], rn[0], bnorm[0], conv[0]
+        s.z_adj = z
+        return {"linear_iter": its, "time": (time.time() - t0) / 60.0, "residual_norm": rn, "rhs_norm": bnorm, "converged": conv,
+                "refresh_s": t_ref, "transpose_s": t_tr, "factor_s": t_fac, "solve_s": t_solve}
+
     def solve(self, rtol=None, atol=None):
         s = self.solver
         if getattr(s, "_last_solve", None) is None:
@@ -134,6 +212,8 @@ class AdjointSolver(object):
         _, adv = s._last_solve
         t0 = time.time()
         t_ref, t_tr, t_fac = self._operators(adv)
+        if s._partitioned:
+            return self._solve_partitioned(t0, (t_ref, t_tr, t_fac), rtol, atol)
         if self.is_list:
             return self._solve_block(t0, (t_ref, t_tr, t_fac), rtol, atol)
         u, p = s.u, s.p
@@ -186,9 +266,11 @@ class AdjointSolver(object):
 
 def setup_adjoint(solver, J):
     """``solver.setup_adjoint(J)``: keep the functional -- or the list of functionals -- and create ``solver.solver_adjoint``."""
-    if solver._partitioned:
-        raise NotImplementedError("adjoint solves on partitioned levels: the mirror blocks of a rank's ghost columns belong to "
-                                  "other ranks")
+    if solver._partitioned and not (getattr(solver, "_asm_ready", False) and getattr(solver, "device_assembly", False)):
+        # (read before any collective: every rank reaches the same verdict, the fallback to host assembly is agreed on)
+        raise NotImplementedError("adjoint solves on partitioned levels need the device-side operator refresh (the transposed "
+                                  "refresh, alfi_level_set_assembly_transposed): with host assembly the mirror blocks of a "
+                                  "rank's ghost columns belong to other ranks")
     solver.J_adj = J
     solver.solver_adjoint = AdjointSolver(solver, J)
     return solver.solver_adjoint

@@ -766,6 +766,20 @@ int alfi_level_apply_bc(alfi_level* L) {
   return launch_apply_bc(L);
 }
 
+// While on, the refresh of this level (alfi_level_assemble / _assemble_supg / _assemble_gls / _assemble_burman and
+// alfi_level_supg / _gls / _burman adding to the operator) writes the values of A^T in the same sparsity: every block sums the
+// transposes of its contributors' mirror element blocks, which needs no other block -- serial and PARTITIONED levels alike.
+// alfi_level_apply_bc's rule is symmetric.  Not affected: alfi_level_assemble_mult and the residual outputs d_F (forward
+// quantities), alfi_level_update_values, alfi_level_transpose, the patch facet correction (its entries s_ab are symmetric).
+int alfi_level_set_assembly_transposed(alfi_level* L, int on) {
+  if (!L) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL level");
+  if (!L->asmb.ready) return alfi_set_error(L->ctx, ALFI_E_ARG, "alfi_level_set_assembly_transposed on a level without alfi_level_set_assembly");
+  L->asmb.transposed = on != 0;
+  return 0;
+}
+
+// (partitioned levels: the mirror blocks of a rank's ghost columns are other ranks' -- a partitioned caller that wants A^T
+// refreshes it with alfi_level_set_assembly_transposed, which forms every rank's rows of A^T with no exchange)
 int alfi_level_transpose(alfi_level* L) {
   if (!L) return alfi_set_error(nullptr, ALFI_E_ARG, "NULL level");
   alfi_ctx* ctx = L->ctx;

@@ -293,6 +293,7 @@ struct AssemblyDev {
                                  // local nodes followed by the other nodes of the cells that touch them, then -- Burman
                                  // terms -- the other nodes of the rank's facets)
   bool full_div = false;         // grad-div term gamma (div u, div v) (Scott-Vogelius) instead of the cell-averaged one
+  bool transposed = false;       // alfi_level_set_assembly_transposed: the refresh writes the values of A^T
   uint8_t* bc_code = nullptr;    // (nnzb) Dirichlet flags of every block's row / column dofs (built on first use)
   uint8_t* bc_all = nullptr;     // (n) partitioned levels: Dirichlet dofs among ALL local dofs, ghosts included
                                  // (alfi_level_set_assembly_bc; the level's own mask marks owned dofs only)

@@ -230,8 +230,12 @@ __global__ __launch_bounds__(256) void bc_code_kernel(int64_t nnzb, int nloc, co
 }
 
 // vals (lane-major planes of the level operator) = / += the element blocks of the cells [c0, c1) in E, every block adding its
-// contributors in list order; then (apply_bc) identity on Dirichlet rows / columns
-template <int D>
+// contributors in list order; then (apply_bc) identity on Dirichlet rows / columns.
+// TR (alfi_level_set_assembly_transposed): the values of A^T in the same sparsity.  Block (i, j) of A^T is the transpose of block
+// (j, i) of A, whose contributor list holds the same cells in the same order with a and b swapped: so a contributor (cell, a, b)
+// adds the d x d transpose of the element block at (b, a) -- bitwise the forward value of the mirror block, with no look at it
+// (on a partitioned level the mirror of a ghost column's block is another rank's).  The Dirichlet rule is its own transpose.
+template <int D, bool TR>
 __global__ __launch_bounds__(256) void element_gather_kernel(int64_t nnzb, int nloc, int64_t c0, int64_t c1,
                                                               const int64_t* __restrict__ cptr, const int32_t* __restrict__ ccell,
                                                               const uint16_t* __restrict__ cba, const double* __restrict__ E,
@@ -253,9 +257,17 @@ __global__ __launch_bounds__(256) void element_gather_kernel(int64_t nnzb, int n
     const unsigned ba = cba[q], b = ba / (unsigned)nloc, a = ba - b * (unsigned)nloc;
     double e[BB];
     const int64_t cs = cell - c0;
-    load_block<BB>(E + (elay ? (((cs >> 6) * (nloc * nloc) + a * nloc + b) * 64 + (cs & 63)) * BB : ((cs * nloc + a) * nloc + b) * BB), e);
+    if constexpr (TR) {
+      load_block<BB>(E + (elay ? (((cs >> 6) * (nloc * nloc) + b * nloc + a) * 64 + (cs & 63)) * BB : ((cs * nloc + b) * nloc + a) * BB), e);
 #pragma unroll
-    for (int t = 0; t < BB; ++t) acc[t] += e[t];
+      for (int cc = 0; cc < D; ++cc)
+#pragma unroll
+        for (int dd = 0; dd < D; ++dd) acc[cc * D + dd] += e[dd * D + cc];
+    } else {
+      load_block<BB>(E + (elay ? (((cs >> 6) * (nloc * nloc) + a * nloc + b) * 64 + (cs & 63)) * BB : ((cs * nloc + a) * nloc + b) * BB), e);
+#pragma unroll
+      for (int t = 0; t < BB; ++t) acc[t] += e[t];
+    }
   }
   if (accumulate && !any && !apply_bc) return;
   const unsigned c = apply_bc ? code[k] : 0u;
@@ -907,7 +919,9 @@ __global__ __launch_bounds__(64) void burman_facet_kernel(int64_t nf, int nu, in
   }
 }
 
-template <int D>
+// TR (alfi_level_set_assembly_transposed): a contributor (f, a, b) computes what the forward kernel computes for the mirror
+// block's contributor (f, b, a) -- the same operands in the same order -- and adds its d x d transpose
+template <int D, bool TR>
 __global__ __launch_bounds__(256) void burman_block_kernel(int64_t nnzb, int nu, int nloc, int nqs, const int64_t* __restrict__ bptr,
                                                            const int32_t* __restrict__ bfac, const uint16_t* __restrict__ bab,
                                                            const double* __restrict__ J, const double* __restrict__ ws,
@@ -924,7 +938,7 @@ __global__ __launch_bounds__(256) void burman_block_kernel(int64_t nnzb, int nu,
   for (int t = 0; t < BB; ++t) acc[t] = 0.0;
   for (int64_t p = p0; p < p1; ++p) {
     const int64_t f = bfac[p];
-    const int a = bab[p] / nu, b = bab[p] % nu;
+    const int a = TR ? bab[p] % nu : bab[p] / nu, b = TR ? bab[p] / nu : bab[p] % nu;
     const double* Jf = J + f * nqs * nu;
     const double* r = R + f * rec;
     double s = 0.0, g[D];
@@ -942,7 +956,7 @@ __global__ __launch_bounds__(256) void burman_block_kernel(int64_t nnzb, int nu,
       acc[i * D + i] += c * r[0] * A * s;
       if (b < nloc)
 #pragma unroll
-        for (int j = 0; j < D; ++j) acc[i * D + j] += c * A * g[i] * r[1 + nqs * D + b * D + j];
+        for (int j = 0; j < D; ++j) acc[TR ? j * D + i : i * D + j] += c * A * g[i] * r[1 + nqs * D + b * D + j];
     }
   }
 #pragma unroll
@@ -1110,10 +1124,12 @@ int launch_operator_refresh(alfi_level* L, double nu, double gamma, double adv, 
     }
     dim3 g2((unsigned)((nnzb + 255) / 256)), b2(256);
     const int acc = (accumulate || c0 > 0) ? 1 : 0, bc = (apply_bc && c1 == S.ncell) ? 1 : 0;
-    if (d == 2)
-      hipLaunchKernelGGL(element_gather_kernel<2>, g2, b2, 0, ctx->stream, nnzb, nloc, c0, c1, S.cptr, S.ccell, S.cba, E, S.bc_code, acc, bc, out_vals, elay);
-    else
-      hipLaunchKernelGGL(element_gather_kernel<3>, g2, b2, 0, ctx->stream, nnzb, nloc, c0, c1, S.cptr, S.ccell, S.cba, E, S.bc_code, acc, bc, out_vals, elay);
+#define ALFI_GATHER(DV, TV)                                                                                                     \
+  hipLaunchKernelGGL((element_gather_kernel<DV, TV>), g2, b2, 0, ctx->stream, nnzb, nloc, c0, c1, S.cptr, S.ccell, S.cba, E,    \
+                     S.bc_code, acc, bc, out_vals, elay)
+    if (d == 2) { if (S.transposed) ALFI_GATHER(2, true); else ALFI_GATHER(2, false); }
+    else { if (S.transposed) ALFI_GATHER(3, true); else ALFI_GATHER(3, false); }
+#undef ALFI_GATHER
     ALFI_HIP_CHECK(ctx, hipGetLastError());
   }
   return 0;
@@ -1206,12 +1222,12 @@ int launch_burman(alfi_level* L, double weight, const double* d_state, bool add_
   if (add_to_operator) {
     const int64_t nnzb = L->A.nnzb;
     dim3 grid((unsigned)((nnzb + 255) / 256)), block(256);
-    if (d == 2)
-      hipLaunchKernelGGL(burman_block_kernel<2>, grid, block, 0, ctx->stream, nnzb, S.bnu, S.nloc, S.bnqs, S.fbptr, S.fbfac, S.fbab, S.fJ,
-                         S.fws, S.farea, S.fcoef, (const double*)R, weight, L->A.vals);
-    else
-      hipLaunchKernelGGL(burman_block_kernel<3>, grid, block, 0, ctx->stream, nnzb, S.bnu, S.nloc, S.bnqs, S.fbptr, S.fbfac, S.fbab, S.fJ,
-                         S.fws, S.farea, S.fcoef, (const double*)R, weight, L->A.vals);
+#define ALFI_BURMAN_B(DV, TV)                                                                                                   \
+  hipLaunchKernelGGL((burman_block_kernel<DV, TV>), grid, block, 0, ctx->stream, nnzb, S.bnu, S.nloc, S.bnqs, S.fbptr, S.fbfac, \
+                     S.fbab, S.fJ, S.fws, S.farea, S.fcoef, (const double*)R, weight, L->A.vals)
+    if (d == 2) { if (S.transposed) ALFI_BURMAN_B(2, true); else ALFI_BURMAN_B(2, false); }
+    else { if (S.transposed) ALFI_BURMAN_B(3, true); else ALFI_BURMAN_B(3, false); }
+#undef ALFI_BURMAN_B
     ALFI_HIP_CHECK(ctx, hipGetLastError());
   }
   if (d_F) {

@@ -205,8 +205,16 @@ class DistNavierStokesSolver(HipNavierStokesSolver):
         self.dmg.update(self.levels)
 
     def setup_adjoint(self, J):
-        raise NotImplementedError("adjoint solves on partitioned levels: J^T needs the mirror block of every ghost column, "
-                                  "and those belong to other ranks")
+        """``solver_adjoint`` on partitioned levels: with the operators refreshed on the device every rank forms its own rows
+        of J^T (the transposed refresh, alfi_amd.adjoint).  Host assembly (ALFI_DEVICE_ASSEMBLY=0, a fallback to it, a solver
+        never set up) stays refused: there J^T needs the mirror block of every ghost column, and those belong to other
+        ranks.  The check comes before any collective and every rank reaches the same verdict."""
+        if not (getattr(self, "_asm_ready", False) and getattr(self, "device_assembly", False)):
+            raise NotImplementedError("adjoint solves on partitioned levels need the device-side operator refresh: with host "
+                                      "assembly J^T needs the mirror block of every ghost column, and those belong to other "
+                                      "ranks")
+        from .adjoint import setup_adjoint
+        return setup_adjoint(self, J)
 
     def _supg_host_needs_global_values(self):
         if isinstance(self.levels[-1].A, LazyOperator):

@@ -501,9 +501,16 @@ class Level(object):
 
     def transpose(self):
         """The operator replaced by its block transpose on the device, in the same sparsity and bitwise (alfi_level_transpose:
-        the velocity block of the adjoint J^T).  Serial levels with a structurally symmetric pattern only; the patches and the
-        coarse grid must be factored again afterwards."""
+        the velocity block of the adjoint J^T).  Serial levels with a structurally symmetric pattern only (a partitioned level
+        refreshes A^T instead: ``set_assembly_transposed``); the patches and the coarse grid must be factored again afterwards."""
         self.ctx.check(self.ctx.lib.alfi_level_transpose(self.h))
+
+    def set_assembly_transposed(self, on=True):
+        """While on, every device refresh of this level (``assemble`` / ``assemble_supg`` / ``assemble_gls`` /
+        ``assemble_burman`` and ``supg`` / ``gls`` / ``burman`` adding to the operator) writes A^T in the same sparsity, bitwise
+        what a refresh followed by ``transpose`` gives (alfi_level_set_assembly_transposed).  Serial and partitioned levels,
+        after ``set_assembly``; ``assemble_mult`` and the residual outputs stay forward quantities."""
+        self.ctx.check(self.ctx.lib.alfi_level_set_assembly_transposed(self.h, 1 if on else 0))
 
     def get_values(self):
         """The operator values in the host layout (nnzb, bs, bs)."""

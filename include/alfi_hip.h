@@ -254,8 +254,20 @@ int alfi_level_set_facet_beta(alfi_level* lvl, const double* beta_host, double s
  * block k at (i, j) receives A[j, i]^T), in place and bitwise.  The pattern must be structurally symmetric with ascending
  * columns per row, checked once on the device (mirror map cached on the level: 4 bytes per block); otherwise ALFI_E_ARG and
  * the values are untouched.  Partitioned / distributed levels: ALFI_E_ARG (the mirror blocks of ghost columns live on other
- * ranks).  The patch and coarse factors are stale afterwards, as after a refresh. */
+ * ranks: a partitioned caller refreshes A^T with alfi_level_set_assembly_transposed instead).  The patch and coarse factors
+ * are stale afterwards, as after a refresh. */
 int alfi_level_transpose(alfi_level* lvl);
+/* Transposed operator refresh (after alfi_level_set_assembly, on serial AND partitioned levels; ALFI_E_ARG without an
+ * assembly; off after every alfi_level_set_assembly).  While on != 0, every entry point that writes operator values from the
+ * device assembly writes A^T in the same sparsity: alfi_level_assemble, _assemble_supg, _assemble_gls, _assemble_burman, and
+ * alfi_level_supg / _gls / _burman with add_to_operator != 0.  Block (i, j) of A^T is the sum of the transposed element blocks
+ * A_e[b, a]^T over the contributor list block (i, j) of A already has -- no other block, no halo, no collective --, bitwise
+ * what a forward refresh followed by alfi_level_transpose gives (the lists of (i, j) and (j, i) hold the same cells / facets
+ * in the same order).  alfi_level_apply_bc stays as it is (its rule is symmetric under the transpose).  NOT affected:
+ * alfi_level_assemble_mult and the residual outputs d_F (forward quantities), alfi_level_update_values, alfi_level_transpose,
+ * and the patch facet correction (its entries s_ab are symmetric).  The patch and coarse factors are stale after such a
+ * refresh, as after any. */
+int alfi_level_set_assembly_transposed(alfi_level* lvl, int on);
 /* the operator values in the host layout (nnzb, bs, bs) -- diagnostics / tests */
 int alfi_level_get_values(alfi_level* lvl, double* bvals_host);
 int alfi_level_size(alfi_level* lvl, int64_t* n);

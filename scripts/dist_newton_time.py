@@ -7,6 +7,7 @@ stand-in for librccl (tests/mock_rccl), so the times are FUNCTIONAL (one GPU doe
     python scripts/dist_newton_time.py cfg4 --ranks 4 --re 10 100
     python scripts/dist_newton_time.py cfg5s --ranks 2 --burman 5e-3 --compare
     python scripts/dist_newton_time.py cfg5s --ranks 2 --host-state
+    python scripts/dist_newton_time.py cfg2 --ranks 2 --adjoint --compare
 
 Every config runs with the Newton state distributed on the devices -- the Scott-Vogelius ones (cfg5s, cfg5: the structured
 bfs3d stand-in) included, their coarse levels' states being weighted gathers of the exchanged finest velocity; --host-state
@@ -71,6 +72,11 @@ def rank_main(args):
                      s.timings["assemble_s"] / n, s.timings["factor_s"] / n, s.timings["residual_s"] / n,
                      s.timings["solve_s"] / n, len(calls)), flush=True)
             print("Re %g: bytes across PCIe per Newton step, per rank: %s" % (re, pcie), flush=True)
+        if args.adjoint:              # COLLECTIVE: every rank solves its part (the transposed refresh of its own rows)
+            from newton_step_time import adjoint_functional, adjoint_line
+            ainfo = s.solve_adjoint(adjoint_functional(s))[1]
+            if rank == 0:
+                print(adjoint_line(re, ainfo), flush=True)
     got = [None] * world
     dist.all_gather_object(got, len(calls))
     if rank == 0:
@@ -149,6 +155,9 @@ def main():
                     help="Burman stabilisation of the Scott-Vogelius configs with this weight (the reference's run lines: 5e-3)")
     ap.add_argument("--host-state", action="store_true",
                     help="the Newton state replicated on the hosts (device_state=False), for comparisons")
+    ap.add_argument("--adjoint", action="store_true",
+                    help="one adjoint solve after every forward solve: refresh / factor / solve seconds and the Krylov count "
+                         "(with --compare next to the single-GPU solver's)")
     ap.add_argument("--compare", action="store_true", help="also run the single-GPU solver (counts side by side)")
     ap.add_argument("--rank-process", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -175,6 +184,7 @@ def main():
                                       (["--supg", str(args.supg)] if args.supg is not None else []) +
                                       (["--burman", str(args.burman)] if args.burman is not None else []) +
                                       (["--host-state"] if args.host_state else []) +
+                                      (["--adjoint"] if args.adjoint else []) +
                                       ["--re"] + [str(x) for x in args.re], env=env, cwd=ROOT))
     done = False
     try:
@@ -193,6 +203,7 @@ def main():
         subprocess.check_call([sys.executable, os.path.join(ROOT, "scripts", "newton_step_time.py"), args.config] +
                               (["--supg", str(args.supg)] if args.supg is not None else []) +
                               (["--burman", str(args.burman)] if args.burman is not None else []) +
+                              (["--adjoint"] if args.adjoint else []) +
                               ["--re"] + [str(x) for x in args.re], cwd=ROOT)
 
 

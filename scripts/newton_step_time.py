@@ -24,6 +24,9 @@ def main():
                     help="Burman stabilisation of the Scott-Vogelius configs (cfg5s, cfg5) with this weight")
     ap.add_argument("--gls", type=float, default=None, metavar="WEIGHT",
                     help="GLS stabilisation of the P0-pressure configs with this weight")
+    ap.add_argument("--adjoint", action="store_true",
+                    help="one adjoint solve after every forward solve (refresh / transpose / factor / solve seconds, Krylov "
+                         "count), and at the end the all-levels refresh with the transposed switch on next to the forward one")
     args = ap.parse_args()
     from alfi_amd.nssolver import HipNavierStokesSolver
     from dist_newton_time import problem_and_options
@@ -48,7 +51,47 @@ def main():
               % (re, info["nonlinear_iter"], info["linear_iter"], info["converged"], wall, wall / n,
                  s.timings["assemble_s"] / n, s.timings["factor_s"] / n, s.timings["residual_s"] / n, s.timings["solve_s"] / n),
               flush=True)
+        if args.adjoint:
+            print(adjoint_line(re, s.solve_adjoint(adjoint_functional(s))[1]), flush=True)
+    if args.adjoint and s.device_assembly:
+        t_fwd, t_tr = transposed_refresh_time(s, [dl for dl, _, _ in s._device_levels()])
+        print("refresh of all levels about the final state: forward %.3f ms, transposed %.3f ms, ratio %.3f"
+              % (1e3 * t_fwd, 1e3 * t_tr, t_tr / t_fwd), flush=True)
     s.close()
+
+
+def adjoint_functional(s):
+    """A fixed linear functional of the velocity (the cost of an adjoint solve does not depend on which)."""
+    import numpy as np
+    from alfi_amd.adjoint import LinearFunctional
+    return LinearFunctional(np.random.default_rng(0).standard_normal(s.n_u))
+
+
+def adjoint_line(re, info):
+    return ("Re %g adjoint: %d Krylov its, converged %s, refresh %.3f s, transpose %.3f s, factor %.3f s, solve %.3f s"
+            % (re, info["linear_iter"], info["converged"], info["refresh_s"], info["transpose_s"], info["factor_s"], info["solve_s"]))
+
+
+def transposed_refresh_time(s, levels, reps=5):
+    """Seconds per refresh of all levels about the current state with the transposed switch off and on
+    (alfi_level_set_assembly_transposed), alternating, the best of ``reps`` each; the forward operators are left in place."""
+    _, adv = s._last_solve
+    best = [float("inf"), float("inf")]
+    s._refresh_device(None, adv)
+    for _ in range(reps):
+        for on in (0, 1):
+            with s._on_stream():
+                for dl in levels:
+                    dl.set_assembly_transposed(bool(on))
+            s.ctx.sync()
+            t0 = time.time()
+            s._refresh_device(None, adv)
+            best[on] = min(best[on], time.time() - t0)
+    with s._on_stream():
+        for dl in levels:
+            dl.set_assembly_transposed(False)
+    s._refresh_device(None, adv)
+    return best[0], best[1]
 
 
 if __name__ == "__main__":
