@@ -50,7 +50,7 @@ def lib():
         _lib.alfi_host_f32_index_table.restype = None
         _lib.alfi_host_piece_index_table.restype = None
         _lib.alfi_host_patch_index_table.restype = None
-        for name in ("patch_layout", "condensed", "sweep", "f32_layout", "macro_f32_layout", "f32_ranges"):
+        for name in ("patch_layout", "condensed", "sweep", "sweep_condensed", "f32_layout", "macro_f32_layout", "f32_ranges"):
             getattr(_lib, "alfi_host_plan_" + name).restype = ctypes.c_void_p
         _lib.alfi_host_f32_index.restype = ctypes.c_int64
         _lib.alfi_host_f32_ld.restype = ctypes.c_int
@@ -205,6 +205,20 @@ def plan_sweep(bs, rowptr, colidx, patch_ptr, patch_dofs, iterset, symmetrise):
     it = np.ascontiguousarray(iterset, dtype=np.int64)
     return _plan_dict(lib().alfi_host_plan_sweep(ctypes.c_int(bs), ctypes.c_int64(len(rp) - 1), npatch, _p(pp), _p(pd), _p(rp),
                                                  _p(ci), ctypes.c_int64(len(it)), _p(it), ctypes.c_int(1 if symmetrise else 0)))
+
+
+def plan_sweep_condensed(bs, patch_ptr, patch_dofs, sweep, cond):
+    """The work lists alfi_patches_set_multiplicative_condensed builds per dependency wavefront (csrc/patch_plan.h:
+    plan_sweep_condensed) from the dicts ``sweep`` of ``plan_sweep`` and ``cond`` of ``plan_condensed``, as a dict: ``gchunk`` /
+    ``wk_ptr`` (group chunks), ``schunk`` / ``wc_ptr`` (sigma chunks), ``node`` / ``wn_ptr`` (block rows of the residual)."""
+    pp, pd, npatch = _patch_args(patch_ptr, patch_dofs)
+    wp = np.ascontiguousarray(sweep["wave_ptr"], dtype=np.int64)
+    seq = np.ascontiguousarray(sweep["seq"], dtype=np.int32)
+    gcptr = np.ascontiguousarray(cond["gcptr"], dtype=np.int64)
+    chptr = np.ascontiguousarray(cond["chptr"], dtype=np.int64)
+    assert len(gcptr) == len(pp) and len(chptr) == len(pp) and wp[-1] == len(seq)
+    return _plan_dict(lib().alfi_host_plan_sweep_condensed(ctypes.c_int(bs), npatch, _p(pp), _p(pd), ctypes.c_int64(len(wp) - 1),
+                                                           _p(wp), _p(seq), _p(gcptr), _p(chptr)))
 
 
 def node_graph(cell_nodes, nnode):

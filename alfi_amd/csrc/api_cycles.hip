@@ -602,6 +602,10 @@ static void cycle_signature(alfi_mg* mg, std::vector<uint64_t>* sig) {
     push(L->mf);
     push(L->ws.V);
     push(L->mult_seq);
+    push(L->mcw_gchunk);
+    push(L->mcw_schunk);
+    push(L->mcw_node);
+    push(L->mcw_r);
     sig->push_back((uint64_t)L->npatch);
     sig->push_back((uint64_t)L->ws.K);
     sig->push_back((uint64_t)(L->mult ? 1 + (L->mult_symmetrise ? 1 : 0) + 4 * L->sweep.wave_ptr.size() : 0));

@@ -911,7 +911,14 @@ int level_patch_apply(alfi_level* L, const double* dx, double* dy, bool* ghosts_
     const bool persistent = alfi_env_mult_persistent() && L->sweep.nitems > 0;
     {
       ProfScope prof(ctx, ALFI_EV_PATCH_APPLY);
-      if (persistent) {
+      if (L->held == HELD_COND) {
+        // the level holds condensed factors (alfi_patches_set_multiplicative_condensed): a short sequence of launches per
+        // wavefront, kernel boundaries the only ordering
+        const int64_t nw = (int64_t)L->sweep.wave_ptr.size() - 1;
+        for (int64_t w = 0; w < nw; ++w) ALFI_CHECK(launch_cond_mult_wave(L, w, dx, dy));
+        if (L->mult_symmetrise)
+          for (int64_t w = nw - 1; w >= 0; --w) ALFI_CHECK(launch_cond_mult_wave(L, w, dx, dy));
+      } else if (persistent) {
         // (a wait that runs into its bound sets the ctx's sticky error word, reported by the next synchronising call: no host
         // synchronisation inside the smoother)
         ALFI_CHECK(launch_patch_mult_persistent(L, dx, dy));

@@ -311,12 +311,21 @@ bool auto_cond_to_dense(alfi_level* L) {
 void free_mult_schedule(alfi_level* L) {
   dev_free(L->mult_items); dev_free(L->mult_pred0); dev_free(L->mult_pred); dev_free(L->mult_succ_ptr);
   dev_free(L->mult_succ); dev_free(L->mult_ctl); dev_free(L->mult_rowtab);
+  dev_free(L->mcw_gchunk); dev_free(L->mcw_schunk); dev_free(L->mcw_node); dev_free(L->mcw_r);
+  L->mcw_gchunk = L->mcw_schunk = L->mcw_node = nullptr;
+  L->mcw_r = nullptr;
+  std::vector<int64_t>().swap(L->mcw_wk_ptr);
+  std::vector<int64_t>().swap(L->mcw_wc_ptr);
+  std::vector<int64_t>().swap(L->mcw_wn_ptr);
   L->mult_rowtab = nullptr;
   L->mult_items = L->mult_pred0 = L->mult_pred = L->mult_succ_ptr = L->mult_succ = L->mult_ctl = nullptr;
   L->sweep.nitems = 0;
 }
 
-int alfi_patches_set_multiplicative(alfi_level* L, int64_t nit, const int64_t* iterset, int symmetrise) {
+// alfi_patches_set_multiplicative, and -- keep_cond -- alfi_patches_set_multiplicative_condensed on a level with the caller's
+// groups: the same arguments, refusals and schedule; the level keeps its condensed factors and gets the work lists of the
+// wavefronts (plan_sweep_condensed) in addition
+static int set_multiplicative_impl(alfi_level* L, int64_t nit, const int64_t* iterset, int symmetrise, bool keep_cond) {
   alfi_ctx* ctx = L->ctx;
   if (!L->patch_ptr) return alfi_set_error(ctx, ALFI_E_STATE, "alfi_patches_set_multiplicative before alfi_patches_set");
   ALFI_HIP_CHECK(ctx, hipSetDevice(ctx->device));
@@ -334,7 +343,7 @@ int alfi_patches_set_multiplicative(alfi_level* L, int64_t nit, const int64_t* i
   if (is_or_will_be_f32(L))
     return alfi_set_error(ctx, ALFI_E_STATE, "multiplicative sweeps on a level with FP32 patch storage: the sweeps read FP64 "
                                              "inverses (alfi_patches_set_storage(lvl, 0) first)");
-  if (cond_by_caller(L))
+  if (cond_by_caller(L) && !keep_cond)
     return alfi_set_error(ctx, ALFI_E_STATE, "multiplicative sweeps need dense patch inverses (alfi_patches_set_groups(NULL))");
   // (groups the library found itself are its own business: the sweeps read dense inverses, so such a level goes back to them
   // below, once the arguments have been checked, and is factored again at the end)
@@ -361,6 +370,22 @@ int alfi_patches_set_multiplicative(alfi_level* L, int64_t nit, const int64_t* i
   const int plan_rc = plan_sweep(L->bs, L->A.nbrows, L->npatch, pp, pd, rowptr.data(), colidx.data(), nit, iterset, symmetrise != 0,
                                  sw.big, &sw, &err);
   ALFI_CHECK(dev_upload(ctx, &L->mult_seq, sw.seq.data(), nit));
+  if (keep_cond) {
+    // the lists the condensed launches take per wavefront, and the residual vector; set before the level counts as sweeping
+    SweepCondPlan sc;
+    const int64_t nwave = (int64_t)sw.wave_ptr.size() - 1;
+    if (const int rc = plan_sweep_condensed(L->bs, L->npatch, pp, pd, nwave, sw.wave_ptr.data(), sw.seq.data(), L->cplan.gcptr.data(),
+                                            L->cplan.chptr.data(), &sc, &err))
+      return alfi_set_error(ctx, rc, "%s", err.c_str());
+    ALFI_CHECK(dev_upload(ctx, &L->mcw_gchunk, sc.gchunk.data(), (int64_t)sc.gchunk.size()));
+    ALFI_CHECK(dev_upload(ctx, &L->mcw_schunk, sc.schunk.data(), (int64_t)sc.schunk.size()));
+    ALFI_CHECK(dev_upload(ctx, &L->mcw_node, sc.node.data(), (int64_t)sc.node.size()));
+    ALFI_CHECK(dev_alloc(ctx, &L->mcw_r, L->n));
+    ALFI_HIP_CHECK(ctx, hipMemset(L->mcw_r, 0, sizeof(double) * (size_t)std::max<int64_t>(L->n, 1)));
+    L->mcw_wk_ptr = std::move(sc.wk_ptr);
+    L->mcw_wc_ptr = std::move(sc.wc_ptr);
+    L->mcw_wn_ptr = std::move(sc.wn_ptr);
+  }
   L->sweep.wave_ptr = std::move(sw.wave_ptr);
   L->mult = true;
   L->mult_symmetrise = symmetrise != 0;
@@ -376,6 +401,19 @@ int alfi_patches_set_multiplicative(alfi_level* L, int64_t nit, const int64_t* i
   L->sweep.nitems = sw.nitems;                           // last: until every table is there the sweeps launch per wavefront
   if (refactor) ALFI_CHECK(alfi_patches_factor(L));
   return 0;
+}
+
+int alfi_patches_set_multiplicative(alfi_level* L, int64_t nit, const int64_t* iterset, int symmetrise) {
+  return set_multiplicative_impl(L, nit, iterset, symmetrise, false);
+}
+
+int alfi_patches_set_multiplicative_condensed(alfi_level* L, int64_t nit, const int64_t* iterset, int symmetrise) {
+  // without the caller's groups (a level that condensed itself included: it goes back to dense inverses) this is the call above
+  const bool keep = nit != 0 && cond_by_caller(L);
+  if (keep && level_is_partitioned(L))
+    return alfi_set_error(L->ctx, ALFI_E_ARG, "alfi_patches_set_multiplicative_condensed: sweeps over condensed factors on a "
+                                              "partitioned level are not built");
+  return set_multiplicative_impl(L, nit, iterset, symmetrise, keep);
 }
 
 int alfi_patches_set_partition_of_unity(alfi_level* L, int on) {

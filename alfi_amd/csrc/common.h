@@ -470,6 +470,11 @@ struct alfi_level {
   int32_t *mult_items = nullptr, *mult_pred0 = nullptr, *mult_pred = nullptr, *mult_succ_ptr = nullptr, *mult_succ = nullptr;
   int32_t* mult_ctl = nullptr;          // [0] ticket counter (zeroed before every launch)
   int32_t* mult_rowtab = nullptr;       // (npatch, 64, 3) first block, block count, node of every patch node (zero-padded)
+  // sweeps that read condensed factors (alfi_patches_set_multiplicative_condensed on a level with the caller's groups; taken
+  // while held == HELD_COND): the work lists of every wavefront (plan_sweep_condensed, patch_plan.h) and the residual vector
+  int32_t *mcw_gchunk = nullptr, *mcw_schunk = nullptr, *mcw_node = nullptr;
+  std::vector<int64_t> mcw_wk_ptr, mcw_wc_ptr, mcw_wn_ptr;   // (nwave+1) offsets into the three lists
+  double* mcw_r = nullptr;              // (n) x - A y on the rows of the current wavefront
   // FGMRES workspaces (layout: KrylovWs, krylov_ws.h).  ws: the single call's, one slot; K grows only, and captured cycles hold
   // its addresses, so no block call touches it.  blk_ws: one slot per column of a chunk (alfi_smooth_fgmres_block), with ws's K.
   KrylovWs ws, blk_ws;
@@ -704,6 +709,7 @@ int launch_patch_mult_persistent(alfi_level* lvl, const double* x, double* y);
 // the same with a workgroup per patch: patches of more than 64 nodes (macro stars)
 int launch_big_mult_wave(alfi_level* lvl, const int32_t* seq, int64_t count, const double* x, double* y);
 int launch_big_mult_persistent(alfi_level* lvl, const double* x, double* y);   // ... as one launch over the ticketed schedule
+int launch_cond_mult_wave(alfi_level* lvl, int64_t w, const double* x, double* y);   // wavefront w of a sweep over condensed patches
 int launch_invert_small_any(alfi_ctx* ctx, int nmax, int64_t nmat, const int64_t* ptr, const int64_t* inv_ptr,
                             int fixed_n, int64_t fixed_stride, double* inv, int* status);
 int launch_block_build_invert(alfi_transfer* tr);

@@ -785,6 +785,7 @@ struct alfi_host_plan {
   PatchLayout lay;
   CondPlan cond;
   SweepPlan sweep;
+  SweepCondPlan swc;
   std::vector<int64_t> f32_ptr, ranges;
   int rc = 0;
   std::string err;
@@ -904,6 +905,19 @@ alfi_host_plan* alfi_host_plan_sweep(int bs, int64_t nbrows, int64_t npatch, con
   ALFI_PLAN_TABLE(sweep, seq); ALFI_PLAN_TABLE(sweep, wave_ptr); ALFI_PLAN_TABLE(sweep, items); ALFI_PLAN_TABLE(sweep, pred0);
   ALFI_PLAN_TABLE(sweep, succ_ptr); ALFI_PLAN_TABLE(sweep, succ); ALFI_PLAN_TABLE(sweep, rowtab);
   ALFI_PLAN_SCALAR(sweep, big); ALFI_PLAN_SCALAR(sweep, nitems);
+  return h;
+}
+
+// the work lists of a sweep over condensed patches (patch_plan.h: plan_sweep_condensed): seq / wave_ptr as alfi_host_plan_sweep
+// returns them, gcptr / chptr as alfi_host_plan_condensed does
+alfi_host_plan* alfi_host_plan_sweep_condensed(int bs, int64_t npatch, const int64_t* patch_ptr, const int32_t* patch_dofs,
+                                               int64_t nwave, const int64_t* wave_ptr, const int32_t* seq, const int64_t* gcptr,
+                                               const int64_t* chptr) {
+  alfi_host_plan* h = new alfi_host_plan();
+  h->rc = plan_sweep_condensed(bs, npatch, patch_ptr, patch_dofs, nwave, wave_ptr, seq, gcptr, chptr, &h->swc, &h->err);
+  if (h->rc != 0) return h;
+  ALFI_PLAN_TABLE(swc, wk_ptr); ALFI_PLAN_TABLE(swc, wc_ptr); ALFI_PLAN_TABLE(swc, wn_ptr); ALFI_PLAN_TABLE(swc, gchunk);
+  ALFI_PLAN_TABLE(swc, schunk); ALFI_PLAN_TABLE(swc, node);
   return h;
 }
 #undef ALFI_PLAN_TABLE

@@ -422,6 +422,38 @@ __global__ __launch_bounds__(256) void big_apply_kernel(int64_t p0, int64_t npat
 //     apply.  Patches of one wavefront neither read what another one writes nor write the same dofs: plain stores, the
 //     result is that of the sequential sweep.
 // ---------------------------------------------------------------------------------------------------------------------
+// (A y)[node], the BS components in s: a wave per block row, lanes over the row's blocks (coalesced value planes), shuffle-reduced
+// -- every lane holds the sums.  The residual rows of big_mult_patch and of the sweeps over condensed patches (section 4b).
+template <int BS, bool NT>
+__device__ __forceinline__ void big_mult_row(int node, int lane, const int32_t* __restrict__ rowptr,
+                                             const int32_t* __restrict__ colidx, const double* __restrict__ vals, int flat,
+                                             const double* y, double (&s)[BS]) {
+  constexpr int BB = BS * BS;
+  const int32_t lo = rowptr[node], hi = rowptr[node + 1];
+#pragma unroll
+  for (int r = 0; r < BS; ++r) s[r] = 0.0;
+  for (int32_t k = lo + lane; k < hi; k += 64) {
+    const int64_t col = colidx[k] & 0x7fffffff;
+    double a[BB], yv[BS];
+#pragma unroll
+    for (int e = 0; e < BB; ++e) {
+      const double* v = vals + bsr_val_index(flat, k, e, BB);
+      a[e] = NT ? __builtin_nontemporal_load(v) : *v;
+    }
+#pragma unroll
+    for (int c = 0; c < BS; ++c) yv[c] = y[col * BS + c];
+#pragma unroll
+    for (int r = 0; r < BS; ++r)
+#pragma unroll
+      for (int c = 0; c < BS; ++c) s[r] = __builtin_fma(a[r * BS + c], yv[c], s[r]);
+  }
+#pragma unroll
+  for (int r = 0; r < BS; ++r) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s[r] += __shfl_xor(s[r], o);
+  }
+}
+
 // one patch of a multiplicative sweep by a workgroup of 4 waves: r = (x - A y) on the patch's rows (a wave per node, lanes over
 // the row's blocks), ys = inv(A_p) r by row pieces, y += ys
 template <int BS, bool NT>
@@ -431,37 +463,14 @@ __device__ __forceinline__ void big_mult_patch(int64_t p, double* __restrict__ r
                                                const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
                                                const double* __restrict__ vals, int flat, const double* __restrict__ x,
                                                double* y) {
-  constexpr int BB = BS * BS;
   const int64_t off = patch_ptr[p];
   const int n = (int)(patch_ptr[p + 1] - off);
   const int nn = n / BS;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int i = wave; i < nn; i += 4) {
     const int node = patch_dofs[off + (int64_t)i * BS] / BS;
-    const int32_t lo = rowptr[node], hi = rowptr[node + 1];
     double s[BS];
-#pragma unroll
-    for (int r = 0; r < BS; ++r) s[r] = 0.0;
-    for (int32_t k = lo + lane; k < hi; k += 64) {
-      const int64_t col = colidx[k] & 0x7fffffff;
-      double a[BB], yv[BS];
-#pragma unroll
-      for (int e = 0; e < BB; ++e) {
-        const double* v = vals + bsr_val_index(flat, k, e, BB);
-        a[e] = NT ? __builtin_nontemporal_load(v) : *v;
-      }
-#pragma unroll
-      for (int c = 0; c < BS; ++c) yv[c] = y[col * BS + c];
-#pragma unroll
-      for (int r = 0; r < BS; ++r)
-#pragma unroll
-        for (int c = 0; c < BS; ++c) s[r] = __builtin_fma(a[r * BS + c], yv[c], s[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < BS; ++r) {
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) s[r] += __shfl_xor(s[r], o);
-    }
+    big_mult_row<BS, NT>(node, lane, rowptr, colidx, vals, flat, y, s);
     if (lane == 0) {
 #pragma unroll
       for (int r = 0; r < BS; ++r) rs[i * BS + r] = x[(int64_t)node * BS + r] - s[r];
@@ -1471,10 +1480,12 @@ __device__ __forceinline__ CondBPair cond_bpair(const CondDev& cd, const CondChu
   return d;
 }
 
+// (the three bodies take the chunk's index: the kernels of the additive apply pass k0 / c0 + blockIdx.x, the list kernels of the
+// sweeps over condensed patches, section 4b, an entry of the wavefront's list -- the same sums for the same patch)
 template <bool NT>
-__global__ __launch_bounds__(256) void cond_gfront_kernel(int64_t k0, CondDev cd, const double* __restrict__ x) {
+__device__ __forceinline__ void cond_gfront_body(int64_t k, const CondDev& cd, const double* __restrict__ x) {
   extern __shared__ double cond_dsmem[];
-  const CondChunk c = cd.gc[k0 + blockIdx.x];
+  const CondChunk c = cd.gc[k];
   double* xs = cond_dsmem;                           // c.ne
   double* ts = xs + c.ne;                            // c.ne
   const int tid = threadIdx.x;
@@ -1512,16 +1523,19 @@ __global__ __launch_bounds__(256) void cond_gfront_kernel(int64_t k0, CondDev cd
     }
   }
 }
+template <bool NT>
+__global__ __launch_bounds__(256) void cond_gfront_kernel(int64_t k0, CondDev cd, const double* __restrict__ x) {
+  cond_gfront_body<NT>(k0 + blockIdx.x, cd, x);
+}
 
 // y_S = inv(Sigma) rhs for a chunk of <= 256 rows, the right-hand side formed here: rhs_i = x_i - sum of the row's
 // contributions in cd.ubuf (adjacent, ascending: the order of the other forms of the apply); the chunk's rows of y_S go to
 // cd.tmp AND to their staging slots.
 template <bool NT>
-__global__ __launch_bounds__(256) void cond_gsigma_kernel(int64_t c0, CondDev cd, const int64_t* __restrict__ patch_ptr,
-                                                          const int64_t* __restrict__ stage_ptr, const double* __restrict__ x,
-                                                          double* __restrict__ stage) {
+__device__ __forceinline__ void cond_gsigma_body(int64_t c, const CondDev& cd, const int64_t* __restrict__ patch_ptr,
+                                                 const int64_t* __restrict__ stage_ptr, const double* __restrict__ x,
+                                                 double* __restrict__ stage) {
   extern __shared__ double cond_dsmem[];
-  const int64_t c = c0 + blockIdx.x;
   const int64_t p = cd.ch_patch[c];
   const int r0 = cd.ch_row[c];
   const int64_t off = patch_ptr[p];
@@ -1556,11 +1570,17 @@ __global__ __launch_bounds__(256) void cond_gsigma_kernel(int64_t c0, CondDev cd
     out[cd.slot[off + nI + i]] = v;
   }
 }
+template <bool NT>
+__global__ __launch_bounds__(256) void cond_gsigma_kernel(int64_t c0, CondDev cd, const int64_t* __restrict__ patch_ptr,
+                                                          const int64_t* __restrict__ stage_ptr, const double* __restrict__ x,
+                                                          double* __restrict__ stage) {
+  cond_gsigma_body<NT>(c0 + blockIdx.x, cd, patch_ptr, stage_ptr, x, stage);
+}
 
 template <bool NT>
-__global__ __launch_bounds__(256) void cond_gback_kernel(int64_t k0, CondDev cd, double* __restrict__ stage) {
+__device__ __forceinline__ void cond_gback_body(int64_t k, const CondDev& cd, double* __restrict__ stage) {
   extern __shared__ double cond_dsmem[];
-  const CondChunk c = cd.gc[k0 + blockIdx.x];
+  const CondChunk c = cd.gc[k];
   const int tid = threadIdx.x;
   const bool act = c.xq0 + tid < c.xq1;
   const CondXPair xd = cond_xpair(cd, c, c.xq0 + tid, act);
@@ -1581,6 +1601,72 @@ __global__ __launch_bounds__(256) void cond_gback_kernel(int64_t k0, CondDev cd,
     out[xd.sl0] = tg0 - y0;
     if (xd.sl1 >= 0) out[xd.sl1] = tg1 - y1;
   }
+}
+template <bool NT>
+__global__ __launch_bounds__(256) void cond_gback_kernel(int64_t k0, CondDev cd, double* __restrict__ stage) {
+  cond_gback_body<NT>(k0 + blockIdx.x, cd, stage);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// 4b. Multiplicative sweeps that read condensed factors (alfi_patches_set_multiplicative_condensed): per dependency wavefront
+//     one short sequence of launches, kernel boundaries the only ordering (no resident grid, nothing waits):
+//       residual   r[row] = x[row] - (A y)[row] for every block row of the wavefront's patches (big_mult_row: a wave per row,
+//                  whatever the number of patches -- four macro stars are ~2000 waves);
+//       front / sigma / back   the chunked condensed apply with r as its operand, the workgroup's chunk taken from the
+//                  wavefront's list (plan_sweep_condensed, patch_plan.h) instead of a range: the bodies above, so a patch's
+//                  staged result has the bits of the additive apply of the same operand;
+//       update     y[patch_dofs[off + i]] += stage[stage_ptr[p] + i] (cd.slot maps a condensed position to its place in
+//                  patch_dofs' order, the order launch_patch_sum reads the staging slots in).
+//     Patches of one wavefront share no dof and read nothing another one writes: plain stores, as in big_mult_kernel.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int BS, bool NT>
+__global__ __launch_bounds__(256) void cond_mult_residual_kernel(int64_t count, const int32_t* __restrict__ nodes,
+                                                                  const int32_t* __restrict__ rowptr,
+                                                                  const int32_t* __restrict__ colidx,
+                                                                  const double* __restrict__ vals, int flat,
+                                                                  const double* __restrict__ x, const double* y,
+                                                                  double* __restrict__ r) {
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (i >= count) return;                                  // (wave-uniform)
+  const int node = nodes[i];
+  double s[BS];
+  big_mult_row<BS, NT>(node, lane, rowptr, colidx, vals, flat, y, s);
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < BS; ++c) r[(int64_t)node * BS + c] = x[(int64_t)node * BS + c] - s[c];
+  }
+}
+
+template <bool NT>
+__global__ __launch_bounds__(256) void cond_gfront_list_kernel(const int32_t* __restrict__ list, CondDev cd,
+                                                               const double* __restrict__ x) {
+  cond_gfront_body<NT>(list[blockIdx.x], cd, x);
+}
+template <bool NT>
+__global__ __launch_bounds__(256) void cond_gsigma_list_kernel(const int32_t* __restrict__ list, CondDev cd,
+                                                               const int64_t* __restrict__ patch_ptr,
+                                                               const int64_t* __restrict__ stage_ptr,
+                                                               const double* __restrict__ x, double* __restrict__ stage) {
+  cond_gsigma_body<NT>(list[blockIdx.x], cd, patch_ptr, stage_ptr, x, stage);
+}
+template <bool NT>
+__global__ __launch_bounds__(256) void cond_gback_list_kernel(const int32_t* __restrict__ list, CondDev cd,
+                                                              double* __restrict__ stage) {
+  cond_gback_body<NT>(list[blockIdx.x], cd, stage);
+}
+
+// a workgroup per patch of the wavefront (gridDim.y workgroups share a big one)
+__global__ __launch_bounds__(256) void cond_mult_update_kernel(const int32_t* __restrict__ seq,
+                                                               const int64_t* __restrict__ patch_ptr,
+                                                               const int32_t* __restrict__ patch_dofs,
+                                                               const int64_t* __restrict__ stage_ptr,
+                                                               const double* __restrict__ stage, double* __restrict__ y) {
+  const int64_t p = seq[blockIdx.x];
+  const int64_t off = patch_ptr[p];
+  const int n = (int)(patch_ptr[p + 1] - off);
+  const double* in = stage + stage_ptr[p];
+  for (int i = blockIdx.y * 256 + threadIdx.x; i < n; i += gridDim.y * 256) y[patch_dofs[off + i]] += in[i];
 }
 
 // out (n x n, row-major) = the leading n x n part of the padded N x N scratch
@@ -2001,6 +2087,43 @@ int launch_cond_apply_range(alfi_level* L, int64_t p0, int64_t p1, const double*
 #endif
 #undef ALFI_COND_LAUNCH3_W
 #undef ALFI_COND_LAUNCH3
+  ALFI_HIP_CHECK(ctx, hipGetLastError());
+  return 0;
+}
+
+// Wavefront w of a sweep over condensed patches (section 4b): residual, front, sigma, back, update -- five launches, fewer
+// for a wavefront whose patches have no interior group or no skeleton.  The LDS sizes and the nontemporal choices are those of
+// the chunked additive apply above.
+int launch_cond_mult_wave(alfi_level* L, int64_t w, const double* x, double* y) {
+  alfi_ctx* ctx = L->ctx;
+  const int64_t t0 = L->sweep.wave_ptr[w], t1 = L->sweep.wave_ptr[w + 1];
+  if (t1 <= t0) return 0;
+  if (!L->cd.tmp || !L->mcw_r) return alfi_set_error(ctx, ALFI_E_STATE, "condensed sweep without its tables");
+  const int64_t k0 = L->mcw_wk_ptr[w], k1 = L->mcw_wk_ptr[w + 1], c0 = L->mcw_wc_ptr[w], c1 = L->mcw_wc_ptr[w + 1];
+  const int64_t n0 = L->mcw_wn_ptr[w], n1 = L->mcw_wn_ptr[w + 1];
+  const size_t lds_f = (size_t)L->cplan.lds_gfront, lds_b = (size_t)L->cplan.lds_gback;
+  const size_t lds_s = (size_t)(L->cplan.max_s + 2 + COND_SIGMA_ROWS) * sizeof(double);
+  const dim3 rgrid((unsigned)((n1 - n0 + 3) / 4)), block(256);
+  // (ordinary loads for the operator values; nontemporal ones, as in big_mult_kernel, are not measured here)
+#define ALFI_CMR(BSV)                                                                                                        \
+  hipLaunchKernelGGL((cond_mult_residual_kernel<BSV, false>), rgrid, block, 0, ctx->stream, n1 - n0, L->mcw_node + n0, L->A.rowptr, \
+                     L->A.colidx, L->A.vals, L->A.flat, x, y, L->mcw_r)
+  if (L->bs == 2) ALFI_CMR(2);
+  else if (L->bs == 3) ALFI_CMR(3);
+  else return alfi_set_error(ctx, ALFI_E_ARG, "unsupported block size %d", L->bs);
+#undef ALFI_CMR
+  if (k1 > k0)
+    hipLaunchKernelGGL((cond_gfront_list_kernel<false>), dim3((unsigned)(k1 - k0)), block, lds_f, ctx->stream, L->mcw_gchunk + k0,
+                       L->cd, L->mcw_r);
+  if (c1 > c0)
+    hipLaunchKernelGGL((cond_gsigma_list_kernel<true>), dim3((unsigned)(c1 - c0)), block, lds_s, ctx->stream, L->mcw_schunk + c0,
+                       L->cd, L->patch_ptr, L->stage_ptr, L->mcw_r, L->stage);
+  if (k1 > k0)
+    hipLaunchKernelGGL((cond_gback_list_kernel<false>), dim3((unsigned)(k1 - k0)), block, lds_b, ctx->stream, L->mcw_gchunk + k0,
+                       L->cd, L->stage);
+  const int split = std::max(1, std::min(8, (L->lay.max_np + 511) / 512));
+  hipLaunchKernelGGL(cond_mult_update_kernel, dim3((unsigned)(t1 - t0), (unsigned)split), block, 0, ctx->stream, L->mult_seq + t0,
+                     L->patch_ptr, L->patch_dofs, L->stage_ptr, L->stage, y);
   ALFI_HIP_CHECK(ctx, hipGetLastError());
   return 0;
 }

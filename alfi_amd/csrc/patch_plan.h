@@ -585,4 +585,43 @@ inline int plan_sweep(int bs, int64_t nb, int64_t npatch, const int64_t* pp, con
   return 0;
 }
 
+// ---- sweeps that read condensed factors (alfi_patches_set_multiplicative_condensed) -------------------------------------------
+// The work lists of one dependency wavefront w of a sweep over condensed patches: what the chunked condensed launches
+// (cond_gfront / cond_gsigma / cond_gback, kernels_bigpatch.hip) and the residual launch take in place of a patch range.
+struct SweepCondPlan {
+  std::vector<int64_t> wk_ptr, wc_ptr, wn_ptr;   // (nwave+1) offsets into gchunk, schunk, node
+  std::vector<int32_t> gchunk;   // group chunks (indices into CondPlan::gc): [gcptr[p], gcptr[p+1]) of the wavefront's patches, seq order
+  std::vector<int32_t> schunk;   // sigma chunks (indices into ch_patch / ch_row): the same over chptr
+  std::vector<int32_t> node;     // the block rows of the wavefront's patches, patch after patch: the rows of the residual
+};
+
+// seq / wave_ptr: SweepPlan's; gcptr / chptr: CondPlan's; the patches as check_sweep has passed them (whole nodes).  The reverse
+// pass of a symmetrised sweep walks the same wavefronts backwards: no second table.
+inline int plan_sweep_condensed(int bs, int64_t npatch, const int64_t* pp, const int32_t* pd, int64_t nwave,
+                                const int64_t* wave_ptr, const int32_t* seq, const int64_t* gcptr, const int64_t* chptr,
+                                SweepCondPlan* out, std::string* err) {
+  if (npatch > 0 && (gcptr[npatch] > INT32_MAX || chptr[npatch] > INT32_MAX))
+    return plan_fail(err, "condensed sweeps: too many chunks for int32 lists");
+  SweepCondPlan& o = *out;
+  o.wk_ptr.assign((size_t)nwave + 1, 0);
+  o.wc_ptr.assign((size_t)nwave + 1, 0);
+  o.wn_ptr.assign((size_t)nwave + 1, 0);
+  o.gchunk.clear();
+  o.schunk.clear();
+  o.node.clear();
+  for (int64_t w = 0; w < nwave; ++w) {
+    for (int64_t t = wave_ptr[w]; t < wave_ptr[w + 1]; ++t) {
+      const int64_t p = seq[t];
+      if (p < 0 || p >= npatch) return plan_fail(err, "condensed sweeps: sequence entry out of range");
+      for (int64_t k = gcptr[p]; k < gcptr[p + 1]; ++k) o.gchunk.push_back((int32_t)k);   // (none: a patch without interior group)
+      for (int64_t c = chptr[p]; c < chptr[p + 1]; ++c) o.schunk.push_back((int32_t)c);
+      for (int64_t q = pp[p]; q < pp[p + 1]; q += bs) o.node.push_back(pd[q] / bs);
+    }
+    o.wk_ptr[(size_t)w + 1] = (int64_t)o.gchunk.size();
+    o.wc_ptr[(size_t)w + 1] = (int64_t)o.schunk.size();
+    o.wn_ptr[(size_t)w + 1] = (int64_t)o.node.size();
+  }
+  return 0;
+}
+
 #pragma GCC visibility pop

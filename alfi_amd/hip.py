@@ -596,11 +596,14 @@ class Level(object):
     def set_partition_of_unity(self, on=True):
         self.ctx.check(self.ctx.lib.alfi_patches_set_partition_of_unity(self.h, 1 if on else 0))
 
-    def set_multiplicative(self, iterset, symmetrise):
+    def set_multiplicative(self, iterset, symmetrise, condensed=False):
         """Multiplicative sweeps in the order ``iterset`` (None / empty = back to additive); returns the number of
-        dependency wavefronts one sweep was scheduled into."""
+        dependency wavefronts one sweep was scheduled into.  ``condensed``: a level with the caller's groups
+        (``set_patch_groups``) keeps its condensed factors and sweeps over them (alfi_patches_set_multiplicative_condensed);
+        on any other level the flag changes nothing."""
         it = np.ascontiguousarray(iterset if iterset is not None else [], dtype=np.int64)
-        self.ctx.check(self.ctx.lib.alfi_patches_set_multiplicative(self.h, len(it), _ptr(it), 1 if symmetrise else 0))
+        fn = self.ctx.lib.alfi_patches_set_multiplicative_condensed if condensed else self.ctx.lib.alfi_patches_set_multiplicative
+        self.ctx.check(fn(self.h, len(it), _ptr(it), 1 if symmetrise else 0))
         self._record_storage()
         nw = ctypes.c_int64()
         self.ctx.check(self.ctx.lib.alfi_patches_multiplicative_levels(self.h, ctypes.byref(nw)))

@@ -27,6 +27,7 @@ SUPPORTED_PATCH_KEYS = {
     "patch_pc_patch_construct_type", "patch_pc_patch_construct_dim", "patch_pc_patch_construct_python_type",
     "patch_pc_patch_sub_mat_type", "patch_pc_patch_dense_inverse", "patch_pc_patch_multiplicative",
     "patch_sub_ksp_type", "patch_sub_pc_type", "patch_sub_pc_factor_mat_solver_type", "patch_pc_patch_sub_pc_type",
+    "patch_pc_patch_condensed_sweeps",
 }
 
 
@@ -34,9 +35,11 @@ def _truthy(v):
     return v if isinstance(v, bool) else str(v).lower() in ("1", "true", "yes")
 
 
-def mg_levels_solver(tdim, patch="star", patch_composition="additive", smoothing=None, relaxation_direction=None):
+def mg_levels_solver(tdim, patch="star", patch_composition="additive", smoothing=None, relaxation_direction=None,
+                     condensed_sweeps=False):
     """The ``mg_levels_solver`` dictionary of alfi/solver.py:313-344 with ``configure_patch_solver`` of
-    ConstantPressureSolver (solver.py:599-602) applied."""
+    ConstantPressureSolver (solver.py:599-602) applied.  ``condensed_sweeps`` (this project's, not the reference's): emits
+    ``patch_pc_patch_condensed_sweeps``, with which multiplicative sweeps read condensed patch factors (``HipPatchPC``)."""
     multiplicative = patch_composition == "multiplicative"
     if multiplicative and relaxation_direction is None:
         raise NotImplementedError("Need to specify a relaxation_direction in the problem.")
@@ -75,6 +78,8 @@ def mg_levels_solver(tdim, patch="star", patch_composition="additive", smoothing
         opts["patch_pc_patch_construction_MacroStar_sort_order"] = relaxation_direction
     else:
         raise NotImplementedError("Unknown patch type %s" % patch)
+    if condensed_sweeps:
+        opts["patch_pc_patch_condensed_sweeps"] = True
     return opts
 
 
@@ -388,15 +393,28 @@ class HipPatchPC(object):
         self.level.set_patches(ptr, dofs)
         # macro-star patches on an Alfeld-split mesh (ScottVogeliusSolver: the reference keeps SPARSE patch factors there,
         # solver.py:655-659): store the factors condensed -- interiors of the macro cells + skeleton -- unless the sweep is
-        # multiplicative (that kernel multiplies with dense inverses)
+        # multiplicative (that kernel multiplies with dense inverses) and patch_pc_patch_condensed_sweeps is not set
         self.condensed = False
-        if (ctype == "python" and getattr(L.V.mesh, "macro_mesh", None) is not None and not self.multiplicative
+        # opt-in: multiplicative sweeps that read condensed factors (hip.Level.set_multiplicative(..., condensed=True))
+        self.condensed_sweeps = self.multiplicative and _truthy(opts.getString("patch_pc_patch_condensed_sweeps", "false"))
+        if (ctype == "python" and getattr(L.V.mesh, "macro_mesh", None) is not None
+                and (not self.multiplicative or self.condensed_sweeps)
                 and env.condense() and type(ctor).__name__ == "MacroStar"
                 and ctype == "python" and not getattr(L, "facet_coupling", False)):
             # (not on facet-coupled levels: the Burman term couples the interiors of neighbouring macro cells)
             from .sv import macro_cell_groups
             self.level.set_patch_groups(macro_cell_groups(L.V, dofs))
             self.condensed = True
+        elif (self.condensed_sweeps and env.condense() and ctype == "star" and cdim == 0
+              and not getattr(L, "facet_coupling", False)):
+            # built-in vertex stars: the groups the level finds in its own sparsity, handed back as the caller's -- a level
+            # that condensed itself would go back to dense inverses for the sweeps
+            groups = self.level.find_patch_groups()
+            if (groups >= 0).any():
+                self.level.set_patch_groups(groups)
+                self.condensed = True
+            else:
+                self.level.set_patch_groups(None)
         elif self.multiplicative or not env.condense() or getattr(L, "facet_coupling", False):
             # ... and no search for groups by the level itself either (large vertex-star levels, alfi_patches_find_groups):
             # the sweeps and PCPATCH's facet rule need dense inverses, ALFI_CONDENSE=0 asks for them
@@ -416,7 +434,8 @@ class HipPatchPC(object):
         hip.note_patch_level(L, self.level)
         if self.partition_of_unity:
             self.level.set_partition_of_unity(True)
-        self.wavefronts = self.level.set_multiplicative(self.iterset, self.symmetrise) if self.multiplicative else 0
+        self.wavefronts = (self.level.set_multiplicative(self.iterset, self.symmetrise, condensed=self.condensed_sweeps)
+                           if self.multiplicative else 0)
         self.n = L.n
 
     def update(self, pc):

@@ -397,6 +397,15 @@ int alfi_patches_set_partition_of_unity(alfi_level* lvl, int on);
  * wave sweeps a patch of up to 64 nodes / 160 dofs, a workgroup the larger ones (macro stars, solver.py:339-342).  On a partitioned level every rank sweeps over its own patches (local Gauss-Seidel,
  * additive between ranks, ghost contributions reverse-added at the end), as PCPATCH does under MPI. */
 int alfi_patches_set_multiplicative(alfi_level* lvl, int64_t nit, const int64_t* iterset_host, int symmetrise);
+/* The same sweeps on a level that keeps its condensed factors.  On a level with the caller's groups (alfi_patches_set_groups)
+ * the call is accepted: the level keeps the factors and its factored state (alfi_patches_factor_bytes and alfi_patches_condensed
+ * are unchanged), and every dependency wavefront becomes a short sequence of launches -- the residual rows of its patches, the
+ * chunked condensed apply on them, the update of y -- ordered by kernel boundaries alone.  On a level without the caller's
+ * groups, one that condensed itself included, the call IS alfi_patches_set_multiplicative.  Arguments and refusals are those of
+ * that call; a partitioned level with the caller's groups is refused (ALFI_E_ARG).  Afterwards alfi_patches_set_groups(non-NULL)
+ * stays refused; alfi_patches_set_groups(NULL) drops the condensed storage, and after the next alfi_patches_factor the sweeps
+ * read dense inverses. */
+int alfi_patches_set_multiplicative_condensed(alfi_level* lvl, int64_t nit, const int64_t* iterset_host, int symmetrise);
 /* number of dependency wavefronts of one sweep (0 = additive) */
 int alfi_patches_multiplicative_levels(alfi_level* lvl, int64_t* nwave);
 /* sum_p n_p^2 (doubles held as inverses) and sum_p n_p, for roofline accounting */
